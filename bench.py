@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- stereo pairs/s (enc+dec = one HSIC.forward) of the MI355X-native MASIC codec.
 
-    python bench.py [--gpus N --steps K --warmup W] [--batch 8 --height 512 --width 512]
+    python bench.py [--gpus N --steps K --warmup W] [--batch 8 --height 512 --width 512] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one HSIC(N=128,M=192,K=5) eval forward over a batch of synthetic stereo pairs already resident
@@ -16,6 +16,7 @@ data-path collective).  Rank 0 prints ONE JSON line with the contract fields plu
   extras       -- training step, float32 parity path, accuracy of both operand modes against the oracle
                   (bpp / PSNR / symbol mismatch: BASELINE.json's "bpp/PSNR vs ref"), upload-inclusive rates,
                   Independent_EN (CQE) forward + training step, the real bitstream of one pair.
+  dump_outputs -- with --dump-outputs DIR only: what the last timed step returned (rank 0), written as DIR/<name>.npy.
 """
 import argparse
 import hashlib
@@ -330,6 +331,47 @@ def traffic_for(symbol, pmc, pmc_reason):
     return None, f"not measured: {pmc_reason}"
 
 
+# ------------------------------------------------------------------------------------------------ output dump (--dump-outputs)
+DUMP_BUDGET_BYTES = 60 << 20     # under the 64 MB the dump may take, all arrays together
+DUMP_SAMPLE_SEED = 20251015
+
+
+def dump_outputs(out, directory):
+    """Writes the forward's outputs (the dict a caller of the timed step receives; nested dicts flattened as `outer_inner`) as
+    float32 `.npy` files.  When the whole set exceeds DUMP_BUDGET_BYTES, every array above its share of the budget is
+    replaced by that many elements at sorted positions drawn without replacement from a generator seeded by DUMP_SAMPLE_SEED and the
+    array's name: the same positions for the same name and shape in every run and every build.  Returns what was written."""
+    import zlib
+    import numpy as np
+    flat = {}
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                walk(f"{prefix}_{k}" if prefix else k, v[k])
+        elif torch.is_tensor(v):
+            flat[prefix] = v.detach().float().cpu().numpy()
+    walk("", out)
+    os.makedirs(directory, exist_ok=True)
+    # element allowance per array: the budget shared out smallest array first, what a small array leaves over going to the larger ones
+    left, allow = DUMP_BUDGET_BYTES // 4, {}
+    for i, name in enumerate(sorted(flat, key=lambda n: (flat[n].size, n))):
+        allow[name] = min(flat[name].size, left // (len(flat) - i))
+        left -= allow[name]
+    info = {"dir": directory, "dtype": "float32", "sample_seed": DUMP_SAMPLE_SEED, "arrays": {}}
+    for name, a in flat.items():
+        e = {"shape": list(a.shape)}
+        share = allow[name]
+        if a.size > share:
+            rng = np.random.Generator(np.random.PCG64([DUMP_SAMPLE_SEED, zlib.crc32(name.encode())]))
+            e["sampled"] = f"{share} of {a.size} elements (flattened C order, sorted seeded positions)"
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        e["written"] = int(a.size)
+        info["arrays"][name] = e
+    return info
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -352,11 +394,16 @@ def main():
     ap.add_argument("--no-upload", action="store_true", help="skip the upload-inclusive timings (extras.with_upload)")
     ap.add_argument("--no-trained", action="store_true", help="skip extras.accuracy_vs_ref_trained (trains HSIC for --trained-steps steps first)")
     ap.add_argument("--trained-steps", type=int, default=3000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32; arrays are sampled at fixed seeded "
+                         "positions where the whole set would exceed 64 MB")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--train-steps", type=int, default=5,
                     help="also time this many full training steps (forward + RD loss + backward + gradient all-reduce + "
                          "2x Adam) after the headline region; reported under extras.train_step, 0 to skip")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.pmc_child:
         return pmc_child(args)
 
@@ -437,6 +484,8 @@ def main():
             out = step(xa, xb, hm, **ahead)
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        # the graph's output buffers are overwritten by every later replay: keep the last timed step's result as it was
+        dump_info = dump_outputs(out, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
         # ---- the same step WITHOUT the look-ahead: the homography arrives with its own batch, as the reference computes it right before
         # model(d1, d2, h_matrix) (newtrain_codec_real.py:124-137) -- each call waits for the previous replay, reads it, runs the host chain
@@ -905,6 +954,8 @@ def main():
             extras["rehearsal_reducer_check"] = rehearsal_info
         if extras:
             line["extras"] = extras
+        if dump_info is not None:
+            line["dump_outputs"] = dump_info
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, M, K, seed=100)
         print(json.dumps(line), flush=True)
