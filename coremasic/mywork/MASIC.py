@@ -34,8 +34,8 @@ from masic_amd.streams import ForkJoin as _ForkJoin
 from masic_amd import fp8 as _fp8
 
 _RELU, _LEAKY, _NONE = _hip.ACT_RELU, _hip.ACT_LEAKY, _hip.ACT_NONE
-_CAT_F16K = os.environ.get("MASIC_CAT_F16K", "1") != "0"               # 0: float32 concat buffers in front of the heads (A/B timing)
-_HEADS_GROUPED = os.environ.get("MASIC_HEADS_GROUPED", "1") != "0"     # layer i of a head's three stacks in one launch (0: A/B timing)
+_CAT_F16K = True           # F16K concat buffers in front of the heads; tests set False for the float32 concat as their reference
+_HEADS_GROUPED = True      # layer i of a head's three stacks in one launch; tests set False for one launch per layer as their reference
 
 
 class CompressionModel(nn.Module):
@@ -875,7 +875,7 @@ class HSIC(CompressionModel):
         producers (last hyper-synthesis layer, context model, the rounded warped latent) then write their gated slices as bf16 records
         and the head's grouped GEMMs read them directly -- no float32 concat, no conversion pass of the whole buffer on the entropy
         chain (same values bit for bit: the gate multiplies in float32 before the one rounding to bf16 either way).  None otherwise
-        (float32 / fp8 operands, fp8 calibration, head widths without the grouped GEMM form; MASIC_CAT_F16K=0)."""
+        (float32 / fp8 operands, fp8 calibration, head widths without the grouped GEMM form; _CAT_F16K off)."""
         from masic_amd import nn as _mnn
         if not (_CAT_F16K and _HEADS_GROUPED and _bf16_inference(y) and not _mnn._FP8 and not _fp8.recording() and C % 16 == 0
                 and _fp8.scales(head) is None and head._grouped_heads_ok()):
@@ -1030,11 +1030,10 @@ class HSIC(CompressionModel):
 
     def _skinny_params(self, head, ctx, cat16, C, h, w, gate=None):
         """Buffers and layer descriptions of _PixelParams' pixel-list form, or None when it does not apply (float32 / fp8 operands, widths
-        the kernels are not built for; MASIC_CODEC_SKINNY=0)."""
-        import os
+        the kernels are not built for)."""
         from masic_amd import nn as _mnn
         M, K = self.M, self.K
-        if (cat16 is None or os.environ.get("MASIC_CODEC_SKINNY", "1") == "0" or M % 16 or (2 * M) % 32 or not head._grouped_heads_ok()
+        if (cat16 is None or M % 16 or (2 * M) % 32 or not head._grouped_heads_ok()
                 or ctx.kernel_size != (5, 5)):
             return None
         dev = cat16[0].device

@@ -6,7 +6,6 @@ engine only orders the calls and accumulates parameter gradients (`AccumulateGra
 `zero_grad` work unchanged.  Formulas: SURVEY.md appendix B (checked there against autograd in float64).
 """
 import math
-import os
 
 import torch
 from torch.autograd import Function
@@ -21,28 +20,19 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
-_DGRAD_F16K = os.environ.get("MASIC_DGRAD_F16K", "1") != "0"      # 0: input gradients on the implicit-GEMM kernel only (A/B timing)
-
-
 def _gemm_1x1(mod, act=0):
     from . import nn as _mnn
-    return (_GEMM_1X1 and _mnn._PRECISION != PREC_F32 and tuple(mod.kernel_size) == (1, 1) and tuple(mod.stride) == (1, 1) and tuple(mod.padding) == (0, 0)
+    return (_mnn._PRECISION != PREC_F32 and tuple(mod.kernel_size) == (1, 1) and tuple(mod.stride) == (1, 1) and tuple(mod.padding) == (0, 0)
             and mod.in_channels % 32 == 0 and mod.out_channels % 32 == 0 and act in (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LEAKY))
-
-
-_FWD_F16K = os.environ.get("MASIC_TRAIN_FWD_F16K", "1") != "0"      # 0: training-mode forward of the hyper / context layers on the NCHW kernel (A/B timing)
 
 
 def _fwd_f16k(mod, x, act):
     from . import nn as _mnn
-    if not _FWD_F16K or _mnn._PRECISION == PREC_F32 or _mnn._FP8 or x.dim() != 4 or x.shape[1] != mod.in_channels:
+    if _mnn._PRECISION == PREC_F32 or _mnn._FP8 or x.dim() != 4 or x.shape[1] != mod.in_channels:
         return False
     kh, kw, _, _ = mod._geometry()
     return (kh * kw > 1 and mod.in_channels % 16 == 0 and mod.out_channels % 32 == 0 and act in (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LEAKY)
             and mod.f16k_supported(x.shape[0], x.shape[2], x.shape[3]))
-
-
-_GEMM_1X1 = os.environ.get("MASIC_TRAIN_GEMM_1X1", "1") != "0"      # 0: 1x1 layers of the training step on the implicit-GEMM kernel (A/B timing)
 
 
 class ConvFn(Function):
@@ -86,13 +76,7 @@ class ConvFn(Function):
         return gx, gw, gb, None, None
 
 
-_PIC_END_DGRAD = os.environ.get("MASIC_PIC_END_DGRAD", "1") != "0"   # 0: input gradients of g_a_conv1 / g_s_conv4 on the float32 NCHW kernels (A/B timing)
-_GDN_BWD_SMALL = os.environ.get("MASIC_GDN_BWD_SMALL", "1") != "0"   # 0: GDN(3) backward as the nine-launch generic chain (A/B timing)
-_WGRAD5_F16K = os.environ.get("MASIC_WGRAD5_F16K", "1") != "0"     # 0: 5x5 stride-1 weight gradients on the float32-tile kernel (A/B timing)
-_DGRAD_FEW = os.environ.get("MASIC_DGRAD_FEW", "1") != "0"         # 0: input gradients of the <= 8-channel-input layers on the float32 direct kernel (A/B timing)
-_PIC_WGRAD = os.environ.get("MASIC_PIC_WGRAD", "1") != "0"         # 0: weight gradients of g_a_conv1 / g_s_conv4 on the float32-tile kernel (A/B timing)
-_WGRAD1_F16K = os.environ.get("MASIC_WGRAD1_F16K", "1") != "0"     # 0: 1x1 weight gradients on the float32 NCHW kernel (A/B timing)
-_WGRAD3_F16K = os.environ.get("MASIC_WGRAD3_F16K", "1") != "0"     # 0: 3x3 weight gradients on the tap-generic float32-tile kernel (A/B timing)
+_WGRAD1_F16K = True     # 1x1 weight gradients from the two F16K operands; tests set False for the float32 NCHW kernel as their reference
 
 
 def conv_backward(mod, x, weight, y, g, act, need_gx=True, need_gw=True, need_gb=True, x16=None, g16=None, gb=None, gx_f16k=False,
@@ -132,27 +116,27 @@ def conv_backward(mod, x, weight, y, g, act, need_gx=True, need_gw=True, need_gb
         if (d.Ho, d.Wo) != (Hi, Wi):
             raise RuntimeError("masic_amd: input-gradient geometry mismatch (odd spatial size?)")
         dx_gemm = _gemm_1x1(mod)
-        if not dx_gemm and _DGRAD_F16K and bf16 and Cout % 16 == 0 and kh * kw > 1:
+        if not dx_gemm and bf16 and Cout % 16 == 0 and kh * kw > 1:
             # bf16 mode: the DMA-staged F16K kernel of the inference path (conv_f16k.hip) -- g converted once to the channel-blocked
             # bf16 layout, float32 NCHW out; measured 1.1 ms of a 30 ms step against the implicit-GEMM kernel
             d16 = ops.make_conv_desc(B, Cout, Ho, Wo, Cin, kh, kw, s, p, transposed=not mod.transposed_conv, in_ctot=Cout, prec=_mnn._PRECISION)
             dx_f16k = ops.conv_f16k_supported(d16)
-            if not dx_f16k and _DGRAD_FEW and Cin <= 8 and s == 1 and not mod.transposed_conv and not mod.masked_conv:
+            if not dx_f16k and Cin <= 8 and s == 1 and not mod.transposed_conv and not mod.masked_conv:
                 # few input channels (the 3 / 6 -> 32 input layers of Independent_EN, MASIC.py:1456-1470): dx as the transposed convolution
                 # to 32 zero-padded channels on the MFMA path, only the real ones stored (masic_conv_f16k_few_fwd); the generic float32
                 # kernel took 263 us per launch at 8 x 512 x 512
                 d_few = ops.make_conv_desc(B, Cout, Ho, Wo, 32, kh, kw, s, p, transposed=True, in_ctot=Cout, prec=_mnn._PRECISION)
                 dx_few = ops.conv_f16k_supported(d_few)
     # 3x3 stride-1 layers (Independent_EN, hyper transforms): dW from both operands in F16K, transposed LDS reads (wgrad_f16k.hip)
-    dw_f16k = (need_gw and _WGRAD3_F16K and bf16 and not mod.transposed_conv and not mod.masked_conv and (kh, kw, s, p) == (3, 3, 1, 1)
+    dw_f16k = (need_gw and bf16 and not mod.transposed_conv and not mod.masked_conv and (kh, kw, s, p) == (3, 3, 1, 1)
                and Cin % 32 == 0 and Cout % 32 == 0 and x_shape[1] == Cin)
     # 5x5 stride-1 layers at latent resolution (encode_hyper[0], the context model): the same kernel with five kernel-row waves
-    dw5_f16k = (need_gw and _WGRAD5_F16K and bf16 and not mod.transposed_conv and (kh, kw, s, p) == (5, 5, 1, 2)
+    dw5_f16k = (need_gw and bf16 and not mod.transposed_conv and (kh, kw, s, p) == (5, 5, 1, 2)
                 and Cin % 32 == 0 and Cout % 32 == 0 and x_shape[1] == Cin)
     if g16 is None or act != ops.ACT_NONE:
         g16 = ops.nchw_to_f16k(g) if (dx_gemm or dx_f16k or dx_few or dw_f16k or dw5_f16k) else None  # dy in F16K, converted once for both gradients
 
-    pic_end = _PIC_END_DGRAD and bf16 and need_gx and act == ops.ACT_NONE and (kh, kw, s, p) == (5, 5, 2, 2)
+    pic_end = bf16 and need_gx and act == ops.ACT_NONE and (kh, kw, s, p) == (5, 5, 2, 2)
     # the two picture-end layers (MASIC.py:515 g_a_conv1 = Conv2d(3 -> 128), :550 g_s_conv4 = ConvTranspose2d(128 -> 3)); without
     # these forms their input gradients run on the float32 NCHW kernels (266 / 170 us per launch at 8 x 512 x 512)
     dx_d2s = pic_end and not mod.transposed_conv and Cin <= 8 and Cout % 32 == 0 and g16 is not None
@@ -160,7 +144,7 @@ def conv_backward(mod, x, weight, y, g, act, need_gx=True, need_gw=True, need_gb
 
     # ... and their weight gradients: the 128-channel operand in F16K (dy of g_a_conv1, x of g_s_conv4), the 3-channel one float32 NCHW
     dw_pic = 0
-    if need_gw and _PIC_WGRAD and bf16 and act == ops.ACT_NONE and (kh, kw, s, p) == (5, 5, 2, 2):
+    if need_gw and bf16 and act == ops.ACT_NONE and (kh, kw, s, p) == (5, 5, 2, 2):
         if not mod.transposed_conv and (Cin, Cout) == (3, 128) and g16 is not None and x is not None and (Hi, Wi) == (2 * Ho, 2 * Wo):
             dw_pic = 1
         elif mod.transposed_conv and (Cin, Cout) == (128, 3) and x16 is not None and g is not None and (Ho, Wo) == (2 * Hi, 2 * Wi):
@@ -248,7 +232,7 @@ def gdn_backward(x, g, beta, gamma, inverse, beta_min, need_gx=True):
     from . import nn as _mnn
     if C == 128 and _mnn._PRECISION != PREC_F32:       # bf16-operand mode: the whole backward in one kernel
         return ops.gdn_bwd_fused(x, g, beta.detach(), gamma.detach(), inverse, beta_min)
-    if C <= 4 and _GDN_BWD_SMALL:                      # pre_gdn / after_gdn (GDN(3) on pictures): one pass, float32 in every mode
+    if C <= 4:                      # pre_gdn / after_gdn (GDN(3) on pictures): one pass, float32 in every mode
         return ops.gdn_bwd_small(x, g, beta.detach(), gamma.detach(), inverse, beta_min)
     b_bound = float(torch.tensor((beta_min + PEDESTAL) ** 0.5, dtype=torch.float32))
     g_bound = float(torch.tensor(PEDESTAL ** 0.5, dtype=torch.float32))
@@ -462,9 +446,6 @@ class AddFn(Function):
         return g, g
 
 
-_EB_FUSED_EPILOGUES = os.environ.get("MASIC_EB_FUSED_EPILOGUES", "1") != "0"      # 0: g * act'(u) and the bias sums of the block nodes as separate passes (A/B timing)
-
-
 class EnhancementBlockFn(Function):
     """Enhancement_Block -- three residual blocks and the skip over all of them (reference MASIC.py:149-164) -- as ONE node of the CQE
     training step in bf16 mode, forward AND backward on F16K buffers (conv_f16k.hip, wgrad_f16k.hip, f16k_ops.hip):
@@ -534,16 +515,15 @@ class EnhancementBlockFn(Function):
         # bias gradient of the layer they differentiate through (channel sums of their own output) and, for the launch that ends a block,
         # the NEXT block's g_u = g_o * L'(u) as a second output -- per block one elementwise pass and two reduction passes over
         # full-resolution tensors less (masic_conv3x3_resident_ex_fwd); the values are the same bf16 values summed / masked.
-        fused = resident and _EB_FUSED_EPILOGUES
         go, gu, gu_sum = g_out, None, None
         for i in (2, 1, 0):
             rb, x_in, t, u = blocks[i]
             w1, w2 = params[4 * i], params[4 * i + 2]
             if gu is None:
-                gu, gu_sum = ops.f16k_act_bwd_sum(go, u, 0.01, B, C, H * W) if _EB_FUSED_EPILOGUES else (ops.f16k_act_bwd(go, u, 0.01), None)
+                gu, gu_sum = ops.f16k_act_bwd_sum(go, u, 0.01, B, C, H * W)
             grads[4 * i + 2] = ops.conv3x3_wgrad_f16k(t, gu, B, C, C, H, W)
-            grads[4 * i + 3] = gu_sum if gu_sum is not None else ops.f16k_channel_sum(gu, B, C, H * W)
-            if fused:
+            grads[4 * i + 3] = gu_sum
+            if resident:
                 gt, _, gt_sum = dgrad(gu, w2, mask=t, mask_slope=0.01, sum_of=1)
             else:
                 gt = dgrad(gu, w2, mask=t, mask_slope=0.01)
@@ -551,7 +531,7 @@ class EnhancementBlockFn(Function):
             del gu
             grads[4 * i] = ops.conv3x3_wgrad_f16k(x_in, gt, B, C, C, H, W)
             grads[4 * i + 1] = gt_sum
-            if fused and i > 0:
+            if resident and i > 0:
                 go, gu, gu_sum = dgrad(gt, w1, res1=go, mask2=blocks[i - 1][3], mask2_slope=0.01, sum_of=2)
             else:
                 go, gu, gu_sum = dgrad(gt, w1, res1=go, res2=g_out if i == 0 else None), None, None
@@ -655,7 +635,7 @@ class RateDistortionFn(Function):
         return (None, None, None, g1, g2, *gl)
 
 
-_RD_FUSED = os.environ.get("MASIC_RD_FUSED", "1") != "0"             # 0: the criterion as six reductions + torch scalar arithmetic (A/B timing)
+_RD_FUSED = True             # the criterion as two launches; tests set False for six reductions + torch scalar arithmetic as their reference
 
 
 # ------------------------------------------------------------------------------------------ fused transforms (bf16-operand training)
@@ -665,14 +645,10 @@ _RD_FUSED = os.environ.get("MASIC_RD_FUSED", "1") != "0"             # 0: the cr
 # float32 activations the per-layer nodes keep -- and the backward converts each to float32 NCHW right before the kernel that
 # needs it (weight gradient: the layer's input; GDN backward: the GDN's input).  Gradients are those of the same function evaluated
 # on bf16-rounded activations; the float32 mode keeps the per-layer nodes (the parity path).
-_GDN_BWD_F16K = os.environ.get("MASIC_GDN_BWD_F16K", "1") != "0"
-_WGRAD_B16 = os.environ.get("MASIC_WGRAD_B16", "1") != "0" and _GDN_BWD_F16K     # 0: float32 NCHW operands for the 5x5 stride-2 weight gradients (A/B timing)
 
 
 def _wgrad_b16(mod, B, hw_in):
     """True if the weight gradient of `mod` on an input of B x C x hw_in takes bf16 NCHW operands (ops.conv2d_wgrad_b16_supported)."""
-    if not _WGRAD_B16:
-        return False
     kh, kw, s, p = mod._geometry()
     return ops.conv2d_wgrad_b16_supported(ops.make_conv_desc(B, mod.in_channels, hw_in[0], hw_in[1], mod.out_channels, kh, kw, s, p,
                                                              transposed=mod.transposed_conv, prec=PREC_BF16))
@@ -681,13 +657,8 @@ def _wgrad_b16(mod, B, hw_in):
 def _gdn_backward_f16k(u16, g, shape, gdn, want_f16k=True, want_b16=False, want_nchw=True):
     """GDN backward inside the fused transforms: (dx NCHW -- float32, or bf16 with want_b16 --, dx F16K | None, channel sums of dx | None,
     d beta, d gamma); u16: the GDN's saved input (F16K), g: float32 NCHW or F16K."""
-    if not _GDN_BWD_F16K:
-        B, C, H, W = shape
-        g32 = g if g.dtype == torch.float32 else ops.f16k_to_nchw_dev(g, B, C, H, W)
-        gx, gb, gg = gdn_backward(ops.f16k_to_nchw_dev(u16, B, C, H, W), g32, gdn.beta, gdn.gamma, gdn.inverse, gdn.beta_min)
-        return gx, None, None, gb, gg
     return ops.gdn_bwd_fused_ex(u16, _c(g), shape, gdn.beta.detach(), gdn.gamma.detach(), gdn.inverse, gdn.beta_min, want_nchw=want_nchw,
-                                want_f16k=want_f16k, want_sum=True, want_b16=want_b16 and _WGRAD_B16)
+                                want_f16k=want_f16k, want_sum=True, want_b16=want_b16)
 
 
 class GmmHeadsFn(Function):
@@ -712,7 +683,7 @@ class GmmHeadsFn(Function):
         wds = [params[2 * n].detach().contiguous() for n in range(9)]
         jobs = ([(w, m.in_channels, m.out_channels, m.transposed_conv) for w, m in zip(wds, mods)] +
                 [(w, m.out_channels, m.in_channels, not m.transposed_conv) for w, m in zip(wds, mods)])
-        packs = ops.pack_gemm_f16k_weights(jobs) if _HEADS_MULTIPACK else [ops.pack_gemm_f16k_weight(*j) for j in jobs]
+        packs = ops.pack_gemm_f16k_weights(jobs)
         ctx.wt_packs = packs[9:]
         t, inter = [x16, x16, x16], []
         for i in range(3):
@@ -763,25 +734,15 @@ class GmmHeadsFn(Function):
             if acts[2] != ops.ACT_NONE:
                 g = ops.elementwise(ops.EW_ACT_BWD, g, ys[k], s0=acts[2])
             g16.append(ops.nchw_to_f16k(g))
-            if mods[k][2].bias is not None and _WGRAD1_BIAS:     # (the bias gradient: sums of dy as the weight gradient sees it, bf16-rounded)
-                grads[6 * k + 4], grads[6 * k + 5] = wgrad(mods[k][2], t1[k], g16[k], with_bias=True)
-                continue
-            if mods[k][2].bias is not None:
-                grads[6 * k + 5] = ops.channel_sum(g)
-            grads[6 * k + 4] = wgrad(mods[k][2], t1[k], g16[k])
+            # (the bias gradient: sums of dy as the weight gradient sees it, bf16-rounded)
+            grads[6 * k + 4], grads[6 * k + 5] = wgrad(mods[k][2], t1[k], g16[k], with_bias=True)
         for level, saved in ((1, t1), (0, t0)):
             gin = dgrad(level + 1, g16, "f16k")
             g16 = []
             for k, (_, _, acts) in enumerate(stacks):
                 gm = gin[k] if acts[level] == ops.ACT_NONE else ops.f16k_act_bwd(gin[k], saved[k], slope(acts[level]))
                 g16.append(gm)
-                mod = mods[k][level]
-                if mod.bias is not None and _WGRAD1_BIAS:
-                    grads[6 * k + 2 * level], grads[6 * k + 2 * level + 1] = wgrad(mod, x16 if level == 0 else t0[k], gm, with_bias=True)
-                    continue
-                if mod.bias is not None:
-                    grads[6 * k + 2 * level + 1] = ops.f16k_channel_sum(gm, B, mod.out_channels, HW)
-                grads[6 * k + 2 * level] = wgrad(mod, x16 if level == 0 else t0[k], gm)
+                grads[6 * k + 2 * level], grads[6 * k + 2 * level + 1] = wgrad(mods[k][level], x16 if level == 0 else t0[k], gm, with_bias=True)
         gx = None
         if ctx.needs_input_grad[0]:
             parts = dgrad(0, g16, "nchw")
@@ -812,9 +773,7 @@ def gmm_heads(head, x):
     return GmmHeadsFn.apply(x, head, *params)
 
 
-_WGRAD1_BIAS = os.environ.get("MASIC_WGRAD1_BIAS", "1") != "0"          # 0: bias gradients of the head layers by a reduction pass of their own (A/B timing)
-_HEADS_MULTIPACK = os.environ.get("MASIC_HEADS_MULTIPACK", "1") != "0"     # 0: one pack launch per weight and orientation (A/B timing)
-_GMM_HEADS_FN = os.environ.get("MASIC_GMM_HEADS_FN", "1") != "0"     # 0: one ConvFn per head layer (A/B timing)
+_GMM_HEADS_FN = True     # the three head stacks as one node; tests set False for one ConvFn per head layer as their reference
 
 
 class AnalysisFn(Function):
@@ -848,15 +807,15 @@ class AnalysisFn(Function):
         grads = {}
         # The GDN backward reads its saved input (and the gradient, when an F16K kernel produced it) as F16K and writes dx twice --
         # float32 NCHW for the weight-gradient kernel, F16K for the input-gradient convolution -- plus dx's channel sums (the bias
-        # gradient): no F16K -> NCHW pass on u, no NCHW -> F16K pass and no reduction pass on dx.  MASIC_GDN_BWD_F16K=0: the separate passes.
-        gx, grads["w4"], grads["b4"] = conv_backward(convs[3], nchw(a3, ctx.sizes[2]), convs[3].weight, None, g, ops.ACT_NONE, gx_f16k=_GDN_BWD_F16K)
+        # gradient): no F16K -> NCHW pass on u, no NCHW -> F16K pass and no reduction pass on dx.
+        gx, grads["w4"], grads["b4"] = conv_backward(convs[3], nchw(a3, ctx.sizes[2]), convs[3].weight, None, g, ops.ACT_NONE, gx_f16k=True)
         for i, (u, a_in, hw, hw_in) in ((2, (u3, a2, ctx.sizes[2], ctx.sizes[1])), (1, (u2, a1, ctx.sizes[1], ctx.sizes[0]))):
             b16 = _wgrad_b16(convs[i], B, hw_in)       # the weight gradient's two operands as bf16 NCHW: half the bytes on every side of it
             gu, gu16, gsum, grads["beta%d" % (i + 1)], grads["gamma%d" % (i + 1)] = _gdn_backward_f16k(u, gx, (B, 128) + tuple(hw), gdns[i], want_b16=b16)
             gx, grads["w%d" % (i + 1)], grads["b%d" % (i + 1)] = conv_backward(convs[i], nchw(a_in, hw_in, b16), convs[i].weight, None, gu, ops.ACT_NONE,
-                                                                                g16=gu16, gb=gsum, gx_f16k=_GDN_BWD_F16K)
+                                                                                g16=gu16, gb=gsum, gx_f16k=True)
         # the first layer takes dy in F16K for both gradients (ops.pic_wgrad_f16k, the depth-to-space input gradient): no float32 NCHW dx here
-        f16k_only = _GDN_BWD_F16K and _PIC_WGRAD and _PIC_END_DGRAD and tuple(x.shape[2:]) == (2 * ctx.sizes[0][0], 2 * ctx.sizes[0][1])
+        f16k_only = tuple(x.shape[2:]) == (2 * ctx.sizes[0][0], 2 * ctx.sizes[0][1])
         gu, gu16, gsum, grads["beta1"], grads["gamma1"] = _gdn_backward_f16k(u1, gx, (B, 128) + tuple(ctx.sizes[0]), gdns[0],
                                                                              want_f16k=ctx.needs_input_grad[0] or f16k_only, want_nchw=not f16k_only)
         gimg, grads["w1"], grads["b1"] = conv_backward(convs[0], x, convs[0].weight, None, gu, ops.ACT_NONE, need_gx=ctx.needs_input_grad[0], g16=gu16, gb=gsum,
@@ -923,15 +882,14 @@ class SynthesisFn(Function):
         grads = {}
         # the last layer's weight gradient reads its saved input where it is, in F16K (ops.pic_wgrad_f16k): no float32 NCHW copy of a3
         hw3 = tuple(ctx.sizes[2])
-        f16k_only = (_GDN_BWD_F16K and _PIC_WGRAD and _PIC_END_DGRAD and tuple(convs[3].weight.shape[:2]) == (128, 3)
-                     and tuple(g.shape[2:]) == (2 * hw3[0], 2 * hw3[1]))
+        f16k_only = tuple(convs[3].weight.shape[:2]) == (128, 3) and tuple(g.shape[2:]) == (2 * hw3[0], 2 * hw3[1])
         gx, grads["w4"], grads["b4"] = conv_backward(convs[3], None if f16k_only else nchw(a3, hw3), convs[3].weight, None, g, ops.ACT_NONE,
-                                                     gx_f16k=_GDN_BWD_F16K, x16=a3, x_shape=(B, 128) + hw3)
+                                                     gx_f16k=True, x16=a3, x_shape=(B, 128) + hw3)
         for i, (u, a_in, hw, hw_in) in ((2, (u3, a2, ctx.sizes[2], ctx.sizes[1])), (1, (u2, a1, ctx.sizes[1], ctx.sizes[0]))):
             b16 = _wgrad_b16(convs[i], B, hw_in)       # the weight gradient's two operands as bf16 NCHW: half the bytes on every side of it
             gu, gu16, gsum, grads["beta%d" % (i + 1)], grads["gamma%d" % (i + 1)] = _gdn_backward_f16k(u, gx, (B, 128) + tuple(hw), gdns[i], want_b16=b16)
             gx, grads["w%d" % (i + 1)], grads["b%d" % (i + 1)] = conv_backward(convs[i], nchw(a_in, hw_in, b16), convs[i].weight, None, gu, ops.ACT_NONE,
-                                                                                g16=gu16, gb=gsum, gx_f16k=_GDN_BWD_F16K)
+                                                                                g16=gu16, gb=gsum, gx_f16k=True)
         gu, gu16, gsum, grads["beta1"], grads["gamma1"] = _gdn_backward_f16k(u1, gx, (B, 128) + tuple(ctx.sizes[0]), gdns[0])
         gy, grads["w1"], grads["b1"] = conv_backward(convs[0], y_hat, convs[0].weight, None, gu, ops.ACT_NONE, need_gx=ctx.needs_input_grad[0],
                                                      g16=gu16, gb=gsum)

@@ -32,14 +32,9 @@ static inline int masic_launch_status(const char* what) {
 __global__ static void masic_zero_kernel(unsigned* __restrict__ p, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
 }
-static inline hipError_t masic_zero_async(void* ptr, size_t bytes, hipStream_t st, int site = 0) {
+static inline hipError_t masic_zero_async(void* ptr, size_t bytes, hipStream_t st) {
     const size_t n = bytes / 4;
     if (n == 0) return hipSuccess;
-    // experiment (tools/micro/memset_graph.hip): MASIC_ZERO_MEMSET=1|2 issues the fills as hipMemsetAsync (memset nodes
-    // under capture); MASIC_ZERO_MEMSET_SITES = bit mask of the call sites that do (default all)
-    static const bool as_memset = getenv("MASIC_ZERO_MEMSET") != nullptr && (getenv("MASIC_ZERO_MEMSET")[0] == '2');
-    static const int sites = getenv("MASIC_ZERO_MEMSET_SITES") ? atoi(getenv("MASIC_ZERO_MEMSET_SITES")) : -1;
-    if (as_memset && ((sites >> site) & 1)) return hipMemsetAsync(ptr, 0, bytes, st);
     size_t nb = (n + 255) / 256;
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(masic_zero_kernel, dim3((unsigned)nb), dim3(256), 0, st, (unsigned*)ptr, n);

@@ -25,8 +25,6 @@
 //
 // Epilogue: bias + activation, then either float32 NCHW (channel view of a concat buffer, optional gate) or F16K bf16
 // for the next layer.
-#include <stdlib.h>
-
 #include "common.h"
 #include <type_traits>
 #include "conv_geom.h"
@@ -156,7 +154,6 @@ __device__ __forceinline__ void store_f16k_tile(const f32x16& t, unsigned short*
 // the same through a buffer resource: voff = byte offset of the lane's pixel in the first record + 16h, or any offset >= the resource's
 // size for a lane that has nothing to store (dropped by the range check) -- the instruction is issued unconditionally, so the number
 // of store instructions a wave has in flight is known at compile time (counted s_waitcnt vmcnt in conv_a_gdn_f16k)
-template <int AUX = 0>
 __device__ __forceinline__ void store_f16k_tile_buf(const f32x16& t, __amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned rec_stride_bytes) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -165,7 +162,7 @@ __device__ __forceinline__ void store_f16k_tile_buf(const f32x16& t, __amdgpu_bu
         const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
         const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
         v4u st = {s0[0], s1[0], s0[1], s1[1]};
-        __builtin_amdgcn_raw_buffer_store_b128(st, rs, (int)(voff + r * rec_stride_bytes), 0, AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(st, rs, (int)(voff + r * rec_stride_bytes), 0, 0);
     }
 }
 
@@ -231,9 +228,6 @@ struct F16kArgs {
     int xcd_images;               // B % 8 == 0: image b runs on XCD b % 8 (the halos of its tiles meet in one L2)
     int msplit;                   // workgroups per 128-channel co-block (4 / NM for layers whose grid would not fill the chip, else 1):
                                   //   blockIdx.y = co-block * msplit + sub-block, a sub-block = NM accumulator tiles of the slab
-    int exp_store;                // timing experiments only (MASIC_F16K_STORE_EXP; results are WRONG when set): 1 the F16K stores of the epilogue are
-                                  //   skipped at run time (the arithmetic stays), 2 a transposed layer's phases store to phase-planar positions
-                                  //   (pixel (r + oph Ho/2, c + opw Wo/2): every wave writes whole contiguous records, as if one workgroup owned both x-phases)
 };
 
 #ifndef F16K_DMA_SPREAD
@@ -802,8 +796,7 @@ __global__ __launch_bounds__(512, D == 1 ? 2 : 1) void conv_f16k(const F16kArgs 
         if (NP > 1) __builtin_amdgcn_sched_barrier(0);      // one sub-tile's epilogue at a time (register pressure)
         const int r = r0 + (wave * NP + n) * a.SR + jr, c = c0 + jc;
         const bool pok = r < g.Hp && c < g.Wp;
-        int oh = pok ? r * g.os + g.oph : 0, ow = pok ? c * g.os + g.opw : 0;
-        if (a.exp_store == 2 && g.os == 2 && pok) { oh = r + g.oph * (a.Ho >> 1); ow = c + g.opw * (a.Wo >> 1); }
+        const int oh = pok ? r * g.os + g.oph : 0, ow = pok ? c * g.os + g.opw : 0;
         const size_t opix = (size_t)oh * a.Wo + ow;
         if constexpr (GDN) {
             if (a.y16_pre != nullptr && pok) {
@@ -889,7 +882,7 @@ __global__ __launch_bounds__(512, D == 1 ? 2 : 1) void conv_f16k(const F16kArgs 
                 }
 #pragma unroll
                 for (int m = 0; m < NM; ++m)
-                    if (m0 + m * 32 < a.Cout && a.exp_store != 1) store_f16k_tile(acc[n][m], yb + (size_t)(2 * m) * op16, op16);
+                    if (m0 + m * 32 < a.Cout) store_f16k_tile(acc[n][m], yb + (size_t)(2 * m) * op16, op16);
             }
         }
     }
@@ -915,7 +908,6 @@ struct ConvAArgs {
     float out_inv_scale;
     unsigned short* y16_pre;      // also store conv + bias before the GDN (F16K), or null
     unsigned long long* stamps;   // diagnostics: s_memrealtime (100 MHz) at 6 points of every tile of workgroup 0 / wave 0, or null
-    int store_aux;                // cache policy of the output stores of the wave-private form: 0 plain, 2 nt, 16 sc1 (MASIC_CONVA_STORE_AUX)
 };
 
 #ifndef CONVA_ABLATE
@@ -1322,16 +1314,8 @@ __global__ __launch_bounds__(512, 1) void conv_a_gdn_f16k_w(const ConvAArgs a) {
             const int oh = (t / a.tiles_w) * 8 + wave, ow = (t % a.tiles_w) * 32 + j;
             const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)(a.y16 + (size_t)b * 8 * oplane * 16), 0, (int)(8 * rec_bytes), 0x00020000);
             const unsigned voff = (oh < a.Ho && ow < a.Wo) ? ((unsigned)oh * a.Wo + ow) * 32 + 16 * h : 0xC0000000u;
-            if (a.store_aux == 16) {
 #pragma unroll
-                for (int m = 0; m < 4; ++m) store_f16k_tile_buf<16>(acc[m], ry, voff + (unsigned)(2 * m) * rec_bytes, rec_bytes);
-            } else if (a.store_aux == 2) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) store_f16k_tile_buf<2>(acc[m], ry, voff + (unsigned)(2 * m) * rec_bytes, rec_bytes);
-            } else {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) store_f16k_tile_buf<0>(acc[m], ry, voff + (unsigned)(2 * m) * rec_bytes, rec_bytes);
-            }
+            for (int m = 0; m < 4; ++m) store_f16k_tile_buf(acc[m], ry, voff + (unsigned)(2 * m) * rec_bytes, rec_bytes);
         }
         if (stamp) { stamp[5] = __builtin_amdgcn_s_memrealtime(); stamp += 6; }
     }
@@ -1350,6 +1334,7 @@ struct F16kCfg {
 };
 
 constexpr int F16K_D = 3;
+constexpr int F16K_LITE_MIN_COUT = 33;      // smallest Cout that takes the lite configuration (choose_f16k)
 
 unsigned long long* g_f16k_stamps = nullptr;
 
@@ -1374,26 +1359,21 @@ F16kCfg choose_f16k(const masic_conv_desc_t& d, const ConvGeom* g, int nphase) {
     else { c.KS = 2; c.T = 2; NPI = 8; c.L = 2; }             // stride-1 walk (transposed phases, 3x3, 5x5 s1, masked): 32-channel chunks
     // strided 5x5: 5 taps per step -- 25 taps need no zero-weight padding (4 per step pad to 28: 12 % more MFMAs) and a chunk
     // takes 5 barriers instead of 7; the 20-KiB slab groups leave room for a 3-slot ring only (look-ahead 2 steps = 40 MFMAs per
-    // wave).  MASIC_F16K_T5=0 keeps 4 taps per step (A/B timing).
-    static const bool t5 = !(getenv("MASIC_F16K_T5") && getenv("MASIC_F16K_T5")[0] == '0');
-    if (!f8 && t5 && is == 2 && min_taps == 25 && max_taps == 25) { c.T = 5; c.D = 2; }
+    // wave).
+    if (!f8 && is == 2 && min_taps == 25 && max_taps == 25) { c.T = 5; c.D = 2; }
     // large stride-1-walk layers: 512- (128-channel blocks) or 1024-pixel tiles (<= 32 channels), 16-channel chunks
     if (!f8 && is == 1 && Wp >= 32) {
         const int np = d.Cout <= 32 ? 4 : 2;
         const long tiles = (long)ceil_div(Wp, 32) * ceil_div(Hp, 8 * np) * nphase * d.B * ceil_div(d.Cout, 128);
         if (tiles >= 512 && ceil_div(min_taps, 2) >= 2) { c.NP = np; c.KS = 1; c.T = 2; c.L = 2; NPI = np == 4 ? 10 : 6; }
         // 128-channel blocks: 32-channel chunks (2 taps x 2 channel blocks = 32 MFMAs per wave and barrier instead of 16), one chunk of
-        // patch look-ahead and a 3-slot ring.  MASIC_F16K_KS2=0 keeps 16-channel chunks (A/B timing).
-        static const bool ks2 = !(getenv("MASIC_F16K_KS2") && getenv("MASIC_F16K_KS2")[0] == '0');
-        if (ks2 && c.NP == 2 && d.Cin % 32 == 0) { c.KS = 2; c.D = 2; c.L = 1; NPI = 10; }
+        // patch look-ahead and a 3-slot ring.
+        if (c.NP == 2 && d.Cin % 32 == 0) { c.KS = 2; c.D = 2; c.L = 1; NPI = 10; }
         // 64 / 96 output channels (no GDN: that needs 128) (the 3x3 layers of Independent_EN and their input gradients): the K loop is short (K = 9 x
         // 32 ... 96) and the per-workgroup prologue + epilogue were 35 % of a workgroup's life (in-kernel stamps: 4.9 + 17.5 + 5.6 us
         // on the 96 -> 96 layer).  "Lite" configuration: 256-pixel tiles, 2-slot weight ring, 2 patch buffers = 77 KiB of LDS and
         // <= 128 VGPRs, so that TWO workgroups share a CU and one's prologue / epilogue / barrier waits run under the other's MFMAs.
-        // MASIC_F16K_LITE=0 keeps the 512-pixel single-workgroup form (A/B timing).
-        static const bool lite = !(getenv("MASIC_F16K_LITE") && getenv("MASIC_F16K_LITE")[0] == '0');
-        static const int lite_min = getenv("MASIC_F16K_LITE_MIN") ? atoi(getenv("MASIC_F16K_LITE_MIN")) : 33;     // smallest Cout that takes it
-        if (lite && c.NP > 1 && d.Cout >= lite_min && d.Cout <= 96 && d.Cin % 32 == 0 && ceil_div(min_taps, 2) >= 2) {
+        if (c.NP > 1 && d.Cout >= F16K_LITE_MIN_COUT && d.Cout <= 96 && d.Cin % 32 == 0 && ceil_div(min_taps, 2) >= 2) {
             c.NP = 1; c.KS = 2; c.T = 2; c.D = 1; c.L = 1; NPI = 6;
         }
     }
@@ -1431,14 +1411,12 @@ F16kCfg choose_f16k(const masic_conv_desc_t& d, const ConvGeom* g, int nphase) {
 
 // Layers whose grid leaves most of the 256 CUs idle (the 128 -> 192 layer at 64^2 -> 32^2, hyper transforms, context models:
 // 8 ... 128 workgroups): the 128-channel co-block is split over 2 or 4 workgroups of 2 / 1 accumulator tiles each.  The patch and
-// the slab DMA are repeated per workgroup (they come from L2), the MFMA work is not.  MASIC_F16K_MSPLIT=1 disables it (A/B).
+// the slab DMA are repeated per workgroup (they come from L2), the MFMA work is not.
 int f16k_msplit(const masic_conv_desc_t& d, const F16kCfg& c, int np, const ConvGeom* g, bool gdn, bool special) {
     if (d.prec == MASIC_PREC_FP8 || gdn || c.NP != 1 || special || d.Cout < 64) return 1;
-    static const int forced = getenv("MASIC_F16K_MSPLIT") ? atoi(getenv("MASIC_F16K_MSPLIT")) : 0;
     const int ntiles = ceil_div(g[0].Wp, c.TW) * ceil_div(g[0].Hp, c.TH);
     const long wgs = (long)ntiles * np * c.ncb * d.B;
-    const int ms = forced ? forced : (wgs <= 64 ? 4 : (wgs <= 160 ? 2 : 1));
-    return (ms == 2 || ms == 4) ? ms : 1;
+    return wgs <= 64 ? 4 : (wgs <= 160 ? 2 : 1);
 }
 int msplit_nm(const masic_conv_desc_t& d, const F16kCfg& c, int np, const ConvGeom* g) { return 4 / f16k_msplit(d, c, np, g, false, false); }
 
@@ -1462,7 +1440,6 @@ extern "C" int masic_conv_f16k_kernel_name(const masic_conv_desc_t* d, int gdn, 
     const int nm = (d->Cout <= 32 && !gdn) ? 1 : 4;
     if (d->prec == MASIC_PREC_FP8) snprintf(buf, n, "conv_f16k<%d, %d, %d, %d, %d, %s, 4, 1, true>", c.KS, c.T, F16K_D, c.KS == 1 ? 6 : 4, c.L, gdn ? "true" : "false");
     else if (c.D == 1) snprintf(buf, n, "conv_f16k<2, 2, 1, 3, 1, false, %d, 1, false>", d->Cout <= 32 ? 1 : (d->Cout <= 64 ? 2 : 3));
-    else if (c.NP == 2 && c.KS == 2 && !gdn && d->Cout <= 96) snprintf(buf, n, "conv_f16k<2, 2, 2, 5, 1, false, %d, 2, false>", d->Cout <= 64 ? 2 : 3);
     else if (c.NP == 2 && c.KS == 2) snprintf(buf, n, "conv_f16k<2, 2, 2, 5, 1, %s, 4, 2, false>", gdn ? "true" : "false");
     else if (c.NP > 1) snprintf(buf, n, "conv_f16k<1, 2, %d, %d, 2, %s, %d, %d, false>", F16K_D, c.NP == 4 ? 5 : 3, gdn ? "true" : "false", nm, c.NP);
     else if (c.KS == 1) snprintf(buf, n, "conv_f16k<1, %d, %d, 6, 1, %s, %d, 1, false>", c.T, c.D, gdn ? "true" : "false", gdn ? 4 : msplit_nm(*d, c, np, g));
@@ -1712,8 +1689,6 @@ int f16k_launch(const void* x_f16k, const void* w_packed, const float* bias, con
                {c.stream_bytes[0], c.stream_bytes[1], c.stream_bytes[2], c.stream_bytes[3]}, geom_params(*d), np, d->B % 8 == 0, 1};
     const int msplit = f16k_msplit(*d, c, np, g, gdn_packed != nullptr, d2s != 0 || cout_store != 0 || y_f8k != nullptr);
     a.msplit = msplit;
-    static const int exp_store = getenv("MASIC_F16K_STORE_EXP") ? atoi(getenv("MASIC_F16K_STORE_EXP")) : 0;
-    a.exp_store = exp_store;
     dim3 grid(round_up(ntiles, 8) * np, c.ncb * msplit, d->B);
     hipStream_t st = (hipStream_t)stream;
 #define F16K_LAUNCH_D(KSV, TV, DV, PSPV, LV, GDNV, NMV, NPV)                                                                   \
@@ -1751,9 +1726,8 @@ int f16k_launch(const void* x_f16k, const void* w_packed, const float* bias, con
         F16K_LAUNCH(1, 2, 5, 2, false, 1, 4);
     } else if (c.NP == 2) {
         if (c.KS == 2) {
+            // (64 / 96 output channels never get here: choose_f16k gives them the lite configuration)
             if (gdn_packed) F16K_LAUNCH_D(2, 2, 2, 5, 1, true, 4, 2);
-            else if (d->Cout <= 64) F16K_LAUNCH_D(2, 2, 2, 5, 1, false, 2, 2);       // 64 / 96 output channels (Independent_EN): 2 / 3 accumulator
-            else if (d->Cout <= 96) F16K_LAUNCH_D(2, 2, 2, 5, 1, false, 3, 2);       // tiles per pixel sub-tile instead of 4 with idle MFMAs
             else F16K_LAUNCH_D(2, 2, 2, 5, 1, false, 4, 2);
         } else if (gdn_packed) F16K_LAUNCH(1, 2, 3, 2, true, 4, 2);
         else F16K_LAUNCH(1, 2, 3, 2, false, 4, 2);
@@ -1827,8 +1801,7 @@ int conv_a_launch(const float* x, const void* w_packed, const float* bias, const
     const int Ho = (Hi + 4 - 5) / 2 + 1, Wo = (Wi + 4 - 5) / 2 + 1;
     const int tiles_w = ceil_div(Wo, 32), tiles_per_img = tiles_w * ceil_div(Ho, 8), ntiles = tiles_per_img * B;
     ConvAArgs a{x, (const uint4*)w_packed, bias, (const uint4*)gdn_packed, (unsigned short*)y_f16k, gdn_inverse, Hi, Wi, in_ctot, in_coff,
-                Ho, Wo, tiles_w, tiles_per_img, ntiles, (unsigned char*)y_f8k, out_inv_scale, (unsigned short*)y_pre, g_f16k_stamps,
-                getenv("MASIC_CONVA_STORE_AUX") ? atoi(getenv("MASIC_CONVA_STORE_AUX")) : 0};
+                Ho, Wo, tiles_w, tiles_per_img, ntiles, (unsigned char*)y_f8k, out_inv_scale, (unsigned short*)y_pre, g_f16k_stamps};
     const size_t lds_bytes = 65536 + CA_WIMG_BYTES + 1024 + 2 * CA_PATCH_BYTES;
     const dim3 grid(ntiles < 256 ? ntiles : 256);
 #define CONV_A_LAUNCH(X3V, OUTV)                                                                                                   \
@@ -1843,8 +1816,8 @@ int conv_a_launch(const float* x, const void* w_packed, const float* bias, const
     } while (0)
     const bool x3 = (gdn_inverse & 2) != 0;
     const int out = y_f8k != nullptr ? 1 : (y_pre != nullptr ? 2 : 0);
-    static const bool priv_on = !(getenv("MASIC_CONVA_PRIV") && getenv("MASIC_CONVA_PRIV")[0] == '0');      // 0: the shared-patch kernel (A/B timing)
-    if (priv_on && gdn_packed != nullptr && !x3 && out == 0 && Wi % 4 == 0 && ((size_t)x & 15) == 0 && ((size_t)Hi * Wi) % 4 == 0) {
+    // the wave-private kernel where it applies; the shared-patch kernel for the rest (no GDN, x3, fp8 or pre-GDN outputs, unaligned input)
+    if (gdn_packed != nullptr && !x3 && out == 0 && Wi % 4 == 0 && ((size_t)x & 15) == 0 && ((size_t)Hi * Wi) % 4 == 0) {
         static bool attr_w = false;
         if (!attr_w) {
             (void)hipFuncSetAttribute((const void*)conv_a_gdn_f16k_w, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2366,47 +2339,39 @@ extern "C" int masic_gemm_f16k_group_fwd(const masic_gemm_group_t* groups, int n
         ga.cb_end[i] = ncb;
     }
     ga.n = ngroups;
-    dim3 grid(ceil_div(HW, 256), ncb, B);
-    // bf16 operands: 32-channel chunks, 72 KiB of LDS -- two workgroups per CU, or one next to a workgroup of another stream's kernel.
-    // The 64-channel form (144 KiB, a CU to itself) is as fast when the launch has the chip to itself, but inside the three-stream
-    // forward it shuts the other streams' kernels out of its CUs: 2.54 -> 2.41 ms per step at 8 x 512 x 512 with KC = 2 everywhere
-    // (A/B on one box, 100 replays each, twice).  fp8 operands: 128-channel chunks only.  MASIC_GEMM_KC = 4 restores the old rule
-    // (64-channel chunks when the grid is a whole number of 256-workgroup rounds).
-    const long blocks = (long)grid.x * grid.y * grid.z;
-    static const int forced = getenv("MASIC_GEMM_KC") ? atoi(getenv("MASIC_GEMM_KC")) : 0;
-    const bool kc2 = !f8 && (forced != 4 || blocks % 256 != 0 || blocks < 256);
+    bool f8_out = false;
+    for (int i = 0; i < ngroups; ++i) f8_out = f8_out || groups[i].y_f8k != nullptr;
+    // bf16 operands, no fp8 output: gemm_f16k2 (64-channel chunks).  Otherwise gemm_f16k: bf16 operands in 32-channel chunks, 72 KiB of
+    // LDS -- two workgroups per CU, or one next to a workgroup of another stream's kernel.  (The 64-channel form, 144 KiB, a CU to itself,
+    // was as fast when the launch had the chip to itself, but inside the three-stream forward it shut the other streams' kernels out of
+    // its CUs: 2.54 -> 2.41 ms per step at 8 x 512 x 512 with KC = 2 everywhere, A/B on one box, 100 replays each, twice.)  fp8
+    // operands: 128-channel chunks only.
+    const int kc = f8 ? 4 : (f8_out ? 2 : G2_KC);
     for (int i = 0; i < ngroups; ++i) {
         const masic_gemm_group_t& g = groups[i];
         const int cin_b = g.Cin / cblk, nkb = round_up(cin_b, 4);
         ga.g[i] = GemmF16kArgs{(const unsigned short*)g.x, (const unsigned short*)g.w_packed, g.bias, (unsigned short*)g.y_f16k, g.y_nchw,
-                               cin_b, nkb / (kc2 ? 2 : 4), g.Cout, HW, g.out_ctot, g.out_coff, g.act, g.wscale, (unsigned char*)g.y_f8k, g.out_inv_scale};
+                               cin_b, nkb / kc, g.Cout, HW, g.out_ctot, g.out_coff, g.act, g.wscale, (unsigned char*)g.y_f8k, g.out_inv_scale};
+    }
+    if (!f8 && !f8_out) {
+        const int npx = ceil_div(HW, 256), tiles_per_img = npx * ncb;
+        static bool attr2 = false;
+        if (!attr2) {
+            (void)hipFuncSetAttribute((const void*)gemm_f16k2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            attr2 = true;
+        }
+        hipLaunchKernelGGL(gemm_f16k2, dim3(B >= 8 ? 8 * tiles_per_img * ceil_div(B, 8) : B * tiles_per_img), dim3(256), G2_NS * G2_STAGE, (hipStream_t)stream, ga, B, npx, tiles_per_img);
+        return masic_launch_status("gemm_f16k_fwd");
     }
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_f16k<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)gemm_f16k<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)gemm_f16k<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    static const bool v2 = !(getenv("MASIC_GEMM_V2") && getenv("MASIC_GEMM_V2")[0] == '0');      // 0: gemm_f16k (A/B timing)
-    if (!f8 && v2) {
-        bool ok = true;
-        for (int i = 0; i < ngroups; ++i) ok = ok && groups[i].y_f8k == nullptr;
-        if (ok) {
-            for (int i = 0; i < ngroups; ++i) ga.g[i].nchunks = round_up(groups[i].Cin / 16, 4) / G2_KC;
-            const int npx = ceil_div(HW, 256), tiles_per_img = npx * ncb;
-            static bool attr2 = false;
-            if (!attr2) {
-                (void)hipFuncSetAttribute((const void*)gemm_f16k2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr2 = true;
-            }
-            hipLaunchKernelGGL(gemm_f16k2, dim3(B >= 8 ? 8 * tiles_per_img * ceil_div(B, 8) : B * tiles_per_img), dim3(256), G2_NS * G2_STAGE, (hipStream_t)stream, ga, B, npx, tiles_per_img);
-            return masic_launch_status("gemm_f16k_fwd");
-        }
-    }
+    const dim3 grid(ceil_div(HW, 256), ncb, B);
     if (f8) hipLaunchKernelGGL((gemm_f16k<4, true>), grid, dim3(512), 3 * 4 * 12288, (hipStream_t)stream, ga);
-    else if (kc2) hipLaunchKernelGGL(gemm_f16k<2>, grid, dim3(512), 3 * 2 * 12288, (hipStream_t)stream, ga);
-    else hipLaunchKernelGGL(gemm_f16k<4>, grid, dim3(512), 3 * 4 * 12288, (hipStream_t)stream, ga);
+    else hipLaunchKernelGGL(gemm_f16k<2>, grid, dim3(512), 3 * 2 * 12288, (hipStream_t)stream, ga);
     return masic_launch_status("gemm_f16k_fwd");
 }
 

@@ -808,8 +808,7 @@ namespace {
 constexpr int SMALL_WGS = 512;       // workgroups of conv_wgrad_small_s1 (two per CU), each with one partial of 150 floats in the workspace
 // the 5x5 stride-1 layers with 3 / 6 channels on either side (pre_conv, after_conv) take conv_wgrad_small_s1
 bool small_path(const masic_conv_desc_t* d) {
-    static const bool on = [] { const char* e = getenv("MASIC_WGRAD_SMALL"); return e == nullptr || e[0] != '0'; }();
-    if (!on || d->stride != 1 || d->KH != 5 || d->KW != 5 || d->pad != 2 || d->Wi % 4 != 0 || d->Hi != d->Ho || d->Wi != d->Wo) return false;
+    if (d->stride != 1 || d->KH != 5 || d->KW != 5 || d->pad != 2 || d->Wi % 4 != 0 || d->Hi != d->Ho || d->Wi != d->Wo) return false;
     const int CA = d->transposed ? d->Cin : d->Cout, CQ = d->transposed ? d->Cout : d->Cin;
     return (CQ == 6 || CQ == 3) && CA <= 8;
 }
@@ -892,14 +891,14 @@ int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, co
         int nsplit = ceil_div(512, base);
         if (nsplit > g.ntk) nsplit = g.ntk;
         g.nsplit = nsplit < 1 ? 1 : nsplit;
-        if (masic_zero_async(dw, wbytes, st, 0) != hipSuccess) {
+        if (masic_zero_async(dw, wbytes, st) != hipSuccess) {
             masic_set_error("conv2d_wgrad: memset failed");
             return MASIC_ERR_LAUNCH;
         }
         hipLaunchKernelGGL(conv_wgrad_1x1_bf16, dim3(base, 1, g.nsplit), dim3(256), 0, st, g);
         return masic_launch_status("conv2d_wgrad");
     }
-    if (!workspace_clean && masic_zero_async(workspace, wbytes, st, 1) != hipSuccess) {
+    if (!workspace_clean && masic_zero_async(workspace, wbytes, st) != hipSuccess) {
         masic_set_error("conv2d_wgrad: workspace memset failed");
         return MASIC_ERR_LAUNCH;
     }

@@ -27,8 +27,6 @@
 //         records through v_permlane32_swap) next to -- or instead of -- the float32 NCHW tensor the weight gradient reads,
 //   and the per-channel sums of dx (the bias gradient of the convolution in front of the GDN) ride along: per-lane float32
 //   sums over the workgroup's tiles, reduced across lanes and waves once at the end, one more row of the partial slot.
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace {
@@ -76,7 +74,6 @@ struct GdnBwdArgs {
     float* part;                 // [GB_NBLK][GB_SLOT]
     long long npix;              // B * HW
     int HW, ntiles, inverse, want_sum;
-    int dbg;                     // timing-only ablations (MASIC_GDNB_DBG): 1 no stores, 2 no third contraction, 4 no loads, 8 no first two contractions
 };
 
 __device__ __forceinline__ unsigned gb_pack2bf(float lo, float hi) {
@@ -143,8 +140,8 @@ __global__ __launch_bounds__(256, 1) void gdn_bwd_c128(const GdnBwdArgs a) {
         const size_t base16 = ((size_t)b * 8 * hw + pix) * 16 + 4 * h;       // F16K: record 0 of the pixel, + 4h elements
         const size_t rs16 = (size_t)hw * 16;
         f32x16 xv[4], gv[4];
-        if constexpr (X16) gb_load_f16k(xv, a.x16 + base16, rs16, ok && !(a.dbg & 4));
-        if constexpr (G16) gb_load_f16k(gv, a.g16 + base16, rs16, ok && !(a.dbg & 4));
+        if constexpr (X16) gb_load_f16k(xv, a.x16 + base16, rs16, ok);
+        if constexpr (G16) gb_load_f16k(gv, a.g16 + base16, rs16, ok);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -178,7 +175,7 @@ __global__ __launch_bounds__(256, 1) void gdn_bwd_c128(const GdnBwdArgs a) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const gbf16x8 ga = __builtin_bit_cast(gbf16x8, *reinterpret_cast<const uint4*>(gi0 + (m * 8 + s) * 1024));
-                if (!(a.dbg & 8)) nv[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga, bq, nv[m], 0, 0, 0);
+                nv[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga, bq, nv[m], 0, 0, 0);
             }
         }
         // ---- s (kept in nv) and t (kept in gv)
@@ -207,7 +204,7 @@ __global__ __launch_bounds__(256, 1) void gdn_bwd_c128(const GdnBwdArgs a) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const gbf16x8 ga = __builtin_bit_cast(gbf16x8, *reinterpret_cast<const uint4*>(gi1 + (m * 8 + s) * 1024));
-                if (!(a.dbg & 8)) uv[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga, bq, uv[m], 0, 0, 0);
+                uv[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga, bq, uv[m], 0, 0, 0);
             }
         }
         // ---- dx = s + 2 x u (kept in uv); rows past the end contribute zeros (x = g = 0 there)
@@ -218,14 +215,14 @@ __global__ __launch_bounds__(256, 1) void gdn_bwd_c128(const GdnBwdArgs a) {
                 uv[m][e] = fmaf(2.0f * xv[m][e], uv[m][e], nv[m][e]);
                 dsum[m][e] += uv[m][e];
             }
-        if (ok && a.gx != nullptr && !(a.dbg & 1)) {
+        if (ok && a.gx != nullptr) {
             float* op = a.gx + base;
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) op[(unsigned)(32 * m + (e & 3) + 8 * (e >> 2)) * hw] = uv[m][e];
         }
-        if (ok && a.gxb != nullptr && !(a.dbg & 1)) {
+        if (ok && a.gxb != nullptr) {
             unsigned short* ob = a.gxb + base;
 #pragma unroll
             for (int m = 0; m < 4; ++m)
@@ -250,14 +247,13 @@ __global__ __launch_bounds__(256, 1) void gdn_bwd_c128(const GdnBwdArgs a) {
                     const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
                     uint4 st;
                     st.x = s0[0]; st.y = s1[0]; st.z = s0[1]; st.w = s1[1];
-                    if (ok && !(a.dbg & 1)) *reinterpret_cast<uint4*>(rec + (size_t)(2 * m + r) * rs16) = st;
+                    if (ok) *reinterpret_cast<uint4*>(rec + (size_t)(2 * m + r) * rs16) = st;
                 }
         }
         __syncthreads();                                           // both tiles complete
         // ---- d gamma^[32w + .][.] += t x^2^T over the 128 pixels, d beta^ with B = ones
         const unsigned char* ta = tl + (32 * w + j) * GB_TP + 16 * h;
         const unsigned char* xb = xl + j * GB_TP + 16 * h;
-        if (!(a.dbg & 2))
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             const gbf16x8 af = __builtin_bit_cast(gbf16x8, *reinterpret_cast<const uint4*>(ta + 32 * ks));
@@ -303,7 +299,7 @@ __global__ __launch_bounds__(256, 1) void gdn_bwd_c128(const GdnBwdArgs a) {
 
 // ------------------------------------------------------------------------------------------ eight-wave form (F16K operands)
 // The four-wave kernel above holds 400 registers per lane -- one wave per SIMD -- and is bound by that single wave's instruction
-// issue: with no loads, no stores and no MFMAs at all it still takes 60 % of its time (tools/bench_gdn_bwd.py: MASIC_GDNB_DBG=15),
+// issue: with no loads, no stores and no MFMAs at all it still took 60 % of its time (measured with those parts ablated),
 // a quarter of it 2-byte LDS stores of the [channel][pixel] tiles.  Here a workgroup is 8 waves = 4 pixel groups x 2 channel halves
 // (two waves per SIMD, 64 channels of 32 pixels per wave: half the registers), and ONE pair of LDS tiles serves all three
 // contractions: x^2 and t are written as F16K-like records [16-channel block s][pixel][16] (16 bytes per lane and k-step: the 8
@@ -331,8 +327,8 @@ __device__ __forceinline__ void g8_barrier() {       // LDS traffic of this wave
     __builtin_amdgcn_s_barrier();
 }
 
-// NML: 32-channel blocks per wave -- 2: eight waves (4 pixel groups x 2 channel halves), 1: sixteen waves (x 4 channel quarters, four
-// waves per SIMD at <= 128 registers)
+// NML: 32-channel blocks per wave -- 2: eight waves (4 pixel groups x 2 channel halves), the only instance (a sixteen-wave NML = 1 was
+// measured and retired)
 template <int NML>
 __global__ __launch_bounds__(1024 / NML, 1) void gdn_bwd_c128_wn(const GdnBwdArgs a) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
@@ -387,7 +383,7 @@ __global__ __launch_bounds__(1024 / NML, 1) void gdn_bwd_c128_wn(const GdnBwdArg
             for (int q = 0; q < 4; ++q) {
                 const size_t ro = (size_t)(2 * (m0 + ml) + (q >> 1)) * rs16 + 8 * (q & 1);
                 uint2 rx = make_uint2(0u, 0u), rg = make_uint2(0u, 0u);
-                if (ok && !(a.dbg & 4)) { rx = *reinterpret_cast<const uint2*>(xr + ro); rg = *reinterpret_cast<const uint2*>(gr + ro); }
+                if (ok) { rx = *reinterpret_cast<const uint2*>(xr + ro); rg = *reinterpret_cast<const uint2*>(gr + ro); }
                 xv[ml][4 * q + 0] = __builtin_bit_cast(float, rx.x << 16);
                 xv[ml][4 * q + 1] = __builtin_bit_cast(float, rx.x & 0xffff0000u);
                 xv[ml][4 * q + 2] = __builtin_bit_cast(float, rx.y << 16);
@@ -464,14 +460,14 @@ __global__ __launch_bounds__(1024 / NML, 1) void gdn_bwd_c128_wn(const GdnBwdArg
                 uv[ml][e] = fmaf(2.0f * xv[ml][e], uv[ml][e], nv[ml][e]);
                 dsum[ml][e] += uv[ml][e];
             }
-        if (ok && a.gx != nullptr && !(a.dbg & 1)) {
+        if (ok && a.gx != nullptr) {
             float* op = a.gx + base;
 #pragma unroll
             for (int ml = 0; ml < NML; ++ml)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) op[(unsigned)(32 * (m0 + ml) + (e & 3) + 8 * (e >> 2)) * hw] = uv[ml][e];
         }
-        if (ok && a.gxb != nullptr && !(a.dbg & 1)) {
+        if (ok && a.gxb != nullptr) {
             unsigned short* ob = a.gxb + base;
 #pragma unroll
             for (int ml = 0; ml < NML; ++ml)
@@ -493,11 +489,10 @@ __global__ __launch_bounds__(1024 / NML, 1) void gdn_bwd_c128_wn(const GdnBwdArg
                     const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
                     uint4 st;
                     st.x = s0[0]; st.y = s1[0]; st.z = s0[1]; st.w = s1[1];
-                    if (ok && !(a.dbg & 1)) *reinterpret_cast<uint4*>(rec + (size_t)(2 * (m0 + ml) + r) * rs16) = st;
+                    if (ok) *reinterpret_cast<uint4*>(rec + (size_t)(2 * (m0 + ml) + r) * rs16) = st;
                 }
         }
         // ---- d gamma^ block (rows: t block pg, columns: x^2 blocks m0 .. m0 + NML - 1) over the 128 pixels; d beta^ with B = ones
-        if (!(a.dbg & 2))
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             g8v2u af[2], bf[NML][2];
@@ -617,12 +612,10 @@ extern "C" int masic_gdn_bwd_fused_ex2(const float* x, const void* x_f16k, const
     a.x16 = (const unsigned short*)x_f16k; a.g16 = (const unsigned short*)g_f16k; a.gx16 = (unsigned short*)gx_f16k; a.gxb = (unsigned short*)gx_bf16;
     a.HW = H * W; a.npix = (long long)B * H * W; a.inverse = inverse; a.want_sum = g_sum != nullptr;
     a.ntiles = (int)((a.npix + 127) / 128);
-    { const char* e = getenv("MASIC_GDNB_DBG"); a.dbg = e ? atoi(e) : 0; }
     const int nblk = a.ntiles < GB_NBLK ? a.ntiles : GB_NBLK;
     static bool attr_set = false;
     if (!attr_set) {
-        const void* fns[4] = {(const void*)gdn_bwd_c128<false, false>, (const void*)gdn_bwd_c128<true, false>, (const void*)gdn_bwd_c128<false, true>,
-                              (const void*)gdn_bwd_c128<true, true>};
+        const void* fns[3] = {(const void*)gdn_bwd_c128<false, false>, (const void*)gdn_bwd_c128<true, false>, (const void*)gdn_bwd_c128<false, true>};
         for (const void* fn : fns)
             if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS) != hipSuccess) {
                 masic_set_error("gdn_bwd_fused: cannot reserve %d bytes of LDS", GB_LDS);
@@ -630,22 +623,17 @@ extern "C" int masic_gdn_bwd_fused_ex2(const float* x, const void* x_f16k, const
             }
         attr_set = true;
     }
-    static const bool w8 = [] { const char* e = getenv("MASIC_GDNB_W8"); return e == nullptr || e[0] != '0'; }();
-    if (x_f16k && g_f16k && w8) {
+    if (x_f16k && g_f16k) {
         static bool attr8 = false;
         if (!attr8) {
-            if (hipFuncSetAttribute((const void*)gdn_bwd_c128_wn<1>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) != hipSuccess ||
-                hipFuncSetAttribute((const void*)gdn_bwd_c128_wn<2>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) != hipSuccess) {
+            if (hipFuncSetAttribute((const void*)gdn_bwd_c128_wn<2>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) != hipSuccess) {
                 masic_set_error("gdn_bwd_fused: cannot reserve %d bytes of LDS", G8_LDS);
                 return MASIC_ERR_LAUNCH;
             }
             attr8 = true;
         }
-        static const int waves = getenv("MASIC_GDNB_WAVES") ? atoi(getenv("MASIC_GDNB_WAVES")) : 8;
-        if (waves == 16) hipLaunchKernelGGL(gdn_bwd_c128_wn<1>, dim3(nblk), dim3(1024), G8_LDS, st, a);
-        else hipLaunchKernelGGL(gdn_bwd_c128_wn<2>, dim3(nblk), dim3(512), G8_LDS, st, a);
-    } else if (x_f16k && g_f16k) hipLaunchKernelGGL((gdn_bwd_c128<true, true>), dim3(nblk), dim3(256), GB_LDS, st, a);
-    else if (x_f16k) hipLaunchKernelGGL((gdn_bwd_c128<true, false>), dim3(nblk), dim3(256), GB_LDS, st, a);
+        hipLaunchKernelGGL(gdn_bwd_c128_wn<2>, dim3(nblk), dim3(512), G8_LDS, st, a);
+    } else if (x_f16k) hipLaunchKernelGGL((gdn_bwd_c128<true, false>), dim3(nblk), dim3(256), GB_LDS, st, a);
     else if (g_f16k) hipLaunchKernelGGL((gdn_bwd_c128<false, true>), dim3(nblk), dim3(256), GB_LDS, st, a);
     else hipLaunchKernelGGL((gdn_bwd_c128<false, false>), dim3(nblk), dim3(256), GB_LDS, st, a);
     hipLaunchKernelGGL(gdn_bwd_reduce_kernel, dim3((128 * 128 + 128 + (g_sum ? 128 : 0)) / 32), dim3(256), 0, st, (const float*)part, nblk,

@@ -21,8 +21,6 @@
 // (mod 256) apart so that the two 16-lane groups of a half wave never share a bank.  Workgroups take a strided share of the
 // tiles and add their partial dW into a [tap][co][ci] workspace with float atomics (ci contiguous: full 128-byte segments);
 // a last pass transposes it into the weight layout.
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace {
@@ -611,7 +609,7 @@ extern "C" int masic_conv3x3_wgrad_f16k_ws(const void* x_f16k, const void* dy_f1
                   "conv3x3_wgrad_f16k: needs Cin, Cout multiples of 32");
     MASIC_REQUIRE((long)B * (Cin > Cout ? Cin : Cout) * H * W * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "conv3x3_wgrad_f16k: tensor too large for 32-bit offsets");
     hipStream_t st = (hipStream_t)stream;
-    if (!workspace_clean && masic_zero_async(workspace, masic_conv3x3_wgrad_f16k_workspace_bytes(Cin, Cout), st, 2) != hipSuccess) {
+    if (!workspace_clean && masic_zero_async(workspace, masic_conv3x3_wgrad_f16k_workspace_bytes(Cin, Cout), st) != hipSuccess) {
         masic_set_error("conv3x3_wgrad_f16k: workspace memset failed");
         return MASIC_ERR_LAUNCH;
     }
@@ -664,7 +662,7 @@ extern "C" int masic_conv5x5_wgrad_f16k_ws(const void* x_f16k, const void* dy_f1
                   "conv5x5_wgrad_f16k: needs Cin, Cout multiples of 32");
     MASIC_REQUIRE((long)B * (Cin > Cout ? Cin : Cout) * H * W * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "conv5x5_wgrad_f16k: tensor too large for 32-bit offsets");
     hipStream_t st = (hipStream_t)stream;
-    if (!workspace_clean && masic_zero_async(workspace, masic_conv5x5_wgrad_f16k_workspace_bytes(Cin, Cout), st, 3) != hipSuccess) {
+    if (!workspace_clean && masic_zero_async(workspace, masic_conv5x5_wgrad_f16k_workspace_bytes(Cin, Cout), st) != hipSuccess) {
         masic_set_error("conv5x5_wgrad_f16k: workspace memset failed");
         return MASIC_ERR_LAUNCH;
     }
@@ -732,7 +730,7 @@ extern "C" int masic_gemm_wgrad_bias_f16k(const void* rows_f16k, const void* col
     MASIC_REQUIRE((long)B * (CA > CQ ? CA : CQ) * HW * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "gemm_wgrad_f16k: tensor too large for 32-bit offsets");
     hipStream_t st = (hipStream_t)stream;
     const size_t nb = bias_of == 1 ? CA : (bias_of == 2 ? CQ : 0);
-    if (masic_zero_async(dw, ((size_t)CA * CQ + nb) * sizeof(float), st, 4) != hipSuccess) {
+    if (masic_zero_async(dw, ((size_t)CA * CQ + nb) * sizeof(float), st) != hipSuccess) {
         masic_set_error("gemm_wgrad_f16k: zero fill failed");
         return MASIC_ERR_LAUNCH;
     }
@@ -742,9 +740,9 @@ extern "C" int masic_gemm_wgrad_bias_f16k(const void* rows_f16k, const void* col
     const int base = ceil_div(CA, 128) * a.q_tiles;
     // pixel splits: as many as keep the grid within ONE round of the 256 CUs -- every split adds a full output tile of float atomics
     // (64 KiB per workgroup, ~13 us at the chip's atomic rate), which outweighs a second co-resident workgroup: 55 us per layer at
-    // 540 workgroups, 40 at 216 (1152 x 768 x 8192; MASIC_WGRAD1_WGS overrides the 256 for A/B timing)
-    static const int target = getenv("MASIC_WGRAD1_WGS") ? atoi(getenv("MASIC_WGRAD1_WGS")) : 256;
-    int nsplit = target / base;
+    // 540 workgroups, 40 at 216 (1152 x 768 x 8192)
+    constexpr int target_wgs = 256;
+    int nsplit = target_wgs / base;
     if (nsplit > a.ntk) nsplit = a.ntk;
     a.nsplit = nsplit < 1 ? 1 : nsplit;
     static bool attr_set = false;

@@ -18,7 +18,6 @@ from ._lib import PREC_BF16, PREC_F32, PREC_FP8
 
 _PRECISION = {"f32": PREC_F32, "bf16": PREC_BF16, "fp8": PREC_BF16}[os.environ.get("MASIC_PRECISION", "f32")]
 _FP8 = os.environ.get("MASIC_PRECISION", "f32") == "fp8"
-_C3_RESIDENT = os.environ.get("MASIC_C3_RESIDENT", "1") != "0"
 
 
 def set_precision(name):
@@ -272,8 +271,8 @@ class _PackedWeightMixin:
 
     def resident_supported(self, B, Hi, Wi):
         """Conv2d(Cin -> 32 | 64, k3, s1, p1), Cin <= Cout, at W % 32 == 0 and H % 16 (8) == 0: the resident-weight kernel
-        (MASIC_C3_RESIDENT=0: conv_f16k, A/B timing)."""
-        return (_C3_RESIDENT and not self.transposed_conv and not self.masked_conv and self._geometry() == (3, 3, 1, 1)
+        (conv_f16k otherwise)."""
+        return (not self.transposed_conv and not self.masked_conv and self._geometry() == (3, 3, 1, 1)
                 and ops.conv3x3_resident_supported(B, self.in_channels, self.out_channels, Hi, Wi))
 
     def few_supported(self, B, Hi, Wi):

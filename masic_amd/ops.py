@@ -788,9 +788,6 @@ def entropy_bottleneck_auxloss_bwd(table, quantiles, gout, tail_mass=1e-9):
     return g_q
 
 
-_WARP_BWD_GATHER = _os.environ.get("MASIC_WARP_BWD_GATHER", "1") != "0"      # 0: the scatter form (float atomics) always (A/B timing)
-
-
 def warp_perspective_bwd(g_dst, minv_norm, src_shape, want_flag=False):
     """d loss / d src of warp_perspective.  Default: the gather form (masic_warp_perspective_bwd_gather: no atomics, reproducible, no zero
     fill), which falls back to the scatter form on the device when the homography is outside its bounds; want_flag: also return the int32
@@ -798,7 +795,7 @@ def warp_perspective_bwd(g_dst, minv_norm, src_shape, want_flag=False):
     _dev(g_dst); _dev(minv_norm)
     B, C, Hs, Ws = src_shape
     Hd, Wd = g_dst.shape[-2:]
-    if _WARP_BWD_GATHER and min(Hs, Ws, Hd, Wd) > 1:
+    if min(Hs, Ws, Hd, Wd) > 1:
         g_src = torch.empty(src_shape, dtype=torch.float32, device=g_dst.device)
         flag = torch.empty(1, dtype=torch.int32, device=g_dst.device).fill_(0)
         check(lib.masic_warp_perspective_bwd_gather(_p(g_dst), _p(minv_norm), _p(g_src), _p(flag), B, C, Hs, Ws, Hd, Wd, _stream()),
@@ -859,7 +856,7 @@ def pack_conv_f16k_weight(weight, desc, persistent=False):
     registered with StreamPacks below and refreshed together with all the other registered packs in ONE launch when the parameters
     change (a training step), instead of one launch per layer and orientation."""
     _dev(weight, "weight")
-    if persistent and _PACK_MULTI:
+    if persistent:
         return _stream_packs(weight.device).get(weight, desc)
     nbytes = _desc_query("masic_conv_f16k_packed_bytes", desc)
     if nbytes == 0:
@@ -869,7 +866,6 @@ def pack_conv_f16k_weight(weight, desc, persistent=False):
     return packed
 
 
-_PACK_MULTI = _os.environ.get("MASIC_PACK_MULTI", "1") != "0"      # 0: one pack launch per weight and orientation (A/B timing)
 _DESC_KEY = ("B", "Cin", "Hi", "Wi", "in_ctot", "Cout", "KH", "KW", "stride", "pad", "transposed", "masked", "prec")
 
 

@@ -2,7 +2,6 @@
 (coremasic/mywork/newtrain_codec_real.py:135-146): zero_grad x2 -> forward -> RD loss -> backward -> Adam step ->
 aux loss -> backward -> aux Adam step.  Optimizers are torch's (plumbing); every tensor op of forward and backward
 is a HIP launch.  With a GradientAllReducer the main-loss gradients are averaged across ranks before the step."""
-import os
 
 import torch
 
@@ -26,7 +25,7 @@ def _step(optimizer):
     optimizer.step()
 
 
-_AUX_FUSED = os.environ.get("MASIC_AUX_FUSED", "1") != "0"      # 0: model.aux_loss().backward() through autograd (A/B timing)
+_AUX_FUSED = True      # the auxiliary loss's backward in one pass; tests set False for model.aux_loss().backward() as their reference
 
 
 def aux_backward(model):

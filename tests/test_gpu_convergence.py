@@ -77,7 +77,7 @@ def test_first_training_steps_from_default_init_match_the_oracle_loop():
     # With the side streams of HSIC._forward_graph the float atomics of the weight gradients land in another order from run to run --
     # gradients agree to 5e-7 (test_two_stream_training_forward_is_the_one_stream_computation) -- and Adam, whose first update is
     # lr * sign(g) for every element, turns the sign of the few elements with |g| below that noise into +-2 lr: the losses then agree to
-    # 1e-7 on steps 1-2, 1e-6 on step 3 and 1e-4 on step 5 (measured, tools/scratch/first_steps_var.py), which says nothing about parity.
+    # 1e-7 on steps 1-2, 1e-6 on step 3 and 1e-4 on step 5 (measured, tools/scratch/first_steps_var.py at commit 4b3b61b), which says nothing about parity.
     prev_streams, MASIC._TRAIN_STREAMS = MASIC._TRAIN_STREAMS, False
     try:
         for it in range(5):

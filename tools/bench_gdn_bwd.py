@@ -1,5 +1,5 @@
-"""Times the fused GDN backward (masic_gdn_bwd_fused_ex2) at the three resolutions of a transform, with the timing-only ablations of
-MASIC_GDNB_DBG (1 no stores, 2 no third contraction, 4 no loads, 8 no first two contractions):  python tools/bench_gdn_bwd.py"""
+"""Times the fused GDN backward (masic_gdn_bwd_fused_ex2) on F16K operands at the three resolutions of a transform:
+python tools/bench_gdn_bwd.py"""
 import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -2,7 +2,7 @@
 """The 1x1 layers of the entropy-parameter heads (reference MASIC.py:330-468) as launched by the forward: layer i of the three stacks of
 a head in ONE grouped launch (masic_gemm_f16k_group_fwd).  Checks every grouped launch against float32 matmuls on bf16-rounded
 operands, and prints the algorithmic bytes / FLOPs of each launch; device times come from a kernel trace of this script
-(tools/scratch/prof.sh tools/bench_heads_gemm.py, or rocprofv3 --kernel-trace --stats).  MASIC_GEMM_V2=0 selects the round-2 kernel."""
+(rocprofv3 --kernel-trace --stats)."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
