@@ -636,6 +636,25 @@ int masic_rans_decoder_decode_indexes(void* handle, const int32_t* indexes, int 
                                       const int32_t* cdf_sizes, const int32_t* offsets, int ncdfs, int32_t* symbols);
 void masic_rans_decoder_close(void* handle);
 
+/* ------------------------------------------------------------------------------------------
+ * SSIM / MS-SSIM (masic_amd/csrc/ssim.hip): pytorch-msssim 0.2.1's `ssim` / `ms_ssim` as the reference drivers call them
+ * (coremasic/mywork/test3_real.py:102-103, newtrain_cqe_real.py:93-94).  X, Y: float32 [N][C][H][W] device tensors.
+ * taps: the 11 normalised Gaussian taps (host memory, computed by the caller); weights: the `levels` level weights (host; MS-SSIM only);
+ * C1 = (K1 * data_range)^2, C2 = (K2 * data_range)^2.  SSIM is levels = 1 without MASIC_SSIM_MS.  Every level must be >= 11 x 11.
+ * ws (masic_ssim_workspace_bytes(..., 0) bytes): written by masic_ssim_fwd (the pooled pyramid and per-tile partial sums) and
+ * masic_ssim_finish (per-plane statistics), read by masic_ssim_bwd -- keep it from the forward to the backward.
+ * bws (masic_ssim_workspace_bytes(..., 1) bytes): backward scratch.  out: [N] per-image values, or [1] with MASIC_SSIM_SIZE_AVERAGE.
+ * gout: the gradient of out (same shape).  dX / dY (either nullable, not both): written, not accumulated.
+ * No atomics: results are bit-reproducible.  No fills, no host synchronisation: capturable into a HIP graph.
+ * Launches: masic_ssim_fwd `levels`, masic_ssim_finish 1, masic_ssim_bwd levels + 1.  0 bytes from the size query: bad shape. */
+enum { MASIC_SSIM_MS = 1, MASIC_SSIM_SIZE_AVERAGE = 2, MASIC_SSIM_NONNEG = 4 /* relu on the SSIM value (ssim's nonnegative_ssim) */ };
+size_t masic_ssim_workspace_bytes(int N, int C, int H, int W, int levels, int backward);
+int masic_ssim_fwd(const float* X, const float* Y, int N, int C, int H, int W, int levels, const float* taps, float C1, float C2,
+                   void* ws, void* stream);
+int masic_ssim_finish(void* ws, int N, int C, int H, int W, int levels, const float* weights, int flags, float* out, void* stream);
+int masic_ssim_bwd(const float* X, const float* Y, const float* gout, int N, int C, int H, int W, int levels, const float* taps,
+                   const float* weights, float C1, float C2, int flags, const void* ws, void* bws, float* dX, float* dY, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

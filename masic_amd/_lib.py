@@ -15,6 +15,7 @@ EB_PARAMS_PER_CHANNEL = 58
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SOFTMAX_C = 0, 1, 2, 3
 INOP_NONE, INOP_ABS, INOP_ROUND = 0, 1, 2
 PREC_F32, PREC_BF16, PREC_FP8 = 0, 1, 2
+SSIM_MS, SSIM_SIZE_AVERAGE, SSIM_NONNEG = 1, 2, 4
 
 
 class ConvDesc(ctypes.Structure):
@@ -184,6 +185,11 @@ SIGNATURES = {
     "masic_entropy_bottleneck_aux_step": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P]),
     "masic_warp_perspective_bwd": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
     "masic_warp_perspective_bwd_gather": (c_int, [_P, _P, _P, _P] + [c_int] * 6 + [_P]),
+    # SSIM / MS-SSIM
+    "masic_ssim_workspace_bytes": (c_size_t, [c_int] * 6),
+    "masic_ssim_fwd": (c_int, [_P, _P] + [c_int] * 5 + [_P, c_float, c_float, _P, _P]),
+    "masic_ssim_finish": (c_int, [_P] + [c_int] * 5 + [_P, c_int, _P, _P]),
+    "masic_ssim_bwd": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P, _P, c_float, c_float, c_int, _P, _P, _P, _P, _P]),
 }
 
 

@@ -1595,3 +1595,43 @@ def conv3x3_wgrad_f16k(x16, dy16, B, Cin, Cout, H, W):
         _drop_workspace(x16.device, n)
         raise
     return dw
+
+
+# ------------------------------------------------------------------------------------------ SSIM / MS-SSIM (masic_amd/ssim.py)
+def _f32_array(values, n):
+    return (ctypes.c_float * n)(*[float(v) for v in values])
+
+
+def ssim_fwd(X, Y, taps, weights, C1, C2, flags):
+    """Per-image SSIM (weights None) or MS-SSIM of X, Y [N, C, H, W]: returns (out, ws).  out: float32 [N], or [] with
+    SSIM_SIZE_AVERAGE in flags; ws: the workspace the backward reads (pooled pyramid, per-plane statistics)."""
+    _dev(X, "X")
+    _dev(Y, "Y")
+    N, C, H, W = X.shape
+    levels = 1 if weights is None else len(weights)
+    nbytes = lib.masic_ssim_workspace_bytes(N, C, H, W, levels, 0)
+    if nbytes == 0:
+        raise RuntimeError(f"masic_amd.ssim_fwd: unsupported shape {tuple(X.shape)} with {levels} levels: {lib.masic_last_error().decode()}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    out = torch.empty(() if flags & _lib.SSIM_SIZE_AVERAGE else (N,), dtype=torch.float32, device=X.device)
+    w = None if weights is None else _f32_array(weights, levels)
+    st = _stream()
+    check(lib.masic_ssim_fwd(_p(X), _p(Y), N, C, H, W, levels, _f32_array(taps, 11), float(C1), float(C2), _p(ws), st), "ssim_fwd")
+    check(lib.masic_ssim_finish(_p(ws), N, C, H, W, levels, w, int(flags), _p(out), st), "ssim_finish")
+    return out, ws
+
+
+def ssim_bwd(X, Y, ws, gout, taps, weights, C1, C2, flags, need_x=True, need_y=False):
+    """(dX, dY) of ssim_fwd's output for the upstream gradient gout (its shape); the one not needed is None."""
+    _dev(X, "X")
+    _dev(Y, "Y")
+    gout = _dev(gout.to(torch.float32).contiguous(), "grad")
+    N, C, H, W = X.shape
+    levels = 1 if weights is None else len(weights)
+    bws = torch.empty(lib.masic_ssim_workspace_bytes(N, C, H, W, levels, 1), dtype=torch.uint8, device=X.device)
+    dX = torch.empty_like(X) if need_x else None
+    dY = torch.empty_like(Y) if need_y else None
+    w = None if weights is None else _f32_array(weights, levels)
+    check(lib.masic_ssim_bwd(_p(X), _p(Y), _p(gout), N, C, H, W, levels, _f32_array(taps, 11), w, float(C1), float(C2), int(flags),
+                             _p(ws), _p(bws), _p(dX), _p(dY), _stream()), "ssim_bwd")
+    return dX, dY
