@@ -655,6 +655,42 @@ int masic_ssim_finish(void* ws, int N, int C, int H, int W, int levels, const fl
 int masic_ssim_bwd(const float* X, const float* Y, const float* gout, int N, int C, int H, int W, int levels, const float* taps,
                    const float* weights, float C1, float C2, int flags, const void* ws, void* bws, float* dX, float* dY, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Deterministic mode (masic_amd/determinism.py).  Siblings of the weight-gradient and warp-backward entry points
+ * above with the same arguments and the same results up to summation order, but NO float atomics: each pixel split stores its partial
+ * tile with plain stores into its own slab of `workspace` ([split][...], indexed by split number), and a finishing launch sums the slabs
+ * in ascending split order in float32.  The split count depends only on the shape (and is capped so that one layer's slabs stay within
+ * 64 MiB).  The result is therefore bitwise reproducible: the same inputs on the same device model and library build give the same
+ * bits, whatever else runs concurrently.  `workspace` (at least the matching _det_workspace_bytes; for a weight gradient a whole
+ * multiple of the weight's float32 size) has contents irrelevant on entry and on exit: no fill is needed and none is left behind.  A
+ * weight gradient makes as many launches as the default call with a clean workspace.  The library keeps no mode of its own: the caller
+ * picks the entry point.  0 from a size query: bad shape. */
+size_t masic_conv2d_wgrad_det_workspace_bytes(const masic_conv_desc_t* d);
+/* as masic_conv2d_wgrad / masic_conv2d_wgrad_ws */
+int masic_conv2d_wgrad_det(const float* x, const float* dy, float* dw, void* workspace, const masic_conv_desc_t* d, void* stream);
+/* as masic_conv2d_wgrad_bf16in (only layers masic_conv2d_wgrad_bf16in_supported); workspace: masic_conv2d_wgrad_det_workspace_bytes(d) */
+int masic_conv2d_wgrad_bf16in_det(const void* x_bf16, const void* dy_bf16, float* dw, void* workspace, const masic_conv_desc_t* d,
+                                  void* stream);
+/* as masic_conv3x3_wgrad_f16k / masic_conv5x5_wgrad_f16k_ws */
+size_t masic_conv3x3_wgrad_f16k_det_workspace_bytes(int B, int Cin, int Cout, int H, int W);
+int masic_conv3x3_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
+                                 int B, int Cin, int Cout, int H, int W, void* stream);
+size_t masic_conv5x5_wgrad_f16k_det_workspace_bytes(int B, int Cin, int Cout, int H, int W);
+int masic_conv5x5_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
+                                 int B, int Cin, int Cout, int H, int W, void* stream);
+/* as masic_gemm_wgrad_bias_f16k (dw: CA*CQ weights, then the nb bias sums); the bias sums come from per-split, per-workgroup slots of the
+ * same workspace, summed in a fixed order by the same finishing launch */
+size_t masic_gemm_wgrad_bias_f16k_det_workspace_bytes(int bias_of, int B, int CA, int CQ, int HW);
+int masic_gemm_wgrad_bias_f16k_det(const void* rows_f16k, const void* cols_f16k, float* dw, void* workspace, int bias_of, int B, int CA,
+                                   int CQ, int HW, void* stream);
+/* as masic_warp_perspective_bwd_gather, but where the gather form raises *flag the fallback is a deterministic store-and-sum (entries
+ * grouped by source pixel with integer counting atomics, each group summed in destination-pixel order) instead of the float-atomic
+ * scatter; it covers every homography, a horizon inside the picture included.  The flag is still tested on the device.  workspace:
+ * masic_warp_perspective_bwd_gather_det_workspace_bytes, int32 counters and entries. */
+size_t masic_warp_perspective_bwd_gather_det_workspace_bytes(int B, int Hs, int Ws, int Hd, int Wd);
+int masic_warp_perspective_bwd_gather_det(const float* g_dst, const float* minv_norm, float* g_src, int* flag, void* workspace,
+                                          int B, int C, int Hs, int Ws, int Hd, int Wd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,18 @@ SIGNATURES = {
     "masic_entropy_bottleneck_aux_step": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P]),
     "masic_warp_perspective_bwd": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
     "masic_warp_perspective_bwd_gather": (c_int, [_P, _P, _P, _P] + [c_int] * 6 + [_P]),
+    # deterministic mode: per-split slabs, no float atomics
+    "masic_conv2d_wgrad_det_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
+    "masic_conv2d_wgrad_det": (c_int, [_P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),
+    "masic_conv2d_wgrad_bf16in_det": (c_int, [_P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),
+    "masic_conv3x3_wgrad_f16k_det_workspace_bytes": (c_size_t, [c_int] * 5),
+    "masic_conv3x3_wgrad_f16k_det": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "masic_conv5x5_wgrad_f16k_det_workspace_bytes": (c_size_t, [c_int] * 5),
+    "masic_conv5x5_wgrad_f16k_det": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "masic_gemm_wgrad_bias_f16k_det_workspace_bytes": (c_size_t, [c_int] * 5),
+    "masic_gemm_wgrad_bias_f16k_det": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "masic_warp_perspective_bwd_gather_det_workspace_bytes": (c_size_t, [c_int] * 5),
+    "masic_warp_perspective_bwd_gather_det": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 6 + [_P]),
     # SSIM / MS-SSIM
     "masic_ssim_workspace_bytes": (c_size_t, [c_int] * 6),
     "masic_ssim_fwd": (c_int, [_P, _P] + [c_int] * 5 + [_P, c_float, c_float, _P, _P]),

@@ -770,6 +770,120 @@ __global__ __launch_bounds__(256) void warp_bwd_if_kernel(const float* __restric
     }
 }
 
+// ---- the deterministic fallback (masic_warp_perspective_bwd_gather_det): store and sum instead of the scatter, every launch gated by *flag.
+// Each destination pixel p stores its (up to) four entries e = 4 p + tap, grouped by source pixel by a counting sort: cnt[q] (integer
+// atomics: totals do not depend on order) -> exclusive scan off[q] -> entries at off[q] + (integer cursor); each source pixel then sorts
+// its group by destination index (the cursor's order is arrival order) and sums g[p] w(p, q) over the group in that order -- the order
+// of the gather form.  Covers every homography, the horizon inside the picture included.  Slow (it runs only for extreme ones).
+// The weights are recomputed from p with exactly the forward's float operations.
+struct WarpTap {
+    int q;          // source pixel (in the picture) or -1
+    float vx, vy;
+};
+__device__ __forceinline__ WarpTap warp_tap(const float* m, int pix, int k, int Hs, int Ws, int Hd, int Wd, int align_corners) {
+    WarpTap r{-1, 0.0f, 0.0f};
+    const int oy = pix / Wd, ox = pix - oy * Wd;
+    const float gx = __fmul_rn(__fsub_rn(__fdiv_rn((float)ox, (float)(Wd - 1)), 0.5f), 2.0f);
+    const float gy = __fmul_rn(__fsub_rn(__fdiv_rn((float)oy, (float)(Hd - 1)), 0.5f), 2.0f);
+    const float X = __fadd_rn(__fadd_rn(__fmul_rn(gx, m[0]), __fmul_rn(gy, m[1])), m[2]);
+    const float Y = __fadd_rn(__fadd_rn(__fmul_rn(gx, m[3]), __fmul_rn(gy, m[4])), m[5]);
+    const float Z = __fadd_rn(__fadd_rn(__fmul_rn(gx, m[6]), __fmul_rn(gy, m[7])), m[8]);
+    const float scale = fabsf(Z) > 1e-8f ? __fdiv_rn(1.0f, __fadd_rn(Z, 1e-8f)) : 1.0f;
+    const float fx = masic_grid_unnormalize(__fmul_rn(X, scale), Ws, align_corners);
+    const float fy = masic_grid_unnormalize(__fmul_rn(Y, scale), Hs, align_corners);
+    if (!(fx == fx) || !(fy == fy)) return r;
+    const float x0f = floorf(fx), y0f = floorf(fy);
+    const float wx = fx - x0f, wy = fy - y0f;
+    const float lim = 1.0e9f;
+    const int x0 = (int)fminf(fmaxf(x0f, -lim), lim), y0 = (int)fminf(fmaxf(y0f, -lim), lim);
+    const int xs = x0 + (k & 1), ys = y0 + (k >> 1);
+    if (xs < 0 || xs >= Ws || ys < 0 || ys >= Hs) return r;
+    r.q = ys * Ws + xs;
+    r.vx = (k & 1) ? wx : 1.0f - wx;
+    r.vy = (k >> 1) ? wy : 1.0f - wy;
+    return r;
+}
+__global__ __launch_bounds__(256) void warp_det_zero_if(int* __restrict__ cnt, size_t n, const int* __restrict__ flag) {
+    if (*flag == 0) return;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) cnt[i] = 0;
+}
+__global__ __launch_bounds__(256) void warp_det_count_if(const float* __restrict__ minv, int* __restrict__ cnt, int Hs, int Ws, int Hd, int Wd,
+                                                         int align_corners, const int* __restrict__ flag) {
+    if (*flag == 0) return;
+    const int b = blockIdx.y, pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= Hd * Wd) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const WarpTap t = warp_tap(minv + b * 9, pix, k, Hs, Ws, Hd, Wd, align_corners);
+        if (t.q >= 0) atomicAdd(cnt + (size_t)b * Hs * Ws + t.q, 1);
+    }
+}
+// one workgroup per image: off = exclusive scan of cnt; cnt is reset to 0 (the fill's cursors)
+__global__ __launch_bounds__(1024) void warp_det_scan_if(int* __restrict__ cnt, int* __restrict__ off, int n, const int* __restrict__ flag) {
+    if (*flag == 0) return;
+    __shared__ int part[1024];
+    int* c = cnt + (size_t)blockIdx.x * n;
+    int* o = off + (size_t)blockIdx.x * n;
+    const int per = (n + 1023) / 1024, lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += c[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {                 // inclusive scan of the 1024 chunk sums
+        const int v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - s;
+    for (int i = lo; i < hi; ++i) {
+        const int v = c[i];
+        o[i] = run;
+        run += v;
+        c[i] = 0;
+    }
+}
+__global__ __launch_bounds__(256) void warp_det_fill_if(const float* __restrict__ minv, int* __restrict__ cur, const int* __restrict__ off,
+                                                        int* __restrict__ ent, int Hs, int Ws, int Hd, int Wd, int align_corners,
+                                                        const int* __restrict__ flag) {
+    if (*flag == 0) return;
+    const int b = blockIdx.y, pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= Hd * Wd) return;
+    const size_t sb = (size_t)b * Hs * Ws;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const WarpTap t = warp_tap(minv + b * 9, pix, k, Hs, Ws, Hd, Wd, align_corners);
+        if (t.q >= 0) ent[(size_t)b * 4 * Hd * Wd + off[sb + t.q] + atomicAdd(cur + sb + t.q, 1)] = 4 * pix + k;
+    }
+}
+__global__ __launch_bounds__(256) void warp_det_sum_if(const float* __restrict__ g_dst, const float* __restrict__ minv, float* __restrict__ g_src,
+                                                       const int* __restrict__ cnt, const int* __restrict__ off, int* __restrict__ ent,
+                                                       int C, int Hs, int Ws, int Hd, int Wd, int align_corners, const int* __restrict__ flag) {
+    if (*flag == 0) return;
+    const int b = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Hs * Ws) return;
+    const size_t splane = (size_t)Hs * Ws, dplane = (size_t)Hd * Wd;
+    const int n = cnt[b * splane + q];
+    int* e = ent + (size_t)b * 4 * dplane + off[b * splane + q];
+    for (int i = 1; i < n; ++i) {                        // the group in destination order (entries are distinct: one per (p, tap))
+        const int v = e[i];
+        int j = i - 1;
+        for (; j >= 0 && e[j] > v; --j) e[j + 1] = e[j];
+        e[j + 1] = v;
+    }
+    const float* gb = g_dst + (size_t)b * C * dplane;
+    float* sb = g_src + (size_t)b * C * splane + q;
+    for (int c = 0; c < C; ++c) {
+        float acc = 0.0f;
+        for (int i = 0; i < n; ++i) {
+            const int pix = e[i] >> 2;
+            const WarpTap t = warp_tap(minv + b * 9, pix, e[i] & 3, Hs, Ws, Hd, Wd, align_corners);
+            acc += gb[(size_t)c * dplane + pix] * t.vx * t.vy;
+        }
+        sb[(size_t)c * splane] = acc;
+    }
+}
+
 }  // namespace
 
 extern "C" int masic_elementwise(const float* a, const float* b, float* y, size_t n, int op, float s0, float s1, void* stream) {
@@ -960,6 +1074,35 @@ extern "C" int masic_warp_perspective_bwd_gather(const float* g_dst, const float
     hipLaunchKernelGGL(zero_if_kernel, dim3(grid_for(n)), dim3(256), 0, st, g_src, n, (const int*)flag);
     hipLaunchKernelGGL(warp_bwd_if_kernel, dim3(ceil_div(Hd * Wd, 256), B), dim3(256), 0, st, g_dst, minv_norm, g_src, C, Hs, Ws, Hd, Wd, ac, (const int*)flag);
     return masic_launch_status("warp_perspective_bwd_gather");
+}
+
+// The deterministic sibling: the same gather form, and where it raises *flag the store-and-sum fallback above instead of the scatter.
+// workspace: masic_warp_perspective_bwd_gather_det_workspace_bytes, contents irrelevant on entry and exit.
+extern "C" size_t masic_warp_perspective_bwd_gather_det_workspace_bytes(int B, int Hs, int Ws, int Hd, int Wd) {
+    if (B <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return 0;
+    return ((size_t)2 * B * Hs * Ws + (size_t)4 * B * Hd * Wd) * sizeof(int);
+}
+
+extern "C" int masic_warp_perspective_bwd_gather_det(const float* g_dst, const float* minv_norm, float* g_src, int* flag, void* workspace,
+                                                     int B, int C, int Hs, int Ws, int Hd, int Wd, void* stream) {
+    MASIC_REQUIRE(g_dst && minv_norm && g_src && flag && workspace, MASIC_ERR_ARG, "warp_perspective_bwd_gather_det: null pointer");
+    MASIC_REQUIRE(B > 0 && C > 0 && Hs > 1 && Ws > 1 && Hd > 1 && Wd > 1, MASIC_ERR_SHAPE, "warp_perspective_bwd_gather_det: sizes");
+    MASIC_REQUIRE((long)4 * Hd * Wd < (1l << 31) && (long)Hs * Ws < (1l << 31), MASIC_ERR_UNSUPPORTED, "warp_perspective_bwd_gather_det: picture too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int ac = masic_warp_align_corners_value();
+    int* cnt = (int*)workspace;
+    int* off = cnt + (size_t)B * Hs * Ws;
+    int* ent = off + (size_t)B * Hs * Ws;
+    hipLaunchKernelGGL(warp_bwd_gather_kernel, dim3(ceil_div(Hs * Ws, 256), B), dim3(256), 0, st, g_dst, minv_norm, g_src, flag, C, Hs, Ws, Hd, Wd, ac);
+    const size_t ns = (size_t)B * Hs * Ws;
+    hipLaunchKernelGGL(warp_det_zero_if, dim3(grid_for(ns)), dim3(256), 0, st, cnt, ns, (const int*)flag);
+    hipLaunchKernelGGL(warp_det_count_if, dim3(ceil_div(Hd * Wd, 256), B), dim3(256), 0, st, minv_norm, cnt, Hs, Ws, Hd, Wd, ac, (const int*)flag);
+    hipLaunchKernelGGL(warp_det_scan_if, dim3(B), dim3(1024), 0, st, cnt, off, Hs * Ws, (const int*)flag);
+    hipLaunchKernelGGL(warp_det_fill_if, dim3(ceil_div(Hd * Wd, 256), B), dim3(256), 0, st, minv_norm, cnt, (const int*)off, ent, Hs, Ws, Hd, Wd, ac,
+                       (const int*)flag);
+    hipLaunchKernelGGL(warp_det_sum_if, dim3(ceil_div(Hs * Ws, 256), B), dim3(256), 0, st, g_dst, minv_norm, g_src, (const int*)cnt, (const int*)off, ent,
+                       C, Hs, Ws, Hd, Wd, ac, (const int*)flag);
+    return masic_launch_status("warp_perspective_bwd_gather_det");
 }
 
 extern "C" int masic_warp_perspective_bwd(const float* g_dst, const float* minv_norm, float* g_src,

@@ -57,7 +57,9 @@ __device__ __forceinline__ wbf16x8 frag8(const float* p, int st) {
 // BF16: operands rounded to bf16 while they are read from the (float32) LDS tiles, v_mfma_f32_32x32x16_bf16 with
 // k = 16 consecutive pixels of a row (lane half h takes pixels 8h .. 8h+7), float32 accumulate -- the training step of the
 // bf16-operand mode; the float32 form (k = a pixel pair, exact products) is the parity path.
-template <int QT, int TPW, bool BF16>
+// DET (the deterministic mode, masic_conv2d_wgrad_det): no atomics -- the workgroups of pixel split z store their partial tiles into
+// slab z of the workspace ([nsplit][tap][a][q]) and the finishing pass sums the slabs in split order (wgrad_slab_transpose_kernel)
+template <int QT, int TPW, bool BF16, bool DET = false>
 __global__ __launch_bounds__(512) void conv_wgrad_f32(const WgradArgs a) {
 
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -223,11 +225,14 @@ __global__ __launch_bounds__(512) void conv_wgrad_f32(const WgradArgs a) {
 #pragma unroll
         for (int k = 0; k < TPW; ++k) {
             if (t_lo + k >= t_hi) continue;
-            float* wsk = a.ws + (size_t)(t_lo + k) * a.CA * a.CQ;
+            float* wsk = a.ws + (size_t)(t_lo + k) * a.CA * a.CQ + (DET ? (size_t)blockIdx.z * T * a.CA * a.CQ : 0);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int ai = a0 + wa * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (ai < a.CA) atomicAdd(wsk + (size_t)ai * a.CQ + q, acc[k][e]);
+                if (ai < a.CA) {
+                    if constexpr (DET) wsk[(size_t)ai * a.CQ + q] = acc[k][e];
+                    else atomicAdd(wsk + (size_t)ai * a.CQ + q, acc[k][e]);
+                }
             }
         }
     }
@@ -238,7 +243,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_f32(const WgradArgs a) {
 // B operand enumerate (tap, q) pairs -- column n = t*CQ + q, T*CQ columns in all -- so a 5x5 kernel over 3 channels is
 // 75 columns = 3 MFMA column tiles instead of 25.  Wave = (which 32 a-channels, column-tile group); everything else
 // (pixel tiles, DMA double buffering, odd channel pitch, atomic reduction into [tap][a][q]) as above.
-template <int TPW, bool BF16>
+template <int TPW, bool BF16, bool DET = false>
 __global__ __launch_bounds__(512) void conv_wgrad_packed_f32(const WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int buf_sz = 64 * PS + a.CQ * a.QS;
@@ -394,7 +399,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_packed_f32(const WgradArgs a) 
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int ai = a0 + wa * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (ai < a.CA) atomicAdd(a.ws + (size_t)colidx[k] + (size_t)ai * a.CQ, acc[k][e]);
+            if (ai < a.CA) {
+                if constexpr (DET) a.ws[(size_t)blockIdx.z * T * a.CA * a.CQ + (size_t)colidx[k] + (size_t)ai * a.CQ] = acc[k][e];
+                else atomicAdd(a.ws + (size_t)colidx[k] + (size_t)ai * a.CQ, acc[k][e]);
+            }
         }
     }
 }
@@ -412,6 +420,8 @@ struct Wgrad1x1Args {
 
 constexpr int W1_PITCH = 144;
 
+// DET: split z stores its partial blocks into slab z ([nsplit][CA][CQ], at a.dw = the workspace); the finishing pass sums the slabs
+template <bool DET = false>
 __global__ __launch_bounds__(256) void conv_wgrad_1x1_bf16(const Wgrad1x1Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 128 * W1_PITCH];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -481,7 +491,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_1x1_bf16(const Wgrad1x1Args a)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int ai = a0 + 64 * wa + 32 * mi + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (ai < a.CA) atomicAdd(a.dw + (size_t)ai * a.CQ + q, acc[mi][ni][e]);
+                if (ai < a.CA) {
+                    if constexpr (DET) a.dw[(size_t)blockIdx.z * a.CA * a.CQ + (size_t)ai * a.CQ + q] = acc[mi][ni][e];
+                    else atomicAdd(a.dw + (size_t)ai * a.CQ + q, acc[mi][ni][e]);
+                }
             }
         }
 }
@@ -506,7 +519,8 @@ constexpr int W5_LDS = 64 * W5_PP + 32 * W5_QP;
 // IN16: P and Q are bf16 NCHW tensors (masic_conv2d_wgrad_bf16in: the GDN backward writes dx that way, the saved F16K activation is
 // converted that way) -- 8-byte loads of 4 pixels instead of 16-byte ones, no conversion on the way into LDS, half the L2 -> CU stream
 // that bounds this kernel
-template <bool IN16>
+// DET: split `split` stores into slab `split` ([nsplit][25][CA][CQ]); summed by wgrad_slab_transpose_kernel
+template <bool IN16, bool DET = false>
 __global__ __launch_bounds__(512) void conv_wgrad_k5s2_bf16(const WgradArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[W5_LDS];
     unsigned char* const pl = lds;
@@ -642,13 +656,16 @@ __global__ __launch_bounds__(512) void conv_wgrad_k5s2_bf16(const WgradArgs a) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     const int kw = EVEN ? 2 * t : 2 * t + 1;
-                    float* wsk = a.ws + (size_t)((kh_first + kk) * 5 + kw) * a.CA * a.CQ;
+                    float* wsk = a.ws + (size_t)((kh_first + kk) * 5 + kw) * a.CA * a.CQ + (DET ? (size_t)split * 25 * a.CA * a.CQ : 0);
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
                         for (int e = 0; e < 16; ++e) {
                             const int ai = a0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-                            if (ai < a.CA) atomicAdd(wsk + (size_t)ai * a.CQ + q, acc[(kk * NT + t) * 2 + i][e]);
+                            if (ai < a.CA) {
+                                if constexpr (DET) wsk[(size_t)ai * a.CQ + q] = acc[(kk * NT + t) * 2 + i][e];
+                                else atomicAdd(wsk + (size_t)ai * a.CQ + q, acc[(kk * NT + t) * 2 + i][e]);
+                            }
                         }
                 }
         }
@@ -802,6 +819,30 @@ __global__ __launch_bounds__(256) void wgrad_transpose_kernel(float* __restrict_
     }
 }
 
+
+// deterministic finishing pass: slabs [nsplit][T][AQ] -> dw [AQ][T], dw = slab 0 + slab 1 + ... in split order (float32); T = 1: the plain
+// sum of [nsplit][AQ] slabs.  Threads walk the slab layout (coalesced reads) and keep 8 slab loads in flight; the adds stay in split order.
+// Slab contents are left as they are (the deterministic workspace is irrelevant on entry and exit).
+__global__ __launch_bounds__(256) void wgrad_slab_transpose_kernel(const float* __restrict__ ws, float* __restrict__ dw, int T, int AQ, int nsplit) {
+    const size_t total = (size_t)T * AQ;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int t = (int)(i / AQ);
+        const size_t aq = i - (size_t)t * AQ;
+        const float* src = ws + i;
+        float s = 0.0f;
+        int z = 0;
+        for (; z + 8 <= nsplit; z += 8) {
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = src[(size_t)(z + k) * total];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += v[k];
+        }
+        for (; z < nsplit; ++z) s += src[(size_t)z * total];
+        dw[aq * T + t] = s;
+    }
+}
+
 }  // namespace
 
 namespace {
@@ -829,10 +870,30 @@ extern "C" int masic_conv2d_wgrad(const float* x, const float* dy, float* dw, vo
 // workspace_clean != 0: `workspace` holds zeros on entry (a persistent buffer: zeroed once by its owner) and holds zeros again when the
 // call's last kernel has run -- no fill launch per weight gradient (a training step computes ~80 of them; a launch costs the device
 // ~10 us whatever it does).  0: contents unknown, zeroed here, left dirty (the behaviour of masic_conv2d_wgrad).
-namespace { int wgrad_launch(const void* x, const void* dy, float* dw, void* workspace, const masic_conv_desc_t* d, int workspace_clean, int in16, void* stream); }
+namespace {
+int wgrad_launch(const void* x, const void* dy, float* dw, void* workspace, const masic_conv_desc_t* d, int workspace_clean, int in16, void* stream,
+                 int det = 0, size_t* det_bytes = nullptr);
+}
 extern "C" int masic_conv2d_wgrad_ws(const float* x, const float* dy, float* dw, void* workspace,
                                      const masic_conv_desc_t* d, int workspace_clean, void* stream) {
     return wgrad_launch(x, dy, dw, workspace, d, workspace_clean, 0, stream);
+}
+
+// the deterministic mode (include/masic_hip.h): per-split partial slabs, no float atomics, bitwise reproducible
+extern "C" size_t masic_conv2d_wgrad_det_workspace_bytes(const masic_conv_desc_t* d) {
+    size_t bytes = 0;
+    if (!d || wgrad_launch(nullptr, nullptr, nullptr, nullptr, d, 0, 0, nullptr, 1, &bytes) != MASIC_OK) return 0;
+    return bytes;
+}
+
+extern "C" int masic_conv2d_wgrad_det(const float* x, const float* dy, float* dw, void* workspace, const masic_conv_desc_t* d, void* stream) {
+    return wgrad_launch(x, dy, dw, workspace, d, 0, 0, stream, 1);
+}
+
+extern "C" int masic_conv2d_wgrad_bf16in_det(const void* x_bf16, const void* dy_bf16, float* dw, void* workspace, const masic_conv_desc_t* d,
+                                             void* stream) {
+    MASIC_REQUIRE(masic_conv2d_wgrad_bf16in_supported(d), MASIC_ERR_UNSUPPORTED, "conv2d_wgrad_bf16in_det: not a 5x5 stride-2 layer of the bf16 mode");
+    return wgrad_launch(x_bf16, dy_bf16, dw, workspace, d, 0, 1, stream, 1);
 }
 
 // 1 if masic_conv2d_wgrad_bf16in takes this layer: the 5x5 stride-2 layers of the analysis / synthesis / hyper transforms in bf16 mode
@@ -852,10 +913,20 @@ extern "C" int masic_conv2d_wgrad_bf16in(const void* x_bf16, const void* dy_bf16
 }
 
 namespace {
-int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, const masic_conv_desc_t* d, int workspace_clean, int in16, void* stream) {
+// slab count cap of the deterministic mode: one layer's slabs stay within 64 MiB
+constexpr size_t DET_SLAB_BYTES = (size_t)64 << 20;
+int det_cap(size_t wbytes) {
+    const size_t c = DET_SLAB_BYTES / wbytes;
+    return c < 1 ? 1 : (c > (1 << 20) ? (1 << 20) : (int)c);
+}
+
+// det: the deterministic form (slabs of the workspace, no fill, no atomics); det_bytes != null: only report the deterministic workspace
+// size through it, launch nothing (the pointers may then be null)
+int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, const masic_conv_desc_t* d, int workspace_clean, int in16, void* stream,
+                 int det, size_t* det_bytes) {
     const float* x = (const float*)xv;
     const float* dy = (const float*)dyv;
-    MASIC_REQUIRE(x && dy && dw && workspace && d, MASIC_ERR_ARG, "conv2d_wgrad: null pointer");
+    MASIC_REQUIRE(d && (det_bytes || (x && dy && dw && workspace)), MASIC_ERR_ARG, "conv2d_wgrad: null pointer");
     MASIC_REQUIRE(d->KH * d->KW == 1 || d->KH * d->KW <= 28, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: kernel %dx%d", d->KH, d->KW);
     MASIC_REQUIRE(d->stride == 1 || d->stride == 2, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: stride %d", d->stride);
     MASIC_REQUIRE(d->in_coff >= 0 && d->in_coff + d->Cin <= d->in_ctot, MASIC_ERR_SHAPE, "conv2d_wgrad: input view out of range");
@@ -891,14 +962,24 @@ int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, co
         int nsplit = ceil_div(512, base);
         if (nsplit > g.ntk) nsplit = g.ntk;
         g.nsplit = nsplit < 1 ? 1 : nsplit;
+        if (det) {
+            if (g.nsplit > det_cap(wbytes)) g.nsplit = det_cap(wbytes);
+            if (det_bytes) { *det_bytes = (size_t)g.nsplit * wbytes; return MASIC_OK; }
+            g.dw = (float*)workspace;
+            hipLaunchKernelGGL(conv_wgrad_1x1_bf16<true>, dim3(base, 1, g.nsplit), dim3(256), 0, st, g);
+            const size_t n1 = (size_t)a.CA * a.CQ;
+            hipLaunchKernelGGL(wgrad_slab_transpose_kernel, dim3((int)(n1 + 255) / 256 < 4096 ? (int)(n1 + 255) / 256 : 4096), dim3(256), 0, st,
+                               (const float*)workspace, dw, 1, (int)n1, g.nsplit);
+            return masic_launch_status("conv2d_wgrad_det");
+        }
         if (masic_zero_async(dw, wbytes, st) != hipSuccess) {
             masic_set_error("conv2d_wgrad: memset failed");
             return MASIC_ERR_LAUNCH;
         }
-        hipLaunchKernelGGL(conv_wgrad_1x1_bf16, dim3(base, 1, g.nsplit), dim3(256), 0, st, g);
+        hipLaunchKernelGGL(conv_wgrad_1x1_bf16<false>, dim3(base, 1, g.nsplit), dim3(256), 0, st, g);
         return masic_launch_status("conv2d_wgrad");
     }
-    if (!workspace_clean && masic_zero_async(workspace, wbytes, st) != hipSuccess) {
+    if (!det && !workspace_clean && masic_zero_async(workspace, wbytes, st) != hipSuccess) {
         masic_set_error("conv2d_wgrad: workspace memset failed");
         return MASIC_ERR_LAUNCH;
     }
@@ -917,11 +998,20 @@ int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, co
             if (best < 0 || cost < best) { best = cost; nsplit = ns; }
         }
         a.nsplit = nsplit;
-        if (in16) hipLaunchKernelGGL(conv_wgrad_k5s2_bf16<true>, dim3(ncombo * nsplit), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL(conv_wgrad_k5s2_bf16<false>, dim3(ncombo * nsplit), dim3(512), 0, st, a);
         const size_t total5 = (size_t)Tt * a.CA * a.CQ;
         int tb5 = (int)((total5 + 255) / 256);
         if (tb5 > 4096) tb5 = 4096;
+        if (det) {         // (a multiple of 8 splits, as above: at least 8 whatever the cap)
+            const int cap8 = det_cap(wbytes) / 8 * 8;
+            if (a.nsplit > cap8) a.nsplit = cap8 < 8 ? 8 : cap8;
+            if (det_bytes) { *det_bytes = (size_t)a.nsplit * wbytes; return MASIC_OK; }
+            if (in16) hipLaunchKernelGGL((conv_wgrad_k5s2_bf16<true, true>), dim3(ncombo * a.nsplit), dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((conv_wgrad_k5s2_bf16<false, true>), dim3(ncombo * a.nsplit), dim3(512), 0, st, a);
+            hipLaunchKernelGGL(wgrad_slab_transpose_kernel, dim3(tb5), dim3(256), 0, st, (const float*)workspace, dw, Tt, a.CA * a.CQ, a.nsplit);
+            return masic_launch_status("conv2d_wgrad_det");
+        }
+        if (in16) hipLaunchKernelGGL(conv_wgrad_k5s2_bf16<true>, dim3(ncombo * nsplit), dim3(512), 0, st, a);
+        else hipLaunchKernelGGL(conv_wgrad_k5s2_bf16<false>, dim3(ncombo * nsplit), dim3(512), 0, st, a);
         hipLaunchKernelGGL(wgrad_transpose_kernel, dim3(tb5), dim3(256), 0, st, (float*)workspace, dw, Tt, a.CA * a.CQ, workspace_clean);
         return masic_launch_status("conv2d_wgrad");
     }
@@ -932,6 +1022,11 @@ int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, co
         const int NA = a.CQ == 6 ? 1 : 2, gy = ceil_div(a.CA, NA), NV = NA * a.CQ * 25;
         int gx = SMALL_WGS / gy;
         if (gx > ntl) gx = ntl;
+        if (det_bytes) {   // (already deterministic: one partial per workgroup, summed in a fixed order; the size in whole weights)
+            const size_t w = (size_t)a.CA * a.CQ * 25;
+            *det_bytes = (((size_t)SMALL_WGS * 150 + w - 1) / w) * w * sizeof(float);
+            return MASIC_OK;
+        }
         if (a.CQ == 6) hipLaunchKernelGGL((conv_wgrad_small_s1<1, 6>), dim3(gx, gy), dim3(256), 0, st, a, (float*)workspace, (int)bf16);
         else hipLaunchKernelGGL((conv_wgrad_small_s1<2, 3>), dim3(gx, gy), dim3(256), 0, st, a, (float*)workspace, (int)bf16);
         hipLaunchKernelGGL(wgrad_small_finish, dim3(gy * NV), dim3(64), 0, st, (float*)workspace, dw, gx, gy, NV, a.CA * a.CQ * 25);
@@ -942,9 +1037,17 @@ int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, co
         int nsplit = ceil_div(512, a_tiles);
         if (nsplit > a.ntiles) nsplit = a.ntiles;
         a.nsplit = nsplit < 1 ? 1 : nsplit;
+        if (det && a.nsplit > det_cap(wbytes)) a.nsplit = det_cap(wbytes);
+        if (det_bytes) { *det_bytes = (size_t)a.nsplit * wbytes; return MASIC_OK; }
         const size_t lds = (size_t)2 * (64 * PS + a.CQ * a.QS) * sizeof(float);
         dim3 grid(a_tiles, 1, a.nsplit);
-        if (bf16 && a.CQ * a.QG <= 64) {                    // (the register-staged form holds 8 (channel, group) pairs per wave)
+        if (det) {
+            if (bf16 && a.CQ * a.QG <= 64) {
+                if (ncol_tiles <= 4) hipLaunchKernelGGL((conv_wgrad_packed_f32<1, true, true>), grid, dim3(512), lds, st, a);
+                else hipLaunchKernelGGL((conv_wgrad_packed_f32<2, true, true>), grid, dim3(512), lds, st, a);
+            } else if (ncol_tiles <= 4) hipLaunchKernelGGL((conv_wgrad_packed_f32<1, false, true>), grid, dim3(512), lds, st, a);
+            else hipLaunchKernelGGL((conv_wgrad_packed_f32<2, false, true>), grid, dim3(512), lds, st, a);
+        } else if (bf16 && a.CQ * a.QG <= 64) {                    // (the register-staged form holds 8 (channel, group) pairs per wave)
             if (ncol_tiles <= 4) hipLaunchKernelGGL((conv_wgrad_packed_f32<1, true>), grid, dim3(512), lds, st, a);
             else hipLaunchKernelGGL((conv_wgrad_packed_f32<2, true>), grid, dim3(512), lds, st, a);
         } else if (ncol_tiles <= 4) hipLaunchKernelGGL((conv_wgrad_packed_f32<1, false>), grid, dim3(512), lds, st, a);
@@ -956,10 +1059,20 @@ int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, co
         int nsplit = ceil_div(512, base);
         if (nsplit > a.ntiles) nsplit = a.ntiles;
         a.nsplit = nsplit < 1 ? 1 : nsplit;
+        if (det && a.nsplit > det_cap(wbytes)) a.nsplit = det_cap(wbytes);
         const size_t lds = (size_t)2 * (64 * PS + 32 * QT * a.QS) * sizeof(float);
         MASIC_REQUIRE(lds <= 160 * 1024, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: tile does not fit LDS");
+        if (det_bytes) { *det_bytes = (size_t)a.nsplit * wbytes; return MASIC_OK; }
         dim3 grid(a_tiles * a.q_tiles, 1, a.nsplit);
-        if (bf16 && a.QG <= 8) {                            // (the register-staged form holds 8 pixel groups per channel patch)
+        if (det) {
+            if (bf16 && a.QG <= 8) {
+                if (Tt == 1) hipLaunchKernelGGL((conv_wgrad_f32<4, 1, true, true>), grid, dim3(512), lds, st, a);
+                else if (Tt <= 12) hipLaunchKernelGGL((conv_wgrad_f32<1, 3, true, true>), grid, dim3(512), lds, st, a);
+                else hipLaunchKernelGGL((conv_wgrad_f32<1, 7, true, true>), grid, dim3(512), lds, st, a);
+            } else if (Tt == 1) hipLaunchKernelGGL((conv_wgrad_f32<4, 1, false, true>), grid, dim3(512), lds, st, a);
+            else if (Tt <= 12) hipLaunchKernelGGL((conv_wgrad_f32<1, 3, false, true>), grid, dim3(512), lds, st, a);
+            else hipLaunchKernelGGL((conv_wgrad_f32<1, 7, false, true>), grid, dim3(512), lds, st, a);
+        } else if (bf16 && a.QG <= 8) {                            // (the register-staged form holds 8 pixel groups per channel patch)
             if (Tt == 1) hipLaunchKernelGGL((conv_wgrad_f32<4, 1, true>), grid, dim3(512), lds, st, a);
             else if (Tt <= 12) hipLaunchKernelGGL((conv_wgrad_f32<1, 3, true>), grid, dim3(512), lds, st, a);
             else hipLaunchKernelGGL((conv_wgrad_f32<1, 7, true>), grid, dim3(512), lds, st, a);
@@ -971,6 +1084,10 @@ int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, co
     const size_t total = (size_t)T * AQ;
     int tb = (int)((total + 255) / 256);
     if (tb > 4096) tb = 4096;
+    if (det) {
+        hipLaunchKernelGGL(wgrad_slab_transpose_kernel, dim3(tb), dim3(256), 0, st, (const float*)workspace, dw, T, AQ, a.nsplit);
+        return masic_launch_status("conv2d_wgrad_det");
+    }
     hipLaunchKernelGGL(wgrad_transpose_kernel, dim3(tb), dim3(256), 0, st, (float*)workspace, dw, T, AQ, workspace_clean);
     return masic_launch_status("conv2d_wgrad");
 }

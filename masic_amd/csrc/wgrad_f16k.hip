@@ -74,7 +74,9 @@ __device__ __forceinline__ bf16x8 frag(const v2u& lo, const v2u& hi) {
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3));
 }
 
-template <int MA, int NQ, int KS>
+// DET (masic_conv3x3_wgrad_f16k_det): workgroup x of every channel group stores its partial tile into slab x ([gridDim.x][T][CA][CQ]) with plain
+// stores; wgrad3_slab_transpose_kernel sums the slabs in that order
+template <int MA, int NQ, int KS, bool DET = false>
 __global__ __launch_bounds__(NQ * KS * 64) void wgrad3x3_f16k(const Wg3Args a) {
     constexpr int XR = XGeom<KS>::XR, XROW = XGeom<KS>::XROW, XP = XGeom<KS>::XP;
     constexpr int NW = NQ * KS;
@@ -209,11 +211,15 @@ __global__ __launch_bounds__(NQ * KS * 64) void wgrad3x3_f16k(const Wg3Args a) {
         for (int m = 0; m < MA; ++m)
 #pragma unroll
             for (int kw = 0; kw < KS; ++kw) {
-                float* wp = a.ws + ((size_t)(kh * KS + kw) * a.CA + ga0 + m * 32 + 4 * h) * a.CQ + ci;
+                float* wp = a.ws + ((size_t)(kh * KS + kw) * a.CA + ga0 + m * 32 + 4 * h) * a.CQ + ci
+                            + (DET ? (size_t)blockIdx.x * KS * KS * a.CA * a.CQ : 0);
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int co = ga0 + m * 32 + 4 * h + (e & 3) + 8 * (e >> 2);
-                    if (co < a.CA) atomicAdd(wp + (size_t)((e & 3) + 8 * (e >> 2)) * a.CQ, acc[m][kw][e]);
+                    if (co < a.CA) {
+                        if constexpr (DET) wp[(size_t)((e & 3) + 8 * (e >> 2)) * a.CQ] = acc[m][kw][e];
+                        else atomicAdd(wp + (size_t)((e & 3) + 8 * (e >> 2)) * a.CQ, acc[m][kw][e]);
+                    }
                 }
             }
     }
@@ -226,6 +232,27 @@ __global__ __launch_bounds__(256) void wgrad3_transpose_kernel(float* __restrict
         const size_t aq = i - (size_t)t * AQ;
         dw[aq * T + t] = ws[i];
         if (rezero) ws[i] = 0.0f;          // a persistent workspace is clean again (masic_conv3x3_wgrad_f16k_ws)
+    }
+}
+
+// deterministic finishing pass: slabs [nsplit][T][AQ] -> dw [AQ][T], summed in slab order (float32; 8 slab loads in flight per thread, the
+// adds in slab order); the slabs are left as they are
+__global__ __launch_bounds__(256) void wgrad3_slab_transpose_kernel(const float* __restrict__ ws, float* __restrict__ dw, int AQ, int T, int nsplit) {
+    const size_t total = (size_t)T * AQ;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int t = (int)(i / AQ);
+        const size_t aq = i - (size_t)t * AQ;
+        float s = 0.0f;
+        int z = 0;
+        for (; z + 8 <= nsplit; z += 8) {
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = ws[(size_t)(z + k) * total + i];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += v[k];
+        }
+        for (; z < nsplit; ++z) s += ws[(size_t)z * total + i];
+        dw[aq * T + t] = s;
     }
 }
 
@@ -254,6 +281,10 @@ struct Wg1Args {
                                   //   ConvTranspose2d); zeroed by the caller; 0: none
 };
 
+// DET (masic_gemm_wgrad_bias_f16k_det): a.dw = the workspace; split z stores its partial tile into slab z ([nsplit][CA][CQ]) and the bias
+// partials of its waves into bias slot (z, duty_i, duty_w) of the area behind the slabs ([nsplit][duty_n][2][nb]: one writer per slot);
+// wgrad1x1_finish sums both in a fixed order
+template <bool DET = false>
 __global__ __launch_bounds__(256, 2) void wgrad1x1_f16k(const Wg1Args a) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     const unsigned ldsb = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
@@ -364,10 +395,18 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_f16k(const Wg1Args a) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int co = a0 + 64 * wa + 32 * m + 8 * (e >> 2) + 4 * h + (e & 3);
-                if (co < a.CA) atomicAdd(a.dw + (size_t)co * a.CQ + ci, acc[m][n][e]);
+                if (co < a.CA) {
+                    if constexpr (DET) a.dw[(size_t)blockIdx.z * a.CA * a.CQ + (size_t)co * a.CQ + ci] = acc[m][n][e];
+                    else atomicAdd(a.dw + (size_t)co * a.CQ + ci, acc[m][n][e]);
+                }
             }
         }
     if (a.bias_mode != 0) {
+        float* db = a.db;
+        if constexpr (DET) {
+            const int nb = a.bias_mode == 1 ? a.CA : a.CQ;
+            db += (((size_t)blockIdx.z * duty_n + duty_i) * 2 + duty_w) * nb;
+        }
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             if (a.bias_mode == 1) {            // row sums: every column of the accumulator holds them; column 0 writes
@@ -375,14 +414,44 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_f16k(const Wg1Args a) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int co = a0 + 64 * wa + 32 * m + 8 * (e >> 2) + 4 * h + (e & 3);
-                        if (co < a.CA) atomicAdd(a.db + co, accb[m][e]);
+                        if (co < a.CA) {
+                            if constexpr (DET) db[co] = accb[m][e];
+                            else atomicAdd(db + co, accb[m][e]);
+                        }
                     }
                 }
             } else {                           // column sums: every row holds them; row 0 (h = 0, e = 0) writes
                 const int ci = q0 + 64 * wq + 32 * m + j;
-                if (h == 0 && ci < a.CQ) atomicAdd(a.db + ci, accb[m][0]);
+                if (h == 0 && ci < a.CQ) {
+                    if constexpr (DET) db[ci] = accb[m][0];
+                    else atomicAdd(db + ci, accb[m][0]);
+                }
             }
         }
+    }
+}
+
+// dw[i] = slab 0 + slab 1 + ... (i < AQ); bias i: the sum over (split, duty slot, wave parity) in that order -- float32, fixed order
+__global__ __launch_bounds__(256) void wgrad1x1_finish(const float* __restrict__ ws, float* __restrict__ dw, int AQ, int nsplit, int nb, int nslot) {
+    const size_t total = (size_t)AQ + nb;
+    const float* bias = ws + (size_t)nsplit * AQ;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        float s = 0.0f;
+        if (i < (size_t)AQ) {
+            int z = 0;
+            for (; z + 8 <= nsplit; z += 8) {         // (8 loads in flight, adds in split order)
+                float v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = ws[(size_t)(z + k) * AQ + i];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s += v[k];
+            }
+            for (; z < nsplit; ++z) s += ws[(size_t)z * AQ + i];
+        } else {
+            const size_t k = i - AQ;
+            for (int z = 0; z < nsplit * nslot; ++z) s += bias[(size_t)z * nb + k];
+        }
+        dw[i] = s;
     }
 }
 
@@ -578,9 +647,9 @@ __global__ __launch_bounds__(256) void wgrad_pic_finish(const float* __restrict_
     if (sl == 0 && o < WP_NOUT) dw[o] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
 }
 
-template <int MA, int NQ, int KS = 3>
+template <int MA, int NQ, int KS = 3, bool DET = false>
 void launch(const Wg3Args& a, int grid, int groups, hipStream_t st) {
-    auto kfn = wgrad3x3_f16k<MA, NQ, KS>;
+    auto kfn = wgrad3x3_f16k<MA, NQ, KS, DET>;
     static bool attr_set = false;
     constexpr size_t lds = 3 * (size_t)(2 * MA * GP + 2 * NQ * XGeom<KS>::XP) + 1024;
     static_assert(lds <= 160 * 1024, "three tile buffers must fit the LDS");
@@ -591,7 +660,84 @@ void launch(const Wg3Args& a, int grid, int groups, hipStream_t st) {
     hipLaunchKernelGGL(kfn, dim3(grid, groups), dim3(NQ * KS * 64), lds, st, a);
 }
 
+// slab count of the deterministic 3x3 / 5x5 forms: ONE workgroup count for every channel group of the layer (the default's rule with all
+// the groups in one round of the CUs), capped so that the slabs stay within 64 MiB
+int det3_splits(int B, int Cin, int Cout, int H, int W, int KS) {
+    const int ntiles = ceil_div(W, TC) * ceil_div(H, TR) * B;
+    const int groups = KS == 3 ? ceil_div(Cout, 96) * ceil_div(Cin, 64) : ceil_div(Cout, 64) * (Cin / 32);
+    int grid = ntiles < 256 ? ntiles : 256;
+    if (ntiles < 256 && grid * groups > 256) grid = 256 / groups > 0 ? 256 / groups : 1;
+    const size_t w = (size_t)KS * KS * Cin * Cout * sizeof(float), cap = ((size_t)64 << 20) / w;
+    if ((size_t)grid > cap) grid = cap < 1 ? 1 : (int)cap;
+    return grid < 1 ? 1 : grid;
+}
+
+int wgrad_k3k5_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace, int B, int Cin, int Cout, int H, int W, int KS, void* stream) {
+    const char* what = KS == 3 ? "conv3x3_wgrad_f16k_det" : "conv5x5_wgrad_f16k_det";
+    MASIC_REQUIRE(x_f16k && dy_f16k && dw && workspace, MASIC_ERR_ARG, "%s: null pointer", what);
+    MASIC_REQUIRE(B > 0 && H > 0 && W > 0 && Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0, MASIC_ERR_UNSUPPORTED,
+                  "%s: needs Cin, Cout multiples of 32", what);
+    MASIC_REQUIRE((long)B * (Cin > Cout ? Cin : Cout) * H * W * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "%s: tensor too large for 32-bit offsets", what);
+    hipStream_t st = (hipStream_t)stream;
+    Wg3Args a{(const unsigned short*)dy_f16k, (const unsigned short*)x_f16k, (float*)workspace, B, H, W, Cout / 16, Cin / 16, Cout, Cin, 0, 0,
+              KS == 3 ? 96 : 64, KS == 3 ? 64 : 32, ceil_div(W, TC), ceil_div(H, TR), 0};
+    a.ntiles = a.tiles_w * a.tiles_h * B;
+    const int grid = det3_splits(B, Cin, Cout, H, W, KS);
+    if (KS == 3) {       // the channel groups of masic_conv3x3_wgrad_f16k_ws, every one with the same `grid`
+        const int na = Cout / 96, ra = (Cout % 96) / 32, nqf = Cin / 64, rq = (Cin % 64) / 32;
+        auto go = [&](int a0, int q0, int ma, int nq, int ga, int gq) {
+            if (ga <= 0 || gq <= 0 || ma <= 0 || nq <= 0) return;
+            a.a0 = a0; a.q0 = q0; a.gq = gq;
+            switch (ma * 4 + nq) {
+                case 1 * 4 + 1: launch<1, 1, 3, true>(a, grid, ga * gq, st); break;
+                case 1 * 4 + 2: launch<1, 2, 3, true>(a, grid, ga * gq, st); break;
+                case 2 * 4 + 1: launch<2, 1, 3, true>(a, grid, ga * gq, st); break;
+                case 2 * 4 + 2: launch<2, 2, 3, true>(a, grid, ga * gq, st); break;
+                case 3 * 4 + 1: launch<3, 1, 3, true>(a, grid, ga * gq, st); break;
+                default: launch<3, 2, 3, true>(a, grid, ga * gq, st); break;
+            }
+        };
+        go(0, 0, 3, 2, na, nqf);
+        go(96 * na, 0, ra, 2, 1, nqf);
+        go(0, 64 * nqf, 3, rq, na, 1);
+        go(96 * na, 64 * nqf, ra, rq, 1, 1);
+    } else {             // masic_conv5x5_wgrad_f16k_ws's groups
+        const int na = Cout / 64, ra = (Cout % 64) / 32, nq = Cin / 32;
+        auto go = [&](int a0, int ma, int ga) {
+            if (ga <= 0 || ma <= 0) return;
+            a.a0 = a0; a.q0 = 0; a.gq = nq;
+            if (ma == 2) launch<2, 1, 5, true>(a, grid, ga * nq, st);
+            else launch<1, 1, 5, true>(a, grid, ga * nq, st);
+        };
+        go(0, 2, na);
+        go(64 * na, ra, 1);
+    }
+    const int T = KS * KS, AQ = Cin * Cout;
+    int tb = (T * AQ + 255) / 256;
+    if (tb > 2048) tb = 2048;
+    hipLaunchKernelGGL(wgrad3_slab_transpose_kernel, dim3(tb), dim3(256), 0, st, (const float*)workspace, dw, AQ, T, grid);
+    return masic_launch_status(what);
+}
+
 }  // namespace
+
+// the deterministic mode (include/masic_hip.h): per-split slabs, no float atomics, workspace contents irrelevant on entry and exit
+extern "C" size_t masic_conv3x3_wgrad_f16k_det_workspace_bytes(int B, int Cin, int Cout, int H, int W) {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)det3_splits(B, Cin, Cout, H, W, 3) * 9 * Cin * Cout * sizeof(float);
+}
+extern "C" int masic_conv3x3_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
+                                            int B, int Cin, int Cout, int H, int W, void* stream) {
+    return wgrad_k3k5_det(x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, 3, stream);
+}
+extern "C" size_t masic_conv5x5_wgrad_f16k_det_workspace_bytes(int B, int Cin, int Cout, int H, int W) {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)det3_splits(B, Cin, Cout, H, W, 5) * 25 * Cin * Cout * sizeof(float);
+}
+extern "C" int masic_conv5x5_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
+                                            int B, int Cin, int Cout, int H, int W, void* stream) {
+    return wgrad_k3k5_det(x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, 5, stream);
+}
 
 extern "C" size_t masic_conv3x3_wgrad_f16k_workspace_bytes(int Cin, int Cout) { return (size_t)9 * Cin * Cout * sizeof(float); }
 
@@ -747,9 +893,59 @@ extern "C" int masic_gemm_wgrad_bias_f16k(const void* rows_f16k, const void* col
     a.nsplit = nsplit < 1 ? 1 : nsplit;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad1x1_f16k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)wgrad1x1_f16k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    hipLaunchKernelGGL(wgrad1x1_f16k, dim3(base, 1, a.nsplit), dim3(256), 2 * W1_BUF, st, a);
+    hipLaunchKernelGGL(wgrad1x1_f16k<false>, dim3(base, 1, a.nsplit), dim3(256), 2 * W1_BUF, st, a);
     return masic_launch_status("gemm_wgrad_f16k");
+}
+
+namespace {
+// the deterministic 1x1 form's splits: the default's, capped so that the weight slabs stay within 64 MiB; bias slots per split: duty_n x 2
+int det1_splits(int B, int CA, int CQ, int HW) {
+    const int base = ceil_div(CA, 128) * ceil_div(CQ, 128), ntk = B * ceil_div(HW, W1_PX);
+    int nsplit = 256 / base;
+    if (nsplit > ntk) nsplit = ntk;
+    const size_t cap = ((size_t)64 << 20) / ((size_t)CA * CQ * sizeof(float));
+    if ((size_t)nsplit > cap) nsplit = (int)cap;
+    return nsplit < 1 ? 1 : nsplit;
+}
+int det1_slots(int bias_of, int CA, int CQ) { return bias_of == 1 ? 2 * ceil_div(CQ, 128) : (bias_of == 2 ? 2 * ceil_div(CA, 128) : 0); }
+}  // namespace
+
+// slabs [nsplit][CA][CQ], then the bias partials [nsplit][slots][nb]; the total rounded up to whole weights
+extern "C" size_t masic_gemm_wgrad_bias_f16k_det_workspace_bytes(int bias_of, int B, int CA, int CQ, int HW) {
+    if (B <= 0 || CA <= 0 || CQ <= 0 || HW <= 0 || bias_of < 0 || bias_of > 2) return 0;
+    const size_t w = (size_t)CA * CQ, nb = bias_of == 1 ? CA : (bias_of == 2 ? CQ : 0);
+    const int ns = det1_splits(B, CA, CQ, HW);
+    const size_t n = (size_t)ns * w + (size_t)ns * det1_slots(bias_of, CA, CQ) * nb;
+    return (n + w - 1) / w * w * sizeof(float);
+}
+
+extern "C" int masic_gemm_wgrad_bias_f16k_det(const void* rows_f16k, const void* cols_f16k, float* dw, void* workspace, int bias_of, int B, int CA,
+                                              int CQ, int HW, void* stream) {
+    MASIC_REQUIRE(rows_f16k && cols_f16k && dw && workspace, MASIC_ERR_ARG, "gemm_wgrad_f16k_det: null pointer");
+    MASIC_REQUIRE(bias_of >= 0 && bias_of <= 2, MASIC_ERR_ARG, "gemm_wgrad_f16k_det: bias_of %d", bias_of);
+    MASIC_REQUIRE(B > 0 && HW > 0 && CA > 0 && CQ > 0 && CA % 16 == 0 && CQ % 16 == 0, MASIC_ERR_UNSUPPORTED, "gemm_wgrad_f16k_det: channel counts must be multiples of 16");
+    MASIC_REQUIRE((long)B * (CA > CQ ? CA : CQ) * HW * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "gemm_wgrad_f16k_det: tensor too large for 32-bit offsets");
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = bias_of == 1 ? CA : (bias_of == 2 ? CQ : 0);
+    float* ws = (float*)workspace;
+    Wg1Args a{(const unsigned short*)rows_f16k, (const unsigned short*)cols_f16k, ws, B, HW, CA / 16, CQ / 16, CA, CQ, ceil_div(CQ, 128), ceil_div(HW, W1_PX), 0, 0,
+              nullptr, bias_of};
+    a.ntk = a.B * a.tpi;
+    a.nsplit = det1_splits(B, CA, CQ, HW);
+    a.db = ws + (size_t)a.nsplit * CA * CQ;
+    const int base = ceil_div(CA, 128) * a.q_tiles;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)wgrad1x1_f16k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(wgrad1x1_f16k<true>, dim3(base, 1, a.nsplit), dim3(256), 2 * W1_BUF, st, a);
+    const size_t total = (size_t)CA * CQ + nb;
+    int tb = (int)((total + 255) / 256);
+    if (tb > 2048) tb = 2048;
+    hipLaunchKernelGGL(wgrad1x1_finish, dim3(tb), dim3(256), 0, st, (const float*)ws, dw, CA * CQ, a.nsplit, nb, det1_slots(bias_of, CA, CQ));
+    return masic_launch_status("gemm_wgrad_f16k_det");
 }

@@ -12,6 +12,7 @@ buffers and replaying.
 import torch
 
 from . import ops
+from .determinism import is_deterministic
 from .homography import warp_matrices_host
 
 
@@ -201,7 +202,11 @@ class GraphedTrainStep:
     train_step stays the default.
 
     The graph owns its optimizers (Adam, capturable); `optimizer` / `aux_optimizer` expose them (state_dict for checkpoints).  Inputs
-    are copied into static buffers; the returned criterion dict and aux loss are static tensors overwritten by the next call."""
+    are copied into static buffers; the returned criterion dict and aux loss are static tensors overwritten by the next call.
+
+    Deterministic mode (masic_amd/determinism.py): the mode in effect at capture is what every replay runs -- the graph holds the kernels
+    that were launched while it was captured.  The step records that mode, and a call raises if the effective mode has changed since
+    (capture a new GraphedTrainStep under the other mode instead)."""
 
     def __init__(self, model, d1, d2, h_matrix, lmbda, lr=1e-4, aux_lr=1e-3, warmup=3):
         from . import nn as _mnn
@@ -217,6 +222,7 @@ class GraphedTrainStep:
         self.d1, self.d2, self.h = d1.clone(), d2.clone(), h_matrix.clone()
         self._params = [p for _, p in model.named_parameters()]
         self._precision = _mnn.get_precision()
+        self._deterministic = is_deterministic()
         # warm-up on a side stream (allocator pools, weight packs, one-time kernel attributes), then put parameters, buffers and
         # optimizer state back: the warm-up steps are not part of the training run
         saved = {k: v.clone() for k, v in model.state_dict().items()}
@@ -257,6 +263,9 @@ class GraphedTrainStep:
         from .loss import LazyPSNR
         if not self.model.training or _mnn.get_precision() != self._precision:
             raise RuntimeError("GraphedTrainStep: the model left training mode or the operand precision changed since the capture")
+        if is_deterministic() != self._deterministic:
+            raise RuntimeError(f"GraphedTrainStep: captured with the deterministic mode {'on' if self._deterministic else 'off'}, "
+                               f"replayed with it {'on' if is_deterministic() else 'off'}: the graph replays the kernels of its capture")
         if d1 is not self.d1:
             self.d1.copy_(d1)
         if d2 is not self.d2:

@@ -8,6 +8,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .determinism import is_deterministic as _det_mode
 from .fresh import stamp as _stamp
 from ._lib import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SOFTMAX_C, INOP_ABS, INOP_NONE, INOP_ROUND,  # noqa: F401
                    ConvDesc, check, lib)
@@ -707,6 +708,11 @@ def conv2d_wgrad(x, dy, desc, weight_shape):
     nbytes = _desc_query("masic_conv2d_wgrad_workspace_bytes", desc)
     if desc.Cin * desc.Cout * desc.KH * desc.KW != dw.numel() or nbytes < dw.numel() * 4:
         raise RuntimeError("masic_amd.conv2d_wgrad: weight shape does not match the descriptor")
+    if _det_mode():
+        ws = _det_workspace(x.device, _desc_query("masic_conv2d_wgrad_det_workspace_bytes", desc))
+        fn = lib.masic_conv2d_wgrad_bf16in_det if b16 else lib.masic_conv2d_wgrad_det
+        check(fn(_p(x), _p(dy), _p(dw), _p(ws), ctypes.byref(desc), _stream()), "conv2d_wgrad_det")
+        return dw
     ws = _clean_workspace(x.device, nbytes // 4)       # (>= the weight: the few-channel 5x5 kernel keeps per-workgroup partials in it)
     try:
         fn = lib.masic_conv2d_wgrad_bf16in if b16 else lib.masic_conv2d_wgrad_ws
@@ -733,6 +739,29 @@ def _clean_workspace(device, numel):
 
 def _drop_workspace(device, numel):
     _CLEAN_WS.pop((device, int(_stream().value or 0), int(numel)), None)
+
+
+_DET_WS = {}
+
+
+def _det_workspace(device, nbytes):
+    """Slab workspace of the deterministic weight-gradient kernels (masic_amd/determinism.py): contents irrelevant on entry and exit, so
+    it is never filled.  One buffer per (device, stream, size), as _clean_workspace: two streams never share one."""
+    if nbytes <= 0:
+        raise RuntimeError("masic_amd: the deterministic workspace query rejected the shape")
+    key = (device, int(_stream().value or 0), int(nbytes))
+    ws = _DET_WS.get(key)
+    if ws is None:
+        ws = _DET_WS[key] = torch.empty((int(nbytes) + 3) // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def det_workspace_bytes():
+    """Bytes held by the deterministic mode's cached workspaces: {(device, stream): bytes}."""
+    out = {}
+    for (dev, st, n), ws in _DET_WS.items():
+        out[(dev, st)] = out.get((dev, st), 0) + ws.numel() * 4
+    return out
 
 
 def gmm_likelihood_bwd(y_hat, sigma, mu, wts, g_lik, g_yhat, K, weights_are_logits, scale_bound=SCALE_BOUND, lik_bound=LIK_BOUND):
@@ -790,14 +819,20 @@ def entropy_bottleneck_auxloss_bwd(table, quantiles, gout, tail_mass=1e-9):
 
 def warp_perspective_bwd(g_dst, minv_norm, src_shape, want_flag=False):
     """d loss / d src of warp_perspective.  Default: the gather form (masic_warp_perspective_bwd_gather: no atomics, reproducible, no zero
-    fill), which falls back to the scatter form on the device when the homography is outside its bounds; want_flag: also return the int32
-    device flag that says it did."""
+    fill), which falls back to the scatter form on the device when the homography is outside its bounds (in the deterministic mode: to a
+    store-and-sum without float atomics, masic_amd/determinism.py); want_flag: also return the int32 device flag that says it did."""
     _dev(g_dst); _dev(minv_norm)
     B, C, Hs, Ws = src_shape
     Hd, Wd = g_dst.shape[-2:]
     if min(Hs, Ws, Hd, Wd) > 1:
         g_src = torch.empty(src_shape, dtype=torch.float32, device=g_dst.device)
         flag = torch.empty(1, dtype=torch.int32, device=g_dst.device).fill_(0)
+        if _det_mode():      # the fallback is a deterministic store-and-sum instead of the scatter (int32 workspace, per call)
+            ws = torch.empty(_int_query("masic_warp_perspective_bwd_gather_det_workspace_bytes", B, Hs, Ws, Hd, Wd) // 4, dtype=torch.int32,
+                             device=g_dst.device)
+            check(lib.masic_warp_perspective_bwd_gather_det(_p(g_dst), _p(minv_norm), _p(g_src), _p(flag), _p(ws), B, C, Hs, Ws, Hd, Wd, _stream()),
+                  "warp_perspective_bwd_gather_det")
+            return (g_src, flag) if want_flag else g_src
         check(lib.masic_warp_perspective_bwd_gather(_p(g_dst), _p(minv_norm), _p(g_src), _p(flag), B, C, Hs, Ws, Hd, Wd, _stream()),
               "warp_perspective_bwd_gather")
         return (g_src, flag) if want_flag else g_src
@@ -1543,7 +1578,11 @@ def gemm_wgrad_f16k(rows16, cols16, B, CA, CQ, HW, bias_of=0):
         raise RuntimeError("masic_amd.gemm_wgrad_f16k: F16K buffer sizes do not match (B, C, HW)")
     nb = CA if bias_of == 1 else (CQ if bias_of == 2 else 0)
     out = torch.empty(CA * CQ + nb, dtype=torch.float32, device=rows16.device)
-    check(lib.masic_gemm_wgrad_bias_f16k(_p(rows16), _p(cols16), _p(out), int(bias_of), B, CA, CQ, HW, _stream()), "gemm_wgrad_f16k")
+    if _det_mode():
+        ws = _det_workspace(rows16.device, _int_query("masic_gemm_wgrad_bias_f16k_det_workspace_bytes", int(bias_of), B, CA, CQ, HW))
+        check(lib.masic_gemm_wgrad_bias_f16k_det(_p(rows16), _p(cols16), _p(out), _p(ws), int(bias_of), B, CA, CQ, HW, _stream()), "gemm_wgrad_f16k_det")
+    else:
+        check(lib.masic_gemm_wgrad_bias_f16k(_p(rows16), _p(cols16), _p(out), int(bias_of), B, CA, CQ, HW, _stream()), "gemm_wgrad_f16k")
     dw = out[:CA * CQ].view(CA, CQ)
     return (dw, out[CA * CQ:]) if nb else dw
 
@@ -1572,6 +1611,10 @@ def conv5x5_wgrad_f16k(x16, dy16, B, Cin, Cout, H, W):
     if x16.dtype != torch.int16 or dy16.dtype != torch.int16 or x16.numel() != B * Cin * H * W or dy16.numel() != B * Cout * H * W:
         raise RuntimeError("masic_amd.conv5x5_wgrad_f16k: F16K buffer sizes do not match (B, C, H, W)")
     dw = torch.empty((Cout, Cin, 5, 5), dtype=torch.float32, device=x16.device)
+    if _det_mode():
+        ws = _det_workspace(x16.device, _int_query("masic_conv5x5_wgrad_f16k_det_workspace_bytes", B, Cin, Cout, H, W))
+        check(lib.masic_conv5x5_wgrad_f16k_det(_p(x16), _p(dy16), _p(dw), _p(ws), B, Cin, Cout, H, W, _stream()), "conv5x5_wgrad_f16k_det")
+        return dw
     n = _int_query("masic_conv5x5_wgrad_f16k_workspace_bytes", Cin, Cout) // 4
     ws = _clean_workspace(x16.device, n)
     try:
@@ -1587,6 +1630,10 @@ def conv3x3_wgrad_f16k(x16, dy16, B, Cin, Cout, H, W):
     if x16.dtype != torch.int16 or dy16.dtype != torch.int16 or x16.numel() != B * Cin * H * W or dy16.numel() != B * Cout * H * W:
         raise RuntimeError("masic_amd.conv3x3_wgrad_f16k: F16K buffer sizes do not match (B, C, H, W)")
     dw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=x16.device)
+    if _det_mode():
+        ws = _det_workspace(x16.device, _int_query("masic_conv3x3_wgrad_f16k_det_workspace_bytes", B, Cin, Cout, H, W))
+        check(lib.masic_conv3x3_wgrad_f16k_det(_p(x16), _p(dy16), _p(dw), _p(ws), B, Cin, Cout, H, W, _stream()), "conv3x3_wgrad_f16k_det")
+        return dw
     n = _int_query("masic_conv3x3_wgrad_f16k_workspace_bytes", Cin, Cout) // 4
     ws = _clean_workspace(x16.device, n)
     try:
