@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- stereo pairs/s (enc+dec = one HSIC.forward) of the MI355X-native MASIC codec.
 
-    python bench.py [--gpus N --steps K --warmup W] [--batch 8 --height 512 --width 512] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--batch 8 --height 512 --width 512] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one HSIC(N=128,M=192,K=5) eval forward over a batch of synthetic stereo pairs already resident
 in HBM (BASELINE.json configs[1]: 8 x 512x512 per GPU; weak scaling: every rank runs its own batch, no
-data-path collective).  Rank 0 prints ONE JSON line with the contract fields plus
+data-path collective).  Rank 0 prints ONE JSON line with the contract fields (metric, value, unit, ms_per_step, dtype, ...) and
+  dump_outputs -- with --dump-outputs DIR only: what the last timed step returned (rank 0), written as DIR/<name>.npy.
+A plain run does nothing else: set-up, warm-up, the timed steps, the dump, the line.  `--full` also measures and checks
+everything below (several minutes) and adds it to the line:
   roofline     -- the dominant kernel symbol (by device time): algorithmic FLOPs per launch / average launch
                   duration, both measured with HIP events on the launch stream; `traffic` = HBM bytes per launch
                   from two rocprofv3 --pmc child passes of this same script run before the parent touches the GPU
@@ -16,7 +19,6 @@ data-path collective).  Rank 0 prints ONE JSON line with the contract fields plu
   extras       -- training step, float32 parity path, accuracy of both operand modes against the oracle
                   (bpp / PSNR / symbol mismatch: BASELINE.json's "bpp/PSNR vs ref"), upload-inclusive rates,
                   Independent_EN (CQE) forward + training step, the real bitstream of one pair.
-  dump_outputs -- with --dump-outputs DIR only: what the last timed step returned (rank 0), written as DIR/<name>.npy.
 """
 import argparse
 import hashlib
@@ -373,7 +375,7 @@ def dump_outputs(out, directory):
 
 
 # ------------------------------------------------------------------------------------------------ main
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -401,9 +403,33 @@ def main():
     ap.add_argument("--train-steps", type=int, default=5,
                     help="also time this many full training steps (forward + RD loss + backward + gradient all-reduce + "
                          "2x Adam) after the headline region; reported under extras.train_step, 0 to skip")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure and check everything else: roofline (with its rocprofv3 --pmc child passes), "
+                         "CPU baseline, other precisions, extras (several minutes); the --no-* switches, --train-steps and --trained-steps "
+                         "only shape such a run")
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def result_line(args, world, elapsed):
+    """The contract fields of rank 0's JSON line, the same in a plain and a --full run."""
+    B, H, W = args.batch, args.height, args.width
+    return {
+        "metric": "stereo pairs/sec (enc+dec)", "value": world * B * args.steps / elapsed, "unit": "stereo pairs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+        "config": {"workload": f"HSIC(N=128,M=192,K=5) eval forward (enc+dec both views), {B}x3x{H}x{W} stereo pairs per GPU "
+                               "(BASELINE.json configs[1] shape), inputs resident in HBM (the graph's static input buffers); "
+                               "the device homography of batch k+1 is handed over with batch k (one-batch look-ahead of a loader): its device->host "
+                               "read, the float32 host chain and the upload of the sampling matrices are done every step, under the running replay",
+                   "pairs_per_gpu": B, "height": H, "width": W, "parallelism": f"dp{world} (pairs sharded, no data-path collective)"},
+    }
+
+
+def main():
+    args = parse_args()
     if args.pmc_child:
         return pmc_child(args)
 
@@ -416,7 +442,7 @@ def main():
 
     # HBM traffic of the kernels: child processes under rocprofv3, before anything here touches the GPU
     pmc, pmc_reason = None, "skipped (--no-pmc or N > 1)"
-    if world == 1 and not args.no_pmc:
+    if world == 1 and args.full and not args.no_pmc:
         t0 = time.perf_counter()
         pmc, pmc_reason = measure_pmc_traffic(args)
         pmc_seconds = time.perf_counter() - t0
@@ -438,7 +464,7 @@ def main():
     from masic_amd import nn as mnn
     from masic_amd import ops, synth
     from masic_amd.loss import distortion, rate_distortion
-    rehearsal_info = rehearsal_reducer_check(dev, rank, world) if (rehearsal and world > 1) else None
+    rehearsal_info = rehearsal_reducer_check(dev, rank, world) if (rehearsal and world > 1 and args.full) else None
     mnn.set_precision(args.precision)
 
     N, M, K = 128, 192, 5
@@ -449,7 +475,7 @@ def main():
     x1h, x2h, hmh = synth.synth_inputs(B, H, W, seed=100 + rank)
     x1, x2, hm = x1h.to(dev), x2h.to(dev), hmh.to(dev)
     fp8_table = None
-    if args.precision == "fp8" or (args.precision == "bf16" and not args.no_fp8):
+    if args.precision == "fp8" or (args.precision == "bf16" and args.full and not args.no_fp8):
         # activation scales of the fp8 mode from ONE calibration batch that is not the measured one (same on every rank)
         from masic_amd import fp8
         fp8_table = fp8.calibrate(net, [tuple(t.to(dev) for t in synth.synth_inputs(2, H, W, seed=1100))])
@@ -487,6 +513,17 @@ def main():
         # the graph's output buffers are overwritten by every later replay: keep the last timed step's result as it was
         dump_info = dump_outputs(out, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
+    if not args.full:
+        if rank == 0:
+            line = result_line(args, world, elapsed)
+            if dump_info is not None:
+                line["dump_outputs"] = dump_info
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    with torch.no_grad():
         # ---- the same step WITHOUT the look-ahead: the homography arrives with its own batch, as the reference computes it right before
         # model(d1, d2, h_matrix) (newtrain_codec_real.py:124-137) -- each call waits for the previous replay, reads it, runs the host chain
         no_lookahead = None
@@ -917,17 +954,8 @@ def main():
             shutil.rmtree(tmp, ignore_errors=True)
 
     if rank == 0:
-        line = {
-            "metric": "stereo pairs/sec (enc+dec)", "value": world * B * args.steps / elapsed, "unit": "stereo pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": f"HSIC(N=128,M=192,K=5) eval forward (enc+dec both views), {B}x3x{H}x{W} stereo pairs per GPU "
-                                   "(BASELINE.json configs[1] shape), inputs resident in HBM (the graph's static input buffers); "
-                                   "the device homography of batch k+1 is handed over with batch k (one-batch look-ahead of a loader): its device->host "
-                                   "read, the float32 host chain and the upload of the sampling matrices are done every step, under the running replay",
-                       "pairs_per_gpu": B, "height": H, "width": W, "parallelism": f"dp{world} (pairs sharded, no data-path collective)"},
-            "roofline": roofline,
-        }
+        line = result_line(args, world, elapsed)
+        line["roofline"] = roofline
         extras = {}
         if train_info is not None:
             extras["train_step"] = train_info

@@ -1,12 +1,13 @@
-"""Builds the profiles/ artefacts of a round from the files `bash tools/profile_round.sh <tag>` left in gpurun_out/ (see profiles/README.md):
-python tools/refresh_profiles.py r02"""
+"""Builds the profiles/ artefacts of a round from the files `bash tools/profile_round.sh <tag>` left in $PROFILE_OUT (default profile_out/;
+see profiles/README.md): python tools/refresh_profiles.py r02"""
 import glob, json, os, re, shutil, sqlite3, statistics as st, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))) + "/"
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r02"
 sys.path.insert(0, R)
-d = json.load(open(R + "gpurun_out/bench_n1.json"))
+O = R + os.environ.get("PROFILE_OUT", "profile_out") + "/"
+d = json.load(open(O + "bench_n1.json"))
 dom = d["roofline"]["kernel"]
-shutil.copy(R + "gpurun_out/bench_n1.json", R + f"profiles/{TAG}_bench_n1.json")
+shutil.copy(O + "bench_n1.json", R + f"profiles/{TAG}_bench_n1.json")
 head = subprocess.run(["git", "-C", R, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
 # roofline.traffic of the bench line was measured by its own PMC child passes; keep it as the stamped fallback for boxes without rocprofv3
 import bench
@@ -16,7 +17,7 @@ if d["roofline"].get("traffic"):
                         "section). Only reported while the kernel sources still hash to source_stamp.",
                dom: {"bytes": d["roofline"]["traffic"], "source_stamp": bench.kernel_source_stamp(), "commit": head}},
               open(R + "profiles/pmc_traffic.json", "w"), indent=1)
-db_path = glob.glob(R + f"gpurun_out/prof_{TAG}/**/*results.db", recursive=True)[0]
+db_path = glob.glob(O + f"prof_{TAG}/**/*results.db", recursive=True)[0]
 subprocess.run([sys.executable, R + "tools/rocpd_stats.py", db_path, R + f"profiles/{TAG}_kernel_stats.csv"], capture_output=True)
 db = sqlite3.connect(db_path)
 norm = lambda n: re.sub(r"\(.*", "", n.replace("(anonymous namespace)::", "").replace("void ", ""))
@@ -28,7 +29,7 @@ json.dump({"symbol": dom, "launches": len(dd), "avg_launch_us_all_launches_of_th
                    "extras of that process all launch it or not; the all-launch average of the stats file therefore sits between the bench line's in-situ and isolated figures)"},
           open(R + f"profiles/{TAG}_dominant.json", "w"), indent=1)
 # SQ counters (one pass over the eager bf16 forward, bench.py --pmc-child)
-sq = glob.glob(R + "gpurun_out/pmc_sq/**/*counter_collection.csv", recursive=True)
+sq = glob.glob(O + "pmc_sq/**/*counter_collection.csv", recursive=True)
 if sq:
     subprocess.run([sys.executable, R + "tools/pmc_summary.py", R + f"profiles/{TAG}_sq_counters_raw.json"] + sq, capture_output=True)
     raw = json.load(open(R + f"profiles/{TAG}_sq_counters_raw.json"))
@@ -47,8 +48,8 @@ if sq:
     json.dump(out, open(R + f"profiles/{TAG}_sq_counters.json", "w"), indent=1, sort_keys=True)
     os.remove(R + f"profiles/{TAG}_sq_counters_raw.json")
 for name, log, n in (("train", "prof_train", 3), ("cqe", "prof_cqe", 3), ("cqe_train", "prof_cqetrain", 3)):
-    dbs = glob.glob(R + f"gpurun_out/{log}/**/*results.db", recursive=True)
-    m = re.search(r"ms/step ([0-9.]+)", open(R + f"gpurun_out/{log}.log").read()) if os.path.exists(R + f"gpurun_out/{log}.log") else None
+    dbs = glob.glob(O + f"{log}/**/*results.db", recursive=True)
+    m = re.search(r"ms/step ([0-9.]+)", open(O + f"{log}.log").read()) if os.path.exists(O + f"{log}.log") else None
     if dbs and m:
         txt = subprocess.run([sys.executable, R + "tools/prof_stats.py", dbs[0], str(n), m.group(1), "60"], capture_output=True, text=True).stdout
         open(R + f"profiles/{TAG}_{name}_step_kernels.txt", "w").write(f"# rocprofv3 --kernel-trace -- python3 tools/{'train_prof.py bf16' if name == 'train' else ('cqe_prof.py bf16 train' if name == 'cqe_train' else 'cqe_prof.py bf16')} (commit {head}); ms/step under the profiler {m.group(1)}" + (" -- the step runs on three streams (MASIC.py: _forward_graph): kernels share the chip, so a kernel's duration here is longer than alone and the column adds up to more than the step; MASIC_TRAIN_STREAMS=0 gives the one-stream table" if name == "train" else "") + "\n" + txt)
