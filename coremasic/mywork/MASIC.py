@@ -1010,9 +1010,10 @@ class HSIC(CompressionModel):
         pixels in one launch per layer) and decoder (one coding wavefront per launch) run the same kernels with the same k order, and a
         pixel's result does not depend on its tile mates: bit-identical parameters on both sides."""
 
-        def __init__(self, full, skinny=None):
+        def __init__(self, full, skinny=None, cat16=None, gate=None):
             self._full, self._sk = full, skinny
             self.skinny = skinny is not None
+            self.cat16, self.gate = cat16, gate            # the view's F16K concat buffer (hyper part filled) and gates: what a batch stacks
             if self.skinny:
                 self.y16, self.sigma, self.mu, self.logits = skinny["y16"], skinny["sigma"], skinny["mu"], skinny["logits"]
 
@@ -1024,13 +1025,13 @@ class HSIC(CompressionModel):
 
         def run(self, pix, step, list_stride, npix):
             k = self._sk
-            _hip.skinny_group([k["ctx"]], pix, step, list_stride, npix, k["h"], k["w"], ctx=True, gate=k["gate"], gate_c=1)
+            _hip.skinny_group([k["ctx"]], pix, step, list_stride, npix, k["h"], k["w"], ctx=True, gate=k["gate"], gate_c=1, nimg=k["B"])
             for layers in k["heads"]:
-                _hip.skinny_group(layers, pix, step, list_stride, npix, k["h"], k["w"])
+                _hip.skinny_group(layers, pix, step, list_stride, npix, k["h"], k["w"], nimg=k["B"])
 
-    def _skinny_params(self, head, ctx, cat16, C, h, w, gate=None):
+    def _skinny_params(self, head, ctx, cat16, C, h, w, gate=None, B=1):
         """Buffers and layer descriptions of _PixelParams' pixel-list form, or None when it does not apply (float32 / fp8 operands, widths
-        the kernels are not built for)."""
+        the kernels are not built for).  B > 1: over a batch of B pairs (cat16 and gate stacked [B, ...])."""
         from masic_amd import nn as _mnn
         M, K = self.M, self.K
         if (cat16 is None or M % 16 or (2 * M) % 32 or not head._grouped_heads_ok()
@@ -1040,8 +1041,8 @@ class HSIC(CompressionModel):
         ctx.zero_masked_taps()
         wpc = _mnn._cached(ctx, "_packed_skinny_cache", _mnn.weight_key(ctx.weight), (), lambda: _hip.pack_skinny_ctx_weight(ctx.weight.detach()))
         M16 = (M + 15) // 16 * 16
-        y16 = torch.zeros(M16 * h * w, dtype=torch.int16, device=dev)
-        outs = [torch.empty((1, K * M, h, w), dtype=torch.float32, device=dev) for _ in range(3)]
+        y16 = torch.zeros(B * M16 * h * w, dtype=torch.int16, device=dev)
+        outs = [torch.empty((B, K * M, h, w), dtype=torch.float32, device=dev) for _ in range(3)]
         heads, t = [], [cat16[0]] * 3
         for i in range(3):
             layers, nxt = [], []
@@ -1052,15 +1053,16 @@ class HSIC(CompressionModel):
                     L["y32"], L["out_ctot"] = outs[k_], layer.out_channels
                 else:
                     L["out_ctot"] = (layer.out_channels + 15) // 16 * 16
-                    L["y16"] = torch.zeros(L["out_ctot"] * h * w, dtype=torch.int16, device=dev)
+                    L["y16"] = torch.zeros(B * L["out_ctot"] * h * w, dtype=torch.int16, device=dev)
                     nxt.append(L["y16"])
                 layers.append(L)
             heads.append(layers)
             t = nxt
         ctxl = dict(x=y16, wp=wpc, bias=None if ctx.bias is None else ctx.bias.detach(), Cin=M16, Cout=2 * M, act=_NONE, y16=cat16[0], out_ctot=C, out_coff=2 * M)
-        return dict(y16=y16, M16=M16, sigma=outs[0], mu=outs[1], logits=outs[2], ctx=ctxl, heads=heads, h=h, w=w, gate=gate)
+        return dict(y16=y16, M16=M16, sigma=outs[0], mu=outs[1], logits=outs[2], ctx=ctxl, heads=heads, h=h, w=w, gate=gate, B=B)
 
-    def _left_params_fn(self, z1_hat, h, w):
+    def _left_params_fn(self, z1_hat, h, w, pixel_list=True):
+        """pixel_list=False: without the pixel-list buffers (a batch builds its own over all pairs, _batch_params)."""
         M = self.M
         # (bf16 operands: the concat buffer is F16K, as in the eval forward -- the context model writes its slice as bf16 records and the
         # grouped head GEMMs read the buffer directly: no conversion pass over the 768-channel buffer per coding step)
@@ -1073,9 +1075,10 @@ class HSIC(CompressionModel):
             if cat16 is not None:
                 return self._h_s1_same_resolution.heads((1, 4 * M, h, w), x16=cat16[0])
             return self._h_s1_same_resolution.heads(cat1)
-        return HSIC._PixelParams(params, self._skinny_params(self._h_s1_same_resolution, self.context_prediction1, cat16, 4 * M, h, w))
+        sk = self._skinny_params(self._h_s1_same_resolution, self.context_prediction1, cat16, 4 * M, h, w) if pixel_list else None
+        return HSIC._PixelParams(params, sk, cat16=cat16)
 
-    def _right_params_fn(self, z2_hat, x1_hat, m_fwd, m_back, H, W, h, w):
+    def _right_params_fn(self, z2_hat, x1_hat, m_fwd, m_back, H, W, h, w, pixel_list=True):
         """-> (params_fn, x1_hat_warp): everything of the right view's tables that the decoder knows before y2."""
         M = self.M
         dev = z2_hat.device
@@ -1096,8 +1099,8 @@ class HSIC(CompressionModel):
             if cat16 is not None:
                 return self._h_s2_same_resolution.heads((1, 5 * M, h, w), x16=cat16[0])
             return self._h_s2_same_resolution.heads(cat2)
-        sk = self._skinny_params(self._h_s2_same_resolution, self.context_prediction2, cat16, 5 * M, h, w, gate=gates.contiguous())
-        return HSIC._PixelParams(params, sk), x1_hat_warp
+        sk = self._skinny_params(self._h_s2_same_resolution, self.context_prediction2, cat16, 5 * M, h, w, gate=gates.contiguous()) if pixel_list else None
+        return HSIC._PixelParams(params, sk, cat16=cat16, gate=gates.contiguous()), x1_hat_warp
 
     @staticmethod
     def _channel_flags(y_hat):
@@ -1142,13 +1145,23 @@ class HSIC(CompressionModel):
             params2, x1_hat_warp = self._right_params_fn(z2_hat, x1_hat, m_fwd, m_back, H, W, h, w)
             s_y2 = codec.encode_view(params2, y2_hat, M, K, chan2, minmax2, self.gaussian2._scale_bound_value)
             x2_hat = self.decoder2(y2_hat, x1_hat_warp)
-        for s_z in (z1_strings[0], z2_strings[0]):
-            if len(s_z) > 65535 or max(minmax1, minmax2) > 65535:
+        nbytes = self._write_pair(output_path, output_name, H, W, ((z1_strings[0], flag1, minmax1, s_y1), (z2_strings[0], flag2, minmax2, s_y2)),
+                                  fp8_table)
+        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat,
+                "bytes": nbytes, "bpp": nbytes * 8.0 / (H * W)}
+
+    @staticmethod
+    def _write_pair(output_path, output_name, H, W, views, fp8_table):
+        """The two files of one pair; views: per view (z string, channel flags, minmax, framed y streams).  -> bytes written."""
+        import os
+        from masic_amd import codec, nn as _mnn
+        for s_z, _, mm, _ in views:
+            if len(s_z) > 65535 or mm > 65535:
                 raise ValueError("HSIC.compress: the header stores string lengths and minmax as uint16 (reference :941-946)")
         out1 = os.path.join(output_path, str(output_name) + ".npz")
         with open(out1, "wb") as f:
             f.write(np.array([H, W], dtype=np.uint16).tobytes())
-            for s_z, flag, mm in ((z1_strings[0], flag1, minmax1), (z2_strings[0], flag2, minmax2)):
+            for s_z, flag, mm, _ in views:
                 f.write(np.array([len(s_z), mm], dtype=np.uint16).tobytes())
                 f.write(np.packbits(flag).tobytes())
                 f.write(s_z)
@@ -1160,20 +1173,16 @@ class HSIC(CompressionModel):
                 # state_dict(): the stream carries them, so any decoder holding the same weights rebuilds the same tables
                 f.write(np.array([len(fp8_table)], dtype=np.uint32).tobytes())
                 f.write(fp8_table)
-            for s_y in (s_y1, s_y2):        # each: u32 n, n x u32 lengths, the n channel streams (masic_amd/codec.py)
+            for _, _, _, s_y in views:      # each: u32 n, n x u32 lengths, the n channel streams (masic_amd/codec.py)
                 f.write(s_y)
-        nbytes = os.path.getsize(out1) + os.path.getsize(out2)
-        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat,
-                "bytes": nbytes, "bpp": nbytes * 8.0 / (H * W)}
+        return os.path.getsize(out1) + os.path.getsize(out2)
 
-    def decompress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu"):
-        """Reads the two files compress wrote.  x1 / x2 are not used for decoding (the reference only takes sizes from them,
-        :1308-1310) and may be None; tensors are created on the model's device."""
+    def _read_pair(self, output_path, output_name, dev, who="HSIC.decompress"):
+        """The two files of one pair -> H, W, per view (z string, minmax, coded channels as a device int32 tensor), per view the framed
+        y streams, the fp8 scale table or None.  ValueError for a foreign stream or one written in another operand mode."""
         import os
         from masic_amd import codec, nn as _mnn
-        self._codec_check(1)
-        M, K = self.M, self.K
-        dev = self.encoder1.g_a_conv1.weight.device
+        M = self.M
         with open(os.path.join(output_path, str(output_name) + ".npz"), "rb") as f:
             H, W = (int(v) for v in np.frombuffer(f.read(4), dtype=np.uint16))
             views = []
@@ -1184,22 +1193,33 @@ class HSIC(CompressionModel):
         with open(os.path.join(output_path, str(output_name) + ".bin"), "rb") as f:
             head = f.read(8)
             if head[:4] != codec.MAGIC:
-                raise ValueError("HSIC.decompress: not a stream of this library (magic %r)" % head[:4])
+                raise ValueError(f"{who}: not a stream of this library (magic %r)" % head[:4])
             if head[4] != {"f32": 0, "bf16": 1, "fp8": 2}[_mnn.get_precision()]:
-                raise ValueError("HSIC.decompress: the stream was written in the %s operand mode; the coding tables depend on it "
+                raise ValueError(f"{who}: the stream was written in the %s operand mode; the coding tables depend on it "
                                  "(masic_amd.nn.set_precision)" % ("f32", "bf16", "fp8")[head[4] if head[4] < 3 else 0])
             fp8_table = None
             if head[5] & 1:
                 n = int(np.frombuffer(f.read(4), dtype=np.uint32)[0])
                 fp8_table = f.read(n)
             elif head[4] == 2:
-                raise ValueError("HSIC.decompress: an fp8-mode stream without its activation-scale table")
+                raise ValueError(f"{who}: an fp8-mode stream without its activation-scale table")
             rest = f.read()
             streams = []
             for _ in range(2):
                 _, used = codec.split_channels(rest)
                 streams.append(rest[:used])
                 rest = rest[used:]
+        return H, W, views, streams, fp8_table
+
+    def decompress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu"):
+        """Reads the two files compress wrote.  x1 / x2 are not used for decoding (the reference only takes sizes from them,
+        :1308-1310) and may be None; tensors are created on the model's device."""
+        import os
+        from masic_amd import codec, nn as _mnn
+        self._codec_check(1)
+        M, K = self.M, self.K
+        dev = self.encoder1.g_a_conv1.weight.device
+        H, W, views, streams, fp8_table = self._read_pair(output_path, output_name, dev)
         self._codec_check(1, H, W)
         h, w = H // 16, W // 16
         with torch.no_grad(), _fp8.stream_scales(self, fp8_table):
@@ -1213,6 +1233,169 @@ class HSIC(CompressionModel):
             y2_hat = codec.decode_view(params2, streams[1], (h, w), M, K, views[1][2], views[1][1], self.gaussian2._scale_bound_value, dev)
             x2_hat = self.decoder2(y2_hat, x1_hat_warp)
         return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
+
+    # ---- B pairs per call (INTEGRATION.md "Batched bitstream coding").  The files are byte for byte those of compress on each pair:
+    # the once-per-call work (transforms, hyper path, reconstruction, warp, gates, z coder) runs per pair as B = 1 calls -- several bf16
+    # layers pick or order their kernels by batch shape, so their bits at B > 1 differ from those at B = 1 -- and the coding-step loops,
+    # where the time goes, run over all B pairs at once (codec.encode_views / decode_views).  float32 / fp8 operands (no pixel-list
+    # form) code the pairs one after the other.
+    def _batch_check(self, B, names, H=None, W=None):
+        if self.training:
+            raise RuntimeError("HSIC.compress_batch/decompress_batch: call .eval() first (the reference quantises with noise in training mode)")
+        if H is not None and (H % 64 or W % 64):
+            raise ValueError(f"HSIC.compress_batch/decompress_batch: picture size {H}x{W} must be a multiple of 64 in both dimensions "
+                             "(pad the pairs as the reference's drivers do)")
+        if B < 1 or len(names) != B:
+            raise ValueError(f"HSIC.compress_batch/decompress_batch: {B} pairs and {len(names)} output names")
+
+    def _batch_params(self, parts, head, ctx, C, h, w):
+        """One _PixelParams over the B pairs of `parts` (per-pair params built with pixel_list=False): their concat buffers and gates
+        stacked, the pixel-list buffers sized for B; None when the pixel-list form does not apply."""
+        if any(p.cat16 is None for p in parts):
+            return None
+        cat = torch.cat([p.cat16[0] for p in parts])
+        gate = torch.cat([p.gate for p in parts]) if parts[0].gate is not None else None
+        sk = self._skinny_params(head, ctx, (cat, C), C, h, w, gate=gate, B=len(parts))
+        return None if sk is None else HSIC._PixelParams(None, sk, cat16=(cat, C), gate=gate)
+
+    def _code_views(self, parts, head, ctx, C, y_hat, chans, minmaxes, bound, names):
+        """compress side of one view over the batch -> per pair the framed y streams."""
+        from masic_amd import codec
+        h, w = y_hat.shape[-2:]
+        bp = self._batch_params(parts, head, ctx, C, h, w)
+        if bp is not None:
+            return codec.encode_views(bp, y_hat, self.M, self.K, [c.tolist() for c in chans], minmaxes, bound, names=names)
+        out = []
+        for i, p in enumerate(parts):
+            chan = torch.from_numpy(chans[i]).to(y_hat.device)
+            with _pair_errors(i, names[i]):
+                out.append(codec.encode_view(p, y_hat[i:i + 1], self.M, self.K, chan, minmaxes[i], bound))
+        return out
+
+    def _decode_views(self, parts, head, ctx, C, blobs, hw, chans, minmaxes, bound, names, dev):
+        """decompress side of one view over the batch -> y_hat [B, M, h, w]."""
+        from masic_amd import codec
+        bp = self._batch_params(parts, head, ctx, C, *hw)
+        if bp is not None:
+            return codec.decode_views(bp, blobs, hw, self.M, self.K, [c.cpu().tolist() for c in chans], minmaxes, bound, dev, names=names)
+        out = []
+        for i, p in enumerate(parts):
+            with _pair_errors(i, names[i]):
+                out.append(codec.decode_view(p, blobs[i], hw, self.M, self.K, chans[i], minmaxes[i], bound, dev))
+        return torch.cat(out)
+
+    def compress_batch(self, x1, x2, h_matrix, output_names, output_path=""):
+        """compress for B pairs: x1, x2 [B, 3, H, W], h_matrix [B, 3, 3], B output names.  Writes <name_i>.npz / <name_i>.bin, byte for
+        byte what compress(x1[i:i+1], x2[i:i+1], h_matrix[i:i+1], name_i) writes, and returns compress's dict with [B, ...] tensors
+        ("bytes" / "bpp": lists of B)."""
+        from masic_amd import nn as _mnn
+        x1, x2 = x1.contiguous(), x2.contiguous()
+        B, _, H, W = x1.shape
+        names = [str(n) for n in output_names]
+        self._batch_check(B, names, H, W)
+        if x2.shape != x1.shape or h_matrix.shape[0] != B:
+            raise ValueError("HSIC.compress_batch: x1, x2 and h_matrix must hold the same number of pairs")
+        M = self.M
+        fp8_table = _fp8.stream_table(self) if _mnn.get_precision() == "fp8" else None
+        pr = []
+        with torch.no_grad():
+            for i in range(B):          # left view, per pair (as compress)
+                a, b_ = x1[i:i + 1], x2[i:i + 1]
+                m_fwd, m_back = _warp_matrices(h_matrix[i:i + 1], (H, W), (H, W), want_inverse=True)
+                y1 = self.encoder1.latent(a)
+                z1 = self._h_a1(y1)
+                z1_strings = self.entropy_bottleneck1.compress(z1)
+                z1_hat = self.entropy_bottleneck1.decompress(z1_strings, z1.size()[-2:])
+                y1_hat = _hip.quantize(y1, "dequantize")
+                flag1, minmax1 = self._channel_flags(y1_hat)
+                pr.append(dict(x1=a, x2=b_, m_fwd=m_fwd, m_back=m_back, z1_strings=z1_strings, z1_hat=z1_hat, y1_hat=y1_hat, flag1=flag1,
+                               minmax1=minmax1))
+            h, w = pr[0]["y1_hat"].shape[-2:]
+            s_y1 = self._code_views([self._left_params_fn(p["z1_hat"], h, w, pixel_list=False) for p in pr], self._h_s1_same_resolution,
+                                    self.context_prediction1, 4 * M, torch.cat([p["y1_hat"] for p in pr]),
+                                    [np.flatnonzero(p["flag1"]).astype(np.int32) for p in pr], [p["minmax1"] for p in pr],
+                                    self.gaussian1._scale_bound_value, names)
+            parts2 = []
+            for p in pr:                # right view, per pair
+                p["x1_hat"] = self.decoder1.reconstruct(p["y1_hat"])
+                y2 = self.encoder2.forward_views(_hip.warp_perspective(p["x1"], p["m_fwd"], (H, W)), p["x2"])
+                z2 = self._h_a2(y2)
+                p["z2_strings"] = self.entropy_bottleneck2.compress(z2)
+                p["z2_hat"] = self.entropy_bottleneck2.decompress(p["z2_strings"], z2.size()[-2:])
+                p["y2_hat"] = _hip.quantize(y2, "dequantize")
+                p["flag2"], p["minmax2"] = self._channel_flags(p["y2_hat"])
+                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w, pixel_list=False)
+                parts2.append(params2)
+            s_y2 = self._code_views(parts2, self._h_s2_same_resolution, self.context_prediction2, 5 * M, torch.cat([p["y2_hat"] for p in pr]),
+                                    [np.flatnonzero(p["flag2"]).astype(np.int32) for p in pr], [p["minmax2"] for p in pr],
+                                    self.gaussian2._scale_bound_value, names)
+            for p in pr:
+                p["x2_hat"] = self.decoder2(p["y2_hat"], p["x1_hat_warp"])
+        nbytes = [self._write_pair(output_path, names[i], H, W, ((p["z1_strings"][0], p["flag1"], p["minmax1"], s_y1[i]),
+                                                                  (p["z2_strings"][0], p["flag2"], p["minmax2"], s_y2[i])), fp8_table)
+                  for i, p in enumerate(pr)]
+        out = {k: torch.cat([p[k] for p in pr]) for k in ("x1_hat", "x2_hat", "y1_hat", "y2_hat", "z1_hat", "z2_hat")}
+        out.update(bytes=nbytes, bpp=[n * 8.0 / (H * W) for n in nbytes])
+        return out
+
+    def decompress_batch(self, output_names, h_matrix, output_path=""):
+        """decompress for B pairs written by compress or compress_batch (one picture size, the current operand mode, in the fp8 mode
+        one activation-scale table) -> decompress's dict with [B, ...] tensors; slice i equals decompress of pair i alone."""
+        names = [str(n) for n in output_names]
+        B = len(names)
+        self._batch_check(B, names)
+        if h_matrix.shape[0] != B:
+            raise ValueError("HSIC.decompress_batch: h_matrix must hold one matrix per name")
+        M = self.M
+        dev = self.encoder1.g_a_conv1.weight.device
+        files = [self._read_pair(output_path, n, dev, who=f"HSIC.decompress_batch: pair {i} ({n})") for i, n in enumerate(names)]
+        H, W = files[0][:2]
+        for i, f in enumerate(files):
+            if f[:2] != (H, W):
+                raise ValueError(f"HSIC.decompress_batch: pair {i} ({names[i]}) is {f[0]}x{f[1]}, pair 0 is {H}x{W}: one picture size per batch")
+            if f[4] != files[0][4]:
+                raise ValueError(f"HSIC.decompress_batch: pair {i} ({names[i]}) carries other fp8 activation scales than pair 0: "
+                                 "one calibration per batch")
+        self._batch_check(B, names, H, W)
+        h, w = H // 16, W // 16
+        views = [f[2] for f in files]
+        with torch.no_grad(), _fp8.stream_scales(self, files[0][4]):
+            pr = []
+            for i in range(B):
+                m_fwd, m_back = _warp_matrices(h_matrix[i:i + 1], (H, W), (H, W), want_inverse=True)
+                pr.append(dict(m_fwd=m_fwd, m_back=m_back,
+                               z1_hat=self.entropy_bottleneck1.decompress([views[i][0][0]], (h // 4, w // 4)),
+                               z2_hat=self.entropy_bottleneck2.decompress([views[i][1][0]], (h // 4, w // 4))))
+            y1_hat = self._decode_views([self._left_params_fn(p["z1_hat"], h, w, pixel_list=False) for p in pr], self._h_s1_same_resolution,
+                                        self.context_prediction1, 4 * M, [f[3][0] for f in files], (h, w), [v[0][2] for v in views],
+                                        [v[0][1] for v in views], self.gaussian1._scale_bound_value, names, dev)
+            parts2 = []
+            for i, p in enumerate(pr):
+                p["y1_hat"] = y1_hat[i:i + 1]
+                p["x1_hat"] = self.decoder1.reconstruct(p["y1_hat"])
+                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w, pixel_list=False)
+                parts2.append(params2)
+            y2_hat = self._decode_views(parts2, self._h_s2_same_resolution, self.context_prediction2, 5 * M, [f[3][1] for f in files], (h, w),
+                                        [v[1][2] for v in views], [v[1][1] for v in views], self.gaussian2._scale_bound_value, names, dev)
+            for i, p in enumerate(pr):
+                p["y2_hat"] = y2_hat[i:i + 1]
+                p["x2_hat"] = self.decoder2(p["y2_hat"], p["x1_hat_warp"])
+        return {k: torch.cat([p[k] for p in pr]) for k in ("x1_hat", "x2_hat", "y1_hat", "y2_hat", "z1_hat", "z2_hat")}
+
+
+class _pair_errors:
+    """Coding errors of the per-pair path of compress_batch / decompress_batch name their pair, as the batched kernels' do."""
+
+    def __init__(self, i, name):
+        self.i, self.name = i, name
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, et, ev, tb):
+        if et is not None and issubclass(et, (RuntimeError, ValueError)) and not isinstance(ev, torch.cuda.OutOfMemoryError):
+            raise (ValueError if issubclass(et, ValueError) else RuntimeError)(f"{ev} -- pair {self.i} ({self.name}) of the batch") from ev
+        return False
 
 
 # ------------------------------------------------------------------------------------------ CQE network

@@ -628,6 +628,37 @@ int masic_gmm_cdf_rows_at(const float* sigma, const float* mu, const float* logi
 int masic_rans_decode_step(const uint32_t* words, const uint32_t* word_off, const uint32_t* word_cnt, uint64_t* state, uint32_t* pos,
                            const uint16_t* starts, const int32_t* pix_all, int32_t* step, int npix, const int32_t* chan, int nch,
                            int L, int minmax, float* y_hat, void* y_f16k, int HW, int32_t* err_flag, int32_t* done, void* stream);
+/* Batched forms of the three above: the coding steps of B stereo pairs' views in one launch each (HSIC.compress_batch /
+ * decompress_batch, masic_amd/codec.py encode_views / decode_views).  The single-image entry points are the B = 1 case of the same
+ * kernels.  Images are stacked: sigma / mu / logits [B][K*M][HW], y_hat [B][M][HW], y_f16k [B][ceil16(M) / 16][HW][16].
+ * Pixel lists hold entries q = b * HW + p (-1 = padding); the list of image b is pix[(*step) * list_stride + b * npix + i], i < npix
+ * (step nullable for the tables: no offset).  streams: a DEVICE array of nstreams descriptors, one per coded (image, channel):
+ *   img, chan      the image b and latent channel m of the stream;
+ *   minmax         its alphabet 0 .. 2 * minmax (L entries) -- images differ in minmax and in which channels are coded;
+ *   row0, rstride  table row of the stream's pixel i: row0 + i * rstride -- the start_freq row ([rows][2]);
+ *   soff           u16 offset of the starts row of pixel i: soff + i * rstride * L;
+ *   word_off, word_cnt   the stream's 32-bit words inside `words` (reads never go past word_cnt: a short stream sets err bit 2).
+ * Launches: masic_gmm_cdf_rows_batch = npix * nstreams wavefronts (row r = i * nstreams + s); masic_rans_decode_step_batch = one
+ * wavefront per stream, each taking the register form (L <= 64) or the general form for its own stream; the last wave of the launch
+ * to finish (over ALL streams) increments *step.  state[s] / pos[s]: per stream, as above.  err_flags: one caller-zeroed int per image
+ * (bits as above; bit 0 also for a descriptor whose alphabet exceeds 1024 entries).  Asynchronous on `stream`; capturable. */
+typedef struct {
+    int32_t img, chan, minmax, rstride, row0;
+    uint32_t soff, word_off, word_cnt;
+} masic_code_stream_t;
+int masic_gmm_cdf_rows_batch(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
+                             const int32_t* pix, const int32_t* step, int list_stride, int npix,
+                             const masic_code_stream_t* streams, int nstreams, float scale_bound,
+                             const float* y_hat, uint16_t* starts, int32_t* start_freq, int32_t* err_flags, void* stream);
+int masic_rans_decode_step_batch(const uint32_t* words, const masic_code_stream_t* streams, int nstreams, uint64_t* state, uint32_t* pos,
+                                 const uint16_t* starts, const int32_t* pix_all, int list_stride, int32_t* step, int npix, int M,
+                                 float* y_hat, void* y_f16k, int HW, int32_t* err_flags, int32_t* done, void* stream);
+/* masic_skinny_group_fwd over a batch of nimg images: list entries q = b * HW + p name image b, pixel p; x [nimg][Cin / 16][HW][16]
+ * (exactly Cin channels per image), outputs [nimg][out_ctot]..., gate [nimg][gate_ctot][HW].  A masked tap never reads another image
+ * (outside image b reads zeros, as at the picture edge).  A pixel's result depends on its own operands only: the same bits as the
+ * one-image call on that image, whatever the list order and split.  masic_skinny_group_fwd is this with nimg = 1. */
+int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step,
+                                 int list_stride, int npix, int nimg, int h, int w, const float* gate, int gate_ctot, int gate_c, void* stream);
 int masic_rans_decoder_open(const uint8_t* in, size_t in_len, void** handle);
 int masic_rans_decoder_decode_rows(void* handle, const uint16_t* starts, int nrows, int L, int32_t* symbols);
 /* the next n symbols with tables picked by indexes (arguments as masic_rans_decode_with_indexes), keeping the coder state between

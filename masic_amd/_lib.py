@@ -27,6 +27,12 @@ class ConvDesc(ctypes.Structure):
         "gate_ctot", "gate_c", "prec")]
 
 
+class CodeStream(ctypes.Structure):
+    """masic_code_stream_t"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("img", "chan", "minmax", "rstride", "row0")] + \
+               [(n, ctypes.c_uint32) for n in ("soff", "word_off", "word_cnt")]
+
+
 class GemmGroup(ctypes.Structure):
     """masic_gemm_group_t"""
     _fields_ = [("x", c_void_p), ("w_packed", c_void_p), ("wscale", c_void_p), ("bias", c_void_p),
@@ -77,6 +83,9 @@ SIGNATURES = {
     "masic_rans_encode_channels": (c_int, [_P, c_int, c_int, _P, c_size_t, _P, _P]),
     "masic_gmm_cdf_rows_at": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, c_int, c_float, _P, _P, _P]),
     "masic_rans_decode_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
+    "masic_gmm_cdf_rows_batch": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_float, _P, _P, _P, _P, _P]),
+    "masic_rans_decode_step_batch": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
+    "masic_skinny_group_fwd_batch": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P]),
     "masic_rans_decoder_open": (c_int, [_P, c_size_t, _P]),
     "masic_rans_decoder_decode_rows": (c_int, [_P, _P, c_int, c_int, _P]),
     "masic_rans_decoder_close": (None, [_P]),

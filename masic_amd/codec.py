@@ -249,3 +249,180 @@ def decode_view(params_fn, data, shape, M, K, chan, minmax, scale_bound, device,
             device_step()
     check_err(err, "decode")
     return y_hat
+
+
+# ---- B pairs per coding loop (HSIC.compress_batch / decompress_batch).  The per-pair framing and container are those of encode_view /
+# decode_view; the device work of a coding step covers all B pairs: one skinny launch per layer over every pair's pixels (list entries
+# b * h * w + p), one table launch and one decode launch over every pair's channel streams (masic_code_stream_t), so the fixed costs of a
+# step -- launch latency, the graph replay, the serial rANS chain -- are paid once for B pairs.
+class PairStreamError(RuntimeError):
+    """A coding error of one pair of a batch (`pair`: its index)."""
+
+    def __init__(self, pair, msg):
+        super().__init__(msg)
+        self.pair = pair
+
+
+def check_errs(err, what, names=None):
+    """err: one int per pair (the batched kernels' flags) -> PairStreamError naming the first pair with a bit set."""
+    for i, e in enumerate(err.cpu().tolist()):
+        if e:
+            name = f" ({names[i]})" if names is not None else ""
+            try:
+                check_err(torch.tensor([e]), what)
+            except RuntimeError as ex:
+                raise PairStreamError(i, f"{ex} -- pair {i}{name} of the batch") from None
+
+
+def _stream_table(chans, minmaxes, rows_per_stream, device, words=None):
+    """masic_code_stream_t per (pair, coded channel) as an int32 device tensor [n, 8], and the u16 size of the starts buffer.  Pair b's
+    table rows are pixel-major ([pixel][its channels]: start_freq rows row0 + i * nch_b, the layout encode_channels reads), its starts
+    rows a block of rows_per_stream * nch_b rows of its own alphabet.  words: per pair (word offsets, word counts) or None."""
+    rows, row_base, s_base = [], 0, 0
+    for b, (ch, mm) in enumerate(zip(chans, minmaxes)):
+        nch, L = len(ch), 2 * int(mm) + 1
+        for c, m in enumerate(ch):
+            wo, wc = (int(words[b][0][c]), int(words[b][1][c])) if words is not None else (0, 0)
+            rows.append((b, int(m), int(mm), nch, row_base + c, s_base + c * L, wo, wc))
+        row_base += rows_per_stream * nch
+        s_base += rows_per_stream * nch * L
+    t = np.array(rows, dtype=np.int64).reshape(-1, 8).astype(np.uint32).view(np.int32)
+    return torch.from_numpy(np.ascontiguousarray(t)).to(device), len(rows), s_base, row_base
+
+
+def _encode_pairs(jobs):
+    """encode_channels over the pairs of a batch: the host rANS coder releases the GIL (ctypes), so a few threads run the pairs at once."""
+    if len(jobs) == 1:
+        return [encode_channels(*jobs[0])]
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=min(16, len(jobs))) as ex:
+        return list(ex.map(lambda j: encode_channels(*j), jobs))
+
+
+def encode_views(params_fn, y_hat, M, K, chans, minmaxes, scale_bound, names=None):
+    """encode_view for B pairs at once: y_hat [B, M, h, w]; chans / minmaxes: pair b's coded channels (int sequence) and alphabet
+    half-width; params_fn: the pixel-list parameters over B images (HSIC._PixelParams with skinny and B = y_hat.shape[0]).  Returns the
+    B byte strings encode_view would write for each pair alone (the same parameters bit for bit: a pixel's result depends on its own
+    operands only; the same table arithmetic on them)."""
+    if not getattr(params_fn, "skinny", False):
+        raise RuntimeError("masic_amd.codec.encode_views: needs the pixel-list parameter kernels (bf16 operands)")
+    B, _, h, w = y_hat.shape
+    HW, dev = h * w, y_hat.device
+    order = np.concatenate(wavefront_steps(h, w))
+    pix = torch.from_numpy((np.arange(B, dtype=np.int64)[:, None] * HW + order[None, :]).reshape(-1).astype(np.int32)).to(dev)
+    params_fn.set_latent(y_hat)
+    params_fn.run(pix, None, 0, B * HW)
+    desc, n, _, nrows = _stream_table(chans, minmaxes, HW, dev)
+    err = torch.zeros(B, dtype=torch.int32, device=dev)
+    sf = torch.empty((max(nrows, 1), 2), dtype=torch.int32, device=dev)
+    if n:
+        check(lib.masic_gmm_cdf_rows_batch(_p(params_fn.sigma), _p(params_fn.mu), _p(params_fn.logits), M, K, HW, _p(pix), None, B * HW, HW,
+                                           _p(desc), n, float(scale_bound), _p(y_hat), None, _p(sf), _p(err),
+                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gmm_cdf_rows_batch")
+    check_errs(err, "encode", names)
+    sf_h = sf.cpu().numpy()
+    jobs, r0 = [], 0
+    for ch in chans:
+        jobs.append((sf_h[r0:r0 + HW * len(ch)], HW if len(ch) else 0, len(ch)))
+        r0 += HW * len(ch)
+    return _encode_pairs(jobs)
+
+
+_BATCH_LISTS = {}
+
+
+def _batch_step_lists(h, w, B, device):
+    """Per coding step, two int32 [steps][B * h] device lists of entries b * h * w + p (-1 padded), kept per shape: the tables' and the
+    decoder's (pair b's pixels at [b * h, (b + 1) * h), the layout of one pair's list), and the pixel-list kernels' (the same pixels packed
+    to the front: workgroups whose 32 entries are all padding leave at once)."""
+    key = (h, w, B, str(device))
+    t = _BATCH_LISTS.get(key)
+    if t is None:
+        steps = wavefront_steps(h, w)
+        per = np.full((len(steps), B, h), -1, dtype=np.int64)
+        packed = np.full((len(steps), B * h), -1, dtype=np.int64)
+        for i, p in enumerate(steps):
+            q = np.arange(B, dtype=np.int64)[:, None] * (h * w) + p[None, :]
+            per[i, :, :p.size] = q
+            packed[i, :q.size] = q.reshape(-1)
+        if len(_BATCH_LISTS) >= 16:
+            _BATCH_LISTS.clear()
+        t = _BATCH_LISTS[key] = tuple(torch.from_numpy(a.reshape(-1).astype(np.int32)).to(device) for a in (per, packed))
+    return t
+
+
+def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, device, names=None, use_graph=True):
+    """decode_view for B pairs at once (datas: pair b's y stream as encode_view / encode_views framed it) -> y_hat [B, M, h, w], every
+    slice equal to what decode_view returns for that pair alone.  One captured step covers all pairs: the pixel-list layers over every
+    pair's wavefront, one table launch and one decode launch over every pair's channel streams; replayed w + 3 (h - 1) times.  A stream
+    error names its pair (PairStreamError)."""
+    h, w = shape
+    B, HW = len(datas), h * w
+    if not getattr(params_fn, "skinny", False):
+        raise RuntimeError("masic_amd.codec.decode_views: needs the pixel-list parameter kernels (bf16 operands)")
+    y_hat = torch.zeros((B, M, h, w), dtype=torch.float32, device=device)
+    blobs, wo, wc, base = [], [], [], 0
+    for b, data in enumerate(datas):
+        streams, _ = split_channels(data)
+        nch = len(chans[b])
+        if len(streams) != nch or any(len(s_) < 8 or len(s_) % 4 for s_ in streams):
+            name = f" ({names[b]})" if names is not None else ""
+            raise ValueError(f"masic_amd.codec: the y stream of pair {b}{name} does not hold one rANS stream per coded channel")
+        cnt = np.array([len(s_) // 4 for s_ in streams], dtype=np.int64)
+        wo.append(base + np.cumsum(cnt) - cnt)
+        wc.append(cnt)
+        base += int(cnt.sum())
+        blobs.extend(streams)
+    if not blobs:
+        return y_hat
+    desc, n, nstarts, _ = _stream_table(chans, minmaxes, h, device, words=list(zip(wo, wc)))
+    words = np.frombuffer(b"".join(blobs), dtype=np.uint32)
+    off = np.concatenate(wo)
+    state0 = words[off].astype(np.uint64) | (words[off + 1].astype(np.uint64) << np.uint64(32))
+    words_d = torch.from_numpy(words.copy().view(np.int32)).to(device)
+    state_init = torch.from_numpy(state0.view(np.int64)).to(device)
+    state_d = state_init.clone()
+    pos_d = torch.full((n,), 2, dtype=torch.int32, device=device)
+    step_d = torch.zeros(1, dtype=torch.int32, device=device)
+    done_d = torch.zeros(1, dtype=torch.int32, device=device)
+    err = torch.zeros(B, dtype=torch.int32, device=device)
+    starts = torch.empty(nstarts, dtype=torch.int16, device=device)
+    pix_d, pix_packed = _batch_step_lists(h, w, B, device)
+    y16 = params_fn.y16
+
+    def device_step():
+        params_fn.run(pix_packed, step_d, B * h, B * h)
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(lib.masic_gmm_cdf_rows_batch(_p(params_fn.sigma), _p(params_fn.mu), _p(params_fn.logits), M, K, HW, _p(pix_d), _p(step_d), B * h, h,
+                                           _p(desc), n, float(scale_bound), None, _p(starts), None, _p(err), st), "gmm_cdf_rows_batch")
+        check(lib.masic_rans_decode_step_batch(_p(words_d), _p(desc), n, _p(state_d), _p(pos_d), _p(starts), _p(pix_d), B * h, _p(step_d), h, M,
+                                               _p(y_hat), _p(y16), HW, _p(err), _p(done_d), st), "rans_decode_step_batch")
+
+    def reset():
+        y_hat.zero_()
+        y16.zero_()
+        state_d.copy_(state_init)
+        pos_d.fill_(2)
+        step_d.zero_()
+        done_d.zero_()
+        err.zero_()
+
+    nsteps = len(wavefront_steps(h, w))
+    cur = torch.cuda.current_stream()
+    if use_graph:
+        side = torch.cuda.Stream()
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            device_step()                                     # weight packs and allocator warm before the capture (advances the coder: reset below)
+        cur.wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            device_step()
+        reset()
+        for _ in range(nsteps):
+            graph.replay()
+    else:
+        for _ in range(nsteps):
+            device_step()
+    check_errs(err, "decode", names)
+    return y_hat

@@ -23,21 +23,56 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
+// The coded streams of a launch.  Batched form: a device table of masic_code_stream_t, one entry per (pair, coded channel) -- pairs
+// differ in their channel sets and alphabets, and every row uses its own pair's.  One-image form (d == null): stream s is channel
+// chan[s] of image 0 with the launch's minmax, rows s, s + nch, ... (pixel-major) and words word_off[s] / word_cnt[s] -- the layout of the
+// single-pair entry points, which are this form of the same kernels.
+struct Streams {
+    const masic_code_stream_t* d;
+    const int* chan;
+    const unsigned* word_off;
+    const unsigned* word_cnt;
+    int n, minmax;
+};
+
+__device__ __forceinline__ masic_code_stream_t stream_at(const Streams& S, int s) {
+    if (S.d != nullptr) return S.d[s];
+    masic_code_stream_t t;
+    t.img = 0;
+    t.chan = S.chan[s];
+    t.minmax = S.minmax;
+    t.rstride = S.n;
+    t.row0 = s;
+    t.soff = (unsigned)s * (unsigned)(2 * S.minmax + 1);
+    t.word_off = S.word_off != nullptr ? S.word_off[s] : 0u;
+    t.word_cnt = S.word_cnt != nullptr ? S.word_cnt[s] : 0u;
+    return t;
+}
+
+// one wavefront per (pixel i, stream s) row, block r = i * nstreams + s; the pixel is entry img * npix + i of the list, q = img * HW + p
 template <int K>
 __global__ __launch_bounds__(64) void gmm_cdf_kernel(const float* __restrict__ sigma, const float* __restrict__ mu,
                                                      const float* __restrict__ logits, int M, int HW,
-                                                     const int* __restrict__ pix, const int* __restrict__ chan, int nch,
-                                                     int minmax, float scale_bound, const float* __restrict__ y_hat,
+                                                     const int* __restrict__ pix, int list_stride, const Streams S,
+                                                     float scale_bound, const float* __restrict__ y_hat,
                                                      unsigned short* __restrict__ starts, int* __restrict__ start_freq,
                                                      int* __restrict__ err, const int* __restrict__ step, int npix) {
     __shared__ float pm[CDF_MAX_L];
     __shared__ unsigned fr[CDF_MAX_L];
     const int r = blockIdx.x, lane = threadIdx.x;
-    if (step != nullptr) pix += (size_t)(*step) * npix;    // the wavefront list of coding step *step (device-side loop of the decoder)
-    const int p = pix[r / nch], m = chan[r % nch];
-    if (p < 0) return;                                     // padding entry of a fixed-size wavefront list (graph replay)
+    const int i = r / S.n;
+    const masic_code_stream_t sd = stream_at(S, r - i * S.n);
+    if (step != nullptr) pix += (size_t)(*step) * list_stride;   // the wavefront list of coding step *step (device-side loop of the decoder)
+    const int q = pix[(size_t)sd.img * npix + i], m = sd.chan, minmax = sd.minmax, b = sd.img;
+    if (q < 0) return;                                     // padding entry of a fixed-size wavefront list (graph replay)
     const int L = 2 * minmax + 1;
-    const size_t base = (size_t)m * HW + p, ks = (size_t)M * HW;
+    if (minmax < 1 || L > CDF_MAX_L) {                     // a descriptor the tables cannot hold
+        if (lane == 0) atomicOr(err + b, 1);
+        return;
+    }
+    const int p = q - b * HW;
+    const int row = sd.row0 + i * sd.rstride;
+    const size_t base = ((size_t)b * K * M + m) * HW + p, ks = (size_t)M * HW;
     float wk[K], sk[K], mk[K];
     float mx = -INFINITY;
 #pragma unroll
@@ -70,12 +105,12 @@ __global__ __launch_bounds__(64) void gmm_cdf_kernel(const float* __restrict__ s
         pm[s] = l;
         part += l;
     }
-    const float S = wave_sum(part);
+    const float Ssum = wave_sum(part);
     unsigned tot = 0, best = 0;
     int besti = 0x7fffffff;
     for (int s = s0; s < s1; ++s) {
-        const float q = rintf(pm[s] / S * 65536.0f);
-        const unsigned f = q < 1.0f ? 1u : (unsigned)q;
+        const float qq = rintf(pm[s] / Ssum * 65536.0f);
+        const unsigned f = qq < 1.0f ? 1u : (unsigned)qq;
         fr[s] = f;
         tot += f;
         if (f > best) { best = f; besti = s; }
@@ -90,7 +125,7 @@ __global__ __launch_bounds__(64) void gmm_cdf_kernel(const float* __restrict__ s
     }
     const int fixed = (int)best + (65536 - (int)T);
     if (fixed < 1) {
-        if (lane == 0) atomicOr(err, 1);
+        if (lane == 0) atomicOr(err + b, 1);
         return;
     }
     __syncthreads();
@@ -107,25 +142,26 @@ __global__ __launch_bounds__(64) void gmm_cdf_kernel(const float* __restrict__ s
     unsigned st = incl - run;
     int sym = -1;
     if (y_hat != nullptr) {
-        sym = (int)y_hat[base] + minmax;
-        if ((sym < 0 || sym >= L) && lane == 0) atomicOr(err, 2);
+        sym = (int)y_hat[((size_t)b * M + m) * HW + p] + minmax;
+        if ((sym < 0 || sym >= L) && lane == 0) atomicOr(err + b, 2);
     }
+    unsigned short* srow = starts != nullptr ? starts + sd.soff + (size_t)i * sd.rstride * L : nullptr;
     for (int s = s0; s < s1; ++s) {
-        if (starts != nullptr) starts[(size_t)r * L + s] = (unsigned short)st;
-        if (s == sym) { start_freq[2 * r] = (int)st; start_freq[2 * r + 1] = (int)fr[s]; }
+        if (srow != nullptr) srow[s] = (unsigned short)st;
+        if (s == sym) { start_freq[2 * (size_t)row] = (int)st; start_freq[2 * (size_t)row + 1] = (int)fr[s]; }
         st += fr[s];
     }
 }
 
-int cdf_launch(const float* sigma, const float* mu, const float* logits, int M, int K, int HW, const int32_t* pix, const int32_t* step, int npix,
-               const int32_t* chan, int nch, int minmax, float scale_bound, const float* y_hat, uint16_t* starts, int32_t* start_freq,
+int cdf_launch(const float* sigma, const float* mu, const float* logits, int M, int K, int HW, const int32_t* pix, const int32_t* step, int list_stride,
+               int npix, const Streams& S, float scale_bound, const float* y_hat, uint16_t* starts, int32_t* start_freq,
                int32_t* err_flag, void* stream) {
-    const dim3 grid((unsigned)((size_t)npix * nch)), blk(64);
+    const dim3 grid((unsigned)((size_t)npix * S.n)), blk(64);
     hipStream_t st = (hipStream_t)stream;
 #define CDF_CASE(KK)                                                                                                        \
     case KK:                                                                                                                \
-        hipLaunchKernelGGL(gmm_cdf_kernel<KK>, grid, blk, 0, st, sigma, mu, logits, M, HW, (const int*)pix, (const int*)chan, nch, \
-                           minmax, scale_bound, y_hat, (unsigned short*)starts, (int*)start_freq, (int*)err_flag, (const int*)step, npix); \
+        hipLaunchKernelGGL(gmm_cdf_kernel<KK>, grid, blk, 0, st, sigma, mu, logits, M, HW, (const int*)pix, list_stride, S, \
+                           scale_bound, y_hat, (unsigned short*)starts, (int*)start_freq, (int*)err_flag, (const int*)step, npix); \
         break;
     switch (K) { CDF_CASE(1) CDF_CASE(2) CDF_CASE(3) CDF_CASE(4) CDF_CASE(5) CDF_CASE(6) CDF_CASE(7) CDF_CASE(8) }
 #undef CDF_CASE
@@ -139,38 +175,46 @@ int cdf_launch(const float* sigma, const float* mu, const float* logits, int M, 
 // of every row; alphabets up to 64 entries in one register per row, larger ones in strides of 64), and the serial part is registers
 // only: cum = x & 0xffff, one ballot finds the interval, x = freq * (x >> 16) + cum - start, and a 32-bit word is pulled in when x
 // drops below 2^31 (the next words of the stream are prefetched two ahead).  The decoded values go straight into the latent
-// (y_hat[chan][pix] = s - minmax), so the next coding step's context convolution sees them: nothing crosses PCIe inside the loop.
-// *step is incremented by the last wave of the launch to finish (an arrival counter): every wave reads it at its start only, and the
-// next reader is the next launch.
+// (y_hat[img][chan][pix] = s - minmax), so the next coding step's context convolution sees them: nothing crosses PCIe inside the loop.
+// Streams of a batch may differ in alphabet: each wave takes the register or the general form for its own stream.
+// *step is incremented by the last wave of the launch to finish (an arrival counter over all streams): every wave reads it at its
+// start only, and the next reader is the next launch.
 constexpr int DEC_MAX_ROWS = 64;      // rows (pixels) per coding step a wave keeps in registers: a wavefront of the 5x5 mask has <= h of them
-__global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __restrict__ words, const unsigned* __restrict__ word_off,
+__global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __restrict__ words, const Streams S,
                                                               unsigned long long* __restrict__ state, unsigned* __restrict__ pos,
                                                               const unsigned short* __restrict__ starts, const int* __restrict__ pix_all,
-                                                              int* __restrict__ step, int npix, const int* __restrict__ chan, int nch, int L,
-                                                              int minmax, float* __restrict__ y_hat, int HW, const unsigned* __restrict__ word_cnt,
+                                                              int list_stride, int* __restrict__ step, int npix, int M,
+                                                              float* __restrict__ y_hat, int HW,
                                                               int* __restrict__ err, int* __restrict__ done, unsigned short* __restrict__ y16) {
     const int c = blockIdx.x, lane = threadIdx.x;
     const int st = *step;
-    const int* pix = pix_all + (size_t)st * npix;
+    const masic_code_stream_t sd = stream_at(S, c);
+    const int b = sd.img, m = sd.chan, minmax = sd.minmax, L = 2 * minmax + 1;
+    const int* pix = pix_all + (size_t)st * list_stride + (size_t)b * npix;
+    const size_t ybase = (size_t)b * M * HW, y16base = (size_t)b * ((M + 15) / 16 * 16) * HW;
+    const unsigned short* srows = starts + sd.soff;
+    const size_t rs = (size_t)sd.rstride * L;              // u16 entries between the stream's consecutive rows
     const int nL = (L + 63) >> 6;                          // table entries per lane
-    if (nL == 1 && npix <= DEC_MAX_ROWS) {
+    if (minmax < 1 || L > CDF_MAX_L) {
+        if (lane == 0) atomicOr(err + b, 1);
+    } else if (nL == 1 && npix <= DEC_MAX_ROWS) {
         unsigned ent[DEC_MAX_ROWS];                        // entry `lane` of row i (0x10000 past the end: never <= cum)
         int pr[DEC_MAX_ROWS];
 #pragma unroll
         for (int i = 0; i < DEC_MAX_ROWS; ++i) {
             pr[i] = i < npix ? pix[i] : -1;
-            ent[i] = (pr[i] >= 0 && lane < L) ? (unsigned)starts[((size_t)i * nch + c) * L + lane] : 0x10000u;
+            ent[i] = (pr[i] >= 0 && lane < L) ? (unsigned)srows[(size_t)i * rs + lane] : 0x10000u;
         }
         unsigned long long x = state[c];
         unsigned pp = pos[c];
-        const unsigned* w = words + word_off[c];
-        const unsigned wn = word_cnt[c];
+        const unsigned* w = words + sd.word_off;
+        const unsigned wn = sd.word_cnt;
         unsigned w0 = pp < wn ? w[pp] : 0u, w1 = pp + 1 < wn ? w[pp + 1] : 0u;
-        const int m = chan[c];
         bool bad = false;
 #pragma unroll
         for (int i = 0; i < DEC_MAX_ROWS; ++i) {
             if (pr[i] < 0) continue;
+            const int p = pr[i] - b * HW;
             const unsigned cum = (unsigned)(x & 0xffffu);
             const unsigned long long le = __ballot(ent[i] <= cum);          // entries 0 .. s are <= cum (strictly increasing starts)
             const int s = 63 - __builtin_clzll(le | 1ull);
@@ -185,27 +229,27 @@ __global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __
                 w1 = pp + 1 < wn ? w[pp + 1] : 0u;
             }
             if (lane == 0) {
-                y_hat[(size_t)m * HW + pr[i]] = (float)(s - minmax);
-                if (y16 != nullptr) { const __bf16 bv = (__bf16)(float)(s - minmax); y16[((size_t)(m >> 4) * HW + pr[i]) * 16 + (m & 15)] = __builtin_bit_cast(unsigned short, bv); }
+                y_hat[ybase + (size_t)m * HW + p] = (float)(s - minmax);
+                if (y16 != nullptr) { const __bf16 bv = (__bf16)(float)(s - minmax); y16[y16base + ((size_t)(m >> 4) * HW + p) * 16 + (m & 15)] = __builtin_bit_cast(unsigned short, bv); }
             }
         }
         if (lane == 0) {
             state[c] = x;
             pos[c] = pp;
-            if (bad) atomicOr(err, 4);
+            if (bad) atomicOr(err + b, 4);
         }
     } else {
         // general form (alphabets above 64 entries or very tall latents): rows re-read per symbol, entries in strides of 64
         unsigned long long x = state[c];
         unsigned pp = pos[c];
-        const unsigned* w = words + word_off[c];
-        const unsigned wn = word_cnt[c];
-        const int m = chan[c];
+        const unsigned* w = words + sd.word_off;
+        const unsigned wn = sd.word_cnt;
         bool bad = false;
         for (int i = 0; i < npix; ++i) {
-            const int p = pix[i];
-            if (p < 0) continue;
-            const unsigned short* row = starts + ((size_t)i * nch + c) * L;
+            const int q = pix[i];
+            if (q < 0) continue;
+            const int p = q - b * HW;
+            const unsigned short* row = srows + (size_t)i * rs;
             const unsigned cum = (unsigned)(x & 0xffffu);
             int s = -1;
             for (int k = 0; k < nL; ++k) {
@@ -223,21 +267,21 @@ __global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __
                 ++pp;
             }
             if (lane == 0) {
-                y_hat[(size_t)m * HW + p] = (float)(s - minmax);
-                if (y16 != nullptr) { const __bf16 bv = (__bf16)(float)(s - minmax); y16[((size_t)(m >> 4) * HW + p) * 16 + (m & 15)] = __builtin_bit_cast(unsigned short, bv); }
+                y_hat[ybase + (size_t)m * HW + p] = (float)(s - minmax);
+                if (y16 != nullptr) { const __bf16 bv = (__bf16)(float)(s - minmax); y16[y16base + ((size_t)(m >> 4) * HW + p) * 16 + (m & 15)] = __builtin_bit_cast(unsigned short, bv); }
             }
         }
         if (lane == 0) {
             state[c] = x;
             pos[c] = pp;
-            if (bad) atomicOr(err, 4);
+            if (bad) atomicOr(err + b, 4);
         }
     }
     // the last wave to finish moves the loop on: the next launch (the next step's table kernel) reads the new *step
     __threadfence();
     if (lane == 0) {
         const int prev = atomicAdd(done, 1);
-        if (prev == nch - 1) {
+        if (prev == S.n - 1) {
             *done = 0;
             *step = st + 1;
         }
@@ -251,22 +295,19 @@ __global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __
 // word_cnt[c]: first word and number of words of channel c's stream; state[c] / pos[c]: coder state (initialised from the stream's first two
 // words) and next word index (2) -- caller-initialised, kept between steps; pix_all: [nsteps][npix] pixel lists (-1 = padding);
 // done: caller-zeroed int.  err_flag bit 2: a stream ended early.  y_f16k (nullable): the latent also as F16K bf16 [ceil16(M) / 16][HW][16]
-// (exact for |value| <= 256) -- the input layout of the context model's kernels.
+// (exact for |value| <= 256) -- the input layout of the context model's kernels.  One image: the batched kernels with the one-image stream form.
 extern "C" int masic_rans_decode_step(const uint32_t* words, const uint32_t* word_off, const uint32_t* word_cnt, uint64_t* state, uint32_t* pos,
                                       const uint16_t* starts, const int32_t* pix_all, int32_t* step, int npix, const int32_t* chan, int nch,
                                       int L, int minmax, float* y_hat, void* y_f16k, int HW, int32_t* err_flag, int32_t* done, void* stream) {
     MASIC_REQUIRE(words && word_off && word_cnt && state && pos && starts && pix_all && step && chan && y_hat && err_flag && done, MASIC_ERR_ARG,
                   "rans_decode_step: null pointer");
     MASIC_REQUIRE(npix >= 1 && nch >= 1 && L >= 1 && L <= CDF_MAX_L && L == 2 * minmax + 1, MASIC_ERR_SHAPE, "rans_decode_step: bad shape");
-    hipLaunchKernelGGL(rans_decode_step_kernel, dim3(nch), dim3(64), 0, (hipStream_t)stream, (const unsigned*)words, (const unsigned*)word_off,
-                       (unsigned long long*)state, (unsigned*)pos, (const unsigned short*)starts, (const int*)pix_all, (int*)step, npix,
-                       (const int*)chan, nch, L, minmax, y_hat, HW, (const unsigned*)word_cnt, (int*)err_flag, (int*)done, (unsigned short*)y_f16k);
+    const Streams S{nullptr, (const int*)chan, (const unsigned*)word_off, (const unsigned*)word_cnt, nch, minmax};
+    hipLaunchKernelGGL(rans_decode_step_kernel, dim3(nch), dim3(64), 0, (hipStream_t)stream, (const unsigned*)words, S,
+                       (unsigned long long*)state, (unsigned*)pos, (const unsigned short*)starts, (const int*)pix_all, npix, (int*)step, npix, 0,
+                       y_hat, HW, (int*)err_flag, (int*)done, (unsigned short*)y_f16k);
     return masic_launch_status("rans_decode_step");
 }
-
-extern "C" int masic_gmm_cdf_rows_at(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
-                                     const int32_t* pix_all, const int32_t* step, int npix, const int32_t* chan, int nch, int minmax, float scale_bound,
-                                     uint16_t* starts, int32_t* err_flag, void* stream);
 
 extern "C" int masic_gmm_cdf_rows(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
                                   const int32_t* pix, int npix, const int32_t* chan, int nch, int minmax, float scale_bound,
@@ -277,7 +318,8 @@ extern "C" int masic_gmm_cdf_rows(const float* sigma, const float* mu, const flo
     MASIC_REQUIRE(minmax >= 1 && 2 * minmax + 1 <= CDF_MAX_L, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows: minmax=%d (alphabet of at most %d symbols)", minmax, CDF_MAX_L);
     MASIC_REQUIRE(K >= 1 && K <= 8, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows: K=%d", K);
     if (npix <= 0 || nch <= 0) return MASIC_OK;
-    return cdf_launch(sigma, mu, logits, M, K, HW, pix, nullptr, npix, chan, nch, minmax, scale_bound, y_hat, starts, start_freq, err_flag, stream);
+    const Streams S{nullptr, (const int*)chan, nullptr, nullptr, nch, minmax};
+    return cdf_launch(sigma, mu, logits, M, K, HW, pix, nullptr, npix, npix, S, scale_bound, y_hat, starts, start_freq, err_flag, stream);
 }
 
 // the tables of coding step *step (device int): pix_all is [nsteps][npix]
@@ -287,5 +329,34 @@ extern "C" int masic_gmm_cdf_rows_at(const float* sigma, const float* mu, const 
     MASIC_REQUIRE(sigma && mu && logits && pix_all && step && chan && starts && err_flag, MASIC_ERR_ARG, "gmm_cdf_rows_at: null pointer");
     MASIC_REQUIRE(minmax >= 1 && 2 * minmax + 1 <= CDF_MAX_L, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows_at: minmax=%d (alphabet of at most %d symbols)", minmax, CDF_MAX_L);
     MASIC_REQUIRE(K >= 1 && K <= 8 && npix >= 1 && nch >= 1, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows_at: K=%d npix=%d nch=%d", K, npix, nch);
-    return cdf_launch(sigma, mu, logits, M, K, HW, pix_all, step, npix, chan, nch, minmax, scale_bound, nullptr, starts, nullptr, err_flag, stream);
+    const Streams S{nullptr, (const int*)chan, nullptr, nullptr, nch, minmax};
+    return cdf_launch(sigma, mu, logits, M, K, HW, pix_all, step, npix, npix, S, scale_bound, nullptr, starts, nullptr, err_flag, stream);
+}
+
+// ---- batched forms (B pairs per launch; include/masic_hip.h): a stream table instead of (chan, nch, minmax), one err int per image
+extern "C" int masic_gmm_cdf_rows_batch(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
+                                        const int32_t* pix, const int32_t* step, int list_stride, int npix,
+                                        const masic_code_stream_t* streams, int nstreams, float scale_bound,
+                                        const float* y_hat, uint16_t* starts, int32_t* start_freq, int32_t* err_flags, void* stream) {
+    MASIC_REQUIRE(sigma && mu && logits && pix && streams && err_flags, MASIC_ERR_ARG, "gmm_cdf_rows_batch: null pointer");
+    MASIC_REQUIRE((y_hat != nullptr) == (start_freq != nullptr), MASIC_ERR_ARG, "gmm_cdf_rows_batch: y_hat and start_freq go together");
+    MASIC_REQUIRE(starts || start_freq, MASIC_ERR_ARG, "gmm_cdf_rows_batch: no output requested");
+    MASIC_REQUIRE(K >= 1 && K <= 8, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows_batch: K=%d", K);
+    MASIC_REQUIRE(npix >= 1 && nstreams >= 0 && list_stride >= npix, MASIC_ERR_SHAPE, "gmm_cdf_rows_batch: bad shape");
+    if (nstreams == 0) return MASIC_OK;
+    const Streams S{streams, nullptr, nullptr, nullptr, nstreams, 0};
+    return cdf_launch(sigma, mu, logits, M, K, HW, pix, step, list_stride, npix, S, scale_bound, y_hat, starts, start_freq, err_flags, stream);
+}
+
+extern "C" int masic_rans_decode_step_batch(const uint32_t* words, const masic_code_stream_t* streams, int nstreams, uint64_t* state, uint32_t* pos,
+                                            const uint16_t* starts, const int32_t* pix_all, int list_stride, int32_t* step, int npix, int M,
+                                            float* y_hat, void* y_f16k, int HW, int32_t* err_flags, int32_t* done, void* stream) {
+    MASIC_REQUIRE(words && streams && state && pos && starts && pix_all && step && y_hat && err_flags && done, MASIC_ERR_ARG,
+                  "rans_decode_step_batch: null pointer");
+    MASIC_REQUIRE(npix >= 1 && nstreams >= 1 && M >= 1 && list_stride >= npix, MASIC_ERR_SHAPE, "rans_decode_step_batch: bad shape");
+    const Streams S{streams, nullptr, nullptr, nullptr, nstreams, 0};
+    hipLaunchKernelGGL(rans_decode_step_kernel, dim3(nstreams), dim3(64), 0, (hipStream_t)stream, (const unsigned*)words, S,
+                       (unsigned long long*)state, (unsigned*)pos, (const unsigned short*)starts, (const int*)pix_all, list_stride, (int*)step, npix, M,
+                       y_hat, HW, (int*)err_flags, (int*)done, (unsigned short*)y_f16k);
+    return masic_launch_status("rans_decode_step_batch");
 }

@@ -17,7 +17,10 @@
 //     the same way.  A pixel's result depends on that pixel's operands and the fixed k order only: encoder (all pixels at once) and
 //     decoder (a wavefront at a time) get bit-identical parameters, which is what makes their coding tables agree.
 // The pixel list of a launch is pix[(*step) * list_stride + i], i < npix (step: device int or null) -- the decoder replays one captured
-// graph per coding step and the step counter lives on the device (codec.hip: masic_rans_decode_step).
+// graph per coding step and the step counter lives on the device (codec.hip: masic_rans_decode_step).  A list entry q names image
+// b = q / HW, pixel p = q % HW of a batch of nimg images: every buffer is [nimg][image] with its own per-image stride, the masked taps
+// stay inside image b (out-of-range rows / columns read zeros as at the picture edge), so a pixel's result still depends on its own
+// operands alone -- batched and one-image launches, in any list order and split, give the same bits.  One image: entries are p.
 #include "common.h"
 
 #include <type_traits>
@@ -44,11 +47,11 @@ __device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
 }
 
 struct SkGroup {
-    const unsigned short* x;      // F16K [Cin16][HW][16] of one image
+    const unsigned short* x;      // F16K [nimg][Cin16][HW][16]
     const unsigned short* w;      // GEMM pack [cb][nk16][hh][co 128][8]; context model: [co tile][step][lane][8] (pack_ctx_skinny_kernel)
     const float* bias;            // [Cout] or null
-    unsigned short* y16;          // F16K [out_ctot / 16][HW][16] or null
-    float* y32;                   // float32 [out_ctot][HW] or null
+    unsigned short* y16;          // F16K [nimg][out_ctot / 16][HW][16] or null
+    float* y32;                   // float32 [nimg][out_ctot][HW] or null
     int Cin16, nsteps, Cout, out_ctot, out_coff, act;
 };
 constexpr int SK_MAXG = 3;
@@ -58,9 +61,9 @@ struct SkArgs {
     int n;
     const int* pix;
     const int* step;
-    int list_stride, npix, HW, h, w;
-    const float* gate;            // [gate_ctot][HW] float32 or null: multiplied after the activation (mask2weights gates of the right view)
-    int gate_c;
+    int list_stride, npix, HW, h, w, nimg;
+    const float* gate;            // [nimg][gate_ctot][HW] float32 or null: multiplied after the activation (mask2weights gates of the right view)
+    int gate_c, gate_ctot;
 };
 
 constexpr int SK_CH = 8;          // k-steps per load batch and wave
@@ -79,24 +82,28 @@ __global__ __launch_bounds__(NW * 64) void skinny_f16k(const SkArgs a) {
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int* pix = a.pix + (a.step != nullptr ? (size_t)(*a.step) * a.list_stride : 0);
     const int pi = blockIdx.y * 32 + j;
-    const int p = pi < a.npix ? pix[pi] : -1;
+    const int q = pi < a.npix ? pix[pi] : -1;
+    const int qb = q >= 0 ? q / a.HW : 0;                             // entries past the batch are skipped like padding
+    const int b = qb < a.nimg ? qb : 0, p = (q >= 0 && qb < a.nimg) ? q - qb * a.HW : -1;
+    if (__ballot(p >= 0) == 0) return;                                // a tile of padding only (every wave of the workgroup sees the same pixels)
     const int nsteps = g.nsteps;
     size_t wbytes;
     if (CTX) wbytes = (size_t)((g.Cout + 31) / 32) * nsteps * 1024;
     else wbytes = (size_t)((g.Cout + 127) / 128) * nsteps * 4096;
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, (int)wbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)g.x, 0, g.Cin16 * a.HW * 32, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)g.x, 0, a.nimg * g.Cin16 * a.HW * 32, 0x00020000);
+    const unsigned xoff = (unsigned)(b * g.Cin16 * a.HW) * 32u;       // image b's records
     const unsigned wlane = CTX ? (unsigned)(ct * nsteps) * 1024u + lane * 16u
                                : (unsigned)((ct >> 2) * nsteps) * 4096u + h * 2048u + ((ct & 3) * 32 + j) * 16u;
     const unsigned wstep = CTX ? 1024u : 4096u;
     const int pr = p >= 0 ? p / a.w : 0, pc = p >= 0 ? p - pr * a.w : 0;
     auto boff = [&](int s) -> unsigned {                              // the lane's activation operand of k-step s
         if (p < 0 || s >= nsteps) return SK_OOR;
-        if (!CTX) return s < g.Cin16 ? (unsigned)(s * a.HW + p) * 32u + 16u * h : SK_OOR;
+        if (!CTX) return s < g.Cin16 ? xoff + (unsigned)(s * a.HW + p) * 32u + 16u * h : SK_OOR;
         const int tap = s / g.Cin16, k16 = s - tap * g.Cin16;         // live taps of the type-A 5x5 mask: rows -2, -1 (5 columns each), row 0 columns -2, -1
         const int dy = tap < 10 ? tap / 5 - 2 : 0, dx = tap < 10 ? tap % 5 - 2 : tap - 12;
         const int r = pr + dy, c = pc + dx;
-        return (r >= 0 && c >= 0 && c < a.w) ? (unsigned)(k16 * a.HW + r * a.w + c) * 32u + 16u * h : SK_OOR;
+        return (r >= 0 && c >= 0 && c < a.w) ? xoff + (unsigned)(k16 * a.HW + r * a.w + c) * 32u + 16u * h : SK_OOR;
     };
     v4u A[2][SK_CH], Bq[2][SK_CH];
     auto load = [&](auto PB, int base) {
@@ -145,12 +152,12 @@ __global__ __launch_bounds__(NW * 64) void skinny_f16k(const SkArgs a) {
         for (int e = 0; e < 16; ++e) acc[e] += g.bias[c0 + 4 * h + (e & 3) + 8 * (e >> 2)];
     }
     float gv = 1.0f;
-    if (a.gate != nullptr && p >= 0) gv = a.gate[(size_t)a.gate_c * a.HW + p];
+    if (a.gate != nullptr && p >= 0) gv = a.gate[((size_t)b * a.gate_ctot + a.gate_c) * a.HW + p];
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = apply_act(acc[e], g.act) * gv;
     if (g.y16 != nullptr) {
         // F16K: the two halves of the wave swap quarters so that lane (j, h) holds channels 8 h .. 8 h + 7 of each 16-channel record
-        unsigned short* rec = g.y16 + (((size_t)((g.out_coff + c0) >> 4)) * a.HW + (p >= 0 ? p : 0)) * 16 + 8 * h;
+        unsigned short* rec = g.y16 + (size_t)b * g.out_ctot * a.HW + (((size_t)((g.out_coff + c0) >> 4)) * a.HW + (p >= 0 ? p : 0)) * 16 + 8 * h;
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const unsigned a0 = pack2bf(acc[8 * r + 0], acc[8 * r + 1]), a1 = pack2bf(acc[8 * r + 2], acc[8 * r + 3]);
@@ -162,7 +169,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_f16k(const SkArgs a) {
             if (p >= 0) *reinterpret_cast<uint4*>(rec + (size_t)r * a.HW * 16) = st;
         }
     } else if (p >= 0) {
-        float* yb = g.y32 + (size_t)(g.out_coff + c0 + 4 * h) * a.HW + p;
+        float* yb = g.y32 + ((size_t)b * g.out_ctot + g.out_coff + c0 + 4 * h) * a.HW + p;
 #pragma unroll
         for (int e = 0; e < 16; ++e) yb[(size_t)((e & 3) + 8 * (e >> 2)) * a.HW] = acc[e];
     }
@@ -202,12 +209,15 @@ extern "C" int masic_skinny_ctx_pack_weight(const float* w, void* w_packed, int 
 }
 
 // Up to three 1x1 layers (w_packed from masic_gemm_f16k_pack_weight) or ONE 5x5 type-A masked convolution (ctx != 0; w_packed from
-// masic_skinny_ctx_pack_weight, latent h x w) on the pixels pix[(*step) * list_stride + i], i < npix, of one image.  x / y_f16k / y_nchw are
-// FULL-SIZE buffers (HW pixels); only the listed pixels are read (plus, for the masked convolution, their causal neighbours) and written.
-extern "C" int masic_skinny_group_fwd(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step, int list_stride,
-                                      int npix, int h, int w, const float* gate, int gate_c, void* stream) {
+// masic_skinny_ctx_pack_weight, latent h x w) on the pixels pix[(*step) * list_stride + i], i < npix, of a batch of nimg images (entry
+// q = image q / HW, pixel q % HW).  x / y_f16k / y_nchw are FULL-SIZE buffers (nimg x HW pixels, x with exactly Cin channels per image);
+// only the listed pixels are read (plus, for the masked convolution, their causal neighbours in the same image) and written.
+extern "C" int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step,
+                                            int list_stride, int npix, int nimg, int h, int w, const float* gate, int gate_ctot, int gate_c,
+                                            void* stream) {
     MASIC_REQUIRE(groups && pix && ngroups >= 1 && ngroups <= SK_MAXG && (!ctx || ngroups == 1), MASIC_ERR_ARG, "skinny_group_fwd: bad argument");
-    MASIC_REQUIRE(npix >= 1 && h >= 1 && w >= 1, MASIC_ERR_SHAPE, "skinny_group_fwd: bad shape");
+    MASIC_REQUIRE(npix >= 1 && nimg >= 1 && h >= 1 && w >= 1, MASIC_ERR_SHAPE, "skinny_group_fwd: bad shape");
+    MASIC_REQUIRE(gate == nullptr || (gate_c >= 0 && (nimg == 1 || gate_c < gate_ctot)), MASIC_ERR_ARG, "skinny_group_fwd: gate plane");
     SkArgs a{};
     int tiles = 0;
     for (int i = 0; i < ngroups; ++i) {
@@ -217,7 +227,7 @@ extern "C" int masic_skinny_group_fwd(const masic_gemm_group_t* groups, int ngro
         MASIC_REQUIRE(g.Cin > 0 && g.Cin % 16 == 0 && g.Cout > 0 && g.Cout % 32 == 0, MASIC_ERR_UNSUPPORTED, "skinny_group_fwd: needs Cin %% 16 == 0 and Cout %% 32 == 0");
         MASIC_REQUIRE(g.out_coff >= 0 && g.out_coff + g.Cout <= g.out_ctot && (g.y_nchw != nullptr || (g.out_ctot % 16 == 0 && g.out_coff % 16 == 0)), MASIC_ERR_SHAPE,
                       "skinny_group_fwd: output channel view");
-        MASIC_REQUIRE((long)(g.Cin / 16) * h * w * 32 < (1l << 30), MASIC_ERR_UNSUPPORTED, "skinny_group_fwd: activation plane too large for 32-bit offsets");
+        MASIC_REQUIRE((long)nimg * (g.Cin / 16) * h * w * 32 < (1l << 30), MASIC_ERR_UNSUPPORTED, "skinny_group_fwd: activation planes too large for 32-bit offsets");
         const int cin16 = g.Cin / 16;
         a.g[i] = SkGroup{(const unsigned short*)g.x, (const unsigned short*)g.w_packed, g.bias, (unsigned short*)g.y_f16k, g.y_nchw, cin16,
                          ctx ? 12 * cin16 : round_up(cin16, 4), g.Cout, g.out_ctot, g.out_coff, g.act};
@@ -225,10 +235,16 @@ extern "C" int masic_skinny_group_fwd(const masic_gemm_group_t* groups, int ngro
         a.tile_end[i] = tiles;
     }
     a.n = ngroups;
-    a.pix = pix; a.step = step; a.list_stride = list_stride; a.npix = npix; a.HW = h * w; a.h = h; a.w = w;
-    a.gate = gate; a.gate_c = gate_c;
+    a.pix = pix; a.step = step; a.list_stride = list_stride; a.npix = npix; a.HW = h * w; a.h = h; a.w = w; a.nimg = nimg;
+    a.gate = gate; a.gate_c = gate_c; a.gate_ctot = gate_ctot;
     const dim3 grid(tiles, ceil_div(npix, 32));
     if (ctx) hipLaunchKernelGGL((skinny_f16k<8, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((skinny_f16k<4, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
     return masic_launch_status("skinny_group_fwd");
+}
+
+// one image: the batched form with nimg = 1 (list entries are pixel indices)
+extern "C" int masic_skinny_group_fwd(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step, int list_stride,
+                                      int npix, int h, int w, const float* gate, int gate_c, void* stream) {
+    return masic_skinny_group_fwd_batch(groups, ngroups, ctx, pix, step, list_stride, npix, 1, h, w, gate, 0, gate_c, stream);
 }

@@ -1,0 +1,104 @@
+"""HSIC.compress_batch / decompress_batch: encode and decode time per pair at B = 1, 2, 4, 8 (run on the GPU box).
+
+HSIC(128,192,5), bf16 operands, synthetic weights and pairs (masic_amd.synth).  Every (size, B) is warmed up first; each timed run is
+wall time around one call that ends in a device synchronise; the table holds the median of --runs runs divided by B.  B = 1 goes
+through the batched methods too (the single-pair methods' time is printed beside it).  Every decode is checked against its encode.
+  python tools/bench_codec_batch.py [--sizes 512x512,1216x2176] [--batches 1,2,4,8] [--runs 5] [--json out.json]
+  python tools/bench_codec_batch.py --profile-one 512x512:8      (one decode_batch, for rocprofv3 --kernel-trace --stats)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "coremasic", "mywork")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+import torch  # noqa: E402
+
+import MASIC  # noqa: E402
+from masic_amd import nn as mnn, synth  # noqa: E402
+
+FIELDS = ("x1_hat", "x2_hat", "y1_hat", "y2_hat", "z1_hat", "z2_hat")
+
+
+def _timed(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t, r
+
+
+def _model():
+    mnn.set_precision("bf16")
+    net = MASIC.HSIC(128, 192, 5)
+    net.load_state_dict(synth.synth_state_dict(net.state_dict(), seed=100))
+    net = net.cuda().eval()
+    net.update()
+    return net
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="512x512,1216x2176")
+    ap.add_argument("--batches", default="1,2,4,8")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--profile-one", default=None)
+    args = ap.parse_args()
+    net = _model()
+    d = tempfile.mkdtemp()
+    if args.profile_one:
+        size, B = args.profile_one.split(":")
+        H, W = (int(v) for v in size.split("x"))
+        B = int(B)
+        x1, x2, hm = (t.cuda() for t in synth.synth_inputs(B, H, W, seed=100))
+        names = [f"p{i}" for i in range(B)]
+        with torch.no_grad():
+            net.compress_batch(x1, x2, hm, names, d)
+            net.decompress_batch(names, hm, d)
+            t, _ = _timed(lambda: net.decompress_batch(names, hm, d))
+        print(f"profile run: decode {H}x{W} B={B}: {1e3 * t / B:.2f} ms per pair")
+        return
+    rows = []
+    with torch.no_grad():
+        for size in args.sizes.split(","):
+            H, W = (int(v) for v in size.split("x"))
+            Bmax = max(int(b) for b in args.batches.split(","))
+            x1a, x2a, hma = (t.cuda() for t in synth.synth_inputs(Bmax, H, W, seed=100))
+            # single-pair methods, for comparison
+            net.compress(x1a[:1], x2a[:1], hma[:1], "single", d)
+            net.decompress(None, None, hma[:1], "single", d)
+            se = statistics.median(_timed(lambda: net.compress(x1a[:1], x2a[:1], hma[:1], "single", d))[0] for _ in range(args.runs))
+            sd = statistics.median(_timed(lambda: net.decompress(None, None, hma[:1], "single", d))[0] for _ in range(args.runs))
+            print(f"{H}x{W} single-pair compress {1e3 * se:.2f} ms, decompress {1e3 * sd:.2f} ms", flush=True)
+            for B in (int(b) for b in args.batches.split(",")):
+                x1, x2, hm = x1a[:B], x2a[:B], hma[:B]
+                names = [f"b{B}_{i}" for i in range(B)]
+                enc = net.compress_batch(x1, x2, hm, names, d)                     # warm-up (allocator, weight packs, step lists)
+                dec = net.decompress_batch(names, hm, d)
+                assert all(torch.equal(enc[k], dec[k]) for k in FIELDS), "round trip"
+                te = [_timed(lambda: net.compress_batch(x1, x2, hm, names, d))[0] for _ in range(args.runs)]
+                td = [_timed(lambda: net.decompress_batch(names, hm, d))[0] for _ in range(args.runs)]
+                row = {"size": f"{H}x{W}", "B": B, "encode_ms_per_pair": 1e3 * statistics.median(te) / B,
+                       "decode_ms_per_pair": 1e3 * statistics.median(td) / B, "single_encode_ms": 1e3 * se, "single_decode_ms": 1e3 * sd,
+                       "bytes_per_pair": sum(enc["bytes"]) / B}
+                rows.append(row)
+                print(f"{H}x{W} B={B}: encode {row['encode_ms_per_pair']:.2f} ms/pair, decode {row['decode_ms_per_pair']:.2f} ms/pair "
+                      f"({row['bytes_per_pair']:.0f} bytes/pair)", flush=True)
+            del x1a, x2a, hma
+            torch.cuda.empty_cache()
+    print("\n| size | B | encode ms/pair | decode ms/pair |\n|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['size']} | {r['B']} | {r['encode_ms_per_pair']:.2f} | {r['decode_ms_per_pair']:.2f} |")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
