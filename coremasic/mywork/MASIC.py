@@ -991,34 +991,37 @@ class HSIC(CompressionModel):
 
     # ---- bitstream (reference :855-1408).  masic_amd/codec.py holds the wavefront coder; here the model
     # side: which tensors condition the tables of each view, computed identically by compress and decompress.
-    def _codec_check(self, B, H=None, W=None):
+    def _codec_check(self, who, H=None, W=None):
+        if self.training:
+            raise RuntimeError(f"{who}: call .eval() first (the reference quantises with noise in training mode)")
         if H is not None and (H % 64 or W % 64):
             # the header stores H, W and the decoder derives the latent geometry as H//16, H//64 (reference :1308-1322); other
             # sizes would be written with ceil-div latents that decompress cannot reproduce
-            raise ValueError(f"HSIC.compress/decompress: picture size {H}x{W} must be a multiple of 64 in both dimensions "
-                             "(pad the pair as the reference's drivers do)")
-        if self.training:
-            raise RuntimeError("HSIC.compress/decompress: call .eval() first (the reference quantises with noise in training mode)")
-        if B != 1:
-            raise ValueError("HSIC.compress/decompress code one stereo pair per call (the reference codes batch element 0 only)")
+            raise ValueError(f"{who}: picture size {H}x{W} must be a multiple of 64 in both dimensions "
+                             "(pad the pairs as the reference's drivers do)")
 
-    class _PixelParams:
-        """The entropy parameters of a view for the bitstream coder.  Callable: y_hat -> (sigma, mu, logits) over the full latent (the
-        float32 / fp8 form, and the fallback).  With bf16 operands (`skinny`): the same layers evaluated on a LIST OF PIXELS by the kernels
-        of masic_amd/csrc/skinny.hip -- `run(pix, step, list_stride, npix)` reads the latent from `y16` (F16K; the device decoder writes it,
-        the encoder fills it with `set_latent`) and writes `sigma`, `mu`, `logits` ([1, K*M, h, w] float32) at those pixels.  Encoder (all
-        pixels in one launch per layer) and decoder (one coding wavefront per launch) run the same kernels with the same k order, and a
-        pixel's result does not depend on its tile mates: bit-identical parameters on both sides."""
+    class _PairParams:
+        """The entropy parameters of one pair's view for the bitstream coder, as far as they are known before the latent.  Callable:
+        y_hat -> (sigma, mu, logits) over the full latent (the coder's form for float32 / fp8 operands).  cat16 / gate: the view's F16K
+        concat buffer (hyper part filled) and gates, which _batch_params stacks for the pixel-list form."""
 
-        def __init__(self, full, skinny=None, cat16=None, gate=None):
-            self._full, self._sk = full, skinny
-            self.skinny = skinny is not None
-            self.cat16, self.gate = cat16, gate            # the view's F16K concat buffer (hyper part filled) and gates: what a batch stacks
-            if self.skinny:
-                self.y16, self.sigma, self.mu, self.logits = skinny["y16"], skinny["sigma"], skinny["mu"], skinny["logits"]
+        def __init__(self, full, cat16=None, gate=None):
+            self._full, self.cat16, self.gate = full, cat16, gate
 
         def __call__(self, y_hat):
             return self._full(y_hat)
+
+    class _PixelParams:
+        """The same layers, with bf16 operands, evaluated on a LIST OF PIXELS of B pairs by the kernels of masic_amd/csrc/skinny.hip --
+        `run(pix, step, list_stride, npix)` reads the latent from `y16` (F16K; the device decoder writes it, the encoder fills it with
+        `set_latent`) and writes `sigma`, `mu`, `logits` ([B, K*M, h, w] float32) at those pixels.  Encoder (all pixels in one launch
+        per layer) and decoder (one coding wavefront per launch) run the same kernels with the same k order, and a pixel's result does
+        not depend on its tile mates: bit-identical parameters on both sides."""
+        skinny = True
+
+        def __init__(self, sk):
+            self._sk = sk
+            self.y16, self.sigma, self.mu, self.logits = sk["y16"], sk["sigma"], sk["mu"], sk["logits"]
 
         def set_latent(self, y_hat):
             _hip.nchw_to_f16k_view(y_hat.contiguous(), self.y16, self._sk["M16"], 0)
@@ -1029,9 +1032,9 @@ class HSIC(CompressionModel):
             for layers in k["heads"]:
                 _hip.skinny_group(layers, pix, step, list_stride, npix, k["h"], k["w"], nimg=k["B"])
 
-    def _skinny_params(self, head, ctx, cat16, C, h, w, gate=None, B=1):
-        """Buffers and layer descriptions of _PixelParams' pixel-list form, or None when it does not apply (float32 / fp8 operands, widths
-        the kernels are not built for).  B > 1: over a batch of B pairs (cat16 and gate stacked [B, ...])."""
+    def _skinny_params(self, head, ctx, cat16, C, h, w, gate, B):
+        """Buffers and layer descriptions of _PixelParams over B pairs (cat16 and gate stacked [B, ...]), or None when the pixel-list form
+        does not apply (float32 / fp8 operands, widths the kernels are not built for)."""
         from masic_amd import nn as _mnn
         M, K = self.M, self.K
         if (cat16 is None or M % 16 or (2 * M) % 32 or not head._grouped_heads_ok()
@@ -1061,8 +1064,7 @@ class HSIC(CompressionModel):
         ctxl = dict(x=y16, wp=wpc, bias=None if ctx.bias is None else ctx.bias.detach(), Cin=M16, Cout=2 * M, act=_NONE, y16=cat16[0], out_ctot=C, out_coff=2 * M)
         return dict(y16=y16, M16=M16, sigma=outs[0], mu=outs[1], logits=outs[2], ctx=ctxl, heads=heads, h=h, w=w, gate=gate, B=B)
 
-    def _left_params_fn(self, z1_hat, h, w, pixel_list=True):
-        """pixel_list=False: without the pixel-list buffers (a batch builds its own over all pairs, _batch_params)."""
+    def _left_params_fn(self, z1_hat, h, w):
         M = self.M
         # (bf16 operands: the concat buffer is F16K, as in the eval forward -- the context model writes its slice as bf16 records and the
         # grouped head GEMMs read the buffer directly: no conversion pass over the 768-channel buffer per coding step)
@@ -1075,10 +1077,9 @@ class HSIC(CompressionModel):
             if cat16 is not None:
                 return self._h_s1_same_resolution.heads((1, 4 * M, h, w), x16=cat16[0])
             return self._h_s1_same_resolution.heads(cat1)
-        sk = self._skinny_params(self._h_s1_same_resolution, self.context_prediction1, cat16, 4 * M, h, w) if pixel_list else None
-        return HSIC._PixelParams(params, sk, cat16=cat16)
+        return HSIC._PairParams(params, cat16)
 
-    def _right_params_fn(self, z2_hat, x1_hat, m_fwd, m_back, H, W, h, w, pixel_list=True):
+    def _right_params_fn(self, z2_hat, x1_hat, m_fwd, m_back, H, W, h, w):
         """-> (params_fn, x1_hat_warp): everything of the right view's tables that the decoder knows before y2."""
         M = self.M
         dev = z2_hat.device
@@ -1099,8 +1100,7 @@ class HSIC(CompressionModel):
             if cat16 is not None:
                 return self._h_s2_same_resolution.heads((1, 5 * M, h, w), x16=cat16[0])
             return self._h_s2_same_resolution.heads(cat2)
-        sk = self._skinny_params(self._h_s2_same_resolution, self.context_prediction2, cat16, 5 * M, h, w, gate=gates.contiguous()) if pixel_list else None
-        return HSIC._PixelParams(params, sk, cat16=cat16, gate=gates.contiguous()), x1_hat_warp
+        return HSIC._PairParams(params, cat16, gates.contiguous()), x1_hat_warp
 
     @staticmethod
     def _channel_flags(y_hat):
@@ -1109,46 +1109,35 @@ class HSIC(CompressionModel):
         flags = (a.flatten(1).amax(1) > 0).cpu().numpy().astype(np.uint8)
         return flags, max(int(a.max().item()), 1)
 
+    # ---- compress / decompress code one pair per call (the reference's methods), compress_batch / decompress_batch B pairs
+    # (INTEGRATION.md "Batched bitstream coding"); one implementation per direction serves both.  A pair's files do not depend on its
+    # batch mates: the once-per-call work (transforms, hyper path, reconstruction, warp, gates, z coder) runs per pair as B = 1 calls --
+    # several bf16 layers pick or order their kernels by batch shape, so their bits at B > 1 differ from those at B = 1 -- and the
+    # coding-step loops, where the time goes, run over all B pairs at once (codec.encode_views / decode_views).  float32 / fp8 operands
+    # (no pixel-list form) code the pairs one after the other.
     def compress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu"):
         """Writes <output_name>.npz (picture size, z1 / z2 strings, channel flags, minmax: the reference's header layout,
         :916-948) and <output_name>.bin (the y1 / y2 streams, masic_amd/codec.py) under output_path.  `device` is accepted
         for signature compatibility; tensors stay where x1 is."""
-        import os
-        from masic_amd import codec, nn as _mnn
-        x1, x2 = x1.contiguous(), x2.contiguous()
-        B, _, H, W = x1.shape
-        self._codec_check(B, H, W)
-        M, K = self.M, self.K
-        fp8_table = _fp8.stream_table(self) if _mnn.get_precision() == "fp8" else None
-        with torch.no_grad():
-            m_fwd, m_back = _warp_matrices(h_matrix, (H, W), (H, W), want_inverse=True)
-            # left view
-            y1 = self.encoder1.latent(x1)
-            z1 = self._h_a1(y1)
-            z1_strings = self.entropy_bottleneck1.compress(z1)
-            z1_hat = self.entropy_bottleneck1.decompress(z1_strings, z1.size()[-2:])
-            y1_hat = _hip.quantize(y1, "dequantize")
-            h, w = y1.shape[-2:]
-            flag1, minmax1 = self._channel_flags(y1_hat)
-            chan1 = torch.from_numpy(np.flatnonzero(flag1).astype(np.int32)).to(x1.device)
-            bound1 = self.gaussian1._scale_bound_value
-            s_y1 = codec.encode_view(self._left_params_fn(z1_hat, h, w), y1_hat, M, K, chan1, minmax1, bound1)
-            x1_hat = self.decoder1.reconstruct(y1_hat)
-            # right view
-            y2 = self.encoder2.forward_views(_hip.warp_perspective(x1, m_fwd, (H, W)), x2)
-            z2 = self._h_a2(y2)
-            z2_strings = self.entropy_bottleneck2.compress(z2)
-            z2_hat = self.entropy_bottleneck2.decompress(z2_strings, z2.size()[-2:])
-            y2_hat = _hip.quantize(y2, "dequantize")
-            flag2, minmax2 = self._channel_flags(y2_hat)
-            chan2 = torch.from_numpy(np.flatnonzero(flag2).astype(np.int32)).to(x1.device)
-            params2, x1_hat_warp = self._right_params_fn(z2_hat, x1_hat, m_fwd, m_back, H, W, h, w)
-            s_y2 = codec.encode_view(params2, y2_hat, M, K, chan2, minmax2, self.gaussian2._scale_bound_value)
-            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
-        nbytes = self._write_pair(output_path, output_name, H, W, ((z1_strings[0], flag1, minmax1, s_y1), (z2_strings[0], flag2, minmax2, s_y2)),
-                                  fp8_table)
-        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat,
-                "bytes": nbytes, "bpp": nbytes * 8.0 / (H * W)}
+        out = self._compress_pairs("HSIC.compress", x1, x2, h_matrix, [output_name], output_path, batch=False)
+        out["bytes"], out["bpp"] = out["bytes"][0], out["bpp"][0]
+        return out
+
+    def decompress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu"):
+        """Reads the two files compress wrote.  x1 / x2 are not used for decoding (the reference only takes sizes from them,
+        :1308-1310) and may be None; tensors are created on the model's device."""
+        return self._decompress_pairs("HSIC.decompress", [output_name], h_matrix, output_path, batch=False)
+
+    def compress_batch(self, x1, x2, h_matrix, output_names, output_path=""):
+        """compress for B pairs: x1, x2 [B, 3, H, W], h_matrix [B, 3, 3], B output names.  Writes <name_i>.npz / <name_i>.bin, byte for
+        byte what compress(x1[i:i+1], x2[i:i+1], h_matrix[i:i+1], name_i) writes, and returns compress's dict with [B, ...] tensors
+        ("bytes" / "bpp": lists of B)."""
+        return self._compress_pairs("HSIC.compress_batch", x1, x2, h_matrix, output_names, output_path, batch=True)
+
+    def decompress_batch(self, output_names, h_matrix, output_path=""):
+        """decompress for B pairs written by compress or compress_batch (one picture size, the current operand mode, in the fp8 mode
+        one activation-scale table) -> decompress's dict with [B, ...] tensors; slice i equals decompress of pair i alone."""
+        return self._decompress_pairs("HSIC.decompress_batch", output_names, h_matrix, output_path, batch=True)
 
     @staticmethod
     def _write_pair(output_path, output_name, H, W, views, fp8_table):
@@ -1177,8 +1166,8 @@ class HSIC(CompressionModel):
                 f.write(s_y)
         return os.path.getsize(out1) + os.path.getsize(out2)
 
-    def _read_pair(self, output_path, output_name, dev, who="HSIC.decompress"):
-        """The two files of one pair -> H, W, per view (z string, minmax, coded channels as a device int32 tensor), per view the framed
+    def _read_pair(self, output_path, output_name, who):
+        """The two files of one pair -> H, W, per view (z string, minmax, coded channels as a list), per view the framed
         y streams, the fp8 scale table or None.  ValueError for a foreign stream or one written in another operand mode."""
         import os
         from masic_amd import codec, nn as _mnn
@@ -1189,7 +1178,7 @@ class HSIC(CompressionModel):
             for _ in range(2):
                 length, minmax = (int(v) for v in np.frombuffer(f.read(4), dtype=np.uint16))
                 flags = np.unpackbits(np.frombuffer(f.read(M // 8), dtype=np.uint8))
-                views.append((f.read(length), minmax, torch.from_numpy(np.flatnonzero(flags).astype(np.int32)).to(dev)))
+                views.append((f.read(length), minmax, np.flatnonzero(flags).tolist()))
         with open(os.path.join(output_path, str(output_name) + ".bin"), "rb") as f:
             head = f.read(8)
             if head[:4] != codec.MAGIC:
@@ -1211,95 +1200,60 @@ class HSIC(CompressionModel):
                 rest = rest[used:]
         return H, W, views, streams, fp8_table
 
-    def decompress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu"):
-        """Reads the two files compress wrote.  x1 / x2 are not used for decoding (the reference only takes sizes from them,
-        :1308-1310) and may be None; tensors are created on the model's device."""
-        import os
-        from masic_amd import codec, nn as _mnn
-        self._codec_check(1)
-        M, K = self.M, self.K
-        dev = self.encoder1.g_a_conv1.weight.device
-        H, W, views, streams, fp8_table = self._read_pair(output_path, output_name, dev)
-        self._codec_check(1, H, W)
-        h, w = H // 16, W // 16
-        with torch.no_grad(), _fp8.stream_scales(self, fp8_table):
-            m_fwd, m_back = _warp_matrices(h_matrix, (H, W), (H, W), want_inverse=True)
-            z1_hat = self.entropy_bottleneck1.decompress([views[0][0]], (h // 4, w // 4))
-            z2_hat = self.entropy_bottleneck2.decompress([views[1][0]], (h // 4, w // 4))
-            y1_hat = codec.decode_view(self._left_params_fn(z1_hat, h, w), streams[0], (h, w), M, K, views[0][2], views[0][1],
-                                       self.gaussian1._scale_bound_value, dev)
-            x1_hat = self.decoder1.reconstruct(y1_hat)
-            params2, x1_hat_warp = self._right_params_fn(z2_hat, x1_hat, m_fwd, m_back, H, W, h, w)
-            y2_hat = codec.decode_view(params2, streams[1], (h, w), M, K, views[1][2], views[1][1], self.gaussian2._scale_bound_value, dev)
-            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
-        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "y1_hat": y1_hat, "y2_hat": y2_hat, "z1_hat": z1_hat, "z2_hat": z2_hat}
-
-    # ---- B pairs per call (INTEGRATION.md "Batched bitstream coding").  The files are byte for byte those of compress on each pair:
-    # the once-per-call work (transforms, hyper path, reconstruction, warp, gates, z coder) runs per pair as B = 1 calls -- several bf16
-    # layers pick or order their kernels by batch shape, so their bits at B > 1 differ from those at B = 1 -- and the coding-step loops,
-    # where the time goes, run over all B pairs at once (codec.encode_views / decode_views).  float32 / fp8 operands (no pixel-list
-    # form) code the pairs one after the other.
-    def _batch_check(self, B, names, H=None, W=None):
-        if self.training:
-            raise RuntimeError("HSIC.compress_batch/decompress_batch: call .eval() first (the reference quantises with noise in training mode)")
-        if H is not None and (H % 64 or W % 64):
-            raise ValueError(f"HSIC.compress_batch/decompress_batch: picture size {H}x{W} must be a multiple of 64 in both dimensions "
-                             "(pad the pairs as the reference's drivers do)")
-        if B < 1 or len(names) != B:
-            raise ValueError(f"HSIC.compress_batch/decompress_batch: {B} pairs and {len(names)} output names")
-
     def _batch_params(self, parts, head, ctx, C, h, w):
-        """One _PixelParams over the B pairs of `parts` (per-pair params built with pixel_list=False): their concat buffers and gates
-        stacked, the pixel-list buffers sized for B; None when the pixel-list form does not apply."""
+        """One _PixelParams over the B >= 1 pairs of `parts` (_PairParams): their concat buffers and gates stacked, the pixel-list
+        buffers sized for B; None when the pixel-list form does not apply."""
         if any(p.cat16 is None for p in parts):
             return None
         cat = torch.cat([p.cat16[0] for p in parts])
         gate = torch.cat([p.gate for p in parts]) if parts[0].gate is not None else None
-        sk = self._skinny_params(head, ctx, (cat, C), C, h, w, gate=gate, B=len(parts))
-        return None if sk is None else HSIC._PixelParams(None, sk, cat16=(cat, C), gate=gate)
+        sk = self._skinny_params(head, ctx, (cat, C), C, h, w, gate, len(parts))
+        return None if sk is None else HSIC._PixelParams(sk)
 
     def _code_views(self, parts, head, ctx, C, y_hat, chans, minmaxes, bound, names):
-        """compress side of one view over the batch -> per pair the framed y streams."""
+        """compress side of one view over the pairs -> per pair the framed y streams.  names: the pairs' names for error messages (a
+        batch) or None."""
         from masic_amd import codec
         h, w = y_hat.shape[-2:]
         bp = self._batch_params(parts, head, ctx, C, h, w)
         if bp is not None:
-            return codec.encode_views(bp, y_hat, self.M, self.K, [c.tolist() for c in chans], minmaxes, bound, names=names)
+            return codec.encode_views(bp, y_hat, self.M, self.K, chans, minmaxes, bound, names=names)
         out = []
         for i, p in enumerate(parts):
-            chan = torch.from_numpy(chans[i]).to(y_hat.device)
-            with _pair_errors(i, names[i]):
-                out.append(codec.encode_view(p, y_hat[i:i + 1], self.M, self.K, chan, minmaxes[i], bound))
+            with _pair_errors(i, names):
+                out += codec.encode_views(p, y_hat[i:i + 1], self.M, self.K, chans[i:i + 1], minmaxes[i:i + 1], bound)
         return out
 
     def _decode_views(self, parts, head, ctx, C, blobs, hw, chans, minmaxes, bound, names, dev):
-        """decompress side of one view over the batch -> y_hat [B, M, h, w]."""
+        """decompress side of one view over the pairs -> y_hat [B, M, h, w]."""
         from masic_amd import codec
         bp = self._batch_params(parts, head, ctx, C, *hw)
         if bp is not None:
-            return codec.decode_views(bp, blobs, hw, self.M, self.K, [c.cpu().tolist() for c in chans], minmaxes, bound, dev, names=names)
+            return codec.decode_views(bp, blobs, hw, self.M, self.K, chans, minmaxes, bound, dev, names=names)
         out = []
         for i, p in enumerate(parts):
-            with _pair_errors(i, names[i]):
-                out.append(codec.decode_view(p, blobs[i], hw, self.M, self.K, chans[i], minmaxes[i], bound, dev))
+            with _pair_errors(i, names):
+                out.append(codec.decode_views(p, blobs[i:i + 1], hw, self.M, self.K, chans[i:i + 1], minmaxes[i:i + 1], bound, dev))
         return torch.cat(out)
 
-    def compress_batch(self, x1, x2, h_matrix, output_names, output_path=""):
-        """compress for B pairs: x1, x2 [B, 3, H, W], h_matrix [B, 3, 3], B output names.  Writes <name_i>.npz / <name_i>.bin, byte for
-        byte what compress(x1[i:i+1], x2[i:i+1], h_matrix[i:i+1], name_i) writes, and returns compress's dict with [B, ...] tensors
-        ("bytes" / "bpp": lists of B)."""
+    def _compress_pairs(self, who, x1, x2, h_matrix, output_names, output_path, batch):
         from masic_amd import nn as _mnn
         x1, x2 = x1.contiguous(), x2.contiguous()
         B, _, H, W = x1.shape
         names = [str(n) for n in output_names]
-        self._batch_check(B, names, H, W)
-        if x2.shape != x1.shape or h_matrix.shape[0] != B:
-            raise ValueError("HSIC.compress_batch: x1, x2 and h_matrix must hold the same number of pairs")
+        self._codec_check(who, H, W)
+        if not batch and B != 1:
+            raise ValueError(f"{who} codes one stereo pair per call (the reference codes batch element 0 only)")
+        if B < 1 or len(names) != B:
+            raise ValueError(f"{who}: {B} pairs and {len(names)} output names")
+        if batch and (x2.shape != x1.shape or h_matrix.shape[0] != B):
+            raise ValueError(f"{who}: x1, x2 and h_matrix must hold the same number of pairs")
         M = self.M
+        tags = names if batch else None
         fp8_table = _fp8.stream_table(self) if _mnn.get_precision() == "fp8" else None
         pr = []
         with torch.no_grad():
-            for i in range(B):          # left view, per pair (as compress)
+            for i in range(B):          # left view, per pair
                 a, b_ = x1[i:i + 1], x2[i:i + 1]
                 m_fwd, m_back = _warp_matrices(h_matrix[i:i + 1], (H, W), (H, W), want_inverse=True)
                 y1 = self.encoder1.latent(a)
@@ -1311,10 +1265,10 @@ class HSIC(CompressionModel):
                 pr.append(dict(x1=a, x2=b_, m_fwd=m_fwd, m_back=m_back, z1_strings=z1_strings, z1_hat=z1_hat, y1_hat=y1_hat, flag1=flag1,
                                minmax1=minmax1))
             h, w = pr[0]["y1_hat"].shape[-2:]
-            s_y1 = self._code_views([self._left_params_fn(p["z1_hat"], h, w, pixel_list=False) for p in pr], self._h_s1_same_resolution,
+            s_y1 = self._code_views([self._left_params_fn(p["z1_hat"], h, w) for p in pr], self._h_s1_same_resolution,
                                     self.context_prediction1, 4 * M, torch.cat([p["y1_hat"] for p in pr]),
-                                    [np.flatnonzero(p["flag1"]).astype(np.int32) for p in pr], [p["minmax1"] for p in pr],
-                                    self.gaussian1._scale_bound_value, names)
+                                    [np.flatnonzero(p["flag1"]).tolist() for p in pr], [p["minmax1"] for p in pr],
+                                    self.gaussian1._scale_bound_value, tags)
             parts2 = []
             for p in pr:                # right view, per pair
                 p["x1_hat"] = self.decoder1.reconstruct(p["y1_hat"])
@@ -1324,11 +1278,11 @@ class HSIC(CompressionModel):
                 p["z2_hat"] = self.entropy_bottleneck2.decompress(p["z2_strings"], z2.size()[-2:])
                 p["y2_hat"] = _hip.quantize(y2, "dequantize")
                 p["flag2"], p["minmax2"] = self._channel_flags(p["y2_hat"])
-                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w, pixel_list=False)
+                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w)
                 parts2.append(params2)
             s_y2 = self._code_views(parts2, self._h_s2_same_resolution, self.context_prediction2, 5 * M, torch.cat([p["y2_hat"] for p in pr]),
-                                    [np.flatnonzero(p["flag2"]).astype(np.int32) for p in pr], [p["minmax2"] for p in pr],
-                                    self.gaussian2._scale_bound_value, names)
+                                    [np.flatnonzero(p["flag2"]).tolist() for p in pr], [p["minmax2"] for p in pr],
+                                    self.gaussian2._scale_bound_value, tags)
             for p in pr:
                 p["x2_hat"] = self.decoder2(p["y2_hat"], p["x1_hat_warp"])
         nbytes = [self._write_pair(output_path, names[i], H, W, ((p["z1_strings"][0], p["flag1"], p["minmax1"], s_y1[i]),
@@ -1338,25 +1292,25 @@ class HSIC(CompressionModel):
         out.update(bytes=nbytes, bpp=[n * 8.0 / (H * W) for n in nbytes])
         return out
 
-    def decompress_batch(self, output_names, h_matrix, output_path=""):
-        """decompress for B pairs written by compress or compress_batch (one picture size, the current operand mode, in the fp8 mode
-        one activation-scale table) -> decompress's dict with [B, ...] tensors; slice i equals decompress of pair i alone."""
+    def _decompress_pairs(self, who, output_names, h_matrix, output_path, batch):
         names = [str(n) for n in output_names]
         B = len(names)
-        self._batch_check(B, names)
-        if h_matrix.shape[0] != B:
-            raise ValueError("HSIC.decompress_batch: h_matrix must hold one matrix per name")
+        self._codec_check(who)
+        if B < 1:
+            raise ValueError(f"{who}: no output names")
+        if batch and h_matrix.shape[0] != B:
+            raise ValueError(f"{who}: h_matrix must hold one matrix per name")
         M = self.M
+        tags = names if batch else None
         dev = self.encoder1.g_a_conv1.weight.device
-        files = [self._read_pair(output_path, n, dev, who=f"HSIC.decompress_batch: pair {i} ({n})") for i, n in enumerate(names)]
+        files = [self._read_pair(output_path, n, f"{who}: pair {i} ({n})" if batch else who) for i, n in enumerate(names)]
         H, W = files[0][:2]
         for i, f in enumerate(files):
             if f[:2] != (H, W):
-                raise ValueError(f"HSIC.decompress_batch: pair {i} ({names[i]}) is {f[0]}x{f[1]}, pair 0 is {H}x{W}: one picture size per batch")
+                raise ValueError(f"{who}: pair {i} ({names[i]}) is {f[0]}x{f[1]}, pair 0 is {H}x{W}: one picture size per batch")
             if f[4] != files[0][4]:
-                raise ValueError(f"HSIC.decompress_batch: pair {i} ({names[i]}) carries other fp8 activation scales than pair 0: "
-                                 "one calibration per batch")
-        self._batch_check(B, names, H, W)
+                raise ValueError(f"{who}: pair {i} ({names[i]}) carries other fp8 activation scales than pair 0: one calibration per batch")
+        self._codec_check(who, H, W)
         h, w = H // 16, W // 16
         views = [f[2] for f in files]
         with torch.no_grad(), _fp8.stream_scales(self, files[0][4]):
@@ -1366,17 +1320,17 @@ class HSIC(CompressionModel):
                 pr.append(dict(m_fwd=m_fwd, m_back=m_back,
                                z1_hat=self.entropy_bottleneck1.decompress([views[i][0][0]], (h // 4, w // 4)),
                                z2_hat=self.entropy_bottleneck2.decompress([views[i][1][0]], (h // 4, w // 4))))
-            y1_hat = self._decode_views([self._left_params_fn(p["z1_hat"], h, w, pixel_list=False) for p in pr], self._h_s1_same_resolution,
+            y1_hat = self._decode_views([self._left_params_fn(p["z1_hat"], h, w) for p in pr], self._h_s1_same_resolution,
                                         self.context_prediction1, 4 * M, [f[3][0] for f in files], (h, w), [v[0][2] for v in views],
-                                        [v[0][1] for v in views], self.gaussian1._scale_bound_value, names, dev)
+                                        [v[0][1] for v in views], self.gaussian1._scale_bound_value, tags, dev)
             parts2 = []
             for i, p in enumerate(pr):
                 p["y1_hat"] = y1_hat[i:i + 1]
                 p["x1_hat"] = self.decoder1.reconstruct(p["y1_hat"])
-                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w, pixel_list=False)
+                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w)
                 parts2.append(params2)
             y2_hat = self._decode_views(parts2, self._h_s2_same_resolution, self.context_prediction2, 5 * M, [f[3][1] for f in files], (h, w),
-                                        [v[1][2] for v in views], [v[1][1] for v in views], self.gaussian2._scale_bound_value, names, dev)
+                                        [v[1][2] for v in views], [v[1][1] for v in views], self.gaussian2._scale_bound_value, tags, dev)
             for i, p in enumerate(pr):
                 p["y2_hat"] = y2_hat[i:i + 1]
                 p["x2_hat"] = self.decoder2(p["y2_hat"], p["x1_hat_warp"])
@@ -1384,17 +1338,18 @@ class HSIC(CompressionModel):
 
 
 class _pair_errors:
-    """Coding errors of the per-pair path of compress_batch / decompress_batch name their pair, as the batched kernels' do."""
+    """Coding errors of the pair-by-pair path of a batch name their pair, as the batched kernels' do (names None: one pair, no tag)."""
 
-    def __init__(self, i, name):
-        self.i, self.name = i, name
+    def __init__(self, i, names):
+        self.i, self.names = i, names
 
     def __enter__(self):
         return self
 
     def __exit__(self, et, ev, tb):
-        if et is not None and issubclass(et, (RuntimeError, ValueError)) and not isinstance(ev, torch.cuda.OutOfMemoryError):
-            raise (ValueError if issubclass(et, ValueError) else RuntimeError)(f"{ev} -- pair {self.i} ({self.name}) of the batch") from ev
+        if (self.names is not None and et is not None and issubclass(et, (RuntimeError, ValueError))
+                and not isinstance(ev, torch.cuda.OutOfMemoryError)):
+            raise (ValueError if issubclass(et, ValueError) else RuntimeError)(f"{ev} -- pair {self.i} ({self.names[self.i]}) of the batch") from ev
         return False
 
 

@@ -582,18 +582,7 @@ int masic_pair_prep(const uint8_t* img_hwc, int H, int W, int start_h, int start
                     int homopic, int patch_x, int patch_y, int homopatch, float* homo_patch, void* stream);
 
 /* ---- HSIC.compress / decompress (MASIC.py:855-1408), SURVEY.md 8(f)-1: the y1 / y2 streams.
- * Per-symbol coding tables (MASIC.py:986-1044 in compress, :1262-1296 in decompress): the K-component Gaussian-mixture
- * PMF of latent element (pixel pix[i], channel chan[j]) over the alphabet 0 .. 2*minmax, clipped to [2^-16, 1],
- * renormalised to 2^16 and rounded (:1040-1043), the count total then forced to exactly 2^16 at the mode.  sigma / mu /
- * logits: [K*M][HW] head outputs of ONE image (the reference codes batch element 0), logits before the softmax over K.
- * Row r = i * nch + j; a negative pix[i] skips its rows (padding of a fixed-size list).  starts (nullable): [npix*nch][2*minmax+1] u16 interval starts -- the decoder's view;
- * y_hat + start_freq (nullable, together): the integer-valued latent [M][HW] and [npix*nch][2] (start, freq) of its
- * symbols -- the encoder's view.  err_flag (device int, caller-zeroed): bit 0 = a table could not be normalised,
- * bit 1 = a symbol outside the alphabet. */
-int masic_gmm_cdf_rows(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
-                       const int32_t* pix, int npix, const int32_t* chan, int nch, int minmax, float scale_bound,
-                       const float* y_hat, uint16_t* starts, int32_t* start_freq, int32_t* err_flag, void* stream);
-/* rANS with one table per symbol (host).  The reference drives the third-party `range_coder` package here
+ * rANS with one table per symbol (host).  The reference drives the third-party `range_coder` package here
  * (MASIC.py:958, :1044, :1221, :1296), which is not part of its tree: the byte stream of this container is this
  * library's own (64-bit state, 32-bit renormalisation, 16-bit tables: the coder of the z streams above).
  * start_freq: [n][2] intervals in coding order.  The decoder is incremental -- the tables of a wavefront of latent pixels
@@ -604,44 +593,47 @@ int masic_rans_encode_freqs(const int32_t* start_freq, size_t n, uint8_t* out, s
  * [npix * nch][2], row i * nch + c = pixel i (coding order), channel c.  out: the nch streams back to back; lengths[c] bytes each
  * (multiples of 4, >= 8).  Replaces the reference's one `range_coder` stream per view (MASIC.py:1046-1140), whose bytes are parity-unpinned. */
 int masic_rans_encode_channels(const int32_t* start_freq, int npix, int nch, uint8_t* out, size_t out_cap, uint32_t* lengths, size_t* out_len);
-/* Device side of the decoder's loop over coding steps (reference MASIC.py:1262-1408 runs it per symbol on the host):
- * masic_gmm_cdf_rows_at = masic_gmm_cdf_rows (decoder's view) for the pixel list pix_all[*step][npix] (step: device int);
- * masic_rans_decode_step decodes that step's symbols -- one wavefront per channel stream -- writes them into the latent
- * y_hat [M][HW] (value = symbol - minmax at [chan[c]][pix]) and increments *step.  words / word_off / word_cnt: the channel streams
- * as 32-bit little-endian words, first word and word count per channel; state / pos: per-channel coder state and next word index,
- * caller-initialised (state = word0 | word1 << 32, pos = 2) and kept across steps; done: caller-zeroed device int; y_f16k (nullable):
- * the latent also as F16K bf16 [ceil16(M) / 16][HW][16].  err_flag bit 2: a stream ended early.  All pointers device memory; asynchronous on `stream`; capturable into a HIP graph. */
 /* The entropy-parameter layers on a short pixel list (masic_amd/csrc/skinny.hip): up to three 1x1 layers (groups as in
  * masic_gemm_f16k_group_fwd, bf16 operands, w_packed from masic_gemm_f16k_pack_weight) or, with ctx != 0, ONE 5x5 type-A masked
  * convolution (w_packed from masic_skinny_ctx_pack_weight; latent h x w) evaluated at the pixels pix[(*step) * list_stride + i], i < npix
- * (step: device int or NULL), of one image.  x and the outputs are FULL-SIZE buffers (h * w pixels): only the listed pixels are
- * written.  gate (nullable): float32 [.][h * w], plane gate_c multiplies the result after the activation.  A pixel's result does not
- * depend on which other pixels are in the list: the encoder (all pixels, one launch) and the decoder (one coding wavefront per
- * launch) get bit-identical parameters.  Replaces the per-symbol crop + Conv2d calls of MASIC.py:986-1003 / :1262-1280. */
+ * (step: device int or NULL), of a batch of nimg images: list entries q = b * HW + p name image b, pixel p (-1 = padding).
+ * x [nimg][Cin / 16][HW][16] (exactly Cin channels per image) and the outputs [nimg][out_ctot]... are FULL-SIZE buffers: only the
+ * listed pixels are written.  gate (nullable): float32 [nimg][gate_ctot][HW], plane gate_c multiplies the result after the activation.
+ * A masked tap never reads another image (outside image b reads zeros, as at the picture edge).  A pixel's result depends on its own
+ * operands only, whatever the list order and split: the encoder (all pixels, one launch) and the decoder (one coding wavefront per
+ * launch) get bit-identical parameters, for one image or many.  Replaces the per-symbol crop + Conv2d calls of MASIC.py:986-1003 /
+ * :1262-1280. */
 size_t masic_skinny_ctx_packed_bytes(int Cin, int Cout);
 int masic_skinny_ctx_pack_weight(const float* w, void* w_packed, int Cin, int Cout, void* stream);
-int masic_skinny_group_fwd(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step, int list_stride,
-                           int npix, int h, int w, const float* gate, int gate_c, void* stream);
-int masic_gmm_cdf_rows_at(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
-                          const int32_t* pix_all, const int32_t* step, int npix, const int32_t* chan, int nch, int minmax, float scale_bound,
-                          uint16_t* starts, int32_t* err_flag, void* stream);
-int masic_rans_decode_step(const uint32_t* words, const uint32_t* word_off, const uint32_t* word_cnt, uint64_t* state, uint32_t* pos,
-                           const uint16_t* starts, const int32_t* pix_all, int32_t* step, int npix, const int32_t* chan, int nch,
-                           int L, int minmax, float* y_hat, void* y_f16k, int HW, int32_t* err_flag, int32_t* done, void* stream);
-/* Batched forms of the three above: the coding steps of B stereo pairs' views in one launch each (HSIC.compress_batch /
- * decompress_batch, masic_amd/codec.py encode_views / decode_views).  The single-image entry points are the B = 1 case of the same
- * kernels.  Images are stacked: sigma / mu / logits [B][K*M][HW], y_hat [B][M][HW], y_f16k [B][ceil16(M) / 16][HW][16].
- * Pixel lists hold entries q = b * HW + p (-1 = padding); the list of image b is pix[(*step) * list_stride + b * npix + i], i < npix
- * (step nullable for the tables: no offset).  streams: a DEVICE array of nstreams descriptors, one per coded (image, channel):
+int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step,
+                                 int list_stride, int npix, int nimg, int h, int w, const float* gate, int gate_ctot, int gate_c, void* stream);
+/* Per-symbol coding tables (MASIC.py:986-1044 in compress, :1262-1296 in decompress) and the device side of the decoder's loop over
+ * coding steps (MASIC.py:1262-1408 runs it per symbol on the host), for the views of B >= 1 stereo pairs in one launch each
+ * (HSIC.compress / decompress with B = 1, compress_batch / decompress_batch; masic_amd/codec.py encode_views / decode_views).
+ * A table is the K-component Gaussian-mixture PMF of one latent element (image, pixel, channel) over the alphabet 0 .. 2*minmax,
+ * clipped to [2^-16, 1], renormalised to 2^16 and rounded (:1040-1043), the count total then forced to exactly 2^16 at the mode.
+ * Images are stacked: sigma / mu / logits [B][K*M][HW] head outputs (logits before the softmax over K), y_hat [B][M][HW],
+ * y_f16k [B][ceil16(M) / 16][HW][16].  Pixel lists hold entries q = b * HW + p (-1 = padding: its rows are skipped); the list of
+ * image b is pix[(*step) * list_stride + b * npix + i], i < npix (step: device int, nullable for the tables: no offset).
+ * streams: a DEVICE array of nstreams descriptors, one per coded (image, channel):
  *   img, chan      the image b and latent channel m of the stream;
  *   minmax         its alphabet 0 .. 2 * minmax (L entries) -- images differ in minmax and in which channels are coded;
  *   row0, rstride  table row of the stream's pixel i: row0 + i * rstride -- the start_freq row ([rows][2]);
  *   soff           u16 offset of the starts row of pixel i: soff + i * rstride * L;
- *   word_off, word_cnt   the stream's 32-bit words inside `words` (reads never go past word_cnt: a short stream sets err bit 2).
- * Launches: masic_gmm_cdf_rows_batch = npix * nstreams wavefronts (row r = i * nstreams + s); masic_rans_decode_step_batch = one
- * wavefront per stream, each taking the register form (L <= 64) or the general form for its own stream; the last wave of the launch
- * to finish (over ALL streams) increments *step.  state[s] / pos[s]: per stream, as above.  err_flags: one caller-zeroed int per image
- * (bits as above; bit 0 also for a descriptor whose alphabet exceeds 1024 entries).  Asynchronous on `stream`; capturable. */
+ *   word_off, word_cnt   the stream's 32-bit little-endian words inside `words` (reads never go past word_cnt: a short stream sets
+ *                  err bit 2).
+ * One pair with channels chan[0 .. nch): stream c = {0, chan[c], minmax, nch, c, c * L, ...}, the pixel-major rows i * nch + c that
+ * masic_rans_encode_channels reads.
+ * masic_gmm_cdf_rows_batch: npix * nstreams wavefronts (row r = i * nstreams + s).  starts (nullable): u16 interval starts -- the
+ * decoder's view; y_hat + start_freq (nullable, together): the integer-valued latent and the (start, freq) of its symbols -- the
+ * encoder's view.
+ * masic_rans_decode_step_batch: one wavefront per stream decodes the step's symbols, each taking the register form (L <= 64) or the
+ * general form for its own stream, and writes them into the latent (y_hat[b][chan][pix] = symbol - minmax; y_f16k, nullable, the same
+ * as bf16); the last wave of the launch to finish (over ALL streams) increments *step.  state[s] / pos[s]: per-stream coder state
+ * and next word index, caller-initialised (state = word0 | word1 << 32, pos = 2) and kept across steps; done: caller-zeroed device int.
+ * err_flags: one caller-zeroed device int per image: bit 0 = a table could not be normalised, or a descriptor whose alphabet is
+ * empty or exceeds 1024 entries; bit 1 = a symbol outside the alphabet; bit 2 = a stream ended early.
+ * All pointers device memory; asynchronous on `stream`; capturable into a HIP graph. */
 typedef struct {
     int32_t img, chan, minmax, rstride, row0;
     uint32_t soff, word_off, word_cnt;
@@ -653,12 +645,6 @@ int masic_gmm_cdf_rows_batch(const float* sigma, const float* mu, const float* l
 int masic_rans_decode_step_batch(const uint32_t* words, const masic_code_stream_t* streams, int nstreams, uint64_t* state, uint32_t* pos,
                                  const uint16_t* starts, const int32_t* pix_all, int list_stride, int32_t* step, int npix, int M,
                                  float* y_hat, void* y_f16k, int HW, int32_t* err_flags, int32_t* done, void* stream);
-/* masic_skinny_group_fwd over a batch of nimg images: list entries q = b * HW + p name image b, pixel p; x [nimg][Cin / 16][HW][16]
- * (exactly Cin channels per image), outputs [nimg][out_ctot]..., gate [nimg][gate_ctot][HW].  A masked tap never reads another image
- * (outside image b reads zeros, as at the picture edge).  A pixel's result depends on its own operands only: the same bits as the
- * one-image call on that image, whatever the list order and split.  masic_skinny_group_fwd is this with nimg = 1. */
-int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step,
-                                 int list_stride, int npix, int nimg, int h, int w, const float* gate, int gate_ctot, int gate_c, void* stream);
 int masic_rans_decoder_open(const uint8_t* in, size_t in_len, void** handle);
 int masic_rans_decoder_decode_rows(void* handle, const uint16_t* starts, int nrows, int L, int32_t* symbols);
 /* the next n symbols with tables picked by indexes (arguments as masic_rans_decode_with_indexes), keeping the coder state between

@@ -23,45 +23,22 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
-// The coded streams of a launch.  Batched form: a device table of masic_code_stream_t, one entry per (pair, coded channel) -- pairs
-// differ in their channel sets and alphabets, and every row uses its own pair's.  One-image form (d == null): stream s is channel
-// chan[s] of image 0 with the launch's minmax, rows s, s + nch, ... (pixel-major) and words word_off[s] / word_cnt[s] -- the layout of the
-// single-pair entry points, which are this form of the same kernels.
-struct Streams {
-    const masic_code_stream_t* d;
-    const int* chan;
-    const unsigned* word_off;
-    const unsigned* word_cnt;
-    int n, minmax;
-};
-
-__device__ __forceinline__ masic_code_stream_t stream_at(const Streams& S, int s) {
-    if (S.d != nullptr) return S.d[s];
-    masic_code_stream_t t;
-    t.img = 0;
-    t.chan = S.chan[s];
-    t.minmax = S.minmax;
-    t.rstride = S.n;
-    t.row0 = s;
-    t.soff = (unsigned)s * (unsigned)(2 * S.minmax + 1);
-    t.word_off = S.word_off != nullptr ? S.word_off[s] : 0u;
-    t.word_cnt = S.word_cnt != nullptr ? S.word_cnt[s] : 0u;
-    return t;
-}
-
-// one wavefront per (pixel i, stream s) row, block r = i * nstreams + s; the pixel is entry img * npix + i of the list, q = img * HW + p
+// one wavefront per (pixel i, stream s) row, block r = i * nstreams + s; the pixel is entry img * npix + i of the list, q = img * HW + p.
+// streams: the launch's masic_code_stream_t table, one entry per (pair, coded channel) -- pairs differ in their channel sets and
+// alphabets, and every row uses its own pair's.
 template <int K>
 __global__ __launch_bounds__(64) void gmm_cdf_kernel(const float* __restrict__ sigma, const float* __restrict__ mu,
                                                      const float* __restrict__ logits, int M, int HW,
-                                                     const int* __restrict__ pix, int list_stride, const Streams S,
+                                                     const int* __restrict__ pix, int list_stride,
+                                                     const masic_code_stream_t* __restrict__ streams, int nstreams,
                                                      float scale_bound, const float* __restrict__ y_hat,
                                                      unsigned short* __restrict__ starts, int* __restrict__ start_freq,
                                                      int* __restrict__ err, const int* __restrict__ step, int npix) {
     __shared__ float pm[CDF_MAX_L];
     __shared__ unsigned fr[CDF_MAX_L];
     const int r = blockIdx.x, lane = threadIdx.x;
-    const int i = r / S.n;
-    const masic_code_stream_t sd = stream_at(S, r - i * S.n);
+    const int i = r / nstreams;
+    const masic_code_stream_t sd = streams[r - i * nstreams];
     if (step != nullptr) pix += (size_t)(*step) * list_stride;   // the wavefront list of coding step *step (device-side loop of the decoder)
     const int q = pix[(size_t)sd.img * npix + i], m = sd.chan, minmax = sd.minmax, b = sd.img;
     if (q < 0) return;                                     // padding entry of a fixed-size wavefront list (graph replay)
@@ -154,13 +131,13 @@ __global__ __launch_bounds__(64) void gmm_cdf_kernel(const float* __restrict__ s
 }
 
 int cdf_launch(const float* sigma, const float* mu, const float* logits, int M, int K, int HW, const int32_t* pix, const int32_t* step, int list_stride,
-               int npix, const Streams& S, float scale_bound, const float* y_hat, uint16_t* starts, int32_t* start_freq,
+               int npix, const masic_code_stream_t* streams, int nstreams, float scale_bound, const float* y_hat, uint16_t* starts, int32_t* start_freq,
                int32_t* err_flag, void* stream) {
-    const dim3 grid((unsigned)((size_t)npix * S.n)), blk(64);
+    const dim3 grid((unsigned)((size_t)npix * nstreams)), blk(64);
     hipStream_t st = (hipStream_t)stream;
 #define CDF_CASE(KK)                                                                                                        \
     case KK:                                                                                                                \
-        hipLaunchKernelGGL(gmm_cdf_kernel<KK>, grid, blk, 0, st, sigma, mu, logits, M, HW, (const int*)pix, list_stride, S, \
+        hipLaunchKernelGGL(gmm_cdf_kernel<KK>, grid, blk, 0, st, sigma, mu, logits, M, HW, (const int*)pix, list_stride, streams, nstreams, \
                            scale_bound, y_hat, (unsigned short*)starts, (int*)start_freq, (int*)err_flag, (const int*)step, npix); \
         break;
     switch (K) { CDF_CASE(1) CDF_CASE(2) CDF_CASE(3) CDF_CASE(4) CDF_CASE(5) CDF_CASE(6) CDF_CASE(7) CDF_CASE(8) }
@@ -180,7 +157,8 @@ int cdf_launch(const float* sigma, const float* mu, const float* logits, int M, 
 // *step is incremented by the last wave of the launch to finish (an arrival counter over all streams): every wave reads it at its
 // start only, and the next reader is the next launch.
 constexpr int DEC_MAX_ROWS = 64;      // rows (pixels) per coding step a wave keeps in registers: a wavefront of the 5x5 mask has <= h of them
-__global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __restrict__ words, const Streams S,
+__global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __restrict__ words,
+                                                              const masic_code_stream_t* __restrict__ streams, int nstreams,
                                                               unsigned long long* __restrict__ state, unsigned* __restrict__ pos,
                                                               const unsigned short* __restrict__ starts, const int* __restrict__ pix_all,
                                                               int list_stride, int* __restrict__ step, int npix, int M,
@@ -188,7 +166,7 @@ __global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __
                                                               int* __restrict__ err, int* __restrict__ done, unsigned short* __restrict__ y16) {
     const int c = blockIdx.x, lane = threadIdx.x;
     const int st = *step;
-    const masic_code_stream_t sd = stream_at(S, c);
+    const masic_code_stream_t sd = streams[c];
     const int b = sd.img, m = sd.chan, minmax = sd.minmax, L = 2 * minmax + 1;
     const int* pix = pix_all + (size_t)st * list_stride + (size_t)b * npix;
     const size_t ybase = (size_t)b * M * HW, y16base = (size_t)b * ((M + 15) / 16 * 16) * HW;
@@ -281,7 +259,7 @@ __global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __
     __threadfence();
     if (lane == 0) {
         const int prev = atomicAdd(done, 1);
-        if (prev == S.n - 1) {
+        if (prev == nstreams - 1) {
             *done = 0;
             *step = st + 1;
         }
@@ -290,50 +268,13 @@ __global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __
 
 }  // namespace
 
-// Device side of the decoder's loop (one coding step): masic_gmm_cdf_rows_at builds the tables of step *step, masic_rans_decode_step decodes
-// its symbols into the latent and increments *step.  words: all channel streams back to back as little-endian 32-bit words; word_off[c] /
-// word_cnt[c]: first word and number of words of channel c's stream; state[c] / pos[c]: coder state (initialised from the stream's first two
-// words) and next word index (2) -- caller-initialised, kept between steps; pix_all: [nsteps][npix] pixel lists (-1 = padding);
-// done: caller-zeroed int.  err_flag bit 2: a stream ended early.  y_f16k (nullable): the latent also as F16K bf16 [ceil16(M) / 16][HW][16]
-// (exact for |value| <= 256) -- the input layout of the context model's kernels.  One image: the batched kernels with the one-image stream form.
-extern "C" int masic_rans_decode_step(const uint32_t* words, const uint32_t* word_off, const uint32_t* word_cnt, uint64_t* state, uint32_t* pos,
-                                      const uint16_t* starts, const int32_t* pix_all, int32_t* step, int npix, const int32_t* chan, int nch,
-                                      int L, int minmax, float* y_hat, void* y_f16k, int HW, int32_t* err_flag, int32_t* done, void* stream) {
-    MASIC_REQUIRE(words && word_off && word_cnt && state && pos && starts && pix_all && step && chan && y_hat && err_flag && done, MASIC_ERR_ARG,
-                  "rans_decode_step: null pointer");
-    MASIC_REQUIRE(npix >= 1 && nch >= 1 && L >= 1 && L <= CDF_MAX_L && L == 2 * minmax + 1, MASIC_ERR_SHAPE, "rans_decode_step: bad shape");
-    const Streams S{nullptr, (const int*)chan, (const unsigned*)word_off, (const unsigned*)word_cnt, nch, minmax};
-    hipLaunchKernelGGL(rans_decode_step_kernel, dim3(nch), dim3(64), 0, (hipStream_t)stream, (const unsigned*)words, S,
-                       (unsigned long long*)state, (unsigned*)pos, (const unsigned short*)starts, (const int*)pix_all, npix, (int*)step, npix, 0,
-                       y_hat, HW, (int*)err_flag, (int*)done, (unsigned short*)y_f16k);
-    return masic_launch_status("rans_decode_step");
-}
-
-extern "C" int masic_gmm_cdf_rows(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
-                                  const int32_t* pix, int npix, const int32_t* chan, int nch, int minmax, float scale_bound,
-                                  const float* y_hat, uint16_t* starts, int32_t* start_freq, int32_t* err_flag, void* stream) {
-    MASIC_REQUIRE(sigma && mu && logits && pix && chan && err_flag, MASIC_ERR_ARG, "gmm_cdf_rows: null pointer");
-    MASIC_REQUIRE((y_hat != nullptr) == (start_freq != nullptr), MASIC_ERR_ARG, "gmm_cdf_rows: y_hat and start_freq go together");
-    MASIC_REQUIRE(starts || start_freq, MASIC_ERR_ARG, "gmm_cdf_rows: no output requested");
-    MASIC_REQUIRE(minmax >= 1 && 2 * minmax + 1 <= CDF_MAX_L, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows: minmax=%d (alphabet of at most %d symbols)", minmax, CDF_MAX_L);
-    MASIC_REQUIRE(K >= 1 && K <= 8, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows: K=%d", K);
-    if (npix <= 0 || nch <= 0) return MASIC_OK;
-    const Streams S{nullptr, (const int*)chan, nullptr, nullptr, nch, minmax};
-    return cdf_launch(sigma, mu, logits, M, K, HW, pix, nullptr, npix, npix, S, scale_bound, y_hat, starts, start_freq, err_flag, stream);
-}
-
-// the tables of coding step *step (device int): pix_all is [nsteps][npix]
-extern "C" int masic_gmm_cdf_rows_at(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
-                                     const int32_t* pix_all, const int32_t* step, int npix, const int32_t* chan, int nch, int minmax, float scale_bound,
-                                     uint16_t* starts, int32_t* err_flag, void* stream) {
-    MASIC_REQUIRE(sigma && mu && logits && pix_all && step && chan && starts && err_flag, MASIC_ERR_ARG, "gmm_cdf_rows_at: null pointer");
-    MASIC_REQUIRE(minmax >= 1 && 2 * minmax + 1 <= CDF_MAX_L, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows_at: minmax=%d (alphabet of at most %d symbols)", minmax, CDF_MAX_L);
-    MASIC_REQUIRE(K >= 1 && K <= 8 && npix >= 1 && nch >= 1, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows_at: K=%d npix=%d nch=%d", K, npix, nch);
-    const Streams S{nullptr, (const int*)chan, nullptr, nullptr, nch, minmax};
-    return cdf_launch(sigma, mu, logits, M, K, HW, pix_all, step, npix, npix, S, scale_bound, nullptr, starts, nullptr, err_flag, stream);
-}
-
-// ---- batched forms (B pairs per launch; include/masic_hip.h): a stream table instead of (chan, nch, minmax), one err int per image
+// Device side of a coding step over B pairs (include/masic_hip.h): masic_gmm_cdf_rows_batch builds the tables of step *step (or, without
+// a step, of the whole list: the encoder's one pass), masic_rans_decode_step_batch decodes the step's symbols into the latent and
+// increments *step.  streams: the device table of masic_code_stream_t (one pair is a table of that pair's streams); words: all channel
+// streams back to back as little-endian 32-bit words; state[s] / pos[s]: coder state (initialised from the stream's first two words) and
+// next word index (2) -- caller-initialised, kept between steps; pix_all: [nsteps][list_stride] pixel lists (-1 = padding); done:
+// caller-zeroed int; err_flags: one int per image, bit 2 = a stream ended early.  y_f16k (nullable): the latent also as F16K bf16
+// [B][ceil16(M) / 16][HW][16] (exact for |value| <= 256) -- the input layout of the context model's kernels.
 extern "C" int masic_gmm_cdf_rows_batch(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
                                         const int32_t* pix, const int32_t* step, int list_stride, int npix,
                                         const masic_code_stream_t* streams, int nstreams, float scale_bound,
@@ -344,8 +285,7 @@ extern "C" int masic_gmm_cdf_rows_batch(const float* sigma, const float* mu, con
     MASIC_REQUIRE(K >= 1 && K <= 8, MASIC_ERR_UNSUPPORTED, "gmm_cdf_rows_batch: K=%d", K);
     MASIC_REQUIRE(npix >= 1 && nstreams >= 0 && list_stride >= npix, MASIC_ERR_SHAPE, "gmm_cdf_rows_batch: bad shape");
     if (nstreams == 0) return MASIC_OK;
-    const Streams S{streams, nullptr, nullptr, nullptr, nstreams, 0};
-    return cdf_launch(sigma, mu, logits, M, K, HW, pix, step, list_stride, npix, S, scale_bound, y_hat, starts, start_freq, err_flags, stream);
+    return cdf_launch(sigma, mu, logits, M, K, HW, pix, step, list_stride, npix, streams, nstreams, scale_bound, y_hat, starts, start_freq, err_flags, stream);
 }
 
 extern "C" int masic_rans_decode_step_batch(const uint32_t* words, const masic_code_stream_t* streams, int nstreams, uint64_t* state, uint32_t* pos,
@@ -354,8 +294,7 @@ extern "C" int masic_rans_decode_step_batch(const uint32_t* words, const masic_c
     MASIC_REQUIRE(words && streams && state && pos && starts && pix_all && step && y_hat && err_flags && done, MASIC_ERR_ARG,
                   "rans_decode_step_batch: null pointer");
     MASIC_REQUIRE(npix >= 1 && nstreams >= 1 && M >= 1 && list_stride >= npix, MASIC_ERR_SHAPE, "rans_decode_step_batch: bad shape");
-    const Streams S{streams, nullptr, nullptr, nullptr, nstreams, 0};
-    hipLaunchKernelGGL(rans_decode_step_kernel, dim3(nstreams), dim3(64), 0, (hipStream_t)stream, (const unsigned*)words, S,
+    hipLaunchKernelGGL(rans_decode_step_kernel, dim3(nstreams), dim3(64), 0, (hipStream_t)stream, (const unsigned*)words, streams, nstreams,
                        (unsigned long long*)state, (unsigned*)pos, (const unsigned short*)starts, (const int*)pix_all, list_stride, (int*)step, npix, M,
                        y_hat, HW, (int*)err_flags, (int*)done, (unsigned short*)y_f16k);
     return masic_launch_status("rans_decode_step_batch");

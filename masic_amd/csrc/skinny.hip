@@ -13,11 +13,11 @@
 //     model the record of the pixel shifted by the tap, or an out-of-range offset (reads as zeros) outside the latent;
 //   * the NW partial accumulators are summed through LDS in wave order (deterministic), then bias, activation, optional per-pixel gate,
 //     and a scatter of the 32 pixels' records (F16K) or planes (float32 NCHW) into FULL-SIZE buffers, so that the next layer, the table
-//     kernel (masic_gmm_cdf_rows) and the encoder's one-pass form (the same kernels over all pixels, 32 per workgroup) address pixels
+//     kernel (masic_gmm_cdf_rows_batch) and the encoder's one-pass form (the same kernels over all pixels, 32 per workgroup) address pixels
 //     the same way.  A pixel's result depends on that pixel's operands and the fixed k order only: encoder (all pixels at once) and
 //     decoder (a wavefront at a time) get bit-identical parameters, which is what makes their coding tables agree.
 // The pixel list of a launch is pix[(*step) * list_stride + i], i < npix (step: device int or null) -- the decoder replays one captured
-// graph per coding step and the step counter lives on the device (codec.hip: masic_rans_decode_step).  A list entry q names image
+// graph per coding step and the step counter lives on the device (codec.hip: masic_rans_decode_step_batch).  A list entry q names image
 // b = q / HW, pixel p = q % HW of a batch of nimg images: every buffer is [nimg][image] with its own per-image stride, the masked taps
 // stay inside image b (out-of-range rows / columns read zeros as at the picture edge), so a pixel's result still depends on its own
 // operands alone -- batched and one-image launches, in any list order and split, give the same bits.  One image: entries are p.
@@ -241,10 +241,4 @@ extern "C" int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, in
     if (ctx) hipLaunchKernelGGL((skinny_f16k<8, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((skinny_f16k<4, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
     return masic_launch_status("skinny_group_fwd");
-}
-
-// one image: the batched form with nimg = 1 (list entries are pixel indices)
-extern "C" int masic_skinny_group_fwd(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step, int list_stride,
-                                      int npix, int h, int w, const float* gate, int gate_c, void* stream) {
-    return masic_skinny_group_fwd_batch(groups, ngroups, ctx, pix, step, list_stride, npix, 1, h, w, gate, 0, gate_c, stream);
 }

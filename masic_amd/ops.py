@@ -1187,20 +1187,16 @@ def pack_skinny_ctx_weight(weight):
 
 
 def skinny_group(layers, pix, step, list_stride, npix, h, w, ctx=False, gate=None, gate_c=0, nimg=1):
-    """masic_skinny_group_fwd: up to three 1x1 layers (or one masked 5x5 convolution, ctx=True) on the pixels pix[step * list_stride + i],
-    i < npix, of one image.  layers: dicts with x (F16K), wp, bias, Cin, Cout, act, out_ctot, out_coff and the FULL-SIZE output buffer
-    y16 (F16K) or y32 (float32 [out_ctot, h, w]); pix / step: int32 device tensors (step may be None).  nimg > 1: the same over a batch
-    of images (masic_skinny_group_fwd_batch; list entries b * h * w + p, buffers and gate [nimg, ...])."""
+    """masic_skinny_group_fwd_batch: up to three 1x1 layers (or one masked 5x5 convolution, ctx=True) on the pixels
+    pix[step * list_stride + i], i < npix, of a batch of nimg images (list entries b * h * w + p).  layers: dicts with x (F16K), wp, bias,
+    Cin, Cout, act, out_ctot, out_coff and the FULL-SIZE output buffer y16 (F16K) or y32 (float32 [nimg, out_ctot, h, w]); gate
+    [nimg, C, h, w]; pix / step: int32 device tensors (step may be None)."""
     arr = (_lib.GemmGroup * len(layers))()
     for g, L in zip(arr, layers):
         g.x, g.w_packed, g.wscale, g.bias = _p(L["x"]), _p(L["wp"]), None, _p(L["bias"])
         g.y_f16k, g.y_f8k, g.y_nchw = _p(L.get("y16")), None, _p(L.get("y32"))
         g.out_inv_scale = 0.0
         g.Cin, g.Cout, g.out_ctot, g.out_coff, g.act = L["Cin"], L["Cout"], L["out_ctot"], L.get("out_coff", 0), int(L["act"])
-    if nimg == 1:
-        check(lib.masic_skinny_group_fwd(arr, len(layers), 1 if ctx else 0, _p(pix), _p(step), int(list_stride), int(npix), int(h), int(w),
-                                         _p(gate), int(gate_c), _stream()), "skinny_group_fwd")
-        return
     if gate is not None and (gate.dim() != 4 or gate.shape[0] != nimg or not gate.is_contiguous()):
         raise RuntimeError("masic_amd.skinny_group: the gate must be a contiguous [nimg, C, h, w] tensor")
     check(lib.masic_skinny_group_fwd_batch(arr, len(layers), 1 if ctx else 0, _p(pix), _p(step), int(list_stride), int(npix), int(nimg), int(h),

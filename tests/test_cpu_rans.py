@@ -1,9 +1,11 @@
 """Host-side entropy coder against golden vectors produced by the reference's own pybind11 extensions
 and EntropyBottleneck (tests/golden/make_rans_goldens.py).  No GPU needed: the coder is host code of libmasic_hip.so."""
+import ctypes
 import os
 
 import numpy as np
 import pytest
+import torch
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "rans_vectors.npz"))
 
@@ -215,3 +217,35 @@ def test_per_channel_streams_decode_with_the_host_decoder():
         assert np.array_equal(got, sym[rows]), c
     empty, used = codec.split_channels(codec.encode_channels(np.zeros((0, 2), dtype=np.int32), 0, 0))
     assert empty == [] and used == 4
+
+
+def test_stream_table_layout_for_one_pair_and_for_a_batch():
+    """codec._stream_table (masic_code_stream_t rows: img, chan, minmax, rstride, row0, soff, word_off, word_cnt).  One pair: stream c is
+    channel chan[c] of image 0 with rows c, c + nch, ... (pixel-major, what encode_channels reads), starts at c * L and the given words --
+    the layout the kernels address.  Several pairs with different channel counts and alphabets: each pair's rows and starts follow the
+    previous pair's block of rows_per_stream * nch rows."""
+    from masic_amd import _lib, codec
+    chan, minmax, rows_per_stream = [2, 5, 6, 11], 9, 13
+    L, nch = 2 * minmax + 1, len(chan)
+    off, cnt = np.array([0, 7, 10, 30], dtype=np.uint32), np.array([7, 3, 20, 4], dtype=np.uint32)
+    t, n, nstarts, nrows = codec._stream_table([chan], [minmax], rows_per_stream, "cpu", words=[(off, cnt)])
+    assert n == nch and nrows == rows_per_stream * nch and nstarts == rows_per_stream * nch * L
+    assert t.dtype == torch.int32 and tuple(t.shape) == (nch, 8) and t.is_contiguous()
+    assert t.tolist() == [[0, chan[c], minmax, nch, c, c * L, int(off[c]), int(cnt[c])] for c in range(nch)]
+    t0, *_ = codec._stream_table([chan], [minmax], rows_per_stream, "cpu")
+    assert t0[:, :6].equal(t[:, :6]) and not t0[:, 6:].any()                       # the encoder's table: no words
+    # three pairs: 3 channels of a 41-entry alphabet, none, 2 channels of a 5-entry one
+    chans, minmaxes = [[0, 1, 7], [], [4, 9]], [20, 3, 2]
+    t, n, nstarts, nrows = codec._stream_table(chans, minmaxes, rows_per_stream, "cpu")
+    want, row_base, s_base = [], 0, 0
+    for b, (ch, mm) in enumerate(zip(chans, minmaxes)):
+        for c, m in enumerate(ch):
+            want.append([b, m, mm, len(ch), row_base + c, s_base + c * (2 * mm + 1), 0, 0])
+        row_base += rows_per_stream * len(ch)
+        s_base += rows_per_stream * len(ch) * (2 * mm + 1)
+    assert t.tolist() == want and n == 5 and nrows == row_base == 13 * 5 and nstarts == s_base == 13 * (3 * 41 + 2 * 5)
+    assert [r[4] for r in want] == [0, 1, 2, 39, 40] and [r[5] for r in want] == [0, 41, 82, 13 * 3 * 41, 13 * 3 * 41 + 5]
+    assert ctypes.sizeof(_lib.CodeStream) == 32                                    # the columns are the descriptor's fields, in order
+    assert [f[0] for f in _lib.CodeStream._fields_] == ["img", "chan", "minmax", "rstride", "row0", "soff", "word_off", "word_cnt"]
+    empty, n, nstarts, nrows = codec._stream_table([[]], [1], rows_per_stream, "cpu")
+    assert tuple(empty.shape) == (0, 8) and (n, nstarts, nrows) == (0, 0, 0)

@@ -120,21 +120,21 @@ def test_batched_pixel_list_kernels_equal_the_single_image_kernels():
         rs = np.random.RandomState(31)
         with torch.no_grad():
             for view in ("left", "right"):
-                def build(i, pixel_list):
+                def build(i):
                     if view == "left":
-                        return net._left_params_fn(z_hat[i:i + 1], h, w, pixel_list=pixel_list)
+                        return net._left_params_fn(z_hat[i:i + 1], h, w)
                     m_fwd, m_back = _warp_matrices(hm[i:i + 1], (H, W), (H, W), want_inverse=True)
-                    return net._right_params_fn(z_hat[i:i + 1], x1_hat[i:i + 1], m_fwd, m_back, H, W, h, w, pixel_list=pixel_list)[0]
+                    return net._right_params_fn(z_hat[i:i + 1], x1_hat[i:i + 1], m_fwd, m_back, H, W, h, w)[0]
                 head, ctx, C = ((net._h_s1_same_resolution, net.context_prediction1, 4 * M) if view == "left"
                                 else (net._h_s2_same_resolution, net.context_prediction2, 5 * M))
                 want = []
                 for i in range(B):
-                    src = build(i, True)
-                    assert src.skinny
+                    src = net._batch_params([build(i)], head, ctx, C, h, w)
+                    assert src is not None and src.skinny
                     src.set_latent(y_hat[i:i + 1])
                     src.run(torch.arange(HW, dtype=torch.int32, device=DEV), None, 0, HW)
                     want.append([t.clone() for t in (src.sigma, src.mu, src.logits)])
-                bp = net._batch_params([build(i, False) for i in range(B)], head, ctx, C, h, w)
+                bp = net._batch_params([build(i) for i in range(B)], head, ctx, C, h, w)
                 assert bp is not None and bp.skinny
                 bp.set_latent(y_hat)
                 for trial in range(2):
@@ -163,8 +163,8 @@ def test_batched_pixel_list_kernels_equal_the_single_image_kernels():
 def test_batched_tables_and_decode_steps_equal_the_single_pair_coder(use_graph):
     """masic_gmm_cdf_rows_batch + masic_rans_decode_step_batch on synthetic entropy parameters: three pairs with different channel sets
     and alphabets -- one with 41 entries (register form of the decode kernel), one with 81 (general form) in the same launch, one with
-    no coded channel.  The encoder's streams equal encode_view's for each pair alone (same (start, freq) of every symbol), and the
-    device decoder gets every symbol back."""
+    no coded channel.  The encoder's streams equal those of each pair alone, coded as B = 1 with the full-latent parameter form as the
+    single-pair methods do (same (start, freq) of every symbol), and the device decoder gets every symbol back."""
     from masic_amd import codec
     B, M, K, h, w = 3, 24, 3, 12, 10
     HW = h * w
@@ -196,16 +196,16 @@ def test_batched_tables_and_decode_steps_equal_the_single_pair_coder(use_graph):
 
     blobs = codec.encode_views(Fixed(), y_hat, M, K, chans, minmaxes, 0.11)
     for b in range(B):
-        single = codec.encode_view(lambda _y, b=b: (sigma[b:b + 1], mu[b:b + 1], logits[b:b + 1]), y_hat[b:b + 1], M, K,
-                                   torch.tensor(chans[b], dtype=torch.int32, device=DEV), minmaxes[b], 0.11)
+        single, = codec.encode_views(lambda _y, b=b: (sigma[b:b + 1], mu[b:b + 1], logits[b:b + 1]), y_hat[b:b + 1], M, K,
+                                     [chans[b]], [minmaxes[b]], 0.11)
         assert blobs[b] == single, b
     assert len(codec.split_channels(blobs[2])[0]) == 0
     got = codec.decode_views(Fixed(), blobs, (h, w), M, K, chans, minmaxes, 0.11, DEV, use_graph=use_graph)
     assert torch.equal(got, y_hat)
     # each pair alone through the single-pair device decoder agrees
     for b in range(2):
-        one = codec.decode_view(lambda _y, b=b: (sigma[b:b + 1], mu[b:b + 1], logits[b:b + 1]), blobs[b], (h, w), M, K,
-                                torch.tensor(chans[b], dtype=torch.int32, device=DEV), minmaxes[b], 0.11, DEV, use_graph=False)
+        one = codec.decode_views(lambda _y, b=b: (sigma[b:b + 1], mu[b:b + 1], logits[b:b + 1]), [blobs[b]], (h, w), M, K,
+                                 [chans[b]], [minmaxes[b]], 0.11, DEV, use_graph=False)
         assert torch.equal(one, y_hat[b:b + 1])
 
 

@@ -1,8 +1,8 @@
 """HSIC.compress_batch / decompress_batch: encode and decode time per pair at B = 1, 2, 4, 8 (run on the GPU box).
 
 HSIC(128,192,5), bf16 operands, synthetic weights and pairs (masic_amd.synth).  Every (size, B) is warmed up first; each timed run is
-wall time around one call that ends in a device synchronise; the table holds the median of --runs runs divided by B.  B = 1 goes
-through the batched methods too (the single-pair methods' time is printed beside it).  Every decode is checked against its encode.
+wall time around one call that ends in a device synchronise; the table holds the median of --runs runs divided by B.  The
+single-pair methods are the B = 1 case behind a thin wrapper: their time is printed beside the B = 1 row and should equal it.  Every decode is checked against its encode.
   python tools/bench_codec_batch.py [--sizes 512x512,1216x2176] [--batches 1,2,4,8] [--runs 5] [--json out.json]
   python tools/bench_codec_batch.py --profile-one 512x512:8      (one decode_batch, for rocprofv3 --kernel-trace --stats)"""
 import argparse
@@ -70,7 +70,7 @@ def main():
             H, W = (int(v) for v in size.split("x"))
             Bmax = max(int(b) for b in args.batches.split(","))
             x1a, x2a, hma = (t.cuda() for t in synth.synth_inputs(Bmax, H, W, seed=100))
-            # single-pair methods, for comparison
+            # the single-pair methods (the B = 1 case of the same implementation)
             net.compress(x1a[:1], x2a[:1], hma[:1], "single", d)
             net.decompress(None, None, hma[:1], "single", d)
             se = statistics.median(_timed(lambda: net.compress(x1a[:1], x2a[:1], hma[:1], "single", d))[0] for _ in range(args.runs))
