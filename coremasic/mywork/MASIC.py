@@ -1168,36 +1168,46 @@ class HSIC(CompressionModel):
 
     def _read_pair(self, output_path, output_name, who):
         """The two files of one pair -> H, W, per view (z string, minmax, coded channels as a list), per view the framed
-        y streams, the fp8 scale table or None.  ValueError for a foreign stream or one written in another operand mode."""
+        y streams, the fp8 scale table or None.  ValueError for a foreign stream, one written in another operand mode, or a
+        container that is cut short, holds impossible length fields or carries bytes after its last field."""
         import os
         from masic_amd import codec, nn as _mnn
         M = self.M
+
+        def take(f, n, what):
+            data = f.read(n)
+            if len(data) != n:
+                raise ValueError(f"{who}: truncated file: {what} needs {n} bytes, {len(data)} are left")
+            return data
+
         with open(os.path.join(output_path, str(output_name) + ".npz"), "rb") as f:
-            H, W = (int(v) for v in np.frombuffer(f.read(4), dtype=np.uint16))
+            H, W = (int(v) for v in np.frombuffer(take(f, 4, "the picture size"), dtype=np.uint16))
             views = []
-            for _ in range(2):
-                length, minmax = (int(v) for v in np.frombuffer(f.read(4), dtype=np.uint16))
-                flags = np.unpackbits(np.frombuffer(f.read(M // 8), dtype=np.uint8))
-                views.append((f.read(length), minmax, np.flatnonzero(flags).tolist()))
+            for v in range(2):
+                length, minmax = (int(x) for x in np.frombuffer(take(f, 4, f"the header of view {v + 1}"), dtype=np.uint16))
+                flags = np.unpackbits(np.frombuffer(take(f, M // 8, f"the channel flags of view {v + 1}"), dtype=np.uint8))
+                views.append((take(f, length, f"the z string of view {v + 1}"), minmax, np.flatnonzero(flags).tolist()))
+            if f.read(1):
+                raise ValueError(f"{who}: bytes follow the second view in the .npz header file")
         with open(os.path.join(output_path, str(output_name) + ".bin"), "rb") as f:
             head = f.read(8)
             if head[:4] != codec.MAGIC:
                 raise ValueError(f"{who}: not a stream of this library (magic %r)" % head[:4])
+            if len(head) != 8:
+                raise ValueError(f"{who}: truncated file: the .bin header needs 8 bytes, {len(head)} are there")
             if head[4] != {"f32": 0, "bf16": 1, "fp8": 2}[_mnn.get_precision()]:
                 raise ValueError(f"{who}: the stream was written in the %s operand mode; the coding tables depend on it "
                                  "(masic_amd.nn.set_precision)" % ("f32", "bf16", "fp8")[head[4] if head[4] < 3 else 0])
             fp8_table = None
             if head[5] & 1:
-                n = int(np.frombuffer(f.read(4), dtype=np.uint32)[0])
-                fp8_table = f.read(n)
+                n = int(np.frombuffer(take(f, 4, "the length of the fp8 table"), dtype=np.uint32)[0])
+                fp8_table = take(f, n, "the fp8 table")
             elif head[4] == 2:
                 raise ValueError(f"{who}: an fp8-mode stream without its activation-scale table")
-            rest = f.read()
-            streams = []
-            for _ in range(2):
-                _, used = codec.split_channels(rest)
-                streams.append(rest[:used])
-                rest = rest[used:]
+            try:
+                streams = codec.split_views(f.read(), 2)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from e
         return H, W, views, streams, fp8_table
 
     def _batch_params(self, parts, head, ctx, C, h, w):
@@ -1349,6 +1359,9 @@ class _pair_errors:
     def __exit__(self, et, ev, tb):
         if (self.names is not None and et is not None and issubclass(et, (RuntimeError, ValueError))
                 and not isinstance(ev, torch.cuda.OutOfMemoryError)):
+            from masic_amd import codec
+            if isinstance(ev, codec.PairStreamError):        # keeps its type (CorruptStreamError) and gets its index in the batch
+                raise type(ev)(self.i, f"{ev} -- pair {self.i} ({self.names[self.i]}) of the batch") from ev
             raise (ValueError if issubclass(et, ValueError) else RuntimeError)(f"{ev} -- pair {self.i} ({self.names[self.i]}) of the batch") from ev
         return False
 

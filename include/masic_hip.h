@@ -633,6 +633,12 @@ int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, int ngroups, 
  * and next word index, caller-initialised (state = word0 | word1 << 32, pos = 2) and kept across steps; done: caller-zeroed device int.
  * err_flags: one caller-zeroed device int per image: bit 0 = a table could not be normalised, or a descriptor whose alphabet is
  * empty or exceeds 1024 entries; bit 1 = a symbol outside the alphabet; bit 2 = a stream ended early.
+ * masic_rans_decode_finish_batch: one thread per stream, to be called ONCE, AFTER the last coding step (outside a graph that is replayed
+ * per step) on the state / pos / err_flags of the steps: ORs bit 3 (value 8) into err_flags[img] of every stream with
+ * pos != word_cnt or state != 2^31.  Every encoder (masic_rans_encode_freqs / _channels / _with_indexes) starts from state 2^31 and a
+ * decoder retraces the encoder's states backwards, so a stream read with the encoder's own tables ends exactly there with exactly its
+ * words consumed; a damaged stream, or one read with other tables (another file's header, other weights, another operand mode), does
+ * so only by a ~2^-31 coincidence.  Before the last step it flags every stream that is not yet at its end.  nstreams = 0: no launch.
  * All pointers device memory; asynchronous on `stream`; capturable into a HIP graph. */
 typedef struct {
     int32_t img, chan, minmax, rstride, row0;
@@ -645,12 +651,17 @@ int masic_gmm_cdf_rows_batch(const float* sigma, const float* mu, const float* l
 int masic_rans_decode_step_batch(const uint32_t* words, const masic_code_stream_t* streams, int nstreams, uint64_t* state, uint32_t* pos,
                                  const uint16_t* starts, const int32_t* pix_all, int list_stride, int32_t* step, int npix, int M,
                                  float* y_hat, void* y_f16k, int HW, int32_t* err_flags, int32_t* done, void* stream);
+int masic_rans_decode_finish_batch(const masic_code_stream_t* streams, int nstreams, const uint64_t* state, const uint32_t* pos,
+                                   int32_t* err_flags, void* stream);
 int masic_rans_decoder_open(const uint8_t* in, size_t in_len, void** handle);
 int masic_rans_decoder_decode_rows(void* handle, const uint16_t* starts, int nrows, int L, int32_t* symbols);
 /* the next n symbols with tables picked by indexes (arguments as masic_rans_decode_with_indexes), keeping the coder state between
  * calls: reference RansDecoder::set_stream / decode_stream (rans_interface.cpp:286-353) */
 int masic_rans_decoder_decode_indexes(void* handle, const int32_t* indexes, int n, const int32_t* cdfs, int cdf_stride,
                                       const int32_t* cdf_sizes, const int32_t* offsets, int ncdfs, int32_t* symbols);
+/* *ok = 1 exactly when the decoder has consumed all words of its stream and its state is 2^31, the state every encoder starts from:
+ * what holds after the last symbol of an intact stream (the host form of masic_rans_decode_finish_batch), else 0 */
+int masic_rans_decoder_finished(void* handle, int* ok);
 void masic_rans_decoder_close(void* handle);
 
 /* ------------------------------------------------------------------------------------------

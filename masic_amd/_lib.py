@@ -81,9 +81,11 @@ SIGNATURES = {
     "masic_rans_encode_channels": (c_int, [_P, c_int, c_int, _P, c_size_t, _P, _P]),
     "masic_gmm_cdf_rows_batch": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_float, _P, _P, _P, _P, _P]),
     "masic_rans_decode_step_batch": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
+    "masic_rans_decode_finish_batch": (c_int, [_P, c_int, _P, _P, _P, _P]),
     "masic_skinny_group_fwd_batch": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P]),
     "masic_rans_decoder_open": (c_int, [_P, c_size_t, _P]),
     "masic_rans_decoder_decode_rows": (c_int, [_P, _P, c_int, c_int, _P]),
+    "masic_rans_decoder_finished": (c_int, [_P, ctypes.POINTER(c_int)]),
     "masic_rans_decoder_close": (None, [_P]),
     "masic_rans_decoder_decode_indexes": (c_int, [_P, _P, c_int, _P, c_int, _P, _P, c_int, _P]),
     "masic_gdn1_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, _P]),

@@ -20,7 +20,10 @@ changes a bit of the parameters of the pixel being coded: the encoder needs ONE 
 one pass per wavefront.
 Container (.bin): b"MSR2", u8 precision id (0 f32 / 1 bf16 / 2 fp8 operands: the tables depend on it), u8 flags (bit 0: an
 activation-scale table follows), 2 pad bytes, [u32 length + the fp8 mode's calibration table as JSON, masic_amd/fp8.py], then per
-view u32 number of channel streams n, n x u32 stream lengths in bytes, the streams back to back (round 2's "MSR1" had one stream per view).  The .npz header keeps the reference's layout (MASIC.py:916-948)."""
+view u32 number of channel streams n, n x u32 stream lengths in bytes, the streams back to back (round 2's "MSR1" had one stream per view).  The .npz header keeps the reference's layout (MASIC.py:916-948).
+The container carries no checksum; what is read back is checked instead: split_views parses the framing strictly, and after the last
+coding step every channel stream must have consumed exactly its words and left the coder at 2^31, the state every encoder starts from
+(masic_rans_decode_finish_batch, CorruptStreamError)."""
 import ctypes
 
 import numpy as np
@@ -99,6 +102,13 @@ class AdaptiveDecoder:
                                                  out.ctypes.data_as(ctypes.c_void_p)), "rans_decoder_decode_rows")
         return out
 
+    def finished(self):
+        """True when every word of the stream is consumed and the coder is back in the state every encoder starts from (2^31): what a
+        correctly read stream ends in once its last symbol is decoded, and a damaged one only by a ~2^-31 coincidence."""
+        ok = ctypes.c_int(0)
+        check(lib.masic_rans_decoder_finished(self._h, ctypes.byref(ok)), "rans_decoder_finished")
+        return bool(ok.value)
+
     def close(self):
         if self._h:
             lib.masic_rans_decoder_close(self._h)
@@ -132,6 +142,31 @@ def split_channels(blob):
     return out, off
 
 
+def split_views(rest, nviews):
+    """The strict form of split_channels for bytes read from a file: `rest` must hold exactly nviews framings (u32 n, n x u32 lengths,
+    the n streams), each stream a whole rANS stream (>= 8 bytes: the two state words; a multiple of 4) -> the nviews framed views, what
+    decode_views takes.  ValueError for a count or length field that reaches past the buffer, a length no stream can have, or bytes
+    left over after the last view (split_channels slices with Python semantics and accepts all three)."""
+    out, off = [], 0
+    for v in range(nviews):
+        if off + 4 > len(rest):
+            raise ValueError(f"masic_amd.codec: the y streams end before the stream count of view {v + 1}")
+        nch = int(np.frombuffer(rest[off:off + 4], dtype=np.uint32)[0])
+        if 4 * nch > len(rest) - off - 4:
+            raise ValueError(f"masic_amd.codec: view {v + 1} counts {nch} channel streams, more than the file holds")
+        lengths = np.frombuffer(rest[off + 4:off + 4 + 4 * nch], dtype=np.uint32).astype(np.int64)
+        if nch and (int(lengths.min()) < 8 or (lengths % 4).any()):
+            raise ValueError(f"masic_amd.codec: view {v + 1} holds a length field no rANS stream has (below 8 bytes or not a multiple of 4)")
+        end = off + 4 + 4 * nch + int(lengths.sum())
+        if end > len(rest):
+            raise ValueError(f"masic_amd.codec: the channel streams of view {v + 1} reach {end - len(rest)} bytes past the end of the file")
+        out.append(rest[off:end])
+        off = end
+    if off != len(rest):
+        raise ValueError(f"masic_amd.codec: {len(rest) - off} bytes follow the last view's streams")
+    return out
+
+
 # ---- the coding loops, over the views of B >= 1 pairs (HSIC.compress / decompress: B = 1; compress_batch / decompress_batch).  The
 # framing and container are per pair; the device work of a coding step covers all B pairs: one skinny launch per layer over every pair's
 # pixels (list entries b * h * w + p), one table launch and one decode launch over every pair's channel streams (masic_code_stream_t),
@@ -144,20 +179,30 @@ class PairStreamError(RuntimeError):
         self.pair = pair
 
 
+class CorruptStreamError(PairStreamError, ValueError):
+    """A channel stream decoded to the end without the coder reaching its final state (err bit 3, masic_rans_decode_finish_batch): the
+    bytes are not what the encoder wrote for these tables."""
+
+
 def check_errs(err, what, names=None):
     """err: the kernels' flags, one int per pair -> PairStreamError for the first pair with a bit set; it names the pair when the call
     holds several or `names` is given."""
     flags = err.cpu().tolist()
     for i, e in enumerate(flags):
+        kind = PairStreamError
         if e & 1:
             msg = "a coding table could not be normalised to 2^16"
         elif e & 2:
             msg = "a symbol lies outside the alphabet (minmax too small)"
         elif e & 4:
             msg = "a channel stream ended before its last symbol (truncated or foreign data)"
+        elif e & 8:
+            kind = CorruptStreamError
+            msg = ("a channel stream did not end in the coder's final state (corrupt data, a header from another file, other weights or "
+                   "another operand mode than the encoder's)")
         else:
             continue
-        raise PairStreamError(i, f"masic_amd.codec: {what}: {msg}{_pair_tag(i, len(flags), names, ' -- pair %s of the batch')}")
+        raise kind(i, f"masic_amd.codec: {what}: {msg}{_pair_tag(i, len(flags), names, ' -- pair %s of the batch')}")
 
 
 check_err = check_errs      # the name gmm_tables' callers use for its one flag
@@ -269,14 +314,17 @@ def _batch_step_lists(h, w, B, device):
     return t
 
 
-def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, device, names=None, use_graph=True):
+def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, device, names=None, use_graph=True, verify=True):
     """The inverse of encode_views (datas: pair b's y stream as it framed it) -> y_hat [B, M, h, w]; a pair's slice does not depend on
     its batch mates.  Coding step by coding step, entirely on the device: parameters from what is decoded so far -> tables of the
     step's pixels -> one wavefront per channel stream finds the symbols and writes them into the latent.  The device side of a step
     (context convolution, nine head layers, table kernel, decode kernel, each over every pair: ~18 launches of a few microseconds) is
     captured once into a HIP graph over static buffers and replayed w + 3 (h - 1) times back to back; the step index lives in device
-    memory (incremented by the decode kernel), so the host neither feeds nor waits for anything until the last replay.  A stream
-    error names its pair (PairStreamError)."""
+    memory (incremented by the decode kernel), so the host neither feeds nor waits for anything until the last replay.  After the
+    last step one more launch (masic_rans_decode_finish_batch, outside the graph) checks that every channel stream consumed exactly its
+    words and left the coder in the encoder's initial state; its flag comes back with the others in the one read of `err`
+    (verify=False leaves the launch out: for timing the check).  A stream error names its pair (PairStreamError; CorruptStreamError
+    for the final-state check)."""
     h, w = shape
     B, HW = len(datas), h * w
     pixel_list = _pixel_list_form(params_fn, B, "decode_views")
@@ -348,5 +396,8 @@ def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, de
     else:
         for _ in range(nsteps):
             device_step()
+    if verify:
+        check(lib.masic_rans_decode_finish_batch(_p(desc), n, _p(state_d), _p(pos_d), _p(err), ctypes.c_void_p(cur.cuda_stream)),
+              "rans_decode_finish_batch")
     check_errs(err, "decode", names)
     return y_hat

@@ -266,6 +266,18 @@ __global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __
     }
 }
 
+// ---- after the last coding step: did every stream end where its encoder began?  Every encoder of rans.hip starts from x = 2^31 and the
+// decoder retraces its states backwards, so a stream read with the encoder's tables leaves the coder at exactly 2^31 with exactly its
+// word_cnt words consumed; anything else (a flipped bit, another file's header, other weights or operand mode: other tables) meets both
+// only by a ~2^-31 coincidence per stream.  One thread per stream; err bit 3.
+__global__ __launch_bounds__(64) void rans_decode_finish_kernel(const masic_code_stream_t* __restrict__ streams, int nstreams,
+                                                                const unsigned long long* __restrict__ state,
+                                                                const unsigned* __restrict__ pos, int* __restrict__ err) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= nstreams) return;
+    if (pos[c] != streams[c].word_cnt || state[c] != (1ull << 31)) atomicOr(err + streams[c].img, 8);
+}
+
 }  // namespace
 
 // Device side of a coding step over B pairs (include/masic_hip.h): masic_gmm_cdf_rows_batch builds the tables of step *step (or, without
@@ -273,7 +285,8 @@ __global__ __launch_bounds__(64) void rans_decode_step_kernel(const unsigned* __
 // increments *step.  streams: the device table of masic_code_stream_t (one pair is a table of that pair's streams); words: all channel
 // streams back to back as little-endian 32-bit words; state[s] / pos[s]: coder state (initialised from the stream's first two words) and
 // next word index (2) -- caller-initialised, kept between steps; pix_all: [nsteps][list_stride] pixel lists (-1 = padding); done:
-// caller-zeroed int; err_flags: one int per image, bit 2 = a stream ended early.  y_f16k (nullable): the latent also as F16K bf16
+// caller-zeroed int; err_flags: one int per image, bit 2 = a stream ended early, bit 3 (masic_rans_decode_finish_batch, once after the last
+// step) = a stream did not end with all its words consumed and the coder in the encoders' initial state.  y_f16k (nullable): the latent also as F16K bf16
 // [B][ceil16(M) / 16][HW][16] (exact for |value| <= 256) -- the input layout of the context model's kernels.
 extern "C" int masic_gmm_cdf_rows_batch(const float* sigma, const float* mu, const float* logits, int M, int K, int HW,
                                         const int32_t* pix, const int32_t* step, int list_stride, int npix,
@@ -298,4 +311,14 @@ extern "C" int masic_rans_decode_step_batch(const uint32_t* words, const masic_c
                        (unsigned long long*)state, (unsigned*)pos, (const unsigned short*)starts, (const int*)pix_all, list_stride, (int*)step, npix, M,
                        y_hat, HW, (int*)err_flags, (int*)done, (unsigned short*)y_f16k);
     return masic_launch_status("rans_decode_step_batch");
+}
+
+extern "C" int masic_rans_decode_finish_batch(const masic_code_stream_t* streams, int nstreams, const uint64_t* state, const uint32_t* pos,
+                                              int32_t* err_flags, void* stream) {
+    MASIC_REQUIRE(streams && state && pos && err_flags, MASIC_ERR_ARG, "rans_decode_finish_batch: null pointer");
+    MASIC_REQUIRE(nstreams >= 0, MASIC_ERR_SHAPE, "rans_decode_finish_batch: nstreams=%d", nstreams);
+    if (nstreams == 0) return MASIC_OK;
+    hipLaunchKernelGGL(rans_decode_finish_kernel, dim3((nstreams + 63) / 64), dim3(64), 0, (hipStream_t)stream, streams, nstreams,
+                       (const unsigned long long*)state, (const unsigned*)pos, (int*)err_flags);
+    return masic_launch_status("rans_decode_finish_batch");
 }

@@ -346,4 +346,13 @@ extern "C" int masic_rans_decoder_decode_indexes(void* handle, const int32_t* in
     return rc;
 }
 
+// ok = 1 exactly when the decoder has consumed every word and is back in the state every encoder above starts from: true after the
+// last symbol of an intact stream read with the encoder's tables (the host form of masic_rans_decode_finish_batch, codec.hip)
+extern "C" int masic_rans_decoder_finished(void* handle, int* ok) {
+    MASIC_REQUIRE(handle && ok, MASIC_ERR_ARG, "rans_decoder_finished: null pointer");
+    const AdaptiveDecoder* d = (const AdaptiveDecoder*)handle;
+    *ok = (d->pos == d->words.size() && d->x == kLow) ? 1 : 0;
+    return MASIC_OK;
+}
+
 extern "C" void masic_rans_decoder_close(void* handle) { delete (AdaptiveDecoder*)handle; }

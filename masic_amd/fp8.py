@@ -98,9 +98,36 @@ def stream_table(net):
     return json.dumps(table, sort_keys=True).encode()         # (repr of a Python float round-trips exactly)
 
 
+def parse_stream_table(net, raw):
+    """The table stream_table wrote, read back from an UNTRUSTED file -> {module name: {tag: scale}}.  ValueError unless the bytes are
+    UTF-8 JSON of a dict that names modules of `net` only, each with a dict of finite floats."""
+    import json
+    import math
+
+    def finite(v):
+        try:
+            return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+        except OverflowError:                                 # an integer beyond the float range
+            return False
+    try:
+        table = json.loads(raw.decode("utf-8"))
+    except ValueError as e:                                   # UnicodeDecodeError and JSONDecodeError are ValueErrors
+        raise ValueError(f"foreign fp8 table: not UTF-8 JSON ({e})") from e
+    if not isinstance(table, dict):
+        raise ValueError(f"foreign fp8 table: the top level is a {type(table).__name__}, not a dict")
+    mods = dict(net.named_modules())
+    for name, sc in table.items():
+        if name not in mods:
+            raise ValueError(f"foreign fp8 table: it names a module {name!r} this model does not have")
+        if not isinstance(sc, dict) or not all(finite(v) for v in sc.values()):
+            raise ValueError(f"foreign fp8 table: the scales of {name!r} are not a dict of finite numbers")
+    return table
+
+
 class stream_scales:
     """Context of HSIC.decompress: while decoding, the modules carry the scales the ENCODER used (read from the stream); whatever the
-    decoder's own calibration was comes back afterwards.  `raw` None: nothing to do (f32 / bf16 streams)."""
+    decoder's own calibration was comes back afterwards.  `raw` None: nothing to do (f32 / bf16 streams).  The table is parsed and
+    validated before any module is touched: a bad one raises ValueError and the net keeps its own scales."""
 
     def __init__(self, net, raw):
         self.net, self.raw = net, raw
@@ -108,11 +135,11 @@ class stream_scales:
     def __enter__(self):
         if self.raw is None:
             return self
-        import json
+        table = parse_stream_table(self.net, self.raw)
         self.saved = {name: m.__dict__.get("_fp8_scale") for name, m in self.net.named_modules()}
         for m in self.net.modules():
             m.__dict__.pop("_fp8_scale", None)
-        load_scales(self.net, json.loads(self.raw.decode()))
+        load_scales(self.net, table)
         return self
 
     def __exit__(self, *exc):

@@ -3,7 +3,8 @@
 HSIC(128,192,5), bf16 operands, synthetic weights and pairs (masic_amd.synth).  Every (size, B) is warmed up first; each timed run is
 wall time around one call that ends in a device synchronise; the table holds the median of --runs runs divided by B.  The
 single-pair methods are the B = 1 case behind a thin wrapper: their time is printed beside the B = 1 row and should equal it.  Every decode is checked against its encode.
-  python tools/bench_codec_batch.py [--sizes 512x512,1216x2176] [--batches 1,2,4,8] [--runs 5] [--json out.json]
+  python tools/bench_codec_batch.py [--sizes 512x512,1216x2176] [--batches 1,2,4,8] [--runs 5] [--json out.json] [--no-verify]
+--no-verify leaves out the decoder's final-state check (codec.decode_views verify=False): the cost of the check is the difference.
   python tools/bench_codec_batch.py --profile-one 512x512:8      (one decode_batch, for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -49,7 +50,12 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--json", default=None)
     ap.add_argument("--profile-one", default=None)
+    ap.add_argument("--no-verify", action="store_true")
     args = ap.parse_args()
+    if args.no_verify:
+        import functools
+        from masic_amd import codec
+        codec.decode_views = functools.partial(codec.decode_views, verify=False)
     net = _model()
     d = tempfile.mkdtemp()
     if args.profile_one:
@@ -86,10 +92,10 @@ def main():
                 td = [_timed(lambda: net.decompress_batch(names, hm, d))[0] for _ in range(args.runs)]
                 row = {"size": f"{H}x{W}", "B": B, "encode_ms_per_pair": 1e3 * statistics.median(te) / B,
                        "decode_ms_per_pair": 1e3 * statistics.median(td) / B, "single_encode_ms": 1e3 * se, "single_decode_ms": 1e3 * sd,
-                       "bytes_per_pair": sum(enc["bytes"]) / B}
+                       "decode_ms_per_pair_runs": [1e3 * t / B for t in td], "bytes_per_pair": sum(enc["bytes"]) / B}
                 rows.append(row)
                 print(f"{H}x{W} B={B}: encode {row['encode_ms_per_pair']:.2f} ms/pair, decode {row['decode_ms_per_pair']:.2f} ms/pair "
-                      f"({row['bytes_per_pair']:.0f} bytes/pair)", flush=True)
+                      f"(runs {1e3 * min(td) / B:.2f} .. {1e3 * max(td) / B:.2f}; {row['bytes_per_pair']:.0f} bytes/pair)", flush=True)
             del x1a, x2a, hma
             torch.cuda.empty_cache()
     print("\n| size | B | encode ms/pair | decode ms/pair |\n|---|---|---|---|")
