@@ -573,6 +573,25 @@ int masic_rans_decode_with_indexes(const uint8_t* in, size_t in_len, const int32
 int masic_homography_from_corners(const float* corners, const float* delta, float* h_out, int B, float scale_a, float scale_b,
                                   void* stream);
 
+/* ---- the UDH homography net itself (coremasic/mywork/model.py: Net), float32 throughout, fixed accumulation order, no float
+ * atomics; a result row does not depend on the other rows of the batch.  Layers 2-8 are masic_conv2d_fwd_ex with MASIC_ACT_RELU.
+ * All pointers device memory; asynchronous on `stream`; capturable into a HIP graph.
+ *   masic_udh_conv1_fwd      y[B][Cout][H][W] = relu(conv3x3_pad1(cat(a, b)) + bias): a, b [B][1][H][W], w [Cout][2][3][3]
+ *                            (the Conv2d weight as it is), Cout a multiple of 16.
+ *   masic_maxpool2_fwd       MaxPool2d(2, 2) of `planes` planes of H x W (both even) -> H/2 x W/2; NaN propagates.
+ *   masic_udh_fc_fwd         hidden[B][N] = relu(x[B][K] . w1[N][K]^T + b1), out[B][M] = hidden . w2[M][N]^T + b2.  w1 is read once
+ *                            per group of <= 8 rows of x.  K a multiple of 512, N a multiple of 128; x and w1 16-byte aligned;
+ *                            workspace: masic_udh_fc_workspace_bytes(B, K, N) bytes (the split-K partial sums; 0 = bad shape);
+ *                            hidden may be NULL.
+ *   masic_udh_shift_corners  out[b][k] = corners[b][k] - corners[b][0] for [B][4][2] corners (newtrain_codec_real.py:123). */
+int masic_udh_conv1_fwd(const float* a, const float* b, const float* w, const float* bias, float* y, int B, int H, int W, int Cout,
+                        void* stream);
+int masic_maxpool2_fwd(const float* x, float* y, int planes, int H, int W, void* stream);
+size_t masic_udh_fc_workspace_bytes(int B, int K, int N);
+int masic_udh_fc_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, void* workspace,
+                     float* hidden, float* out, int B, int K, int N, int M, void* stream);
+int masic_udh_shift_corners(const float* corners, float* out, int B, void* stream);
+
 /* ---- host data path, SURVEY.md 8(f)-4: one view of a dataset item (compressai/datasets/utils.py:207-285) from the decoded
  * uint8 RGB picture [H][W][3] on the device: pic_chw (nullable) = the crop [start_h : +ph, start_w : +pw] as float32
  * [3][ph][pw] / 255 (ToTensor); homo_patch (nullable) = the [homopatch][homopatch] window at (patch_x, patch_y) of

@@ -75,6 +75,12 @@ SIGNATURES = {
     "masic_rans_decode_with_indexes": (c_int, [_P, c_size_t, _P, c_int, _P, c_int, _P, _P, c_int, _P]),
     "masic_homography_from_corners": (c_int, [_P, _P, _P, c_int, c_float, c_float, _P]),
     "masic_pair_prep": (c_int, [_P] + [c_int] * 6 + [_P] + [c_int] * 4 + [_P, _P]),
+    # UDH homography net
+    "masic_udh_conv1_fwd": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
+    "masic_maxpool2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "masic_udh_fc_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "masic_udh_fc_fwd": (c_int, [_P] * 8 + [c_int] * 4 + [_P]),
+    "masic_udh_shift_corners": (c_int, [_P, _P, c_int, _P]),
     "masic_rans_encode_freqs": (c_int, [_P, c_size_t, _P, c_size_t, _P]),
     "masic_skinny_ctx_packed_bytes": (c_size_t, [c_int, c_int]),
     "masic_skinny_ctx_pack_weight": (c_int, [_P, _P, c_int, c_int, _P]),

@@ -412,6 +412,64 @@ def homography_from_corners(corners, delta, ori_hw, patch_hw):
     return out
 
 
+# --------------------------------------------------------------------------------------------- UDH homography net
+def udh_conv1(a, b, weight, bias):
+    """relu(Conv2d(2 -> Cout, k3, p1)(cat(a, b))) for two [B,1,H,W] patch tensors without the concat (coremasic/mywork/model.py:94-95);
+    weight [Cout,2,3,3] as the module holds it."""
+    _dev(a, "patch a"); _dev(b, "patch b"); _dev(weight, "weight"); _dev(bias, "bias")
+    if a.dim() != 4 or a.shape[1] != 1 or a.shape != b.shape:
+        raise RuntimeError(f"masic_amd.udh_conv1: patches must be two [B,1,H,W] tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, 2, 3, 3) or tuple(bias.shape) != (Cout,):
+        raise RuntimeError(f"masic_amd.udh_conv1: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} are not a Conv2d(2, Cout, 3)")
+    B, _, H, W = a.shape
+    y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=a.device)
+    check(lib.masic_udh_conv1_fwd(_p(a), _p(b), _p(weight), _p(bias), _p(y), B, H, W, Cout, _stream()), "udh_conv1_fwd")
+    return y
+
+
+def maxpool2(x):
+    """MaxPool2d(2, 2) of a float32 NCHW tensor with even H and W."""
+    _dev(x, "maxpool input")
+    if x.dim() != 4:
+        raise RuntimeError(f"masic_amd.maxpool2: input must be [B,C,H,W], got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    y = torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    check(lib.masic_maxpool2_fwd(_p(x), _p(y), B * C, H, W, _stream()), "maxpool2_fwd")
+    return y
+
+
+def udh_fc(x, w1, b1, w2, b2, want_hidden=False):
+    """The two linear layers of the homography net: hidden = relu(x . w1^T + b1), out = hidden . w2^T + b2, float32 with a fixed
+    summation order (row i of a batch is bitwise the B = 1 result of row i).  x [B,K] (any view of K contiguous floats per row,
+    e.g. the NCHW output of the last convolution), w1 [N,K], w2 [M,N].  Returns out [B,M], or (hidden [B,N], out)."""
+    _dev(x, "fc input"); _dev(w1, "fc weight 1"); _dev(b1, "fc bias 1"); _dev(w2, "fc weight 2"); _dev(b2, "fc bias 2")
+    B = x.shape[0]
+    N, K = w1.shape
+    M = w2.shape[0]
+    if x.numel() != B * K or tuple(b1.shape) != (N,) or tuple(w2.shape) != (M, N) or tuple(b2.shape) != (M,):
+        raise RuntimeError(f"masic_amd.udh_fc: x {tuple(x.shape)}, w1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, w2 {tuple(w2.shape)}, "
+                           f"b2 {tuple(b2.shape)} do not chain")
+    nbytes = _int_query("masic_udh_fc_workspace_bytes", B, K, N)
+    if nbytes == 0:
+        check(-1, "udh_fc_workspace_bytes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    hidden = torch.empty((B, N), dtype=torch.float32, device=x.device) if want_hidden else None
+    out = torch.empty((B, M), dtype=torch.float32, device=x.device)
+    check(lib.masic_udh_fc_fwd(_p(x), _p(w1), _p(b1), _p(w2), _p(b2), _p(ws), _p(hidden), _p(out), B, K, N, M, _stream()), "udh_fc_fwd")
+    return (hidden, out) if want_hidden else out
+
+
+def udh_shift_corners(corners):
+    """corners - corners[:, 0] for [B,4,2] patch corners (newtrain_codec_real.py:123)."""
+    _dev(corners, "corners")
+    if corners.dim() != 3 or tuple(corners.shape[1:]) != (4, 2):
+        raise RuntimeError("masic_amd.udh_shift_corners: corners must be [B,4,2]")
+    out = torch.empty_like(corners)
+    check(lib.masic_udh_shift_corners(_p(corners), _p(out), corners.shape[0], _stream()), "udh_shift_corners")
+    return out
+
+
 def set_warp_align_corners(flag):
     """grid_sample convention of every warp of the library: True = kornia 0.5.0's default (the reference's pinned version, and the
     default here), False = kornia <= 0.4.1's.  Process-wide (include/masic_hip.h: masic_set_warp_align_corners); captured HIP graphs
