@@ -199,11 +199,11 @@ class EntropyBottleneck(EntropyModel):
         if self.training:
             # drawn in the reference's (C, 1, H*W*B) layout (reference :386-394)
             noise = self._get_noise_cached(x.new_empty((C, 1, H * W * B)))
-        medians = self.quantiles.detach()[:, 0, 1].contiguous()
+        medians = self.quantiles.detach()[:, 0, 1]          # a strided view: the kernel reads the parameter in place
         lb = self.likelihood_bound if self.use_likelihood_bound else 0.0
         if self.training and torch.is_grad_enabled() and (x.requires_grad or self._matrices[0].requires_grad):
             from masic_amd.autograd import EntropyBottleneckFn
-            return EntropyBottleneckFn.apply(x, self._table(differentiable=True), noise, medians, lb)
+            return EntropyBottleneckFn.apply(x, self._table(differentiable=True), noise, medians.contiguous(), lb)
         return _hip.entropy_bottleneck(x.contiguous(), self._table(), medians, training=self.training, noise=noise,
                                        lik_bound=self.likelihood_bound if self.use_likelihood_bound else 0.0)
 
@@ -381,7 +381,8 @@ class GaussianMixtureConditional(_GaussianBase):
         lb = self.likelihood_bound if self.use_likelihood_bound else 0.0
         return A.GmmLikFn.apply(y_hat, scales, means, weights, self.K, self._scale_bound_value, lb, bool(weights_are_logits))
 
-    def forward(self, inputs, scales, means=None, weights=None, weights_are_logits=False):
+    def forward(self, inputs, scales, means=None, weights=None, weights_are_logits=False, want_y_hat=True):
+        """want_y_hat=False (no autograd): only the likelihood is wanted -- the quantised latent is not stored and None is returned for it."""
         noise = self._get_noise_cached(inputs) if self.training else None
         lb = self.likelihood_bound if self.use_likelihood_bound else 0.0
         if self.training and torch.is_grad_enabled() and any(t.requires_grad for t in (inputs, scales, means, weights)):
@@ -390,7 +391,7 @@ class GaussianMixtureConditional(_GaussianBase):
         return _hip.gmm_likelihood(inputs.contiguous(), scales.contiguous(), means.contiguous(), weights.contiguous(),
                                    self.K, training=self.training, noise=noise, weights_are_logits=weights_are_logits,
                                    scale_bound=self._scale_bound_value,
-                                   lik_bound=self.likelihood_bound if self.use_likelihood_bound else 0.0)
+                                   lik_bound=self.likelihood_bound if self.use_likelihood_bound else 0.0, want_y_hat=want_y_hat)
 
 
 class GaussianMixtureConditional_gf(GaussianMixtureConditional):

@@ -157,19 +157,20 @@ def _bf16_inference(*tensors):
     return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
 
 
-def _f16k_chain(convs, acts, x, in_op=0, out=None, out_coff=0, gate=None, gate_c=0, out16=None):
+def _f16k_chain(convs, acts, x, in_op=0, out=None, out_coff=0, gate=None, gate_c=0, out16=None, x16=None, shape=None):
     """A chain of convolutions on the float32 NCHW tensor `x` with the activations between them in F16K bf16
-    (conv_f16k.hip); |x| / round(x) is applied while converting the input. The last layer writes float32 NCHW (a channel
+    (conv_f16k.hip); |x| / round(x) is applied while converting the input -- or x16 IS that converted input already (written by
+    the layer that produced x, Encoder1.latent_layouts), and x only gives the shape (or is None, with `shape` = its [B, C, H, W]). The last layer writes float32 NCHW (a channel
     view of `out`, optionally gated) -- or, with out16 = (F16K buffer, its channel count), the same view of an F16K concat buffer.
     None if a layer shape has no F16K configuration."""
-    B, C, H, W = x.shape
+    B, C, H, W = x.shape if shape is None else shape
     sizes = [(H, W)]
     for cv in convs:
         if not cv.f16k_supported(B, *sizes[-1]):
             return None
         d = cv._desc_f16k(B, *sizes[-1])
         sizes.append((d.Ho, d.Wo))
-    t = _hip.nchw_to_f16k(x, in_op=in_op)
+    t = x16 if x16 is not None else _hip.nchw_to_f16k(x, in_op=in_op)
     last = len(convs) - 1
     for i, (cv, act) in enumerate(zip(convs, acts)):
         if i == last:
@@ -195,10 +196,13 @@ def _gdn_f16k(gdn, x):
     return _hip.gdn_f16k(x, gdn.beta.detach(), gdn.gamma.detach(), inverse=gdn.inverse, beta_min=gdn.beta_min)
 
 
-def _analysis_f16k(owner, convs, gdns, x):
+def _analysis_f16k(owner, convs, gdns, x, layouts=None):
     """conv+GDN x3 -> conv of an analysis transform on the float32 NCHW image `x` with bf16 operands: every GDN runs in
     the epilogue of the convolution that feeds it and the 128-channel activations stay in F16K bf16 in between
     (conv_f16k.hip). None if a shape has no such configuration (the caller then takes the NCHW path).
+    layouts (keyword arguments of Conv2d.run_f16k_multi): the last layer writes the latent once in every layout its consumers read
+    and the dict of those tensors is returned instead of the float32 latent -- None (nothing launched) where that form does not
+    apply: fp8 operands / calibration, a shape without the multi-output configuration.
     fp8 mode (masic_amd/fp8.py; `owner` calibrated): the two 128 -> 128 layers take fp8 operands -- the first layer and the
     second write F8K, the third writes F16K for the latent-producing last layer, which stays bf16."""
     from masic_amd import nn as _mnn
@@ -216,6 +220,8 @@ def _analysis_f16k(owner, convs, gdns, x):
         return None
     b1 = None if c1.bias is None else c1.bias.detach()
     sc = _fp8.scales(owner)
+    if layouts is not None and (sc is not None or _mnn._FP8 or _fp8.recording() or not convs[3].f16k_multi_supported(B, *sizes[2])):
+        return None
     if sc is not None and convs[1].f8k_supported(B, *sizes[0]) and convs[2].f8k_supported(B, *sizes[1]):
         t8, _, _ = _hip.conv_a_gdn_f8k(x, c1.packed_first_layer_weight(), b1, (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse), sc["a1"])
         t8, _, _ = convs[1].run_f8k(t8, sc["a1"], B, *sizes[0], gdn=gdns[1], out="f8k", out_scale=sc["a2"])
@@ -226,6 +232,8 @@ def _analysis_f16k(owner, convs, gdns, x):
     t16, _, _ = convs[1].run_f16k(t16, B, *sizes[0], gdn=gdns[1])
     _fp8.record(owner, "a2", t16)
     t16, _, _ = convs[2].run_f16k(t16, B, *sizes[1], gdn=gdns[2])
+    if layouts is not None:
+        return convs[3].run_f16k_multi(t16, B, *sizes[2], **layouts)
     return convs[3].run_f16k(t16, B, *sizes[2], want_nchw=True)[0]
 
 
@@ -240,10 +248,11 @@ class encode_hyper(nn.Module):
             conv(N, N, kernel_size=5), nn.ReLU(inplace=True),
             conv(N, N, kernel_size=5))
 
-    def forward(self, y):
+    def forward(self, y, abs16=None):
+        """abs16: bf16(|y|) in F16K, where the layer that produced y wrote it (the bf16 eval forward)."""
         s = self.encode_hyper
         if _bf16_inference(y, s[0].weight):
-            z = _f16k_chain((s[0], s[2], s[4]), (_RELU, _RELU, _NONE), y, in_op=_hip.INOP_ABS)
+            z = _f16k_chain((s[0], s[2], s[4]), (_RELU, _RELU, _NONE), y, in_op=_hip.INOP_ABS, x16=abs16)
             if z is not None:
                 return z
         t = s[0].run(y, in_op=_hip.INOP_ABS, act=_RELU)
@@ -436,11 +445,13 @@ class mask2weights(nn.Module):
         return s[6].run(t, act=_hip.ACT_SOFTMAX_C)
 
 
-def _synthesis_f16k(dec, y_hat):
+def _synthesis_f16k(dec, y_hat, y16=None, shape=None):
     """The synthesis transform deconv+IGDN x3 -> deconv(128 -> 3) with bf16 operands: F16K activations in between, the
     inverse GDNs fused into the transposed convolutions, the last layer as a 3x3 convolution with a depth-to-space store.
-    Returns the float32 NCHW output of g_s_conv4, or None if a shape is unsupported."""
-    B, _, H, W = y_hat.shape
+    Returns the float32 NCHW output of g_s_conv4, or None if a shape is unsupported.
+    y16: y_hat in F16K already (written by the analysis transform, _analysis_f16k(layouts=...)); y_hat may then be None and
+    `shape` is its [B, M, h, w]."""
+    B, _, H, W = y_hat.shape if shape is None else shape
     convs = (dec.g_s_conv1, dec.g_s_conv2, dec.g_s_conv3)
     gdns = (dec.g_s_gdn1, dec.g_s_gdn2, dec.g_s_gdn3)
     sizes = [(H, W)]
@@ -451,7 +462,7 @@ def _synthesis_f16k(dec, y_hat):
         sizes.append((d.Ho, d.Wo))
     if not dec.g_s_conv4.d2s_supported(B, *sizes[3]):
         return None
-    t16 = _hip.nchw_to_f16k(y_hat)
+    t16 = y16 if y16 is not None else _hip.nchw_to_f16k(y_hat)
     sc = _fp8.scales(dec)
     if sc is not None and convs[1].f8k_supported(B, *sizes[1]) and convs[2].f8k_supported(B, *sizes[2]):
         # fp8 mode: g_s_conv1 keeps bf16 operands (its input are the integer symbols) and writes F8K for the two 128 -> 128 layers
@@ -494,6 +505,14 @@ class Encoder1(nn.Module):
                 return y
         return self.forward(x)[0]
 
+    def latent_layouts(self, x, **layouts):
+        """latent(x) written once in the layouts its consumers read (bf16 eval forward; _analysis_f16k(layouts=...)): a dict of the
+        tensors, or None where that form does not apply -- the caller then uses latent() and the stand-alone conversions."""
+        if _bf16_inference(x, self.g_a_conv1.weight):
+            return _analysis_f16k(self, (self.g_a_conv1, self.g_a_conv2, self.g_a_conv3, self.g_a_conv4),
+                                  (self.g_a_gdn1, self.g_a_gdn2, self.g_a_gdn3), x.contiguous(), layouts=layouts)
+        return None
+
     def latent_train(self, x):
         """forward(x)[0] inside the training graph: in the bf16-operand mode ONE node that runs the DMA-staged inference kernels and
         keeps bf16 activations for its backward (masic_amd/autograd.py: AnalysisFn); otherwise the per-layer nodes."""
@@ -521,10 +540,10 @@ class Decoder1(nn.Module):
         g3 = self.g_s_gdn3(self.g_s_conv3(g2))
         return self.g_s_conv4(g3), g1, g2, g3
 
-    def reconstruct(self, y_hat):
-        """forward(y_hat)[0]; F16K chain with bf16 operands and no autograd."""
+    def reconstruct(self, y_hat, y16=None):
+        """forward(y_hat)[0]; F16K chain with bf16 operands and no autograd (y16: y_hat in F16K already)."""
         if _bf16_inference(y_hat, self.g_s_conv1.weight):
-            x_hat = _synthesis_f16k(self, y_hat)
+            x_hat = _synthesis_f16k(self, y_hat, y16=y16)
             if x_hat is not None:
                 return x_hat
         return self.forward(y_hat)[0]
@@ -555,9 +574,15 @@ class Encoder2(nn.Module):
             return self.forward_views(x1_warp, x2)
         return self.forward_pair(_ag.cat(x1_warp, x2))
 
-    def forward_views(self, x1_warp, x2):
-        """Inference: pre_conv on [x1_warp | x2] read from the two tensors (no torch.cat) with pre_gdn in its epilogue."""
+    def forward_views(self, x1_warp, x2, layouts=None):
+        """Inference: pre_conv on [x1_warp | x2] read from the two tensors (no torch.cat) with pre_gdn in its epilogue.
+        layouts: as Encoder1.latent_layouts -- the dict of latent layouts where that form applies, else the float32 latent."""
         t = _pair_conv(self.pre_conv, x1_warp.contiguous(), x2.contiguous(), gdn_out=self.pre_gdn)
+        if layouts is not None and _bf16_inference(t, self.g_a_conv1.weight):
+            lay = _analysis_f16k(self, (self.g_a_conv1, self.g_a_conv2, self.g_a_conv3, self.g_a_conv4),
+                                 (self.g_a_gdn1, self.g_a_gdn2, self.g_a_gdn3), t, layouts=layouts)
+            if lay is not None:
+                return lay
         return self._analysis(t)
 
     def forward_pair(self, pair):
@@ -592,8 +617,15 @@ class Decoder2(nn.Module):
         self.after_gdn = GDN(3, inverse=True)
         self.after_conv = deconv(6, 3, stride=1)
 
-    def forward(self, y_hat, x1_hat_warp):
-        t = _synthesis_f16k(self, y_hat) if _bf16_inference(y_hat, self.g_s_conv1.weight) else None
+    def forward(self, y_hat, x1_hat_warp, y16=None, shape=None):
+        """y16 / shape (bf16 eval forward): round(y2) in F16K where the analysis transform wrote it, and its [B, M, h, w]; y_hat may then
+        be None -- the result is None as well where the F16K chain does not apply (the caller quantises to float32 and calls again)."""
+        if y_hat is None:
+            t = _synthesis_f16k(self, None, y16=y16, shape=shape) if _bf16_inference(x1_hat_warp, self.g_s_conv1.weight) else None
+            if t is None:
+                return None
+        else:
+            t = _synthesis_f16k(self, y_hat) if _bf16_inference(y_hat, self.g_s_conv1.weight) else None
         if t is None and torch.is_grad_enabled() and _ag.synthesis_supported(self, y_hat):
             t = _ag.synthesis(self, y_hat)
         if t is None:
@@ -668,7 +700,16 @@ class HSIC(CompressionModel):
         if _bf16_inference(z_hat, seq[0].weight):
             # the two small transposed layers (8^2 -> 16^2 -> 32^2: a few dozen workgroups) are quicker on the register-streamed
             # NCHW kernel; the 3x3 288 -> 384 layer at 32^2 on the F16K one (measured: 21 + 58 + 46 us against 47 + 92 + 46)
-            t = seq[2].run(seq[0].run(z_hat, act=_LEAKY), act=_LEAKY)
+            t = seq[0].run(z_hat, act=_LEAKY)
+            B = t.shape[0]
+            if seq[2].f16k_out_supported(t.shape):
+                # the second layer stores bf16 records for the 3x3 layer itself: no float32 tensor and no conversion pass in between
+                d2 = seq[2]._desc(tuple(t.shape))
+                if seq[4].f16k_supported(B, d2.Ho, d2.Wo):
+                    t16, Ho, Wo = seq[2].run_f16k_out(t, act=_LEAKY)
+                    return _f16k_chain((seq[4],), (_NONE,), None, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c, out16=out16,
+                                       x16=t16, shape=(B, seq[2].out_channels, Ho, Wo))
+            t = seq[2].run(t, act=_LEAKY)
             r = _f16k_chain((seq[4],), (_NONE,), t, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c, out16=out16)
             if r is not None:
                 return r
@@ -679,11 +720,13 @@ class HSIC(CompressionModel):
         t = seq[2].run(t, act=_LEAKY)
         return seq[4].run(t, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
 
-    def _context(self, ctx, y, out, out_coff, gate=None, gate_c=0, out16=None):
-        """Eval-mode context model: masked conv of round(y) into a slice of the concat buffer (optionally gated)."""
+    def _context(self, ctx, y, out, out_coff, gate=None, gate_c=0, out16=None, round16=None):
+        """Eval-mode context model: masked conv of round(y) into a slice of the concat buffer (optionally gated).
+        round16: bf16(round(y)) in F16K, where the layer that produced y wrote it."""
         if _bf16_inference(y, ctx.weight):
             ctx.zero_masked_taps()
-            r = _f16k_chain((ctx,), (_NONE,), y, in_op=_hip.INOP_ROUND, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c, out16=out16)
+            r = _f16k_chain((ctx,), (_NONE,), y, in_op=_hip.INOP_ROUND, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c, out16=out16,
+                            x16=round16)
             if r is not None:
                 return r
         if out16 is not None:
@@ -853,10 +896,12 @@ class HSIC(CompressionModel):
     def _eval_right_branch(self, x1, x2, m_fwd, m_back, on_y2=None):
         M = self.M
         B, _, H, W = x1.shape
-        y2 = self.encoder2.forward_views(_hip.warp_perspective(x1, m_fwd, (H, W)), x2)
+        # y2 once, in the layouts of its readers: float32 (likelihood), round (context model, decoder2), |y2| (hyper analysis)
+        lay = self.encoder2.forward_views(_hip.warp_perspective(x1, m_fwd, (H, W)), x2, layouts={"want": ("y32", "round16", "abs16")})
+        y2, y2_round16, y2_abs16 = (lay["y32"], lay["round16"], lay["abs16"]) if isinstance(lay, dict) else (lay, None, None)
         if on_y2 is not None:
             on_y2()                # the reconstruction chain on the main stream only needs y2, not the entropy side of this branch
-        z2 = self._h_a2(y2)
+        z2 = self._h_a2(y2, abs16=y2_abs16)
         z2_hat, z2_lik = self.entropy_bottleneck2(z2)
         h, w = y2.shape[-2:]
         cat16 = self._cat_f16k(self._h_s2_same_resolution, y2, 5 * M)
@@ -867,8 +912,8 @@ class HSIC(CompressionModel):
         x1_mask_L = _hip.warp_perspective(x1_mask_R, m_back, (H, W))
         gates = self.mask2weights_unit(x1_mask_R)                                    # [B,3,h,w]
         self._hyper_up(self.h_s2_up, z2_hat, cat2, 0, gate=gates, gate_c=0, out16=cat16)
-        self._context(self.context_prediction2, y2, cat2, 2 * M, gates, 1, out16=cat16)
-        return {"y2": y2, "z2_hat": z2_hat, "z2_lik": z2_lik, "cat2": cat2, "cat16": cat16, "gates": gates, "x1_mask_R": x1_mask_R, "x1_mask_L": x1_mask_L}
+        self._context(self.context_prediction2, y2, cat2, 2 * M, gates, 1, out16=cat16, round16=y2_round16)
+        return {"y2": y2, "y2_round16": y2_round16, "y2_abs16": y2_abs16, "z2_hat": z2_hat, "z2_lik": z2_lik, "cat2": cat2, "cat16": cat16, "gates": gates, "x1_mask_R": x1_mask_R, "x1_mask_L": x1_mask_L}
 
     def _cat_f16k(self, head, y, C):
         """(F16K buffer, C) for the concat in front of an entropy-parameter head when the bf16 eval forward can keep it in F16K: the
@@ -883,36 +928,39 @@ class HSIC(CompressionModel):
         B, _, h, w = y.shape
         return (_hip.f16k_empty(B, C, h, w, y.device), C)
 
-    def _eval_left_entropy(self, y1):
-        """On the current (side) stream: everything of the left view that only feeds likelihoods."""
+    def _eval_left_entropy(self, y1, round16=None, abs16=None):
+        """On the current (side) stream: everything of the left view that only feeds likelihoods.
+        round16 / abs16: bf16(round(y1)) / bf16(|y1|) in F16K where encoder1 wrote them."""
         M = self.M
         B = y1.shape[0]
         cat16 = self._cat_f16k(self._h_s1_same_resolution, y1, 4 * M)
         cat1 = None if cat16 is not None else torch.empty((B, 4 * M) + tuple(y1.shape[-2:]), dtype=y1.dtype, device=y1.device)   # params1 | ctx_params1
-        self._context(self.context_prediction1, y1, cat1, 2 * M, out16=cat16)
-        z1 = self._h_a1(y1)
+        self._context(self.context_prediction1, y1, cat1, 2 * M, out16=cat16, round16=round16)
+        z1 = self._h_a1(y1, abs16=abs16)
         z1_hat, z1_lik = self.entropy_bottleneck1(z1)
         self._hyper_up(self.h_s1_up, z1_hat, cat1, 0, out16=cat16)
         if cat16 is not None:
             s1, m1, l1 = self._h_s1_same_resolution.heads((B, 4 * M) + tuple(y1.shape[-2:]), x16=cat16[0])
         else:
             s1, m1, l1 = self._h_s1_same_resolution.heads(cat1, parallel=False)
-        _, y1_lik = self.gaussian1(y1, s1, m1, l1, weights_are_logits=True)
+        _, y1_lik = self.gaussian1(y1, s1, m1, l1, weights_are_logits=True, want_y_hat=False)
         return {"z1_hat": z1_hat, "z1_lik": z1_lik, "y1_lik": y1_lik}
 
     def _eval_right_entropy(self, x1_hat_warp, right):
         """On the right view's stream, after its branch: the warped left reconstruction through the left analysis transform
         (the one left -> right dependency of the entropy model), then the right view's heads and likelihood."""
         M = self.M
-        y1_warp = self.encoder1.latent(x1_hat_warp)
         cat2, cat16, gates, y2 = right["cat2"], right["cat16"], right["gates"], right["y2"]
-        if cat16 is not None:             # round(y1_warp) * gate straight into its F16K slice
-            _hip.nchw_to_f16k_view(y1_warp, cat16[0], cat16[1], 4 * M, in_op=_hip.INOP_ROUND, gate=gates, gate_c=2)
+        if cat16 is not None:             # round(y1_warp) * gate straight into its F16K slice ...
+            # ... from the epilogue of the analysis transform's last layer: no float32 y1_warp, no pass over it in front of the heads
+            if self.encoder1.latent_layouts(x1_hat_warp, want=("round16",), round16=cat16[0], round16_ctot=cat16[1], round16_coff=4 * M,
+                                            gate=gates, gate_c=2) is None:
+                _hip.nchw_to_f16k_view(self.encoder1.latent(x1_hat_warp), cat16[0], cat16[1], 4 * M, in_op=_hip.INOP_ROUND, gate=gates, gate_c=2)
             s2, m2, l2 = self._h_s2_same_resolution.heads((y2.shape[0], 5 * M) + tuple(y2.shape[-2:]), x16=cat16[0])
         else:
-            _hip.quantize(y1_warp, "dequantize", out=cat2, out_coff=4 * M, gate=gates, gate_c=2)
+            _hip.quantize(self.encoder1.latent(x1_hat_warp), "dequantize", out=cat2, out_coff=4 * M, gate=gates, gate_c=2)
             s2, m2, l2 = self._h_s2_same_resolution.heads(cat2, parallel=False)
-        _, y2_lik = self.gaussian2(y2, s2, m2, l2, weights_are_logits=True)
+        _, y2_lik = self.gaussian2(y2, s2, m2, l2, weights_are_logits=True, want_y_hat=False)
         return y2_lik
 
     def _forward_eval(self, x1, x2, m_fwd, m_back, synthesis_grad=False):
@@ -934,16 +982,23 @@ class HSIC(CompressionModel):
             right = self._eval_right_branch(x1, x2, m_fwd, m_back, on_y2=lambda: y2_ready.append(fj.record(sA)))
             ev_y2 = y2_ready[0]
         # left view: analysis, then the reconstruction chain here and the entropy chain beside it
-        y1 = self.encoder1.latent(x1)
+        # y1 once, in the layouts of its readers: float32 (likelihood), float32 round = the y1_hat returned, F16K round (context model and
+        # decoder1 share the buffer), F16K |y1| (hyper analysis); where that form does not apply, the separate launches
+        lay = self.encoder1.latent_layouts(x1, want=("y32", "round32", "round16", "abs16"))
+        if lay is not None:
+            y1, y1_hat, y1_round16, y1_abs16 = lay["y32"], lay["round32"], lay["round16"], lay["abs16"]
+        else:
+            y1, y1_hat, y1_round16, y1_abs16 = self.encoder1.latent(x1), None, None, None
         if not serial:
             fj.fork(sE)
         with fj.on(sE):
-            left = self._eval_left_entropy(y1)
+            left = self._eval_left_entropy(y1, round16=y1_round16, abs16=y1_abs16)
             ev_left = fj.record(sE)
-        _keep_until(y1, sE)
-        y1_hat = _hip.quantize(y1, "dequantize")
+        _keep_until((y1, y1_round16, y1_abs16), sE)
+        if y1_hat is None:
+            y1_hat = _hip.quantize(y1, "dequantize")
         with recorded():
-            x1_hat = self.decoder1(y1_hat)[0] if synthesis_grad else self.decoder1.reconstruct(y1_hat)
+            x1_hat = self.decoder1(y1_hat)[0] if synthesis_grad else self.decoder1.reconstruct(y1_hat, y16=y1_round16)
             x1_hat_warp = (_ag.WarpFn.apply(x1_hat, m_fwd, (H, W)) if synthesis_grad
                            else _hip.warp_perspective(x1_hat, m_fwd, (H, W)))        # used twice (:821, :833)
         if not serial:
@@ -955,9 +1010,13 @@ class HSIC(CompressionModel):
         # right view reconstruction
         if not serial:
             fj.wait(cur, ev_y2)
-        y2_hat = _hip.quantize(right["y2"], "dequantize")
-        with recorded():
-            x2_hat = self.decoder2(y2_hat, x1_hat_warp)
+        x2_hat = None
+        if right["y2_round16"] is not None and not synthesis_grad:       # round(y2) is there in F16K: the float32 y2_hat is no output of the model
+            x2_hat = self.decoder2(None, x1_hat_warp, y16=right["y2_round16"], shape=right["y2"].shape)
+        if x2_hat is None:
+            y2_hat = _hip.quantize(right["y2"], "dequantize")
+            with recorded():
+                x2_hat = self.decoder2(y2_hat, x1_hat_warp)
         if not serial:
             fj.wait(cur, ev_left)
             fj.wait(cur, ev_right)

@@ -87,6 +87,13 @@ int masic_conv2d_fwd(const float* x, const void* w_packed, const float* bias, co
  * ResidualBlock (compressai/layers/layers.py:189), Enhancement_Block (MASIC.py:163) and Independent_EN (:1495-1496) */
 int masic_conv2d_fwd_ex(const float* x, const void* w_packed, const float* bias, const float* gate,
                         const float* res1, const float* res2, float* y, const masic_conv_desc_t* d, void* stream);
+/* The layer with its result stored as F16K bf16 instead of float32 NCHW: y_f16k = [B][out_ctot/16][Ho*Wo][16], channels out_coff ..
+ * (both multiples of 16) = bf16(act(conv(x) + bias)), bit for bit what masic_nchw_to_f16k makes of masic_conv2d_fwd's float32 result
+ * -- for a layer whose only reader is an F16K convolution (the second hyper-synthesis layer in front of the 3x3 one).  bf16 operands
+ * on the implicit-GEMM kernel and Cout % 32 == 0 only (masic_conv2d_f16k_out_supported), no gate, no residuals. */
+int masic_conv2d_f16k_out_supported(const masic_conv_desc_t* d);
+int masic_conv2d_f16k_out_fwd(const float* x, const void* w_packed, const float* bias, void* y_f16k,
+                              const masic_conv_desc_t* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The 1x1 stacks of the GMM parameter heads (MASIC.py:330-468) as bf16 GEMMs whose intermediate activations stay in
@@ -164,6 +171,32 @@ int masic_gdn_pack_f16k(const float* beta, const float* gamma, void* packed, int
 int masic_conv_f16k_gdn_fwd(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
                             const void* gdn_packed, int gdn_inverse, float* y_nchw, void* y_f16k,
                             const masic_conv_desc_t* d, void* stream);
+
+/* The latent-producing last layer of an analysis transform (g_a_conv4: Conv2d(128 -> 192, k5, s2), MASIC.py:522, :570) with its result
+ * v = conv(x) + bias written ONCE, from the float32 accumulators, in every layout a consumer of the eval forward reads -- instead of
+ * float32 NCHW followed by masic_quantize_fwd / masic_nchw_to_f16k_op / masic_nchw_to_f16k_view_op passes over that tensor.  Any
+ * non-empty subset of the four outputs; each is bit-identical to what those calls make of the float32 result (rintf in float32, then
+ * the gate in float32, then one round-to-nearest-even to bf16; the sign of zero included):
+ *   y32      float32 [B][Cout][Ho][Wo]     v
+ *   round32  float32 [B][Cout][Ho][Wo]     rintf(v)                 (masic_quantize_fwd mode 0: the y_hat the model returns)
+ *   round16  F16K of round16_ctot channels, channels round16_coff .. round16_coff + Cout - 1 (both multiples of 16):
+ *                                          bf16(rintf(v) * gate)    (masic_nchw_to_f16k_view_op, MASIC_INOP_ROUND; gate: float32
+ *                                          [B][gate_ctot][Ho][Wo], channel gate_c, or NULL = no gate)
+ *   abs16    F16K [B][Cout/16][Ho*Wo][16]  bf16(|v|)                (masic_nchw_to_f16k_op, MASIC_INOP_ABS)
+ * `d`: the layer with act = MASIC_ACT_NONE and no output view (out_ctot = Cout, out_coff = 0), Cout % 32 == 0; its gate fields are not
+ * read.  masic_conv_f16k_multi_supported: 1 for the shapes that have this epilogue (the strided 5x5 bf16 configuration), else 0 --
+ * masic_conv_f16k_multi_fwd then returns MASIC_ERR_UNSUPPORTED and the caller keeps the separate launches. */
+typedef struct masic_f16k_multi_out {
+    float* y32;
+    float* round32;
+    void* round16;
+    void* abs16;
+    const float* gate;
+    int round16_ctot, round16_coff, gate_ctot, gate_c;
+} masic_f16k_multi_out_t;
+int masic_conv_f16k_multi_supported(const masic_conv_desc_t* d);
+int masic_conv_f16k_multi_fwd(const void* x_f16k, const void* w_packed, const float* bias, const masic_f16k_multi_out_t* out,
+                              const masic_conv_desc_t* d, void* stream);
 
 /* encoder2.pre_conv + pre_gdn (MASIC.py:559-560, :574-576) and decoder2.after_gdn + torch.cat + after_conv (:599-600,
  * :617-621) as one launch each: Conv2d / ConvTranspose2d(6 -> 3, k5, s1, p2) on channels [xa(3) | xb(3)] of two float32
@@ -377,6 +410,11 @@ int masic_symbols_fwd(const float* x, const float* median, int32_t* sym,
 int masic_entropy_bottleneck_fwd(const float* z, const float* params, const float* medians,
                                  const float* noise, float* z_hat, float* lik,
                                  int B, int C, int H, int W, int training, float lik_bound, void* stream);
+/* The same with the medians read at a stride of median_stride floats: (&quantiles[0][0][1], 3) reads them in place from the
+ * quantiles parameter [C][1][3] instead of from a contiguous copy made in front of every call. */
+int masic_entropy_bottleneck_strided_fwd(const float* z, const float* params, const float* medians, int median_stride,
+                                         const float* noise, float* z_hat, float* lik,
+                                         int B, int C, int H, int W, int training, float lik_bound, void* stream);
 /* EntropyBottleneck.loss(): entropy_models.py:345-348. out[0] = sum |logits(quantiles) - target| */
 int masic_entropy_bottleneck_auxloss(const float* params, const float* quantiles, float* out,
                                      int C, double tail_mass, void* stream);
@@ -389,8 +427,10 @@ int masic_entropy_bottleneck_auxloss(const float* params, const float* quantiles
  * weights_are_logits=1 fuses the softmax over K of MASIC.py:389-393/459-464 into the kernel
  * (wts then holds the raw gmm_weights head output, and wts_out, if non-NULL, receives the
  * normalised weights).
- * training: 0 round(y), 1 y + noise, 2 y is the quantised latent already -- likelihood only, y_hat may be NULL
+ * training: 0 round(y), 1 y + noise, 2 y is the quantised latent already -- likelihood only
  * (the training forward draws y + noise where the reference does and evaluates the likelihood beside the synthesis transform).
+ * y_hat may be NULL in every mode: the quantised latent is then not stored (the eval forward only keeps the likelihood); lik is
+ * the same bit for bit.
  */
 int masic_gmm_likelihood_fwd(const float* y, const float* noise, const float* sigma, const float* mu,
                              const float* wts, float* y_hat, float* lik, float* wts_out,

@@ -41,6 +41,12 @@ class GemmGroup(ctypes.Structure):
                 ("act", ctypes.c_int32)]
 
 
+class F16kMultiOut(ctypes.Structure):
+    """masic_f16k_multi_out_t"""
+    _fields_ = [("y32", c_void_p), ("round32", c_void_p), ("round16", c_void_p), ("abs16", c_void_p), ("gate", c_void_p),
+                ("round16_ctot", ctypes.c_int32), ("round16_coff", ctypes.c_int32), ("gate_ctot", ctypes.c_int32), ("gate_c", ctypes.c_int32)]
+
+
 _P = c_void_p
 # name -> (restype, argtypes); every symbol of include/masic_hip.h
 SIGNATURES = {
@@ -52,6 +58,8 @@ SIGNATURES = {
     "masic_conv_pack_weight": (c_int, [_P, _P, ctypes.POINTER(ConvDesc), _P]),
     "masic_conv2d_fwd": (c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),
     "masic_conv2d_fwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),
+    "masic_conv2d_f16k_out_supported": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "masic_conv2d_f16k_out_fwd": (c_int, [_P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),
     "masic_f16k_bytes": (c_size_t, [c_int, c_int, c_int]),
     "masic_nchw_to_f16k": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "masic_nchw_to_f16k_op": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
@@ -102,6 +110,8 @@ SIGNATURES = {
     "masic_gdn_f16k_packed_bytes": (c_size_t, []),
     "masic_gdn_pack_f16k": (c_int, [_P, _P, _P, c_int, c_double, _P]),
     "masic_conv_f16k_gdn_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
+    "masic_conv_f16k_multi_supported": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "masic_conv_f16k_multi_fwd": (c_int, [_P, _P, _P, ctypes.POINTER(F16kMultiOut), ctypes.POINTER(ConvDesc), _P]),
     "masic_conv_f16k_gdn_dual_fwd": (c_int, [_P, _P, _P, _P, c_int, _P, _P, ctypes.POINTER(ConvDesc), _P]),
     "masic_conv_a_gdn_dual_fwd": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "masic_conv_a_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
@@ -156,6 +166,7 @@ SIGNATURES = {
     "masic_quantize_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 9 + [_P]),
     "masic_symbols_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "masic_entropy_bottleneck_fwd": (c_int, [_P] * 6 + [c_int] * 5 + [c_float, _P]),
+    "masic_entropy_bottleneck_strided_fwd": (c_int, [_P, _P, _P, c_int, _P, _P, _P] + [c_int] * 5 + [c_float, _P]),
     "masic_entropy_bottleneck_auxloss": (c_int, [_P, _P, _P, c_int, c_double, _P]),
     "masic_gmm_likelihood_fwd": (c_int, [_P] * 8 + [c_int] * 7 + [c_float, c_float, _P]),
     "masic_softmax_k_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),

@@ -170,6 +170,7 @@ struct IgemmArgs {
     int in_op, act, gate_ctot, gate_c;
     GeomParams q;
     int nphase;
+    unsigned short* y16;      // conv_igemm_bf16 only (masic_conv2d_f16k_out_fwd): instead of y, F16K [B][out_ctot/16][Ho*Wo][16] bf16 of the result
 };
 
 __device__ __attribute__((aligned(16))) float g_zero_word[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -230,6 +231,56 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, const ConvGeo
                 const int co = m0w + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
                 float v = apply_act(acc[m][n][e] + bv[m][e], a.act) * gv + rv[e];
                 if (pok && co < a.Cout) a.y[((size_t)b * a.out_ctot + a.out_coff + co) * oplane + opix] = v;
+            }
+        }
+    }
+}
+
+// ---- F16K output (conv_igemm_bf16, a.y16): bf16(act(acc + bias)) as 32-byte channel records for an F16K consumer -- what
+// nchw_to_f16k_kernel makes of the float32 result of igemm_epilogue, bit for bit (that epilogue computes act(..) * 1.0f + 0.0f when there
+// is no gate and no residual: the + 0.0f turns -0 into +0 and is kept here).  Lane (j, h) holds channels 8q + 4h + i of pixel j, the
+// accumulator layout of conv_f16k.hip: the halves of the wave swap their middle quarters (v_permlane32_swap) and each lane writes the 8
+// consecutive channels 8h .. 8h+7 of a record with one 16-byte store.  Cout % 32 == 0: a 32-channel tile is valid or not as a whole.
+template <int WM, int WN>
+__device__ __forceinline__ void igemm_epilogue_f16k(const IgemmArgs& a, const ConvGeom& g, f32x16 (&acc)[WM][WN], int b, int m0w,
+                                                    int r0, int c0, int wn, int jr, int jc, int h) {
+    const size_t oplane = (size_t)a.Ho * a.Wo;
+    float bv[WM][16];
+#pragma unroll
+    for (int m = 0; m < WM; ++m)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int co = m0w + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            bv[m][e] = (a.bias != nullptr) ? a.bias[co < a.Cout ? co : a.Cout - 1] : 0.0f;
+        }
+#pragma unroll
+    for (int n = 0; n < WN; ++n) {
+        const int r = r0 + (wn * WN + n) * a.SR + jr, c = c0 + jc;
+        const bool pok = r < g.Hp && c < g.Wp;               // (a function of the lane's pixel j: the same in both halves of the wave)
+        const int oh = pok ? r * g.os + g.oph : 0, ow = pok ? c * g.os + g.opw : 0;
+        const size_t opix = (size_t)oh * a.Wo + ow;
+#pragma unroll
+        for (int m = 0; m < WM; ++m) {
+            if (!pok || m0w + m * 32 >= a.Cout) continue;
+            unsigned pk[8];
+#pragma unroll
+            for (int e = 0; e < 16; e += 2) {
+                const float v0 = apply_act(acc[m][n][e] + bv[m][e], a.act) * 1.0f + 0.0f;
+                const float v1 = apply_act(acc[m][n][e + 1] + bv[m][e + 1], a.act) * 1.0f + 0.0f;
+                typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+                bf16x2 t;
+                t[0] = (__bf16)v0;
+                t[1] = (__bf16)v1;
+                pk[e >> 1] = __builtin_bit_cast(unsigned, t);
+            }
+            unsigned short* rec = a.y16 + (((size_t)b * (a.out_ctot >> 4) + ((a.out_coff + m0w + m * 32) >> 4)) * oplane + opix) * 16 + 8 * h;
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) {     // record rr of the tile: channels 16 rr .. 16 rr + 15
+                const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * rr + 0], pk[4 * rr + 2], false, false);
+                const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * rr + 1], pk[4 * rr + 3], false, false);
+                uint4 st;
+                st.x = s0[0]; st.y = s1[0]; st.z = s0[1]; st.w = s1[1];
+                *reinterpret_cast<uint4*>(rec + (size_t)rr * oplane * 16) = st;
             }
         }
     }
@@ -795,6 +846,10 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_bf16(const IgemmArgs a, con
         __syncthreads();
     }
 
+    if (a.y16 != nullptr) {       // (uniform: a kernel argument)
+        igemm_epilogue_f16k<WM, WN>(a, g, acc, b, m0 + wm * (32 * WM), r0, c0, wn, jr, jc, h);
+        return;
+    }
     igemm_epilogue<WM, WN>(a, g, acc, b, m0 + wm * (32 * WM), r0, c0, wn, jr, jc, h);
 }
 
@@ -1004,15 +1059,45 @@ extern "C" int masic_conv2d_fwd(const float* x, const void* w_packed, const floa
     return masic_conv2d_fwd_ex(x, w_packed, bias, gate, nullptr, nullptr, y, d, stream);
 }
 
+namespace {
+int conv2d_launch(const float* x, const void* w_packed, const float* bias, const float* gate,
+                  const float* res1, const float* res2, float* y, void* y_f16k, const masic_conv_desc_t* d, void* stream);
+}
+
 extern "C" int masic_conv2d_fwd_ex(const float* x, const void* w_packed, const float* bias, const float* gate,
                                    const float* res1, const float* res2, float* y, const masic_conv_desc_t* d, void* stream) {
-    int rc = check_desc(d);
-    if (rc != MASIC_OK) return rc;
-    MASIC_REQUIRE(d->prec != MASIC_PREC_FP8, MASIC_ERR_UNSUPPORTED, "conv2d_fwd: fp8 operands exist on the F8K entry points only (masic_conv_f8k_fwd)");
-    MASIC_REQUIRE(x && w_packed && y, MASIC_ERR_ARG, "conv2d_fwd: null pointer");
+    MASIC_REQUIRE(y != nullptr, MASIC_ERR_ARG, "conv2d_fwd: null pointer");
+    return conv2d_launch(x, w_packed, bias, gate, res1, res2, y, nullptr, d, stream);
+}
+
+// 1 when masic_conv2d_f16k_out_fwd has a kernel for the layer: bf16 operands on the implicit-GEMM kernel, whole 32-channel tiles
+extern "C" int masic_conv2d_f16k_out_supported(const masic_conv_desc_t* d) {
+    if (check_desc(d) != MASIC_OK || d->prec != MASIC_PREC_BF16 || d->Cout % 32 != 0 || d->out_ctot % 16 != 0 || d->out_coff % 16 != 0) return 0;
     ConvGeom g[4];
     const int np = build_geoms(*d, g);
     const ConvCfg c = choose_cfg(*d, g, np);
+    return !c.direct && c.bf16;
+}
+
+extern "C" int masic_conv2d_f16k_out_fwd(const float* x, const void* w_packed, const float* bias, void* y_f16k,
+                                         const masic_conv_desc_t* d, void* stream) {
+    MASIC_REQUIRE(y_f16k != nullptr && d != nullptr, MASIC_ERR_ARG, "conv2d_f16k_out_fwd: null pointer");
+    MASIC_REQUIRE(masic_conv2d_f16k_out_supported(d), MASIC_ERR_UNSUPPORTED,
+                  "conv2d_f16k_out_fwd: needs bf16 operands on the implicit-GEMM kernel, Cout % 32 == 0 and a 16-aligned output view");
+    return conv2d_launch(x, w_packed, bias, nullptr, nullptr, nullptr, nullptr, y_f16k, d, stream);
+}
+
+namespace {
+int conv2d_launch(const float* x, const void* w_packed, const float* bias, const float* gate,
+                  const float* res1, const float* res2, float* y, void* y_f16k, const masic_conv_desc_t* d, void* stream) {
+    int rc = check_desc(d);
+    if (rc != MASIC_OK) return rc;
+    MASIC_REQUIRE(d->prec != MASIC_PREC_FP8, MASIC_ERR_UNSUPPORTED, "conv2d_fwd: fp8 operands exist on the F8K entry points only (masic_conv_f8k_fwd)");
+    MASIC_REQUIRE(x && w_packed && (y || y_f16k), MASIC_ERR_ARG, "conv2d_fwd: null pointer");
+    ConvGeom g[4];
+    const int np = build_geoms(*d, g);
+    const ConvCfg c = choose_cfg(*d, g, np);
+    MASIC_REQUIRE(y_f16k == nullptr || (!c.direct && c.bf16), MASIC_ERR_UNSUPPORTED, "conv2d_fwd: F16K output exists on conv_igemm_bf16 only");
     hipStream_t st = (hipStream_t)stream;
     const GeomParams q = geom_params(*d);
     if (g[0].Hp <= 0 || g[0].Wp <= 0) return MASIC_OK;
@@ -1052,7 +1137,7 @@ extern "C" int masic_conv2d_fwd_ex(const float* x, const void* w_packed, const f
                     c.Cin_pad, c.Cout_pad, c.KC, c.KClog,
                     c.TW, c.TWlog, c.SR, c.TH, ceil_div(g[0].Wp, c.TW),
                     c.PH, c.PW, c.PWp, c.PSZ, c.buf_sz, c.vec4,
-                    d->in_op, d->act, d->gate_ctot, d->gate_c, q, np};
+                    d->in_op, d->act, d->gate_ctot, d->gate_c, q, np, (unsigned short*)y_f16k};
         dim3 grid(ceil_div(g[0].Wp, c.TW) * ceil_div(g[0].Hp, c.TH) * np, c.Cout_pad / (32 * c.wm * c.wvm), d->B);
         if (c.bf16) {
 #define BF16_LAUNCH(WV, WMV, WNV, OPV)                                                                                            \
@@ -1101,6 +1186,7 @@ extern "C" int masic_conv2d_fwd_ex(const float* x, const void* w_packed, const f
     }
     return masic_launch_status("conv2d_fwd");
 }
+}  // namespace
 
 // encoder2.pre_conv + pre_gdn and decoder2.after_gdn + cat + after_conv (MASIC.py:559-560, :574-576, :599-600, :617-621) as one
 // launch each: Conv2d / ConvTranspose2d(6 -> 3, k5, s1, p2) whose six input channels come from two 3-channel tensors (no

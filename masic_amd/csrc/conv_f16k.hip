@@ -1,424 +1,14 @@
-// conv_f16k.hip -- bf16 implicit-GEMM convolutions on channel-blocked activations (gfx950 / MI355X).
-//
-// Same layers and the same phase geometry as conv.hip (reference: coremasic/mywork/MASIC.py:510-622 analysis /
-// synthesis transforms, :170-187 and :690-700 hyper transforms; factories compressai/models/utils.py:128-146), for the
-// bf16-operand forward.  conv.hip's bf16 kernel reads float32 NCHW and converts while staging, which makes every
-// workgroup re-convert its halo and leaves the matrix cores waiting on VGPR staging and on L2 latency of the weight
-// fragments.  Here both operands reach LDS by DMA (global_load_lds, 16 bytes per lane, no VGPR round trip):
-//
-//   activations  F16K  [B][C/16][H*W][16] bf16 (gemm_bf16.hip): a pixel's 16 channels are one 32-byte record, so the
-//                patch of a tile for one 16-channel block is rows of contiguous records and an MFMA B fragment
-//                (8 consecutive k of one pixel) is one ds_read_b128;
-//   weights      [phase-tap][ci/16][co][16] bf16 (pack_weight_bf16_kernel): one (tap, 16-channel) slab of a
-//                128-channel block is 4 KiB contiguous, an A fragment is one ds_read_b128.
-//
-// Workgroup = 8 waves (2 along co x 4 along pixels), tile 128 co x 256 pixels, wave tile 64 x 64 (2 x 2 MFMA
-// 32x32x16 accumulators).  K runs over chunks of KS 16-channel blocks; within a chunk over "steps" of T taps.
-// Every step each wave issues the same number of DMA wave-instructions -- WI for the weight slab of step g+D
-// (D+1-deep ring) and PS for a slice of the patch of chunk c+L (L+1 buffers) -- so that completion can be awaited
-// with a counted `s_waitcnt vmcnt((D-1)*(WI+PS))` (never 0 inside the loop) followed by one raw s_barrier per step:
-// DMA stays in flight across barriers.  Unused issue slots go to a dummy 1 KiB LDS region to keep the count fixed.
-//
-// LDS images are XOR-swizzled in 16-byte slots, slot' = slot ^ ((slot >> 4) & 3): the stride-2 pixel walk of a
-// strided conv (64 B between lanes), the stride-1 walk (32 B) and the weight rows (32 B) all become conflict-free for
-// ds_read_b128's four 16-lane groups.  The swizzle is applied on the DMA side by permuting which record a lane fetches.
-//
-// Epilogue: bias + activation, then either float32 NCHW (channel view of a concat buffer, optional gate) or F16K bf16
-// for the next layer.
-#include "common.h"
-#include <type_traits>
-#include "conv_geom.h"
-
-namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// LDS reads / waits the compiler does not see (see the K loop of conv_f16k)
-template <int OFF>
-__device__ __forceinline__ void ds_read128(v4u& dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d, v4u& e) {
-    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d, v4u& e, v4u& f) {
-    asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b) {
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c) {
-    asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d) {
-    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d, v4u& e, v4u& f, v4u& g, v4u& h) {
-    asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d, v4u& e, v4u& f, v4u& g, v4u& h, v4u& i, v4u& j) {
-    asm volatile("s_waitcnt lgkmcnt(%10)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h), "+v"(i), "+v"(j) : "n"(N) : "memory");
-}
-
-// ---- fp8 (OCP e4m3fn) operands: v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales (E8M0 127) = a plain fp8 MFMA at
-// twice the bf16 rate (MI355X_MICROARCH.md, Matrix cores).  A lane's operand is 32 consecutive k (two ds_read_b128 that the
-// register coalescer places in one 8-register tuple); lanes 0-31 / 32-63 hold the two 32-k halves of the instruction's K = 64.
-typedef int v8i __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ v8i cat8(const v4u& lo, const v4u& hi) {
-    return __builtin_bit_cast(v8i, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-__device__ __forceinline__ f32x16 mfma_f8(const v8i& a, const v8i& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
-}
-__device__ __forceinline__ unsigned pack4f8(float a, float b, float c, float d, float inv) {
-    // saturating: e4m3fn has no infinity, its largest finite value is 448
-    a = __builtin_amdgcn_fmed3f(a * inv, -448.0f, 448.0f);
-    b = __builtin_amdgcn_fmed3f(b * inv, -448.0f, 448.0f);
-    c = __builtin_amdgcn_fmed3f(c * inv, -448.0f, 448.0f);
-    d = __builtin_amdgcn_fmed3f(d * inv, -448.0f, 448.0f);
-    int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-    return (unsigned)v;
-}
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void dma16(const void* g, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int swz(int slot) { return slot ^ ((slot >> 4) & 3); }
-
-// F16K store of the 32 channels of accumulator tile `t` (lane (j, h) holds channels 4h + 8q + i, q, i < 4, of pixel j):
-// the two halves of the wave swap their middle quarters (v_permlane32_swap) so that lane (j, h) ends up with the 8
-// consecutive channels 8h .. 8h+7 of each 16-channel record and writes it with one 16-byte store -- the wave writes
-// whole 32-byte records (full sectors; 1 KiB contiguous when the pixels are adjacent) instead of scattered 8-byte pieces.
-// rec: address of the lane's pixel in the first of the two records, + 8h elements; rec_stride: elements between records.
-__device__ __forceinline__ unsigned pack2bf(float lo, float hi);
-// residual add in float32 BEFORE the rounding to bf16: lane (j, h) holds channels 8q + 4h + i of tile t, i.e. 4 consecutive
-// bf16 (8 bytes) at element offset 8(q & 1) + 4h of record q >> 1 of the residual's tile.  res: address of the lane's pixel in
-// the first record of the tile (element units), + 4h.
-__device__ __forceinline__ void add_f16k_residual(f32x16& t, const unsigned short* res, unsigned rec_stride) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint2 r = *reinterpret_cast<const uint2*>(res + (size_t)(q >> 1) * rec_stride + 8 * (q & 1));
-        t[4 * q + 0] += __builtin_bit_cast(float, r.x << 16);
-        t[4 * q + 1] += __builtin_bit_cast(float, r.x & 0xffff0000u);
-        t[4 * q + 2] += __builtin_bit_cast(float, r.y << 16);
-        t[4 * q + 3] += __builtin_bit_cast(float, r.y & 0xffff0000u);
-    }
-}
-// t *= act'(mask): the backward of ReLU / LeakyReLU(0.01) as an epilogue of the input-gradient convolution -- mask = the forward
-// activation's OUTPUT in F16K (its sign is the pre-activation's), addressed like a residual tensor
-__device__ __forceinline__ void mul_f16k_actmask(f32x16& t, const unsigned short* mask, unsigned rec_stride, float slope) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint2 r = *reinterpret_cast<const uint2*>(mask + (size_t)(q >> 1) * rec_stride + 8 * (q & 1));
-        t[4 * q + 0] *= __builtin_bit_cast(float, r.x << 16) > 0.0f ? 1.0f : slope;
-        t[4 * q + 1] *= __builtin_bit_cast(float, r.x & 0xffff0000u) > 0.0f ? 1.0f : slope;
-        t[4 * q + 2] *= __builtin_bit_cast(float, r.y << 16) > 0.0f ? 1.0f : slope;
-        t[4 * q + 3] *= __builtin_bit_cast(float, r.y & 0xffff0000u) > 0.0f ? 1.0f : slope;
-    }
-}
-__device__ __forceinline__ void store_f16k_tile(const f32x16& t, unsigned short* rec, unsigned rec_stride) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const unsigned a0 = pack2bf(t[8 * r + 0], t[8 * r + 1]), a1 = pack2bf(t[8 * r + 2], t[8 * r + 3]);   // channels 4h .. 4h+3
-        const unsigned b0 = pack2bf(t[8 * r + 4], t[8 * r + 5]), b1 = pack2bf(t[8 * r + 6], t[8 * r + 7]);   // channels 8 + 4h ..
-        const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        uint4 st;
-        st.x = s0[0]; st.y = s1[0]; st.z = s0[1]; st.w = s1[1];
-        *reinterpret_cast<uint4*>(rec + (size_t)r * rec_stride) = st;
-    }
-}
-
-// the same through a buffer resource: voff = byte offset of the lane's pixel in the first record + 16h, or any offset >= the resource's
-// size for a lane that has nothing to store (dropped by the range check) -- the instruction is issued unconditionally, so the number
-// of store instructions a wave has in flight is known at compile time (counted s_waitcnt vmcnt in conv_a_gdn_f16k)
-__device__ __forceinline__ void store_f16k_tile_buf(const f32x16& t, __amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned rec_stride_bytes) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const unsigned a0 = pack2bf(t[8 * r + 0], t[8 * r + 1]), a1 = pack2bf(t[8 * r + 2], t[8 * r + 3]);
-        const unsigned b0 = pack2bf(t[8 * r + 4], t[8 * r + 5]), b1 = pack2bf(t[8 * r + 6], t[8 * r + 7]);
-        const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        v4u st = {s0[0], s1[0], s0[1], s1[1]};
-        __builtin_amdgcn_raw_buffer_store_b128(st, rs, (int)(voff + r * rec_stride_bytes), 0, 0);
-    }
-}
-
-// F8K store (fp8 activations [B][C/32][H*W][32]: a pixel's 32 channels are one 32-byte record) of accumulator tile `t` = one
-// whole record per pixel: lane (j, h) holds channels 8q + 4h + i; after two v_permlane32_swap it holds the 16 consecutive
-// channels 16h .. 16h+15 and writes them with one 16-byte store.  rec: address of the lane's pixel record + 16h bytes.
-__device__ __forceinline__ unsigned pack4f8(float a, float b, float c, float d, float inv);
-__device__ __forceinline__ void store_f8k_tile(const f32x16& t, unsigned char* rec, float inv) {
-    unsigned q[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q[k] = pack4f8(t[4 * k], t[4 * k + 1], t[4 * k + 2], t[4 * k + 3], inv);
-    const auto s0 = __builtin_amdgcn_permlane32_swap(q[0], q[2], false, false);     // h = 0: channels 0-3, 4-7;   h = 1: 16-19, 20-23
-    const auto s1 = __builtin_amdgcn_permlane32_swap(q[1], q[3], false, false);     // h = 0: 8-11, 12-15;         h = 1: 24-27, 28-31
-    uint4 st;
-    st.x = s0[0]; st.y = s0[1]; st.z = s1[0]; st.w = s1[1];
-    *reinterpret_cast<uint4*>(rec) = st;
-}
-
-__device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (__bf16)lo;
-    v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
-
-struct F16kArgs {
-    const unsigned short* x;      // F16K [B][in_c16tot][Hi*Wi][16]
-    const unsigned short* w;      // slab stream, see pack_f16k_stream_kernel
-    const float* bias;
-    const float* gate;            // float32 [B][gate_ctot][Ho][Wo] or null (NCHW output only)
-    float* y32;                   // float32 NCHW view, or null
-    unsigned short* y16;          // F16K [B][out_c16tot][Ho*Wo][16], or null
-    const uint4* gdn_img;         // GDN epilogue: gamma^ fragments (gdn.hip: gdn_pack_f16k_kernel), then beta^[128] floats
-    const unsigned short* res1;   // F16K output only: up to two residual tensors [B][res_ctot/16][Ho*Wo][16] added after the activation
-    const unsigned short* res2;   //   (ResidualBlock / Enhancement_Block identities, compressai/layers/layers.py:189, MASIC.py:163)
-    int res_ctot;
-    unsigned short* y16_pre;      // fused GDN + F16K output: also store the convolution's result BEFORE the GDN (same view), or null --
-                                  //   what the GDN backward of a training step needs (masic_amd/autograd.py: AnalysisFn / SynthesisFn);
-                                  //   residual form: the activation's output BEFORE the residual adds (view of res_ctot channels)
-    unsigned long long* stamps;   // diagnostics (masic_conv_f16k_set_stamps): {s_memtime, s_memrealtime} at 4 points of the first and last workgroup
-    const unsigned short* mask16; // F16K output only: multiply by act'(mask) before the residual adds (mask: F16K of res_ctot channels;
-    float mask_slope;             //   slope for mask <= 0: 0.01 LeakyReLU, 0 ReLU) -- input gradients of the training step
-    const float* res32;           // float32 NCHW output only: residual [B][cout_store][Ho][Wo] added after the activation, or null
-    int cout_store;               // float32 NCHW output: channels actually stored (< Cout when the weight was zero-padded to a multiple of 32)
-    const float* wscale;          // fp8 operands: per-output-channel dequantisation factor (weight scale x input scale), else null
-    unsigned char* y8;            // F8K [B][out_c32tot][Ho*Wo][32] fp8 output (quantised with out_inv_scale), or null
-    float out_inv_scale;
-    int gdn_inverse;
-    int d2s;                      // > 0: channel 4c + phase (2x2 phases, c < d2s); y32 is [B][out_ctot][2Ho][2Wo] (depth-to-space store)
-    int in_c16tot, in_c16off, Cin16;
-    int Hi, Wi, Cout, Ho, Wo;
-    int out_ctot, out_coff;       // channel view of the output (NCHW: channels; F16K: channels, multiples of 16)
-    int gate_ctot, gate_c, act;
-    int TW, TWlog, SR, TH, tiles_w, ntiles;
-    int PH, PW, PWh, NPIXp;       // patch rows / row length (pixels), ceil(PW/2), records per k-half plane of the LDS image (x32)
-    int PB;                       // bytes per patch buffer
-    unsigned mg_PW, mg_PWh, mg_gpk;   // ceil(2^32 / d): x / d == __umulhi(x, magic) for the small x, d of the patch maps
-    unsigned phase_off[4];        // byte offset of each phase's slab streams
-    unsigned stream_bytes[4];     // bytes of one (phase, co-block) slab stream
-    GeomParams q;
-    int nphase;
-    int xcd_images;               // B % 8 == 0: image b runs on XCD b % 8 (the halos of its tiles meet in one L2)
-    int msplit;                   // workgroups per 128-channel co-block (4 / NM for layers whose grid would not fill the chip, else 1):
-                                  //   blockIdx.y = co-block * msplit + sub-block, a sub-block = NM accumulator tiles of the slab
-};
-
-#ifndef F16K_DMA_SPREAD
-#define F16K_DMA_SPREAD 1  // 0: the K loop's DMA pieces issued en bloc at the top of every step (A/B timing, tools/ablate_f16k.sh)
-#endif
-#ifndef F16K_ABLATE
-#define F16K_ABLATE 0     // timing experiments only (tools/ablate_f16k.sh): 1 no DMA in the K loop, 2 no barriers, 3 no fragment reads, 4 a quarter of the MFMAs
-#endif
-constexpr int MAXTAPS = 64;   // tap table entries ([step][T rounded up to a power of two])
-
-// Weights for this path, in the order the kernel consumes them ("slab stream"): for each phase, each 128-channel
-// co-block, each chunk c of KS 16-channel blocks, each step t of T taps (taps padded with zeros to a multiple of T):
-// T*KS slabs of 4 KiB, each the LDS image [k-half hh][co 128][8 ci] of W[co, (c*KS+ks)*16 + hh*8 + e, tap].
-// A step's slab group is one contiguous WST = T*KS*4096 bytes, so the DMA of step g is base + g*WST.
-struct PackStreamArgs {
-    const float* w;
-    int Cin, Cout, KH, KW, transposed;
-    int KS, T, nchunks, ncb;
-    ConvGeom gs[4];           // one launch packs every phase (blockIdx.y)
-    unsigned phase_offs[4];   // bytes
-};
-
-__device__ __forceinline__ void pack_f16k_stream_body(const PackStreamArgs& a, unsigned short* __restrict__ wp, int phase, int bx, int nbx) {
-    const ConvGeom g = a.gs[phase];
-    const unsigned phase_off = a.phase_offs[phase];
-    const int spc = (g.ntaps + a.T - 1) / a.T;
-    const size_t total = (size_t)a.ncb * a.nchunks * spc * a.T * a.KS * 2048;        // bf16 elements
-    for (size_t i = (size_t)bx * blockDim.x + threadIdx.x; i < total; i += (size_t)nbx * blockDim.x) {
-        size_t r = i;
-        const int e = (int)(r & 7); r >>= 3;
-        const int co = (int)(r & 127); r >>= 7;
-        const int hh = (int)(r & 1); r >>= 1;
-        const int ks = (int)(r % a.KS); r /= a.KS;
-        const int tt = (int)(r % a.T); r /= a.T;
-        const int t = (int)(r % spc); r /= spc;
-        const int c = (int)(r % a.nchunks); r /= a.nchunks;
-        const int cb = (int)r;
-        const int tap = t * a.T + tt;
-        const int ci = (c * a.KS + ks) * 16 + hh * 8 + e, cog = cb * 128 + co;
-        float v = 0.0f;
-        if (tap < g.ntaps && ci < a.Cin && cog < a.Cout) {
-            const int ta = tap / g.ntw, tb = tap - ta * g.ntw;
-            const int kh = g.kh0 + ta * g.khs, kw = g.kw0 + tb * g.kws;
-            const size_t src = a.transposed ? (((size_t)ci * a.Cout + cog) * a.KH + kh) * a.KW + kw
-                                            : (((size_t)cog * a.Cin + ci) * a.KH + kh) * a.KW + kw;
-            v = a.w[src];
-        }
-        const __bf16 bv = (__bf16)v;
-        wp[(phase_off >> 1) + i] = __builtin_bit_cast(unsigned short, bv);
-    }
-}
-
-__global__ void pack_f16k_stream_kernel(const PackStreamArgs a, unsigned short* __restrict__ wp) {
-    pack_f16k_stream_body(a, wp, blockIdx.y, blockIdx.x, gridDim.x);
-}
-
-// Many layers' streams in one launch (a training step re-packs every weight it touches -- each for its forward and for its input
-// gradient -- ~50 launches of ~5 us whose work is a few microseconds): blockIdx.y = job, blockIdx.z = phase; a job is what one
-// masic_conv_f16k_pack_weight call would launch.  The job table lives in device memory (built once per set of layers).
-struct PackStreamJob { PackStreamArgs a; unsigned short* wp; int nb, np; };
-
-__global__ void pack_f16k_stream_multi_kernel(const PackStreamJob* __restrict__ jobs) {
-    const PackStreamJob& j = jobs[blockIdx.y];
-    if ((int)blockIdx.z >= j.np || (int)blockIdx.x >= j.nb) return;
-    pack_f16k_stream_body(j.a, j.wp, blockIdx.z, blockIdx.x, j.nb);
-}
-
-// fp8 operands: the same stream with 32-channel blocks -- slab (tap, block) = LDS image [k-half hh][co 128][16 ci] of
-// fp8(W[co, (c*KS+ks)*32 + hh*16 + e, tap] / wscale[co]); wscale[co] = max |W[co]| / 448 (per-output-channel scaling).
-__global__ void wscale_f8k_kernel(const float* __restrict__ w, float* __restrict__ ws, int Cin, int Cout, int taps, int transposed) {
-    const int co = blockIdx.x;
-    float m = 0.0f;
-    for (int i = threadIdx.x; i < Cin * taps; i += blockDim.x) {
-        const int ci = i / taps, t = i - ci * taps;
-        m = fmaxf(m, fabsf(transposed ? w[((size_t)ci * Cout + co) * taps + t] : w[((size_t)co * Cin + ci) * taps + t]));
-    }
-    __shared__ float red[256];
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) ws[co] = red[0] > 0.0f ? red[0] / 448.0f : 1.0f;
-}
-
-__global__ void pack_f8k_stream_kernel(const PackStreamArgs a, const float* __restrict__ ws, unsigned char* __restrict__ wp) {
-    const ConvGeom g = a.gs[blockIdx.y];
-    const unsigned phase_off = a.phase_offs[blockIdx.y];
-    const int spc = (g.ntaps + a.T - 1) / a.T;
-    const size_t total = (size_t)a.ncb * a.nchunks * spc * a.T * a.KS * 4096;        // fp8 elements = bytes
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        size_t r = i;
-        const int e = (int)(r & 15); r >>= 4;
-        const int co = (int)(r & 127); r >>= 7;
-        const int hh = (int)(r & 1); r >>= 1;
-        const int ks = (int)(r % a.KS); r /= a.KS;
-        const int tt = (int)(r % a.T); r /= a.T;
-        const int t = (int)(r % spc); r /= spc;
-        const int c = (int)(r % a.nchunks); r /= a.nchunks;
-        const int cb = (int)r;
-        const int tap = t * a.T + tt;
-        const int ci = (c * a.KS + ks) * 32 + hh * 16 + e, cog = cb * 128 + co;
-        float v = 0.0f;
-        if (tap < g.ntaps && ci < a.Cin && cog < a.Cout) {
-            const int ta = tap / g.ntw, tb = tap - ta * g.ntw;
-            const int kh = g.kh0 + ta * g.khs, kw = g.kw0 + tb * g.kws;
-            const size_t src = a.transposed ? (((size_t)ci * a.Cout + cog) * a.KH + kh) * a.KW + kw
-                                            : (((size_t)cog * a.Cin + ci) * a.KH + kh) * a.KW + kw;
-            v = a.w[src] / ws[cog];
-        }
-        wp[phase_off + i] = (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.0f, 0, false) & 0xff);
-    }
-}
-
-__device__ __forceinline__ void dma_buf16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_wave_base, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voffset, soffset, 0, 0);
-}
-
-// (Inverse) GDN over the 128 channels a wave holds for its 32 pixels (accumulator layout of four 32x32 MFMA tiles):
-//   y_i = x_i * rsqrt(beta^_i + sum_j gamma^_ij x_j^2)  (inverse: * sqrt), compressai/layers/gdn.py:77-92.
-// The 128 x 128 contraction runs on the matrix cores with gamma^ and x^2 each split into bf16 hi + lo (three products:
-// error ~2^-16 of a term).  k-step s covers channels 32(s>>1) + 16(s&1) + 8(c>>2) + 4hh + (c&3), c = 0..7 -- exactly the
-// 8 accumulator registers acc[s>>1][8(s&1) + c] the lane already holds for its pixel, so the B operand needs no data
-// movement; the gamma^ fragments lie in LDS pre-arranged in that order (gdn.hip: gdn_pack_f16k_kernel).
-// gimg: LDS address of the fragment image + lane * 16;  bet: LDS address of beta^[128] + 4h (read late: no registers held).
-// X3 = false: one product (bf16 gamma^ x bf16 x^2, error ~2^-10 of the result -- the order of the bf16 rounding the result gets
-// anyway when it is stored as F16K / fed to a bf16-operand layer): a third of the MFMAs, half the fragment reads, no lo split.
-template <bool X3>
-__device__ __forceinline__ void gdn_in_registers(f32x16 (&acc)[4], const unsigned char* gimg, const float* bet, int inverse) {
-    f32x16 nrm[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) nrm[m][e] = 0.0f;
-#pragma unroll
-    for (int sx = 0; sx < 8; ++sx) {
-        bf16x8 bh, blo;
-#pragma unroll
-        for (int cc = 0; cc < 8; ++cc) {
-            const float xv = acc[sx >> 1][8 * (sx & 1) + cc];
-            const float sq = __fmul_rn(xv, xv);
-            const __bf16 hi = (__bf16)sq;
-            bh[cc] = hi;
-            if constexpr (X3) blo[cc] = (__bf16)(sq - (float)hi);
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const bf16x8 gh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(gimg + ((m * 8 + sx) * 2 + 0) * 1024));
-            if constexpr (X3) {
-                const bf16x8 gl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(gimg + ((m * 8 + sx) * 2 + 1) * 1024));
-                nrm[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl, bh, nrm[m], 0, 0, 0);
-                nrm[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, blo, nrm[m], 0, 0, 0);
-            }
-            nrm[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, bh, nrm[m], 0, 0, 0);
-        }
-    }
-    // v_sqrt_f32 / v_rsq_f32 (1 ulp): the result is rounded to bf16 or feeds a bf16-operand convolution anyway.  `inverse` is uniform:
-    // a BRANCH, not a select -- as `inverse ? sqrt : rsq` the compiler evaluated both for every element (128 quarter-rate instructions
-    // and 64 selects per lane where 64 + 0 do)
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 be = *reinterpret_cast<const float4*>(bet + m * 32 + 8 * q);
-            nrm[m][4 * q + 0] += be.x; nrm[m][4 * q + 1] += be.y; nrm[m][4 * q + 2] += be.z; nrm[m][4 * q + 3] += be.w;
-        }
-    if (inverse) {
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][e] *= __builtin_amdgcn_sqrtf(nrm[m][e]);
-    } else {
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][e] *= __builtin_amdgcn_rsqf(nrm[m][e]);
-    }
-}
-
-// KS 16-channel blocks per chunk, T taps per step, D weight-slab look-ahead (steps), PSP patch DMA wave-instructions per
-// patch wave per step during the first 2 steps of a chunk, L patch look-ahead (chunks); GDN: (inverse) GDN over the 128
-// output channels fused into the epilogue.  Output: float32 NCHW if a.y32 else F16K.
-// NM: 32-channel accumulator tiles per wave -- 4 (a 128-channel block) or 1 (layers with <= 32 output channels).
-// NP: 32-pixel sub-tiles per wave (tile = 256 NP pixels): larger tiles for the large stride-1-walk layers, whose
-// per-workgroup fixed cost (launch, first DMA, epilogue) would otherwise rival their K loop.
-// F8: fp8 (e4m3) operands -- the input is F8K (32-channel records), a slab is (tap, 32-channel block) and one MFMA (K = 64)
-// consumes two consecutive slabs of the step, one per lane half: with KS = 2 the two channel blocks of a tap, with KS = 1
-// two consecutive taps.  DMA, LDS images, ring and geometry are the bf16 kernel's (a record is 32 bytes in both layouts).
-template <int KS, int T, int D, int PSP, int L, bool GDN, int NM, int NP, bool F8 = false>
-__global__ __launch_bounds__(512, D == 1 ? 2 : 1) void conv_f16k(const F16kArgs a) {     // D == 1: the two-workgroups-per-CU ("lite") configurations
+#ifdef CONV_F16K_BODY
+// ---- The body of the two conv_f16k kernels.  This file includes ITSELF with CONV_F16K_BODY defined, once inside each kernel template
+// (see conv_f16k / conv_f16k_multi below): conv_f16k<KS, T, D, PSP, L, GDN, NM, NP, F8> with MULTI = false (one output, as F16kArgs
+// describes it) and conv_f16k_multi<NM> with MULTI = true (the latent layer, its result stored in up to four layouts, F16kMulti mo).
+// A textual include and not a shared __device__ function or a further template parameter: the symbols of the conv_f16k instantiations
+// (which profiles, the benchmark and masic_conv_f16k_kernel_name spell out) and their code stay exactly what they were -- as a
+// force-inlined function taking the kernel arguments by reference the same body compiled to different register figures for most of
+// them (the dominant <1, 5, 2, 6, 1, true, 4, 1, false>: 207 -> 209 VGPRs).  In one file, so that whatever hashes or greps the kernel
+// sources sees the K loop and the epilogue where they always were.
+// In scope: the template parameters as compile-time constants, `const F16kArgs a`, `const F16kMulti mo`.
+    static_assert(!MULTI || (!GDN && !F8 && NP == 1), "the multi-output epilogue exists for the plain bf16 form with 256-pixel tiles");
     static_assert(!GDN || NM == 4, "the fused GDN needs all 128 channels");
     static_assert(!F8 || (NM == 4 && NP == 1 && (T * KS) % 2 == 0 && T <= 4), "fp8 operands: 128-channel blocks, 256-pixel tiles, slab pairs");
     static_assert(NM + NP == 2 || NM + NP == 3 || NM + NP == 4 || NM + NP == 5 || NM + NP == 6, "fragment-wait helpers exist for 2, 4, 5 and 6 fragments per k-step");
@@ -798,6 +388,58 @@ __global__ __launch_bounds__(512, D == 1 ? 2 : 1) void conv_f16k(const F16kArgs 
         const bool pok = r < g.Hp && c < g.Wp;
         const int oh = pok ? r * g.os + g.oph : 0, ow = pok ? c * g.os + g.opw : 0;
         const size_t opix = (size_t)oh * a.Wo + ow;
+        if constexpr (MULTI) {
+            // v = conv + bias is stored in up to four layouts; each is what the stand-alone kernel it replaces computes from the float32
+            // tensor (masic_quantize_fwd, nchw_to_f16k_kernel, nchw_to_f16k_view_kernel: common.h / gemm_bf16.hip / f16k_ops.hip), in the
+            // same order -- rintf in float32, times the gate in float32, ONE rounding to bf16 -- so the bits are the same, -0 included.
+            if (pok) {
+                const unsigned op = (unsigned)oplane, op16 = op * 16;
+                const size_t o32 = ((size_t)b * a.Cout + m0 + 4 * h) * oplane + opix;
+                if (mo.y32 != nullptr) {
+                    float* yb = mo.y32 + o32;
+#pragma unroll
+                    for (int m = 0; m < NM; ++m)
+                        if (m0 + m * 32 < a.Cout) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) yb[(unsigned)(m * 32 + (e & 3) + 8 * (e >> 2)) * op] = acc[n][m][e];
+                        }
+                }
+                if (mo.r32 != nullptr) {
+                    float* yb = mo.r32 + o32;
+#pragma unroll
+                    for (int m = 0; m < NM; ++m)
+                        if (m0 + m * 32 < a.Cout) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) yb[(unsigned)(m * 32 + (e & 3) + 8 * (e >> 2)) * op] = rintf(acc[n][m][e]);
+                        }
+                }
+                if (mo.r16 != nullptr) {
+                    // (x * 1.0f is x, sign of zero included: the ungated form needs no second loop)
+                    const float gv = mo.gate != nullptr ? mo.gate[((size_t)b * mo.gate_ctot + mo.gate_c) * oplane + opix] : 1.0f;
+                    unsigned short* yb = mo.r16 + (((size_t)b * (mo.r16_ctot >> 4) + ((mo.r16_coff + m0) >> 4)) * oplane + opix) * 16 + 8 * h;
+#pragma unroll
+                    for (int m = 0; m < NM; ++m)
+                        if (m0 + m * 32 < a.Cout) {
+                            f32x16 t;
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) t[e] = rintf(acc[n][m][e]) * gv;
+                            store_f16k_tile(t, yb + (size_t)(2 * m) * op16, op16);
+                        }
+                }
+                if (mo.a16 != nullptr) {
+                    unsigned short* yb = mo.a16 + (((size_t)b * (a.Cout >> 4) + (m0 >> 4)) * oplane + opix) * 16 + 8 * h;
+#pragma unroll
+                    for (int m = 0; m < NM; ++m)
+                        if (m0 + m * 32 < a.Cout) {
+                            f32x16 t;
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) t[e] = fabsf(acc[n][m][e]);
+                            store_f16k_tile(t, yb + (size_t)(2 * m) * op16, op16);
+                        }
+                }
+            }
+            continue;
+        }
         if constexpr (GDN) {
             if (a.y16_pre != nullptr && pok) {
                 const int c16 = (a.out_coff + m0) >> 4;
@@ -887,6 +529,455 @@ __global__ __launch_bounds__(512, D == 1 ? 2 : 1) void conv_f16k(const F16kArgs 
         }
     }
     if (stamp) { stamp[6] = __builtin_amdgcn_s_memtime(); stamp[7] = __builtin_amdgcn_s_memrealtime(); }
+#else   // !CONV_F16K_BODY: the translation unit proper
+// conv_f16k.hip -- bf16 implicit-GEMM convolutions on channel-blocked activations (gfx950 / MI355X).
+//
+// Same layers and the same phase geometry as conv.hip (reference: coremasic/mywork/MASIC.py:510-622 analysis /
+// synthesis transforms, :170-187 and :690-700 hyper transforms; factories compressai/models/utils.py:128-146), for the
+// bf16-operand forward.  conv.hip's bf16 kernel reads float32 NCHW and converts while staging, which makes every
+// workgroup re-convert its halo and leaves the matrix cores waiting on VGPR staging and on L2 latency of the weight
+// fragments.  Here both operands reach LDS by DMA (global_load_lds, 16 bytes per lane, no VGPR round trip):
+//
+//   activations  F16K  [B][C/16][H*W][16] bf16 (gemm_bf16.hip): a pixel's 16 channels are one 32-byte record, so the
+//                patch of a tile for one 16-channel block is rows of contiguous records and an MFMA B fragment
+//                (8 consecutive k of one pixel) is one ds_read_b128;
+//   weights      [phase-tap][ci/16][co][16] bf16 (pack_weight_bf16_kernel): one (tap, 16-channel) slab of a
+//                128-channel block is 4 KiB contiguous, an A fragment is one ds_read_b128.
+//
+// Workgroup = 8 waves (2 along co x 4 along pixels), tile 128 co x 256 pixels, wave tile 64 x 64 (2 x 2 MFMA
+// 32x32x16 accumulators).  K runs over chunks of KS 16-channel blocks; within a chunk over "steps" of T taps.
+// Every step each wave issues the same number of DMA wave-instructions -- WI for the weight slab of step g+D
+// (D+1-deep ring) and PS for a slice of the patch of chunk c+L (L+1 buffers) -- so that completion can be awaited
+// with a counted `s_waitcnt vmcnt((D-1)*(WI+PS))` (never 0 inside the loop) followed by one raw s_barrier per step:
+// DMA stays in flight across barriers.  Unused issue slots go to a dummy 1 KiB LDS region to keep the count fixed.
+//
+// LDS images are XOR-swizzled in 16-byte slots, slot' = slot ^ ((slot >> 4) & 3): the stride-2 pixel walk of a
+// strided conv (64 B between lanes), the stride-1 walk (32 B) and the weight rows (32 B) all become conflict-free for
+// ds_read_b128's four 16-lane groups.  The swizzle is applied on the DMA side by permuting which record a lane fetches.
+//
+// Epilogue: bias + activation, then either float32 NCHW (channel view of a concat buffer, optional gate) or F16K bf16
+// for the next layer.
+#include "common.h"
+#include <type_traits>
+#include "conv_geom.h"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
+}
+
+// LDS reads / waits the compiler does not see (see the K loop of conv_f16k)
+template <int OFF>
+__device__ __forceinline__ void ds_read128(v4u& dst, unsigned addr) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d, v4u& e) {
+    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d, v4u& e, v4u& f) {
+    asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b) {
+    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c) {
+    asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d, v4u& e, v4u& f, v4u& g, v4u& h) {
+    asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait(v4u& a, v4u& b, v4u& c, v4u& d, v4u& e, v4u& f, v4u& g, v4u& h, v4u& i, v4u& j) {
+    asm volatile("s_waitcnt lgkmcnt(%10)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h), "+v"(i), "+v"(j) : "n"(N) : "memory");
+}
+
+// ---- fp8 (OCP e4m3fn) operands: v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales (E8M0 127) = a plain fp8 MFMA at
+// twice the bf16 rate (MI355X_MICROARCH.md, Matrix cores).  A lane's operand is 32 consecutive k (two ds_read_b128 that the
+// register coalescer places in one 8-register tuple); lanes 0-31 / 32-63 hold the two 32-k halves of the instruction's K = 64.
+typedef int v8i __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ v8i cat8(const v4u& lo, const v4u& hi) {
+    return __builtin_bit_cast(v8i, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+__device__ __forceinline__ f32x16 mfma_f8(const v8i& a, const v8i& b, const f32x16& c) {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
+}
+__device__ __forceinline__ unsigned pack4f8(float a, float b, float c, float d, float inv) {
+    // saturating: e4m3fn has no infinity, its largest finite value is 448
+    a = __builtin_amdgcn_fmed3f(a * inv, -448.0f, 448.0f);
+    b = __builtin_amdgcn_fmed3f(b * inv, -448.0f, 448.0f);
+    c = __builtin_amdgcn_fmed3f(c * inv, -448.0f, 448.0f);
+    d = __builtin_amdgcn_fmed3f(d * inv, -448.0f, 448.0f);
+    int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
+    return (unsigned)v;
+}
+
+__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
+
+__device__ __forceinline__ void dma16(const void* g, void* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+__device__ __forceinline__ int swz(int slot) { return slot ^ ((slot >> 4) & 3); }
+
+// F16K store of the 32 channels of accumulator tile `t` (lane (j, h) holds channels 4h + 8q + i, q, i < 4, of pixel j):
+// the two halves of the wave swap their middle quarters (v_permlane32_swap) so that lane (j, h) ends up with the 8
+// consecutive channels 8h .. 8h+7 of each 16-channel record and writes it with one 16-byte store -- the wave writes
+// whole 32-byte records (full sectors; 1 KiB contiguous when the pixels are adjacent) instead of scattered 8-byte pieces.
+// rec: address of the lane's pixel in the first of the two records, + 8h elements; rec_stride: elements between records.
+__device__ __forceinline__ unsigned pack2bf(float lo, float hi);
+// residual add in float32 BEFORE the rounding to bf16: lane (j, h) holds channels 8q + 4h + i of tile t, i.e. 4 consecutive
+// bf16 (8 bytes) at element offset 8(q & 1) + 4h of record q >> 1 of the residual's tile.  res: address of the lane's pixel in
+// the first record of the tile (element units), + 4h.
+__device__ __forceinline__ void add_f16k_residual(f32x16& t, const unsigned short* res, unsigned rec_stride) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint2 r = *reinterpret_cast<const uint2*>(res + (size_t)(q >> 1) * rec_stride + 8 * (q & 1));
+        t[4 * q + 0] += __builtin_bit_cast(float, r.x << 16);
+        t[4 * q + 1] += __builtin_bit_cast(float, r.x & 0xffff0000u);
+        t[4 * q + 2] += __builtin_bit_cast(float, r.y << 16);
+        t[4 * q + 3] += __builtin_bit_cast(float, r.y & 0xffff0000u);
+    }
+}
+// t *= act'(mask): the backward of ReLU / LeakyReLU(0.01) as an epilogue of the input-gradient convolution -- mask = the forward
+// activation's OUTPUT in F16K (its sign is the pre-activation's), addressed like a residual tensor
+__device__ __forceinline__ void mul_f16k_actmask(f32x16& t, const unsigned short* mask, unsigned rec_stride, float slope) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint2 r = *reinterpret_cast<const uint2*>(mask + (size_t)(q >> 1) * rec_stride + 8 * (q & 1));
+        t[4 * q + 0] *= __builtin_bit_cast(float, r.x << 16) > 0.0f ? 1.0f : slope;
+        t[4 * q + 1] *= __builtin_bit_cast(float, r.x & 0xffff0000u) > 0.0f ? 1.0f : slope;
+        t[4 * q + 2] *= __builtin_bit_cast(float, r.y << 16) > 0.0f ? 1.0f : slope;
+        t[4 * q + 3] *= __builtin_bit_cast(float, r.y & 0xffff0000u) > 0.0f ? 1.0f : slope;
+    }
+}
+__device__ __forceinline__ void store_f16k_tile(const f32x16& t, unsigned short* rec, unsigned rec_stride) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const unsigned a0 = pack2bf(t[8 * r + 0], t[8 * r + 1]), a1 = pack2bf(t[8 * r + 2], t[8 * r + 3]);   // channels 4h .. 4h+3
+        const unsigned b0 = pack2bf(t[8 * r + 4], t[8 * r + 5]), b1 = pack2bf(t[8 * r + 6], t[8 * r + 7]);   // channels 8 + 4h ..
+        const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+        const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+        uint4 st;
+        st.x = s0[0]; st.y = s1[0]; st.z = s0[1]; st.w = s1[1];
+        *reinterpret_cast<uint4*>(rec + (size_t)r * rec_stride) = st;
+    }
+}
+
+// the same through a buffer resource: voff = byte offset of the lane's pixel in the first record + 16h, or any offset >= the resource's
+// size for a lane that has nothing to store (dropped by the range check) -- the instruction is issued unconditionally, so the number
+// of store instructions a wave has in flight is known at compile time (counted s_waitcnt vmcnt in conv_a_gdn_f16k)
+__device__ __forceinline__ void store_f16k_tile_buf(const f32x16& t, __amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned rec_stride_bytes) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const unsigned a0 = pack2bf(t[8 * r + 0], t[8 * r + 1]), a1 = pack2bf(t[8 * r + 2], t[8 * r + 3]);
+        const unsigned b0 = pack2bf(t[8 * r + 4], t[8 * r + 5]), b1 = pack2bf(t[8 * r + 6], t[8 * r + 7]);
+        const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+        const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+        v4u st = {s0[0], s1[0], s0[1], s1[1]};
+        __builtin_amdgcn_raw_buffer_store_b128(st, rs, (int)(voff + r * rec_stride_bytes), 0, 0);
+    }
+}
+
+// F8K store (fp8 activations [B][C/32][H*W][32]: a pixel's 32 channels are one 32-byte record) of accumulator tile `t` = one
+// whole record per pixel: lane (j, h) holds channels 8q + 4h + i; after two v_permlane32_swap it holds the 16 consecutive
+// channels 16h .. 16h+15 and writes them with one 16-byte store.  rec: address of the lane's pixel record + 16h bytes.
+__device__ __forceinline__ unsigned pack4f8(float a, float b, float c, float d, float inv);
+__device__ __forceinline__ void store_f8k_tile(const f32x16& t, unsigned char* rec, float inv) {
+    unsigned q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = pack4f8(t[4 * k], t[4 * k + 1], t[4 * k + 2], t[4 * k + 3], inv);
+    const auto s0 = __builtin_amdgcn_permlane32_swap(q[0], q[2], false, false);     // h = 0: channels 0-3, 4-7;   h = 1: 16-19, 20-23
+    const auto s1 = __builtin_amdgcn_permlane32_swap(q[1], q[3], false, false);     // h = 0: 8-11, 12-15;         h = 1: 24-27, 28-31
+    uint4 st;
+    st.x = s0[0]; st.y = s0[1]; st.z = s1[0]; st.w = s1[1];
+    *reinterpret_cast<uint4*>(rec) = st;
+}
+
+__device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    bf16x2 v;
+    v[0] = (__bf16)lo;
+    v[1] = (__bf16)hi;
+    return __builtin_bit_cast(unsigned, v);
+}
+
+struct F16kArgs {
+    const unsigned short* x;      // F16K [B][in_c16tot][Hi*Wi][16]
+    const unsigned short* w;      // slab stream, see pack_f16k_stream_kernel
+    const float* bias;
+    const float* gate;            // float32 [B][gate_ctot][Ho][Wo] or null (NCHW output only)
+    float* y32;                   // float32 NCHW view, or null
+    unsigned short* y16;          // F16K [B][out_c16tot][Ho*Wo][16], or null
+    const uint4* gdn_img;         // GDN epilogue: gamma^ fragments (gdn.hip: gdn_pack_f16k_kernel), then beta^[128] floats
+    const unsigned short* res1;   // F16K output only: up to two residual tensors [B][res_ctot/16][Ho*Wo][16] added after the activation
+    const unsigned short* res2;   //   (ResidualBlock / Enhancement_Block identities, compressai/layers/layers.py:189, MASIC.py:163)
+    int res_ctot;
+    unsigned short* y16_pre;      // fused GDN + F16K output: also store the convolution's result BEFORE the GDN (same view), or null --
+                                  //   what the GDN backward of a training step needs (masic_amd/autograd.py: AnalysisFn / SynthesisFn);
+                                  //   residual form: the activation's output BEFORE the residual adds (view of res_ctot channels)
+    unsigned long long* stamps;   // diagnostics (masic_conv_f16k_set_stamps): {s_memtime, s_memrealtime} at 4 points of the first and last workgroup
+    const unsigned short* mask16; // F16K output only: multiply by act'(mask) before the residual adds (mask: F16K of res_ctot channels;
+    float mask_slope;             //   slope for mask <= 0: 0.01 LeakyReLU, 0 ReLU) -- input gradients of the training step
+    const float* res32;           // float32 NCHW output only: residual [B][cout_store][Ho][Wo] added after the activation, or null
+    int cout_store;               // float32 NCHW output: channels actually stored (< Cout when the weight was zero-padded to a multiple of 32)
+    const float* wscale;          // fp8 operands: per-output-channel dequantisation factor (weight scale x input scale), else null
+    unsigned char* y8;            // F8K [B][out_c32tot][Ho*Wo][32] fp8 output (quantised with out_inv_scale), or null
+    float out_inv_scale;
+    int gdn_inverse;
+    int d2s;                      // > 0: channel 4c + phase (2x2 phases, c < d2s); y32 is [B][out_ctot][2Ho][2Wo] (depth-to-space store)
+    int in_c16tot, in_c16off, Cin16;
+    int Hi, Wi, Cout, Ho, Wo;
+    int out_ctot, out_coff;       // channel view of the output (NCHW: channels; F16K: channels, multiples of 16)
+    int gate_ctot, gate_c, act;
+    int TW, TWlog, SR, TH, tiles_w, ntiles;
+    int PH, PW, PWh, NPIXp;       // patch rows / row length (pixels), ceil(PW/2), records per k-half plane of the LDS image (x32)
+    int PB;                       // bytes per patch buffer
+    unsigned mg_PW, mg_PWh, mg_gpk;   // ceil(2^32 / d): x / d == __umulhi(x, magic) for the small x, d of the patch maps
+    unsigned phase_off[4];        // byte offset of each phase's slab streams
+    unsigned stream_bytes[4];     // bytes of one (phase, co-block) slab stream
+    GeomParams q;
+    int nphase;
+    int xcd_images;               // B % 8 == 0: image b runs on XCD b % 8 (the halos of its tiles meet in one L2)
+    int msplit;                   // workgroups per 128-channel co-block (4 / NM for layers whose grid would not fill the chip, else 1):
+                                  //   blockIdx.y = co-block * msplit + sub-block, a sub-block = NM accumulator tiles of the slab
+};
+
+// The outputs of conv_f16k_multi (masic_conv_f16k_multi_fwd), each of them optional (null): v = conv(x) + bias, all Cout channels
+struct F16kMulti {
+    float* y32;                   // float32 [B][Cout][Ho][Wo]: v
+    float* r32;                   // float32 [B][Cout][Ho][Wo]: rintf(v)
+    unsigned short* r16;          // F16K of r16_ctot channels, written at channels r16_coff ..: bf16(rintf(v) * gate)
+    unsigned short* a16;          // F16K [B][Cout/16][Ho*Wo][16]: bf16(|v|)
+    const float* gate;            // float32 [B][gate_ctot][Ho][Wo], channel gate_c (r16 only), or null
+    int r16_ctot, r16_coff, gate_ctot, gate_c;
+};
+
+#ifndef F16K_DMA_SPREAD
+#define F16K_DMA_SPREAD 1  // 0: the K loop's DMA pieces issued en bloc at the top of every step (A/B timing, tools/ablate_f16k.sh)
+#endif
+#ifndef F16K_ABLATE
+#define F16K_ABLATE 0     // timing experiments only (tools/ablate_f16k.sh): 1 no DMA in the K loop, 2 no barriers, 3 no fragment reads, 4 a quarter of the MFMAs
+#endif
+constexpr int MAXTAPS = 64;   // tap table entries ([step][T rounded up to a power of two])
+
+// Weights for this path, in the order the kernel consumes them ("slab stream"): for each phase, each 128-channel
+// co-block, each chunk c of KS 16-channel blocks, each step t of T taps (taps padded with zeros to a multiple of T):
+// T*KS slabs of 4 KiB, each the LDS image [k-half hh][co 128][8 ci] of W[co, (c*KS+ks)*16 + hh*8 + e, tap].
+// A step's slab group is one contiguous WST = T*KS*4096 bytes, so the DMA of step g is base + g*WST.
+struct PackStreamArgs {
+    const float* w;
+    int Cin, Cout, KH, KW, transposed;
+    int KS, T, nchunks, ncb;
+    ConvGeom gs[4];           // one launch packs every phase (blockIdx.y)
+    unsigned phase_offs[4];   // bytes
+};
+
+__device__ __forceinline__ void pack_f16k_stream_body(const PackStreamArgs& a, unsigned short* __restrict__ wp, int phase, int bx, int nbx) {
+    const ConvGeom g = a.gs[phase];
+    const unsigned phase_off = a.phase_offs[phase];
+    const int spc = (g.ntaps + a.T - 1) / a.T;
+    const size_t total = (size_t)a.ncb * a.nchunks * spc * a.T * a.KS * 2048;        // bf16 elements
+    for (size_t i = (size_t)bx * blockDim.x + threadIdx.x; i < total; i += (size_t)nbx * blockDim.x) {
+        size_t r = i;
+        const int e = (int)(r & 7); r >>= 3;
+        const int co = (int)(r & 127); r >>= 7;
+        const int hh = (int)(r & 1); r >>= 1;
+        const int ks = (int)(r % a.KS); r /= a.KS;
+        const int tt = (int)(r % a.T); r /= a.T;
+        const int t = (int)(r % spc); r /= spc;
+        const int c = (int)(r % a.nchunks); r /= a.nchunks;
+        const int cb = (int)r;
+        const int tap = t * a.T + tt;
+        const int ci = (c * a.KS + ks) * 16 + hh * 8 + e, cog = cb * 128 + co;
+        float v = 0.0f;
+        if (tap < g.ntaps && ci < a.Cin && cog < a.Cout) {
+            const int ta = tap / g.ntw, tb = tap - ta * g.ntw;
+            const int kh = g.kh0 + ta * g.khs, kw = g.kw0 + tb * g.kws;
+            const size_t src = a.transposed ? (((size_t)ci * a.Cout + cog) * a.KH + kh) * a.KW + kw
+                                            : (((size_t)cog * a.Cin + ci) * a.KH + kh) * a.KW + kw;
+            v = a.w[src];
+        }
+        const __bf16 bv = (__bf16)v;
+        wp[(phase_off >> 1) + i] = __builtin_bit_cast(unsigned short, bv);
+    }
+}
+
+__global__ void pack_f16k_stream_kernel(const PackStreamArgs a, unsigned short* __restrict__ wp) {
+    pack_f16k_stream_body(a, wp, blockIdx.y, blockIdx.x, gridDim.x);
+}
+
+// Many layers' streams in one launch (a training step re-packs every weight it touches -- each for its forward and for its input
+// gradient -- ~50 launches of ~5 us whose work is a few microseconds): blockIdx.y = job, blockIdx.z = phase; a job is what one
+// masic_conv_f16k_pack_weight call would launch.  The job table lives in device memory (built once per set of layers).
+struct PackStreamJob { PackStreamArgs a; unsigned short* wp; int nb, np; };
+
+__global__ void pack_f16k_stream_multi_kernel(const PackStreamJob* __restrict__ jobs) {
+    const PackStreamJob& j = jobs[blockIdx.y];
+    if ((int)blockIdx.z >= j.np || (int)blockIdx.x >= j.nb) return;
+    pack_f16k_stream_body(j.a, j.wp, blockIdx.z, blockIdx.x, j.nb);
+}
+
+// fp8 operands: the same stream with 32-channel blocks -- slab (tap, block) = LDS image [k-half hh][co 128][16 ci] of
+// fp8(W[co, (c*KS+ks)*32 + hh*16 + e, tap] / wscale[co]); wscale[co] = max |W[co]| / 448 (per-output-channel scaling).
+__global__ void wscale_f8k_kernel(const float* __restrict__ w, float* __restrict__ ws, int Cin, int Cout, int taps, int transposed) {
+    const int co = blockIdx.x;
+    float m = 0.0f;
+    for (int i = threadIdx.x; i < Cin * taps; i += blockDim.x) {
+        const int ci = i / taps, t = i - ci * taps;
+        m = fmaxf(m, fabsf(transposed ? w[((size_t)ci * Cout + co) * taps + t] : w[((size_t)co * Cin + ci) * taps + t]));
+    }
+    __shared__ float red[256];
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) ws[co] = red[0] > 0.0f ? red[0] / 448.0f : 1.0f;
+}
+
+__global__ void pack_f8k_stream_kernel(const PackStreamArgs a, const float* __restrict__ ws, unsigned char* __restrict__ wp) {
+    const ConvGeom g = a.gs[blockIdx.y];
+    const unsigned phase_off = a.phase_offs[blockIdx.y];
+    const int spc = (g.ntaps + a.T - 1) / a.T;
+    const size_t total = (size_t)a.ncb * a.nchunks * spc * a.T * a.KS * 4096;        // fp8 elements = bytes
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        size_t r = i;
+        const int e = (int)(r & 15); r >>= 4;
+        const int co = (int)(r & 127); r >>= 7;
+        const int hh = (int)(r & 1); r >>= 1;
+        const int ks = (int)(r % a.KS); r /= a.KS;
+        const int tt = (int)(r % a.T); r /= a.T;
+        const int t = (int)(r % spc); r /= spc;
+        const int c = (int)(r % a.nchunks); r /= a.nchunks;
+        const int cb = (int)r;
+        const int tap = t * a.T + tt;
+        const int ci = (c * a.KS + ks) * 32 + hh * 16 + e, cog = cb * 128 + co;
+        float v = 0.0f;
+        if (tap < g.ntaps && ci < a.Cin && cog < a.Cout) {
+            const int ta = tap / g.ntw, tb = tap - ta * g.ntw;
+            const int kh = g.kh0 + ta * g.khs, kw = g.kw0 + tb * g.kws;
+            const size_t src = a.transposed ? (((size_t)ci * a.Cout + cog) * a.KH + kh) * a.KW + kw
+                                            : (((size_t)cog * a.Cin + ci) * a.KH + kh) * a.KW + kw;
+            v = a.w[src] / ws[cog];
+        }
+        wp[phase_off + i] = (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.0f, 0, false) & 0xff);
+    }
+}
+
+__device__ __forceinline__ void dma_buf16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_wave_base, int voffset, int soffset) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voffset, soffset, 0, 0);
+}
+
+// (Inverse) GDN over the 128 channels a wave holds for its 32 pixels (accumulator layout of four 32x32 MFMA tiles):
+//   y_i = x_i * rsqrt(beta^_i + sum_j gamma^_ij x_j^2)  (inverse: * sqrt), compressai/layers/gdn.py:77-92.
+// The 128 x 128 contraction runs on the matrix cores with gamma^ and x^2 each split into bf16 hi + lo (three products:
+// error ~2^-16 of a term).  k-step s covers channels 32(s>>1) + 16(s&1) + 8(c>>2) + 4hh + (c&3), c = 0..7 -- exactly the
+// 8 accumulator registers acc[s>>1][8(s&1) + c] the lane already holds for its pixel, so the B operand needs no data
+// movement; the gamma^ fragments lie in LDS pre-arranged in that order (gdn.hip: gdn_pack_f16k_kernel).
+// gimg: LDS address of the fragment image + lane * 16;  bet: LDS address of beta^[128] + 4h (read late: no registers held).
+// X3 = false: one product (bf16 gamma^ x bf16 x^2, error ~2^-10 of the result -- the order of the bf16 rounding the result gets
+// anyway when it is stored as F16K / fed to a bf16-operand layer): a third of the MFMAs, half the fragment reads, no lo split.
+template <bool X3>
+__device__ __forceinline__ void gdn_in_registers(f32x16 (&acc)[4], const unsigned char* gimg, const float* bet, int inverse) {
+    f32x16 nrm[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) nrm[m][e] = 0.0f;
+#pragma unroll
+    for (int sx = 0; sx < 8; ++sx) {
+        bf16x8 bh, blo;
+#pragma unroll
+        for (int cc = 0; cc < 8; ++cc) {
+            const float xv = acc[sx >> 1][8 * (sx & 1) + cc];
+            const float sq = __fmul_rn(xv, xv);
+            const __bf16 hi = (__bf16)sq;
+            bh[cc] = hi;
+            if constexpr (X3) blo[cc] = (__bf16)(sq - (float)hi);
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const bf16x8 gh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(gimg + ((m * 8 + sx) * 2 + 0) * 1024));
+            if constexpr (X3) {
+                const bf16x8 gl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(gimg + ((m * 8 + sx) * 2 + 1) * 1024));
+                nrm[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl, bh, nrm[m], 0, 0, 0);
+                nrm[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, blo, nrm[m], 0, 0, 0);
+            }
+            nrm[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, bh, nrm[m], 0, 0, 0);
+        }
+    }
+    // v_sqrt_f32 / v_rsq_f32 (1 ulp): the result is rounded to bf16 or feeds a bf16-operand convolution anyway.  `inverse` is uniform:
+    // a BRANCH, not a select -- as `inverse ? sqrt : rsq` the compiler evaluated both for every element (128 quarter-rate instructions
+    // and 64 selects per lane where 64 + 0 do)
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 be = *reinterpret_cast<const float4*>(bet + m * 32 + 8 * q);
+            nrm[m][4 * q + 0] += be.x; nrm[m][4 * q + 1] += be.y; nrm[m][4 * q + 2] += be.z; nrm[m][4 * q + 3] += be.w;
+        }
+    if (inverse) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[m][e] *= __builtin_amdgcn_sqrtf(nrm[m][e]);
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[m][e] *= __builtin_amdgcn_rsqf(nrm[m][e]);
+    }
+}
+
+// KS 16-channel blocks per chunk, T taps per step, D weight-slab look-ahead (steps), PSP patch DMA wave-instructions per
+// patch wave per step during the first 2 steps of a chunk, L patch look-ahead (chunks); GDN: (inverse) GDN over the 128
+// output channels fused into the epilogue.  Output: float32 NCHW if a.y32 else F16K.
+// NM: 32-channel accumulator tiles per wave -- 4 (a 128-channel block) or 1 (layers with <= 32 output channels).
+// NP: 32-pixel sub-tiles per wave (tile = 256 NP pixels): larger tiles for the large stride-1-walk layers, whose
+// per-workgroup fixed cost (launch, first DMA, epilogue) would otherwise rival their K loop.
+// F8: fp8 (e4m3) operands -- the input is F8K (32-channel records), a slab is (tap, 32-channel block) and one MFMA (K = 64)
+// consumes two consecutive slabs of the step, one per lane half: with KS = 2 the two channel blocks of a tap, with KS = 1
+// two consecutive taps.  DMA, LDS images, ring and geometry are the bf16 kernel's (a record is 32 bytes in both layouts).
+template <int KS, int T, int D, int PSP, int L, bool GDN, int NM, int NP, bool F8 = false>
+__global__ __launch_bounds__(512, D == 1 ? 2 : 1) void conv_f16k(const F16kArgs a) {     // D == 1: the two-workgroups-per-CU ("lite") configurations
+    constexpr bool MULTI = false;
+    constexpr F16kMulti mo{};                    // (never read: every use sits behind `if constexpr (MULTI)`)
+#define CONV_F16K_BODY
+#include "conv_f16k.hip"
+#undef CONV_F16K_BODY
+}
+
+// The latent-producing last layer of an analysis transform (128 -> 192, 5x5, stride 2) with the multi-output epilogue: the strided-5x5
+// configuration <1, 5, 2, 6, 1> of conv_f16k (NM = 1 / 2 / 4 by the co-block split) with MULTI = true -- instead of the one output of
+// `a`, any subset of the four latent layouts of F16kMulti is stored from the accumulators.  The extra stores exist in this kernel only.
+template <int NM>
+__global__ __launch_bounds__(512, 1) void conv_f16k_multi(const F16kArgs a, const F16kMulti mo) {
+    constexpr int KS = 1, T = 5, D = 2, PSP = 6, L = 1, NP = 1;
+    constexpr bool GDN = false, F8 = false, MULTI = true;
+#define CONV_F16K_BODY
+#include "conv_f16k.hip"
+#undef CONV_F16K_BODY
 }
 
 // ------------------------------------------------------------------------------------------ first analysis layer
@@ -1516,7 +1607,7 @@ int f16k_launch(const void* x_f16k, const void* w_packed, const float* bias, con
                 const void* gdn_packed, int gdn_inverse, int d2s, float* y_nchw, void* y_f16k,
                 const masic_conv_desc_t* d, void* stream, const float* wscale = nullptr, void* y_f8k = nullptr, float out_inv_scale = 0.0f,
                 const void* res1 = nullptr, const void* res2 = nullptr, int res_ctot = 0, const float* res32 = nullptr, int cout_store = 0,
-                void* y_pre = nullptr, const void* mask16 = nullptr, float mask_slope = 0.0f);
+                void* y_pre = nullptr, const void* mask16 = nullptr, float mask_slope = 0.0f, const F16kMulti* multi = nullptr);
 }
 
 // Extended residual form for the training step of Independent_EN (masic_amd/autograd.py: EnhancementBlockFn), everything F16K:
@@ -1618,6 +1709,32 @@ extern "C" int masic_conv_f16k_gdn_fwd(const void* x_f16k, const void* w_packed,
     return f16k_launch(x_f16k, w_packed, bias, gate, gdn_packed, gdn_inverse, 0, y_nchw, y_f16k, d, stream);
 }
 
+// The latent layer of an analysis transform with its result written once, in the layouts its consumers read (include/masic_hip.h).
+extern "C" int masic_conv_f16k_multi_supported(const masic_conv_desc_t* d) {
+    if (check_desc(d) != MASIC_OK || d->prec == MASIC_PREC_FP8 || d->act != MASIC_ACT_NONE || d->Cout % 32 != 0) return 0;
+    ConvGeom g[4];
+    const int np = build_geoms(*d, g);
+    const F16kCfg c = choose_f16k(*d, g, np);
+    return c.ok && c.NP == 1 && c.KS == 1 && c.T == 5 && c.D == 2;
+}
+
+extern "C" int masic_conv_f16k_multi_fwd(const void* x_f16k, const void* w_packed, const float* bias, const masic_f16k_multi_out_t* out,
+                                         const masic_conv_desc_t* d, void* stream) {
+    MASIC_REQUIRE(d != nullptr && out != nullptr, MASIC_ERR_ARG, "conv_f16k_multi_fwd: null pointer");
+    MASIC_REQUIRE(out->y32 || out->round32 || out->round16 || out->abs16, MASIC_ERR_ARG, "conv_f16k_multi_fwd: no output");
+    MASIC_REQUIRE(d->act == MASIC_ACT_NONE && d->out_coff == 0 && d->out_ctot == d->Cout && d->Cout % 32 == 0, MASIC_ERR_UNSUPPORTED,
+                  "conv_f16k_multi_fwd: needs no activation, the whole output (no channel view) and Cout % 32 == 0");
+    MASIC_REQUIRE(out->round16 == nullptr || (out->round16_ctot % 16 == 0 && out->round16_coff % 16 == 0 && out->round16_coff >= 0 &&
+                                              out->round16_coff + d->Cout <= out->round16_ctot),
+                  MASIC_ERR_SHAPE, "conv_f16k_multi_fwd: round16 needs a 16-aligned channel view that holds Cout channels");
+    MASIC_REQUIRE(out->gate == nullptr || (out->round16 != nullptr && out->gate_c >= 0 && out->gate_c < out->gate_ctot), MASIC_ERR_SHAPE,
+                  "conv_f16k_multi_fwd: the gate multiplies round16 only; gate channel out of range");
+    const F16kMulti mo{out->y32, out->round32, (unsigned short*)out->round16, (unsigned short*)out->abs16, out->gate,
+                       out->round16_ctot, out->round16_coff, out->gate_ctot, out->gate_c};
+    return f16k_launch(x_f16k, w_packed, bias, nullptr, nullptr, 0, 0, nullptr, nullptr, d, stream, nullptr, nullptr, 0.0f, nullptr, nullptr, 0, nullptr, 0,
+                       nullptr, nullptr, 0.0f, &mo);
+}
+
 // ConvTranspose2d(Cin -> C, k5, s2, p2, output_padding 1) weight [Cin][C][5][5] -> the weight [32][Cin][3][3] (+ bias [32]) of the
 // equivalent stride-1 3x3 convolution to 4C (<= 32) channels whose 2x2 depth-to-space is the transposed convolution's output:
 // row 4c + 2ph + pw, tap (u, v) = W[:, c, ph + 2(2-u), pw + 2(2-v)], zero where that kernel index exceeds 4 (masic_amd/ops.py:
@@ -1655,12 +1772,13 @@ namespace {
 int f16k_launch(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
                 const void* gdn_packed, int gdn_inverse, int d2s, float* y_nchw, void* y_f16k,
                 const masic_conv_desc_t* d, void* stream, const float* wscale, void* y_f8k, float out_inv_scale,
-                const void* res1, const void* res2, int res_ctot, const float* res32, int cout_store, void* y_pre, const void* mask16, float mask_slope) {
+                const void* res1, const void* res2, int res_ctot, const float* res32, int cout_store, void* y_pre, const void* mask16, float mask_slope,
+                const F16kMulti* multi) {
     int rc = check_desc(d);
     if (rc != MASIC_OK) return rc;
     const bool f8 = d->prec == MASIC_PREC_FP8;
     const int cblk = f8 ? 32 : 16;
-    MASIC_REQUIRE(x_f16k && w_packed && ((y_nchw != nullptr) + (y_f16k != nullptr) + (y_f8k != nullptr) == 1), MASIC_ERR_ARG,
+    MASIC_REQUIRE(x_f16k && w_packed && ((y_nchw != nullptr) + (y_f16k != nullptr) + (y_f8k != nullptr) == (multi ? 0 : 1)), MASIC_ERR_ARG,
                   "conv_f16k_fwd: need input, weights and exactly one output");
     MASIC_REQUIRE(y_f8k == nullptr || (d->out_ctot % 32 == 0 && d->out_coff % 32 == 0 && gate == nullptr && d2s == 0), MASIC_ERR_SHAPE,
                   "conv_f16k: an fp8 output needs a 32-aligned channel view and no gate");
@@ -1713,7 +1831,26 @@ int f16k_launch(const void* x_f16k, const void* w_packed, const float* bias, con
         }                                                                                                            \
         hipLaunchKernelGGL(kfn, grid, dim3(512), c.lds_bytes, st, a);                                                \
     } while (0)
-    if (f8) {
+    if (multi) {
+        // the one configuration the multi-output epilogue is compiled for (the 128 -> 192 latent layer); anything else is the caller's
+        // cue to keep the separate launches
+        MASIC_REQUIRE(!f8 && c.NP == 1 && c.KS == 1 && c.T == 5 && c.D == 2 && gdn_packed == nullptr, MASIC_ERR_UNSUPPORTED,
+                      "conv_f16k_multi: only the strided 5x5 bf16 configuration has the multi-output epilogue");
+#define F16K_LAUNCH_MULTI(NMV)                                                                                       \
+    do {                                                                                                             \
+        auto kfn = conv_f16k_multi<NMV>;                                                                             \
+        static bool attr_set = false;                                                                                \
+        if (!attr_set) {                                                                                             \
+            (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
+            attr_set = true;                                                                                         \
+        }                                                                                                            \
+        hipLaunchKernelGGL(kfn, grid, dim3(512), c.lds_bytes, st, a, *multi);                                        \
+    } while (0)
+        if (msplit == 4) F16K_LAUNCH_MULTI(1);
+        else if (msplit == 2) F16K_LAUNCH_MULTI(2);
+        else F16K_LAUNCH_MULTI(4);
+#undef F16K_LAUNCH_MULTI
+    } else if (f8) {
         if (c.KS == 1) {
             if (gdn_packed) F8K_LAUNCH(1, 4, 6, 1, true);
             else F8K_LAUNCH(1, 4, 6, 1, false);
@@ -2787,3 +2924,4 @@ extern "C" int masic_conv3x3_resident_ex_fwd(const void* x_f16k, const void* w_p
     if (sum_of) hipLaunchKernelGGL(c3_sum_finish_kernel, dim3(C), dim3(64), 0, st, (const float*)sum_workspace, sum_out, C, grid);
     return masic_launch_status("conv3x3_resident_fwd");
 }
+#endif  // CONV_F16K_BODY

@@ -97,7 +97,7 @@ __device__ __forceinline__ float eb_logits(const EbParams& p, float x) {
 __global__ __launch_bounds__(256) void eb_fwd_kernel(const float* __restrict__ z, const float* __restrict__ params,
                                                      const float* __restrict__ medians, const float* __restrict__ noise,
                                                      float* __restrict__ z_hat, float* __restrict__ lik,
-                                                     int B, int C, int HW, int training, float lik_bound) {
+                                                     int B, int C, int HW, int training, float lik_bound, int med_stride) {
     const size_t total = (size_t)B * C * HW;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void eb_fwd_kernel(const float* __restrict__ z
     const int b = (int)(bc / C), c = (int)(bc - (size_t)b * C);
     EbParams prm;
     eb_load(params + (size_t)c * MASIC_EB_PARAMS_PER_CHANNEL, prm);
-    const float med = medians[c];
+    const float med = medians[(size_t)c * med_stride];     // (read in place from the quantiles parameter [C][1][3]: stride 3)
     const float v = z[i];
     float vq;
     if (training) vq = v + noise[(size_t)c * HW * B + (size_t)p * B + b];   // (C,1,H*W*B) draw layout
@@ -240,8 +240,21 @@ extern "C" int masic_entropy_bottleneck_fwd(const float* z, const float* params,
     MASIC_REQUIRE(!training || noise, MASIC_ERR_ARG, "entropy_bottleneck_fwd: training without noise");
     const size_t total = (size_t)B * C * H * W;
     hipLaunchKernelGGL(eb_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       z, params, medians, noise, z_hat, lik, B, C, H * W, training, lik_bound);
+                       z, params, medians, noise, z_hat, lik, B, C, H * W, training, lik_bound, 1);
     return masic_launch_status("entropy_bottleneck_fwd");
+}
+
+// The same with the medians read at a stride (elements): medians = &quantiles[0][0][1], median_stride = 3 reads them from the module's
+// quantiles parameter in place -- no contiguous copy of C floats in front of every launch.
+extern "C" int masic_entropy_bottleneck_strided_fwd(const float* z, const float* params, const float* medians, int median_stride,
+                                                    const float* noise, float* z_hat, float* lik,
+                                                    int B, int C, int H, int W, int training, float lik_bound, void* stream) {
+    MASIC_REQUIRE(z && params && medians && z_hat && lik && median_stride >= 1, MASIC_ERR_ARG, "entropy_bottleneck_strided_fwd: null pointer or stride < 1");
+    MASIC_REQUIRE(!training || noise, MASIC_ERR_ARG, "entropy_bottleneck_strided_fwd: training without noise");
+    const size_t total = (size_t)B * C * H * W;
+    hipLaunchKernelGGL(eb_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       z, params, medians, noise, z_hat, lik, B, C, H * W, training, lik_bound, median_stride);
+    return masic_launch_status("entropy_bottleneck_strided_fwd");
 }
 
 extern "C" int masic_entropy_bottleneck_auxloss(const float* params, const float* quantiles, float* out,
@@ -256,7 +269,8 @@ extern "C" int masic_gmm_likelihood_fwd(const float* y, const float* noise, cons
                                         const float* wts, float* y_hat, float* lik, float* wts_out,
                                         int B, int M, int K, int H, int W, int training, int weights_are_logits,
                                         float scale_bound, float lik_bound, void* stream) {
-    MASIC_REQUIRE(y && sigma && mu && wts && lik && (y_hat || training == 2), MASIC_ERR_ARG, "gmm_likelihood_fwd: null pointer");
+    // y_hat NULL: the quantised latent is not stored (the eval forward discards it; training == 2 has nothing to store)
+    MASIC_REQUIRE(y && sigma && mu && wts && lik, MASIC_ERR_ARG, "gmm_likelihood_fwd: null pointer");
     MASIC_REQUIRE(training >= 0 && training <= 2, MASIC_ERR_ARG, "gmm_likelihood_fwd: training = %d", training);
     MASIC_REQUIRE(training != 1 || noise, MASIC_ERR_ARG, "gmm_likelihood_fwd: training without noise");
     MASIC_REQUIRE(K >= 1 && K <= 8, MASIC_ERR_UNSUPPORTED, "gmm_likelihood_fwd: K=%d", K);

@@ -247,6 +247,16 @@ class _PackedWeightMixin:
                             gdn=None if gdn is None else (packed_gdn_f16k(gdn), gdn.inverse), out16=out16)
         return y, desc.Ho, desc.Wo
 
+    def f16k_multi_supported(self, B, Hi, Wi):
+        return ops.conv_f16k_multi_supported(self._desc_f16k(B, Hi, Wi))
+
+    def run_f16k_multi(self, x16, B, Hi, Wi, want, round16=None, round16_ctot=0, round16_coff=0, gate=None, gate_c=0):
+        """Inference-only: conv(x) + bias of a latent layer stored once in the layouts of `want` (ops.conv2d_f16k_multi)."""
+        desc = self._desc_f16k(B, Hi, Wi)
+        bias = None if self.bias is None else self.bias.detach()
+        return ops.conv2d_f16k_multi(x16, self.packed_f16k_weight(desc), bias, desc, want=want, round16=round16, round16_ctot=round16_ctot,
+                                     round16_coff=round16_coff, gate=gate, gate_c=gate_c)
+
     def run_f16k_dual(self, x16, B, Hi, Wi, gdn, products=None):
         """Training-mode forward of conv + (I)GDN on F16K: returns (pre-GDN F16K, post-GDN F16K, Ho, Wo)."""
         desc = self._desc_f16k(B, Hi, Wi, out_ctot=(self.out_channels + 15) // 16 * 16)
@@ -324,6 +334,16 @@ class _PackedWeightMixin:
                           in_op=in_op, act=act, gate_ctot=0 if gate is None else gate.shape[1], gate_c=gate_c)
         bias = None if self.bias is None else self.bias.detach()
         return ops.conv2d(x, self.packed_weight(desc), bias, desc, out=out, gate=gate, res1=res1, res2=res2)
+
+    def f16k_out_supported(self, shape):
+        """run_f16k_out has a kernel for an input of this [B, Cin, H, W] (bf16 operands on the implicit-GEMM kernel, Cout % 32 == 0)."""
+        return reduced_precision() and ops.conv2d_f16k_out_supported(self._desc(tuple(shape), out_ctot=(self.out_channels + 15) // 16 * 16))
+
+    def run_f16k_out(self, x, act=ops.ACT_NONE):
+        """Inference-only: run(x, act=act) with the result as an F16K buffer (ops.conv2d_f16k_out); returns (y16, Ho, Wo)."""
+        desc = self._desc(tuple(x.shape), out_ctot=(self.out_channels + 15) // 16 * 16, act=act)
+        bias = None if self.bias is None else self.bias.detach()
+        return ops.conv2d_f16k_out(x, self.packed_weight(desc), bias, desc), desc.Ho, desc.Wo
 
     def _run_autograd(self, x, in_coff, out, in_op, act, gate, gate_c, res1, res2):
         from . import autograd as A

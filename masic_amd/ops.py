@@ -318,18 +318,21 @@ def eb_table_split(g_table, shapes):
 
 
 def entropy_bottleneck(z, table, medians, training=False, noise=None, lik_bound=LIK_BOUND):
-    _dev(z, "z"); _dev(table, "EB table"); _dev(medians, "medians")
+    """medians: [C] float32, contiguous or a strided view (quantiles[:, 0, 1] of the module's parameter is read in place)."""
+    _dev(z, "z"); _dev(table, "EB table")
     B, C, H, W = z.shape
-    if tuple(table.shape) != (C, _lib.EB_PARAMS_PER_CHANNEL) or medians.numel() != C:
+    if tuple(table.shape) != (C, _lib.EB_PARAMS_PER_CHANNEL) or tuple(medians.shape) != (C,):
         raise RuntimeError("masic_amd.entropy_bottleneck: parameter table does not match channels")
+    if not medians.is_cuda or medians.dtype != torch.float32 or (C > 1 and medians.stride(0) < 1):
+        raise RuntimeError("masic_amd.entropy_bottleneck: medians must be a float32 CUDA vector with a positive stride")
     if training:
         _dev(noise, "noise")
         if noise.numel() != z.numel():
             raise RuntimeError("masic_amd.entropy_bottleneck: noise size mismatch")
     z_hat = torch.empty_like(z)
     lik = torch.empty_like(z)
-    check(lib.masic_entropy_bottleneck_fwd(_p(z), _p(table), _p(medians), _p(noise), _p(z_hat), _p(lik),
-                                           B, C, H, W, int(training), float(lik_bound), _stream()), "entropy_bottleneck_fwd")
+    check(lib.masic_entropy_bottleneck_strided_fwd(_p(z), _p(table), _p(medians), medians.stride(0) if C > 1 else 1, _p(noise), _p(z_hat), _p(lik),
+                                                   B, C, H, W, int(training), float(lik_bound), _stream()), "entropy_bottleneck_fwd")
     return z_hat, lik
 
 
@@ -342,7 +345,8 @@ def entropy_bottleneck_auxloss(table, quantiles, tail_mass=1e-9):
 
 
 def gmm_likelihood(y, sigma, mu, wts, K, training=False, noise=None, weights_are_logits=False,
-                   want_weights=False, scale_bound=SCALE_BOUND, lik_bound=LIK_BOUND):
+                   want_weights=False, scale_bound=SCALE_BOUND, lik_bound=LIK_BOUND, want_y_hat=True):
+    """want_y_hat=False: the quantised latent is not stored (returned as None) -- the eval forward only keeps the likelihood."""
     _dev(y, "y"); _dev(sigma, "sigma"); _dev(mu, "mu"); _dev(wts, "weights")
     B, M, H, W = y.shape
     for t, n in ((sigma, "sigma"), (mu, "mu"), (wts, "weights")):
@@ -354,7 +358,7 @@ def gmm_likelihood(y, sigma, mu, wts, K, training=False, noise=None, weights_are
         _dev(noise, "noise")
         if noise.numel() != y.numel():
             raise RuntimeError("masic_amd.gmm_likelihood: noise size mismatch")
-    y_hat = torch.empty_like(y) if training != 2 else None
+    y_hat = torch.empty_like(y) if (training != 2 and want_y_hat) else None
     lik = torch.empty_like(y)
     wout = torch.empty_like(wts) if (weights_are_logits and want_weights) else None
     check(lib.masic_gmm_likelihood_fwd(_p(y), _p(noise), _p(sigma), _p(mu), _p(wts), _p(y_hat), _p(lik), _p(wout),
@@ -1101,6 +1105,65 @@ def conv2d_f16k(x16, packed, bias, desc, out_nchw=None, want_nchw=False, gate=No
         flops, nbytes = conv_algorithmic_work(desc)
         _timer.records.append((timed[0], 1, flops, nbytes, timed[1], timed[2]))
     return y32 if y32 is not None else y16
+
+
+def conv2d_f16k_out_supported(desc):
+    return bool(_desc_query("masic_conv2d_f16k_out_supported", desc))
+
+
+def conv2d_f16k_out(x, packed, bias, desc):
+    """conv2d() of a bf16-operand layer with the result stored as an F16K buffer of desc.out_ctot channels (masic_conv2d_f16k_out_fwd):
+    bf16(act(conv(x) + bias)), the bits nchw_to_f16k(conv2d(...)) gives, without the float32 tensor in between."""
+    _dev(x, "conv input")
+    if x.dim() != 4 or tuple(x.shape) != (desc.B, desc.in_ctot, desc.Hi, desc.Wi):
+        raise RuntimeError(f"masic_amd.conv2d_f16k_out: input {tuple(x.shape)} does not match descriptor")
+    if bias is not None:
+        _dev(bias, "bias")
+    y16 = torch.empty(desc.B * desc.out_ctot * desc.Ho * desc.Wo, dtype=torch.int16, device=x.device)
+    check(lib.masic_conv2d_f16k_out_fwd(_p(x), _p(packed), _p(bias), _p(y16), ctypes.byref(desc), _stream()), "conv2d_f16k_out_fwd")
+    return y16
+
+
+def conv_f16k_multi_supported(desc):
+    return bool(_desc_query("masic_conv_f16k_multi_supported", desc))
+
+
+def conv2d_f16k_multi(x16, packed, bias, desc, want=("y32", "round32", "round16", "abs16"), round16=None, round16_ctot=0, round16_coff=0,
+                      gate=None, gate_c=0):
+    """The latent layer of an analysis transform (masic_conv_f16k_multi_fwd): v = conv(x) + bias written once, from the accumulators,
+    in the layouts named by `want` -- 'y32' float32 NCHW v, 'round32' float32 NCHW round(v), 'round16' F16K bf16(round(v) * gate)
+    (a fresh buffer of ceil16(Cout) channels, or channels round16_coff.. of the existing buffer `round16` of round16_ctot channels;
+    gate: float32 [B][*][Ho][Wo], channel gate_c), 'abs16' F16K bf16(|v|).  Returns a dict of the tensors written."""
+    if x16.dtype != torch.int16 or not x16.is_cuda or x16.numel() != desc.B * desc.in_ctot * desc.Hi * desc.Wi:
+        raise RuntimeError("masic_amd.conv2d_f16k_multi: input must be the F16K int16 CUDA buffer the descriptor describes")
+    if bias is not None:
+        _dev(bias, "bias")
+    B, C, Ho, Wo = desc.B, desc.Cout, desc.Ho, desc.Wo
+    dev = x16.device
+    out = {}
+    if "y32" in want:
+        out["y32"] = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=dev)
+    if "round32" in want:
+        out["round32"] = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=dev)
+    if "round16" in want:
+        if round16 is None:
+            round16_ctot, round16_coff = (C + 15) // 16 * 16, 0
+            round16 = torch.empty(B * round16_ctot * Ho * Wo, dtype=torch.int16, device=dev)
+        elif round16.dtype != torch.int16 or round16.numel() != B * round16_ctot * Ho * Wo:
+            raise RuntimeError("masic_amd.conv2d_f16k_multi: round16 is not an F16K buffer of round16_ctot channels at the output size")
+        out["round16"] = round16
+    if "abs16" in want:
+        out["abs16"] = torch.empty(B * ((C + 15) // 16 * 16) * Ho * Wo, dtype=torch.int16, device=dev)
+    gate_ctot = 0
+    if gate is not None:
+        _dev(gate, "gate")
+        if gate.shape[0] != B or tuple(gate.shape[2:]) != (Ho, Wo):
+            raise RuntimeError("masic_amd.conv2d_f16k_multi: gate does not match the output")
+        gate_ctot = gate.shape[1]
+    mo = _lib.F16kMultiOut(y32=_p(out.get("y32")), round32=_p(out.get("round32")), round16=_p(out.get("round16")), abs16=_p(out.get("abs16")),
+                           gate=_p(gate), round16_ctot=round16_ctot, round16_coff=round16_coff, gate_ctot=gate_ctot, gate_c=gate_c)
+    check(lib.masic_conv_f16k_multi_fwd(_p(x16), _p(packed), _p(bias), ctypes.byref(mo), ctypes.byref(desc), _stream()), "conv_f16k_multi_fwd")
+    return out
 
 
 def pack_conv_a_weight(weight):
