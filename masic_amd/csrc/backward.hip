@@ -277,7 +277,10 @@ __global__ __launch_bounds__(256) void gdn_bwd_small_finish(const float* __restr
 }
 
 // ---------------------------------------------------------------------------- Gaussian mixture backward
-__device__ __forceinline__ float norm_pdf(float t) { return 0.3989422804014327f * expf(-0.5f * t * t); }
+// phi(t) from x = -t / sqrt(2), the rounded argument erfcf sees: the order of autograd's erfc derivative, (2 / sqrt(pi)) exp(-x^2), which
+// the reference differentiates with.  Taken from t instead, the density and the likelihood it divides by (g = -1 / (lik ln2)) see
+// differently rounded arguments, and d bits / dy in the tail is off by |t^2 / 2| ulp more than the reference's own float32 evaluation.
+__device__ __forceinline__ float norm_pdf_x(float x) { return 0.3989422804014327f * expf(-(x * x)); }
 
 template <int K>
 __global__ __launch_bounds__(256) void gmm_bwd_kernel(const float* __restrict__ y_hat, const float* __restrict__ sigma,
@@ -316,8 +319,9 @@ __global__ __launch_bounds__(256) void gmm_bwd_kernel(const float* __restrict__ 
         const float d = yv - mu[base + k * ks];
         const float v = fabsf(d);
         const float ta = (0.5f - v) / s, tb = (-0.5f - v) / s;
-        const float up = 0.5f * erfcf(cst * ta), lo = 0.5f * erfcf(cst * tb);
-        const float pa = norm_pdf(ta), pb = norm_pdf(tb);
+        const float xa = cst * ta, xb = cst * tb;
+        const float up = 0.5f * erfcf(xa), lo = 0.5f * erfcf(xb);
+        const float pa = norm_pdf_x(xa), pb = norm_pdf_x(xb);
         dcdf[k] = up - lo;                                  // dL/dw_k
         dsig[k] = wk[k] * (tb * pb - ta * pa) / s;          // dL/ds_k
         dv[k] = -wk[k] * (pa - pb) / s;                     // dL/dv_k

@@ -1,4 +1,8 @@
-"""Shared helpers for the parity tests."""
+"""Shared helpers for the parity tests.
+
+Which ruler: `rel_err` / `assert_close` divide by the largest magnitude of the whole reference tensor, which suits activations
+and weight gradients whose elements are of one size.  Likelihood-like tensors (likelihoods, bits, and every gradient of the
+rate) span nine decades; there use `scaled_err` with the per-element scales of tests/entropy_ref.py, which sees the tail."""
 import os
 
 import numpy as np
@@ -29,6 +33,21 @@ def rel_err(a, b):
     b = b.detach().double().cpu()
     scale = float(b.abs().max())
     return float((a - b).abs().max()) / (scale if scale > 0 else 1.0)
+
+
+def scaled_err(got, ref, scale, floor=1e-6):
+    """max_i |got_i - ref_i| / max(scale_i, floor * max_j scale_j): the error of every element in units of the magnitudes of the
+    terms its exact formula adds up (tests/entropy_ref.py returns that scale with every quantity).  inf if `got` is not finite."""
+    got = torch.as_tensor(got).detach().double().cpu().reshape(-1)
+    ref = torch.as_tensor(ref).detach().double().cpu().reshape(-1)
+    scale = torch.as_tensor(scale).detach().double().cpu().reshape(-1)
+    assert got.shape == ref.shape == scale.shape, f"shapes {tuple(got.shape)} {tuple(ref.shape)} {tuple(scale.shape)}"
+    if not bool(torch.isfinite(got).all()):
+        return float("inf")
+    top = float(scale.max())
+    if top <= 0.0:
+        return 0.0 if bool((got == ref).all()) else float("inf")
+    return float(((got - ref).abs() / torch.clamp(scale, min=floor * top)).max())
 
 
 def assert_close(a, b, name="", rtol=RTOL):
