@@ -691,7 +691,7 @@ int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, int ngroups, 
  * as bf16); the last wave of the launch to finish (over ALL streams) increments *step.  state[s] / pos[s]: per-stream coder state
  * and next word index, caller-initialised (state = word0 | word1 << 32, pos = 2) and kept across steps; done: caller-zeroed device int.
  * err_flags: one caller-zeroed device int per image: bit 0 = a table could not be normalised, or a descriptor whose alphabet is
- * empty or exceeds 1024 entries; bit 1 = a symbol outside the alphabet; bit 2 = a stream ended early.
+ * empty or exceeds 1024 entries; bit 1 = a symbol outside the alphabet; bit 2 = a stream ended early (bit 3: masic_rans_decode_finish_batch; bit 4: the device encoder below).
  * masic_rans_decode_finish_batch: one thread per stream, to be called ONCE, AFTER the last coding step (outside a graph that is replayed
  * per step) on the state / pos / err_flags of the steps: ORs bit 3 (value 8) into err_flags[img] of every stream with
  * pos != word_cnt or state != 2^31.  Every encoder (masic_rans_encode_freqs / _channels / _with_indexes) starts from state 2^31 and a
@@ -712,6 +712,24 @@ int masic_rans_decode_step_batch(const uint32_t* words, const masic_code_stream_
                                  float* y_hat, void* y_f16k, int HW, int32_t* err_flags, int32_t* done, void* stream);
 int masic_rans_decode_finish_batch(const masic_code_stream_t* streams, int nstreams, const uint64_t* state, const uint32_t* pos,
                                    int32_t* err_flags, void* stream);
+/* The encoder's coder on the device: masic_rans_encode_channels for every channel stream of B >= 1 pairs in one launch, one lane per
+ * stream, bit for bit the host coder's words.  start_freq: the DEVICE table masic_gmm_cdf_rows_batch wrote ([rows][2]); streams: the
+ * same descriptors (img, rstride, row0 are read: the symbol of pixel i, coding order, is row row0 + i * rstride); npix: symbols per
+ * stream.  Stream s writes backwards into its own region of npix + 2 words of `workspace` (masic_rans_encode_batch_workspace_bytes)
+ * and nowhere else; its words are the last lengths[s] / 4 of that region, lengths[s] in bytes (a multiple of 4, >= 8).  A row with
+ * start < 0, freq < 1 or start + freq > 65536 (the host coder's MASIC_ERR_ARG) is skipped and ORs bit 4 (value 16) into
+ * err_flags[img]: the streams of the other images are unaffected.  nstreams = 0: no launch.
+ * masic_rans_pack_pairs_batch frames them: per pair the bytes masic_amd.codec.encode_channels returns (u32 n, n x u32 lengths, the n
+ * streams back to back), the npairs blobs one after another in `blob` (masic_rans_pack_pairs_bound bytes always suffice), pair b at byte
+ * offsets[b], offsets[npairs] = the bytes used.  first: DEVICE int32 [npairs + 1], the index of every pair's first stream (streams are
+ * ordered by pair; first[npairs] = nstreams), so a pair without coded channels still gets its u32 0.  The order is fixed: the same
+ * bytes every run.  All pointers device memory; asynchronous on `stream`. */
+size_t masic_rans_encode_batch_workspace_bytes(int nstreams, int npix);
+int masic_rans_encode_channels_batch(const int32_t* start_freq, const masic_code_stream_t* streams, int nstreams, int npix,
+                                     void* workspace, uint32_t* lengths, int32_t* err_flags, void* stream);
+size_t masic_rans_pack_pairs_bound(int nstreams, int npix, int npairs);
+int masic_rans_pack_pairs_batch(const void* workspace, const uint32_t* lengths, const masic_code_stream_t* streams, int nstreams, int npix,
+                                const int32_t* first, int npairs, void* blob, uint32_t* offsets, void* stream);
 int masic_rans_decoder_open(const uint8_t* in, size_t in_len, void** handle);
 int masic_rans_decoder_decode_rows(void* handle, const uint16_t* starts, int nrows, int L, int32_t* symbols);
 /* the next n symbols with tables picked by indexes (arguments as masic_rans_decode_with_indexes), keeping the coder state between

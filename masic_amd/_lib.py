@@ -96,6 +96,10 @@ SIGNATURES = {
     "masic_gmm_cdf_rows_batch": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_float, _P, _P, _P, _P, _P]),
     "masic_rans_decode_step_batch": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
     "masic_rans_decode_finish_batch": (c_int, [_P, c_int, _P, _P, _P, _P]),
+    "masic_rans_encode_batch_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "masic_rans_encode_channels_batch": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P]),
+    "masic_rans_pack_pairs_bound": (c_size_t, [c_int, c_int, c_int]),
+    "masic_rans_pack_pairs_batch": (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, _P, _P, _P]),
     "masic_skinny_group_fwd_batch": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P]),
     "masic_rans_decoder_open": (c_int, [_P, c_size_t, _P]),
     "masic_rans_decoder_decode_rows": (c_int, [_P, _P, c_int, c_int, _P]),

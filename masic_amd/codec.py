@@ -17,7 +17,9 @@ Here:
 Encoder and decoder evaluate the SAME kernels on tensors of the same shape, and the masked taps of the context
 convolution are exact zeros, so a not-yet-decoded neighbour (zero in the decoder, the true value in the encoder) never
 changes a bit of the parameters of the pixel being coded: the encoder needs ONE pass over the full latent, the decoder
-one pass per wavefront.
+one pass per wavefront.  The encoder's rANS chains run on the device too, one lane per channel stream over the (start, freq) table
+(masic_rans_encode_channels_batch), and a second kernel frames the pairs: only the flags, the pairs' offsets and the finished bytes
+cross to the host.  The host coder (encode_channels) is kept as its byte-for-byte checker (encode_views(coder="host")).
 Container (.bin): b"MSR2", u8 precision id (0 f32 / 1 bf16 / 2 fp8 operands: the tables depend on it), u8 flags (bit 0: an
 activation-scale table follows), 2 pad bytes, [u32 length + the fp8 mode's calibration table as JSON, masic_amd/fp8.py], then per
 view u32 number of channel streams n, n x u32 stream lengths in bytes, the streams back to back (round 2's "MSR1" had one stream per view).  The .npz header keeps the reference's layout (MASIC.py:916-948).
@@ -200,6 +202,8 @@ def check_errs(err, what, names=None):
             kind = CorruptStreamError
             msg = ("a channel stream did not end in the coder's final state (corrupt data, a header from another file, other weights or "
                    "another operand mode than the encoder's)")
+        elif e & 16:
+            msg = "the encoder was given a symbol interval outside [0, 2^16]"
         else:
             continue
         raise kind(i, f"masic_amd.codec: {what}: {msg}{_pair_tag(i, len(flags), names, ' -- pair %s of the batch')}")
@@ -259,11 +263,57 @@ def _full_latent_params(params_fn, y_hat, KM):
     return out
 
 
-def encode_views(params_fn, y_hat, M, K, chans, minmaxes, scale_bound, names=None):
+def _encode_device(sf, desc, nstreams, npix, first, err, names=None, raise_errs=True):
+    """The device coder on the (start, freq) table `sf` of B pairs (masic_rans_encode_channels_batch + masic_rans_pack_pairs_batch) -> the
+    B framed blobs, byte for byte encode_channels' of each pair's rows, and the pairs' flags as a list.  first: per pair the index of its
+    first stream, plus nstreams; err: the call's flags, int32 [B] on the device (the table kernel's bits are in it already).  Two copies
+    leave the device: the flags together with the pairs' byte offsets, and -- once check_errs has passed -- the used bytes of the blobs."""
+    B, dev = len(first) - 1, sf.device
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    meta = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)          # flags [B], byte offsets [B + 1]
+    meta[:B] = err
+    first_d = torch.tensor(first, dtype=torch.int32).to(dev)
+    ws = torch.empty(max(lib.masic_rans_encode_batch_workspace_bytes(nstreams, npix) // 4, 1), dtype=torch.int32, device=dev)
+    lengths = torch.empty(max(nstreams, 1), dtype=torch.int32, device=dev)
+    blob = torch.empty(lib.masic_rans_pack_pairs_bound(nstreams, npix, B) // 4, dtype=torch.int32, device=dev)
+    check(lib.masic_rans_encode_channels_batch(_p(sf), _p(desc), nstreams, npix, _p(ws), _p(lengths), _p(meta), st), "rans_encode_channels_batch")
+    check(lib.masic_rans_pack_pairs_batch(_p(ws), _p(lengths), _p(desc), nstreams, npix, _p(first_d), B, _p(blob), _p(meta[B:]), st),
+          "rans_pack_pairs_batch")
+    meta_h = meta.cpu()
+    if raise_errs:
+        check_errs(meta_h[:B], "encode", names)
+    off = meta_h[B:].numpy().view(np.uint32).astype(np.int64)
+    data = blob[:int(off[B]) // 4].cpu().numpy().tobytes()
+    return [data[off[b]:off[b + 1]] for b in range(B)], meta_h[:B].tolist()
+
+
+def encode_channels_device(sf_dev, desc, nstreams, npix, B, first):
+    """The device form of encode_channels for the B pairs of one stream table (desc, nstreams: _stream_table's, built with npix rows per
+    stream; first: the pairs' first stream indexes, B + 1 entries; sf_dev: int32 [rows][2] on the device) -> (the B blobs, the pairs'
+    error flags as a list of B ints).  A flagged pair (bit 4: a row no coder can take) raises nothing here; its blob codes the other
+    rows.  For tests of the kernels without a model."""
+    if len(first) != B + 1 or first[0] != 0 or first[B] != nstreams or any(first[b] > first[b + 1] for b in range(B)):
+        raise ValueError("masic_amd.codec.encode_channels_device: first must hold B + 1 ascending stream indexes from 0 to nstreams")
+    if not (sf_dev.is_cuda and sf_dev.is_contiguous() and sf_dev.dtype == torch.int32):
+        raise RuntimeError("masic_amd.codec.encode_channels_device: start_freq must be a contiguous int32 device tensor")
+    err = torch.zeros(B, dtype=torch.int32, device=sf_dev.device)
+    return _encode_device(sf_dev, desc, nstreams, npix, [int(f) for f in first], err, raise_errs=False)
+
+
+def _first_streams(chans):
+    return [0] + np.cumsum([len(ch) for ch in chans]).tolist()
+
+
+def encode_views(params_fn, y_hat, M, K, chans, minmaxes, scale_bound, names=None, coder="device"):
     """One pass over B pairs: y_hat [B, M, h, w]; chans / minmaxes: pair b's coded channels (int sequence) and alphabet half-width;
     params_fn: see _pixel_list_form.  Parameters of every pixel -> (start, freq) of every coded symbol in wavefront order -> per pair
     u32 n, n x u32 lengths and one rANS stream per coded channel.  A pair's bytes do not depend on its batch mates (the same parameters
-    bit for bit: a pixel's result depends on its own operands only; the same table arithmetic on them)."""
+    bit for bit: a pixel's result depends on its own operands only; the same table arithmetic on them).
+    coder: "device" codes and frames the streams where the table is (one lane per channel stream; the flags, the pairs' offsets and the
+    finished bytes are all that cross to the host); "host" copies the table to the host and runs encode_channels per pair -- the same
+    bytes, kept as the checker of the device coder."""
+    if coder not in ("device", "host"):
+        raise ValueError(f"masic_amd.codec.encode_views: coder={coder!r} (\"device\" or \"host\")")
     B, _, h, w = y_hat.shape
     HW, dev = h * w, y_hat.device
     pixel_list = _pixel_list_form(params_fn, B, "encode_views")
@@ -282,6 +332,8 @@ def encode_views(params_fn, y_hat, M, K, chans, minmaxes, scale_bound, names=Non
         check(lib.masic_gmm_cdf_rows_batch(_p(sigma), _p(mu), _p(logits), M, K, HW, _p(pix), None, B * HW, HW,
                                            _p(desc), n, float(scale_bound), _p(y_hat), None, _p(sf), _p(err),
                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gmm_cdf_rows_batch")
+    if coder == "device":
+        return _encode_device(sf, desc, n, HW, _first_streams(chans), err, names)[0]
     check_errs(err, "encode", names)
     sf_h = sf.cpu().numpy()
     jobs, r0 = [], 0

@@ -278,7 +278,164 @@ __global__ __launch_bounds__(64) void rans_decode_finish_kernel(const masic_code
     if (pos[c] != streams[c].word_cnt || state[c] != (1ull << 31)) atomicOr(err + streams[c].img, 8);
 }
 
+// ---- the encoder's coder on the device: one LANE per channel stream (masic_rans_encode_channels of rans.hip, all streams of a call at once).
+// A stream is one serial chain over its npix symbols, walked last pixel first as every rANS encoder does; the 2 M B chains of a call
+// are independent, so lane l of workgroup g (one wavefront) runs stream 64 g + l.  Consecutive streams of a pair are consecutive
+// channels, and the pair's rows are pixel-major (row0 + i * rstride), so the wave's loads of one pixel are one contiguous segment of
+// 8-byte rows (512 bytes for a full wave of one pair).  The rows do not depend on the coder state: a tile of ENC_TILE pixels is loaded
+// into registers while the chain works on the tile before it, which it reads from LDS ([pixel][lane], every lane only its own column:
+// no barrier), and is written there once the chain is through.  The symbol loop is a real loop (not unrolled), so the loads are issued in
+// the block before it and waited for in the block after it -- a prefetch carried in registers over the loop's back edge is waited for at
+// once (README, round 2 third pass).
+// Per symbol, put() of rans.hip: a word leaves when x >= 2^47 * freq, then x = ((x / freq) << 16) + x % freq + start.  x < 2^63 and
+// freq <= 2^16; after the renormalisation the quotient is below 2^47, so the product of x and 1 / freq in double precision (three
+// roundings of 2^-53 relative each) is within 2^47 * 3 * 2^-53 < 0.05 of it, its integer part within one, and the remainder says which.
+// Words go backwards into the stream's own region of npix + 2 words of the workspace (at most one per symbol, and the two of the final
+// state), and the region's tail [npix + 2 - length / 4, npix + 2) is the stream.  A row no coder can take (start < 0, freq < 1,
+// start + freq > 2^16: the argument error of the host coder) is skipped and sets err bit 4 of its pair.
+constexpr int ENC_TILE = 32;          // pixels per staged tile: 16 KB of LDS, 64 registers in flight
+
+__host__ __device__ __forceinline__ void rans_divmod(unsigned long long x, unsigned freq, double rcp, unsigned long long& q, unsigned& r) {
+    unsigned long long qq = (unsigned long long)((double)x * rcp);
+    long long rr = (long long)(x - qq * freq);                 // exact in 64 bits: |x - qq * freq| <= 2 * freq
+    if (rr < 0) { --qq; rr += freq; }
+    if (rr >= (long long)freq) { ++qq; rr -= freq; }
+    q = qq;
+    r = (unsigned)rr;
+}
+
+__global__ __launch_bounds__(64) void rans_encode_channels_kernel(const int2* __restrict__ start_freq,
+                                                                  const masic_code_stream_t* __restrict__ streams, int nstreams, int npix,
+                                                                  unsigned* __restrict__ workspace, unsigned* __restrict__ lengths,
+                                                                  int* __restrict__ err) {
+    __shared__ int2 tile[ENC_TILE][64];
+    const int lane = threadIdx.x, s = blockIdx.x * 64 + lane;
+    if (s >= nstreams) return;                             // lanes share nothing: no barrier follows
+    const masic_code_stream_t sd = streams[s];
+    const int2* rows = start_freq + sd.row0;
+    const size_t rs = (size_t)sd.rstride;
+    const int cap = npix + 2;
+    unsigned* out = workspace + (size_t)s * cap;
+    int p = cap;                                           // next word goes to out[p - 1]; p >= 2 after npix symbols
+    unsigned long long x = 1ull << 31;
+    bool bad = false;
+    const int ntiles = (npix + ENC_TILE - 1) / ENC_TILE;
+    int2 nxt[ENC_TILE];
+    if (ntiles > 0) {                                      // the last tile may be short: its tail repeats the last pixel and is never coded
+        const int i0 = (ntiles - 1) * ENC_TILE;
+#pragma unroll
+        for (int k = 0; k < ENC_TILE; ++k) nxt[k] = rows[(size_t)min(i0 + k, npix - 1) * rs];
+#pragma unroll
+        for (int k = 0; k < ENC_TILE; ++k) tile[k][lane] = nxt[k];
+    }
+    for (int t = ntiles - 1; t >= 0; --t) {
+        const int i0 = t * ENC_TILE, cnt = min(ENC_TILE, npix - i0);
+        if (t > 0) {                                       // tile t - 1 is whole
+#pragma unroll
+            for (int k = 0; k < ENC_TILE; ++k) nxt[k] = rows[(size_t)(i0 - ENC_TILE + k) * rs];
+        }
+#pragma nounroll
+        for (int k = cnt - 1; k >= 0; --k) {
+            const int2 sf = tile[k][lane];
+            const int st = sf.x, fr = sf.y;
+            if (st < 0 || fr < 1 || fr > 65536 || st > 65536 - fr) { bad = true; continue; }
+            const unsigned freq = (unsigned)fr;
+            const double rcp = 1.0 / (double)freq;
+            if (x >= ((unsigned long long)freq << 47)) {
+                out[--p] = (unsigned)x;
+                x >>= 32;
+            }
+            unsigned long long q;
+            unsigned r;
+            rans_divmod(x, freq, rcp, q, r);
+            x = (q << 16) + r + (unsigned)st;
+        }
+        if (t > 0) {
+#pragma unroll
+            for (int k = 0; k < ENC_TILE; ++k) tile[k][lane] = nxt[k];
+        }
+    }
+    p -= 2;
+    out[p] = (unsigned)x;
+    out[p + 1] = (unsigned)(x >> 32);
+    lengths[s] = (unsigned)(cap - p) * 4u;
+    if (bad) atomicOr(err + sd.img, 16);
+}
+
+// ---- framing on the device: workspace + lengths -> per pair the bytes codec.encode_channels returns (u32 n, n x u32 lengths, the n
+// streams back to back), the B blobs one after another in `blob`, pair b at byte offsets[b] (offsets[B] = all bytes).  first[b] is the
+// index of pair b's first stream (first[B] = nstreams), so a pair without streams still gets its four bytes.  Everything is a whole
+// number of 32-bit words.  With S(k) = the words of streams 0 .. k-1, pair b starts at word b + first[b] + S(first[b]) (b headers of
+// one word, first[b] length fields) and stream s of pair b at word b + 1 + first[b + 1] + S(s).  Workgroups 0 .. nstreams-1 copy one
+// stream each, workgroups nstreams .. nstreams + B write one pair's header and offset each (the last one only offsets[B]); each sums the
+// lengths it needs itself (a few thousand integers from L2): no order between workgroups, the same bytes every run.
+constexpr int PACK_THREADS = 256;
+__global__ __launch_bounds__(PACK_THREADS) void rans_pack_pairs_kernel(const unsigned* __restrict__ workspace, const unsigned* __restrict__ lengths,
+                                                                       const masic_code_stream_t* __restrict__ streams, int nstreams, int npix,
+                                                                       const int* __restrict__ first, int npairs,
+                                                                       unsigned* __restrict__ blob, unsigned* __restrict__ offsets) {
+    __shared__ unsigned part[PACK_THREADS / 64];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const bool copy = g < nstreams;
+    const int b = copy ? streams[g].img : g - nstreams;
+    const int upto = copy ? g : first[b];                  // S(upto)
+    unsigned sum = 0;
+    for (int k = tid; k < upto; k += PACK_THREADS) sum += lengths[k] >> 2;
+    sum = wave_sum(sum);
+    if ((tid & 63) == 0) part[tid >> 6] = sum;
+    __syncthreads();
+    unsigned S = 0;
+#pragma unroll
+    for (int k = 0; k < PACK_THREADS / 64; ++k) S += part[k];
+    if (copy) {
+        const unsigned n = lengths[g] >> 2;
+        const unsigned* src = workspace + (size_t)g * (npix + 2) + (npix + 2 - n);
+        unsigned* dst = blob + (size_t)b + 1 + first[b + 1] + S;
+        for (unsigned k = tid; k < n; k += PACK_THREADS) dst[k] = src[k];
+    } else {
+        const size_t w0 = (size_t)b + first[b] + S;
+        if (tid == 0) offsets[b] = (unsigned)(w0 * 4);
+        if (b < npairs) {
+            const int f0 = first[b], n = first[b + 1] - f0;
+            if (tid == 0) blob[w0] = (unsigned)n;
+            for (int k = tid; k < n; k += PACK_THREADS) blob[w0 + 1 + k] = lengths[f0 + k];
+        }
+    }
+}
+
 }  // namespace
+
+// The encoder's coder and framing on the device (include/masic_hip.h).
+extern "C" size_t masic_rans_encode_batch_workspace_bytes(int nstreams, int npix) {
+    if (nstreams < 0 || npix < 0) return 0;
+    return (size_t)nstreams * ((size_t)npix + 2) * sizeof(uint32_t);
+}
+
+extern "C" size_t masic_rans_pack_pairs_bound(int nstreams, int npix, int npairs) {
+    if (nstreams < 0 || npix < 0 || npairs < 0) return 0;
+    return ((size_t)npairs + (size_t)nstreams + (size_t)nstreams * ((size_t)npix + 2)) * sizeof(uint32_t);
+}
+
+extern "C" int masic_rans_encode_channels_batch(const int32_t* start_freq, const masic_code_stream_t* streams, int nstreams, int npix,
+                                                void* workspace, uint32_t* lengths, int32_t* err_flags, void* stream) {
+    MASIC_REQUIRE(nstreams >= 0 && npix >= 0, MASIC_ERR_SHAPE, "rans_encode_channels_batch: nstreams=%d npix=%d", nstreams, npix);
+    if (nstreams == 0) return MASIC_OK;
+    MASIC_REQUIRE(start_freq && streams && workspace && lengths && err_flags, MASIC_ERR_ARG, "rans_encode_channels_batch: null pointer");
+    hipLaunchKernelGGL(rans_encode_channels_kernel, dim3((nstreams + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const int2*)start_freq, streams,
+                       nstreams, npix, (unsigned*)workspace, (unsigned*)lengths, (int*)err_flags);
+    return masic_launch_status("rans_encode_channels_batch");
+}
+
+extern "C" int masic_rans_pack_pairs_batch(const void* workspace, const uint32_t* lengths, const masic_code_stream_t* streams, int nstreams, int npix,
+                                           const int32_t* first, int npairs, void* blob, uint32_t* offsets, void* stream) {
+    MASIC_REQUIRE(nstreams >= 0 && npix >= 0 && npairs >= 1, MASIC_ERR_SHAPE, "rans_pack_pairs_batch: nstreams=%d npix=%d npairs=%d", nstreams, npix, npairs);
+    MASIC_REQUIRE(first && blob && offsets && (nstreams == 0 || (workspace && lengths && streams)), MASIC_ERR_ARG, "rans_pack_pairs_batch: null pointer");
+    MASIC_REQUIRE(masic_rans_pack_pairs_bound(nstreams, npix, npairs) < ((size_t)1 << 32), MASIC_ERR_UNSUPPORTED,
+                  "rans_pack_pairs_batch: the blobs of %d streams of %d symbols may pass 4 GiB (32-bit offsets)", nstreams, npix);
+    hipLaunchKernelGGL(rans_pack_pairs_kernel, dim3(nstreams + npairs + 1), dim3(PACK_THREADS), 0, (hipStream_t)stream, (const unsigned*)workspace,
+                       lengths, streams, nstreams, npix, (const int*)first, npairs, (unsigned*)blob, (unsigned*)offsets);
+    return masic_launch_status("rans_pack_pairs_batch");
+}
 
 // Device side of a coding step over B pairs (include/masic_hip.h): masic_gmm_cdf_rows_batch builds the tables of step *step (or, without
 // a step, of the whole list: the encoder's one pass), masic_rans_decode_step_batch decodes the step's symbols into the latent and
