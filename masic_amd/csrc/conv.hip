@@ -963,6 +963,106 @@ __global__ __launch_bounds__(256) void conv5s1_small(const Conv5s1Args a, const 
     }
 }
 
+// The pair form (6 -> 3, two 3-channel sources) of conv5s1_small<4> for W % 4 == 0 and 16-byte aligned tensors, same bits:
+// a 64x16 output tile per workgroup, lane (tx, ty) owns the four adjacent pixels 4tx .. 4tx+3 of row ty.  Per channel LDS holds
+// 20 rows of 72 floats (image columns tile_x*64 - 4 .. + 67: origin and pitch are 16-byte multiples), staged in 16-byte DMA
+// pieces that are wholly inside or wholly outside the image; an outside piece gets an out-of-range buffer offset and lands
+// as +0.0f.  A channel is 360 pieces, padded to 6 wave-instructions (384), so that one instruction has one source tensor.
+// Per (ci, kh) a lane reads its 8-float window once and keeps it for the five kw and its four pixels; outputs (o0, o1) are
+// one packed FMA, o2 a scalar one (the pack's fourth weight is zero and is not multiplied).  Every output's chain is
+// fmaf(x, w, acc) from 0.0f in the order ci, kh, kw, then + bias: what conv5s1_small<4> computes.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256, 4) void conv5s1_pair_rows(const Conv5s1Args a, const float* __restrict__ wpk) {
+    constexpr int TW = 64, TH = 16, LP = TW + 8, LR = TH + 4, RP = LP / 4, PCS = LR * RP, PSZ = 6 * 256;   // 360 pieces in 6 x 64
+    constexpr int OOR = 0x7ffffff0;     // past every descriptor's range (the launcher keeps 3 planes below it): reads as zero
+    __shared__ __attribute__((aligned(16))) float lds[6 * PSZ];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // a wave takes rows 2w, 2w+8, 2w+1, 2w+9: eight rows are 576 floats = 9 x 64 banks, so the 16-lane runs of rows r and r+8
+    // that share a ds_read_b128 lane group ({0-3, 12-15, 20-27}, ...) read disjoint banks
+    const int tx = tid & 15, ty = wave * 2 + ((tid >> 5) & 1) + ((tid >> 4) & 1) * 8;
+    const int tile_x = blockIdx.x % a.tiles_w, tile_y = blockIdx.x / a.tiles_w;
+    const int b = blockIdx.y;
+    const size_t plane = (size_t)a.H * a.W;
+    const float* srca = a.x + (size_t)b * 3 * plane;
+    const float* srcb = a.xb + (size_t)b * 3 * plane;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int cg = k * 4 + wave;                    // 36 wave-instructions: channel cg / 6, pieces (cg % 6) * 64 + lane
+        const int ci = cg / 6, g = cg - ci * 6;
+        const int e = g * 64 + lane;
+        const int pr = e / RP, pc = e - pr * RP;
+        const int ih = tile_y * TH - 2 + pr, iw = tile_x * TW - 4 + pc * 4;
+        const bool ok = e < PCS && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W;
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)(ci < 3 ? srca : srcb), 0, (int)(3 * plane * 4), 0x00020000);
+        const int c3 = ci < 3 ? ci : ci - 3;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(lds + cg * 256), 16,
+                                                 ok ? ((c3 * a.H + ih) * a.W + iw) * 4 : OOR, 0, 0, 0);
+    }
+    __syncthreads();
+    if (a.gin_beta != nullptr) {            // (I)GDN of the first three channels, per staged pixel (zero padding stays zero)
+        for (int e = tid; e < PCS; e += 256) {
+            f32x4 p[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p[c] = *reinterpret_cast<const f32x4*>(lds + c * PSZ + e * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float v[3] = {p[0][j], p[1][j], p[2][j]};
+                gdn3(v, a.gin_beta, a.gin_gamma, a.gin_inverse, a.beta_bound, a.gamma_bound, a.pedestal);
+                p[0][j] = v[0]; p[1][j] = v[1]; p[2][j] = v[2];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(lds + c * PSZ + e * 4) = p[c];
+        }
+        __syncthreads();
+    }
+    f32x2 acc01[4];
+    float acc2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { acc01[j] = f32x2{0.0f, 0.0f}; acc2[j] = 0.0f; }
+    const float* base = lds + ty * LP + tx * 4;
+    for (int ci = 0; ci < 6; ++ci) {
+        const float* w = wpk + ci * 100;
+        const float* pl = base + ci * PSZ;
+#pragma unroll
+        for (int kh = 0; kh < 5; ++kh) {
+            // LDS columns 4tx+2 .. 4tx+9 of row ty+kh: pixel j's tap kw is element j + kw.  Three 16-byte reads (conflict-free
+            // with the row assignment above, 4 LDS cycles each).  The empty asm keeps the compiler from narrowing the two end
+            // reads to their used halves and merging those into a ds_read2_b64 (8 cycles, two-way conflicts tx / tx + 8)
+            f32x4 lo = *reinterpret_cast<const f32x4*>(pl + kh * LP);
+            const f32x4 mid = *reinterpret_cast<const f32x4*>(pl + kh * LP + 4);
+            f32x4 hi = *reinterpret_cast<const f32x4*>(pl + kh * LP + 8);
+            asm("" : "+v"(lo), "+v"(hi));
+            const float win[8] = {lo[2], lo[3], mid[0], mid[1], mid[2], mid[3], hi[0], hi[1]};
+#pragma unroll
+            for (int kw = 0; kw < 5; ++kw) {
+                const f32x2 w01 = *reinterpret_cast<const f32x2*>(w + (kh * 5 + kw) * 4);
+                const float w2 = w[(kh * 5 + kw) * 4 + 2];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float xv = win[j + kw];
+                    acc01[j] = __builtin_elementwise_fma(f32x2{xv, xv}, w01, acc01[j]);
+                    acc2[j] = fmaf(xv, w2, acc2[j]);
+                }
+            }
+        }
+    }
+    const int oy = tile_y * TH + ty, ox = tile_x * TW + tx * 4;
+    if (oy >= a.H || ox >= a.W) return;     // W % 4 == 0: a strip of four pixels is never ragged
+    f32x4 out[3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float v[3] = {acc01[j][0] + (a.bias ? a.bias[0] : 0.0f), acc01[j][1] + (a.bias ? a.bias[1] : 0.0f), acc2[j] + (a.bias ? a.bias[2] : 0.0f)};
+        if (a.gout_beta != nullptr) gdn3(v, a.gout_beta, a.gout_gamma, a.gout_inverse, a.beta_bound, a.gamma_bound, a.pedestal);
+        out[0][j] = v[0]; out[1][j] = v[1]; out[2][j] = v[2];
+    }
+    float* yb = a.y + (size_t)b * 3 * plane + (size_t)oy * a.W + ox;
+#pragma unroll
+    for (int o = 0; o < 3; ++o) *reinterpret_cast<f32x4*>(yb + (size_t)o * plane) = out[o];
+}
+
 // [ci][kh][kw][CO]; the transposed layer's taps are flipped so that the kernel correlates
 __global__ void pack_conv5s1_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cin, int Cout, int transposed, int CO) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1203,6 +1303,15 @@ extern "C" int masic_conv5s1_pair_fwd(const float* xa, const float* xb, const fl
     Conv5s1Args a{xa, bias, nullptr, nullptr, y, 6, H, W, 3, 0, 3, 3, 0, MASIC_ACT_NONE, ceil_div(W, 16), 0, 0,
                   xb, 3, gin_beta, gin_gamma, gin_inverse, gout_beta, gout_gamma, gout_inverse,
                   (float)__builtin_sqrt(beta_min + ped), (float)__builtin_sqrt(ped), (float)ped};
-    hipLaunchKernelGGL(conv5s1_small<4>, dim3(ceil_div(W, 16) * ceil_div(H, 16), B), dim3(256), 0, (hipStream_t)stream, a, (const float*)w_packed);
+    // conv5s1_pair_rows stages and stores in 16-byte pieces (plane rows and tensors 16-byte aligned) and addresses a source's
+    // three planes by 32-bit buffer offsets below its out-of-range offset; every other call keeps conv5s1_small<4>
+    const bool rows = W % 4 == 0 && (((uintptr_t)xa | (uintptr_t)xb | (uintptr_t)w_packed | (uintptr_t)y) & 15) == 0 &&
+                      (size_t)3 * H * W * 4 <= (size_t)0x7ffffff0;
+    if (rows) {
+        a.tiles_w = ceil_div(W, 64);
+        hipLaunchKernelGGL(conv5s1_pair_rows, dim3(ceil_div(W, 64) * ceil_div(H, 16), B), dim3(256), 0, (hipStream_t)stream, a, (const float*)w_packed);
+    } else {
+        hipLaunchKernelGGL(conv5s1_small<4>, dim3(ceil_div(W, 16) * ceil_div(H, 16), B), dim3(256), 0, (hipStream_t)stream, a, (const float*)w_packed);
+    }
     return masic_launch_status("conv5s1_pair_fwd");
 }
