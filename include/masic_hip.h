@@ -147,7 +147,14 @@ int masic_gemm_f16k_group_fwd(const masic_gemm_group_t* groups, int ngroups, int
  *   masic_conv_f16k_supported    1 when the layer shape has a configuration (Cout >= 64, Cin >= 16, ...), else 0
  *   masic_conv_f16k_packed_bytes / _pack_weight   [phase-tap][ci/16][co][16] bf16 weights for this path */
 int masic_conv_f16k_supported(const masic_conv_desc_t* d);
-int masic_conv_f16k_kernel_name(const masic_conv_desc_t* d, int gdn, char* buf, size_t n);   /* symbol as rocprofv3 prints it */
+/* masic_conv_f16k_kernel_name: the symbol, as rocprofv3 prints it, of the kernel that runs the layer in the form `flags` names;
+ * MASIC_ERR_UNSUPPORTED where the forward call of that form would refuse the layer (fused GDN with Cout != 128 or an activation,
+ * the multi-output form on any other configuration than its own, ...). */
+#define MASIC_F16K_GDN 1       /* fused (I)GDN epilogue (masic_conv_f16k_gdn_fwd with gdn_packed) */
+#define MASIC_F16K_NOSPLIT 2   /* the forms whose co-block is never split: _d2s_fwd, _few_fwd, an fp8 output of masic_conv_f8k_fwd */
+#define MASIC_F16K_MULTI 4     /* masic_conv_f16k_multi_fwd: conv_f16k_multi<NM> */
+int masic_conv_f16k_kernel_name(const masic_conv_desc_t* d, int flags, char* buf, size_t n);
+int masic_conv_f16k_row_name(int row, char* buf, size_t n);   /* every compiled conv_f16k / conv_f16k_multi symbol: rows 0 .., MASIC_ERR_ARG past the last */
 size_t masic_conv_f16k_packed_bytes(const masic_conv_desc_t* d);
 int masic_conv_f16k_pack_weight(const float* w, void* w_packed, const masic_conv_desc_t* d, void* stream);
 /* Batched packing (a training step re-packs every weight it touches, each for its forward and for its input gradient):

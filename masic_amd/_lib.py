@@ -15,6 +15,7 @@ EB_PARAMS_PER_CHANNEL = 58
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SOFTMAX_C = 0, 1, 2, 3
 INOP_NONE, INOP_ABS, INOP_ROUND = 0, 1, 2
 PREC_F32, PREC_BF16, PREC_FP8 = 0, 1, 2
+F16K_GDN, F16K_NOSPLIT, F16K_MULTI = 1, 2, 4      # masic_conv_f16k_kernel_name flags (MASIC_F16K_*)
 SSIM_MS, SSIM_SIZE_AVERAGE, SSIM_NONNEG = 1, 2, 4
 
 
@@ -70,6 +71,7 @@ SIGNATURES = {
     "masic_gemm_f16k_group_fwd": (c_int, [ctypes.POINTER(GemmGroup), c_int, c_int, c_int, _P]),
     "masic_conv_f16k_supported": (c_int, [_P]),
     "masic_conv_f16k_kernel_name": (c_int, [_P, c_int, ctypes.c_char_p, c_size_t]),
+    "masic_conv_f16k_row_name": (c_int, [c_int, ctypes.c_char_p, c_size_t]),
     "masic_conv_f16k_packed_bytes": (c_size_t, [_P]),
     "masic_conv_f16k_pack_weight": (c_int, [_P, _P, _P, _P]),
     "masic_conv_f16k_pack_job_bytes": (c_size_t, []),

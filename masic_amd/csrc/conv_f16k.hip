@@ -1500,75 +1500,166 @@ F16kCfg choose_f16k(const masic_conv_desc_t& d, const ConvGeom* g, int nphase) {
     return c;
 }
 
-// Layers whose grid leaves most of the 256 CUs idle (the 128 -> 192 layer at 64^2 -> 32^2, hyper transforms, context models:
-// 8 ... 128 workgroups): the 128-channel co-block is split over 2 or 4 workgroups of 2 / 1 accumulator tiles each.  The patch and
-// the slab DMA are repeated per workgroup (they come from L2), the MFMA work is not.
-int f16k_msplit(const masic_conv_desc_t& d, const F16kCfg& c, int np, const ConvGeom* g, bool gdn, bool special) {
-    if (d.prec == MASIC_PREC_FP8 || gdn || c.NP != 1 || special || d.Cout < 64) return 1;
-    const int ntiles = ceil_div(g[0].Wp, c.TW) * ceil_div(g[0].Hp, c.TH);
-    const long wgs = (long)ntiles * np * c.ncb * d.B;
-    return wgs <= 64 ? 4 : (wgs <= 160 ? 2 : 1);
+// Raise the dynamic-LDS limit of kernel K once (the flag is K's own), then launch it.
+template <auto K, class... Args>
+void launch_lds(dim3 grid, int block, size_t lds_bytes, hipStream_t st, const Args&... args) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(K, grid, dim3(block), lds_bytes, st, args...);
 }
-int msplit_nm(const masic_conv_desc_t& d, const F16kCfg& c, int np, const ConvGeom* g) { return 4 / f16k_msplit(d, c, np, g, false, false); }
+
+// One row per compiled instantiation of conv_f16k / conv_f16k_multi: its template parameters (what the kernel's name is printed
+// from) and its launcher.  plan_f16k below is the only place a row is chosen; a new instantiation is a new row.
+typedef void (*F16kLaunchFn)(dim3 grid, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti* mo);
+struct F16kRow {
+    int KS, T, D, PSP, L;
+    bool GDN;
+    int NM, NP;
+    bool F8, MULTI;
+    F16kLaunchFn launch;
+};
+template <int KS, int T, int D, int PSP, int L, bool GDN, int NM, int NP, bool F8>
+void f16k_row_launch(dim3 grid, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti*) {
+    launch_lds<conv_f16k<KS, T, D, PSP, L, GDN, NM, NP, F8>>(grid, 512, lds_bytes, st, a);
+}
+template <int NM>
+void f16k_multi_row_launch(dim3 grid, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti* mo) {
+    launch_lds<conv_f16k_multi<NM>>(grid, 512, lds_bytes, st, a, *mo);
+}
+#define F16K_ROW(KS, T, D, PSP, L, GDN, NM, NP, F8) {KS, T, D, PSP, L, GDN, NM, NP, F8, false, f16k_row_launch<KS, T, D, PSP, L, GDN, NM, NP, F8>}
+#define F16K_MULTI_ROW(NM) {1, 5, 2, 6, 1, false, NM, 1, false, true, f16k_multi_row_launch<NM>}
+const F16kRow F16K_ROWS[] = {
+    // strided 5x5, 5 taps per step (NM = 4 / msplit); its multi-output form
+    F16K_ROW(1, 5, 2, 6, 1, true, 4, 1, false),  F16K_ROW(1, 5, 2, 6, 1, false, 1, 1, false),
+    F16K_ROW(1, 5, 2, 6, 1, false, 2, 1, false), F16K_ROW(1, 5, 2, 6, 1, false, 4, 1, false),
+    F16K_MULTI_ROW(1), F16K_MULTI_ROW(2), F16K_MULTI_ROW(4),
+    // other strided convolutions, 4 taps per step
+    F16K_ROW(1, 4, F16K_D, 6, 1, true, 4, 1, false),  F16K_ROW(1, 4, F16K_D, 6, 1, false, 1, 1, false),
+    F16K_ROW(1, 4, F16K_D, 6, 1, false, 2, 1, false), F16K_ROW(1, 4, F16K_D, 6, 1, false, 4, 1, false),
+    // stride-1 walk, 256-pixel tiles (NM = 1: <= 32 output channels)
+    F16K_ROW(2, 2, F16K_D, 4, 2, true, 4, 1, false),  F16K_ROW(2, 2, F16K_D, 4, 2, false, 1, 1, false),
+    F16K_ROW(2, 2, F16K_D, 4, 2, false, 2, 1, false), F16K_ROW(2, 2, F16K_D, 4, 2, false, 4, 1, false),
+    // large stride-1-walk layers: 1024-pixel tiles (<= 32 channels), 512-pixel tiles with 16- / 32-channel chunks
+    F16K_ROW(1, 2, F16K_D, 5, 2, false, 1, 4, false),
+    F16K_ROW(1, 2, F16K_D, 3, 2, true, 4, 2, false), F16K_ROW(1, 2, F16K_D, 3, 2, false, 4, 2, false),
+    F16K_ROW(2, 2, 2, 5, 1, true, 4, 2, false),      F16K_ROW(2, 2, 2, 5, 1, false, 4, 2, false),
+    // lite: 64 / 96 output channels, two workgroups per CU
+    F16K_ROW(2, 2, 1, 3, 1, false, 2, 1, false), F16K_ROW(2, 2, 1, 3, 1, false, 3, 1, false),
+    // fp8 operands
+    F16K_ROW(1, 4, F16K_D, 6, 1, true, 4, 1, true), F16K_ROW(1, 4, F16K_D, 6, 1, false, 4, 1, true),
+    F16K_ROW(2, 2, F16K_D, 4, 2, true, 4, 1, true), F16K_ROW(2, 2, F16K_D, 4, 2, false, 4, 1, true),
+};
+#undef F16K_ROW
+#undef F16K_MULTI_ROW
+
+// Everything a caller needs to pack for, name or launch a layer.  flags: MASIC_F16K_* (include/masic_hip.h).
+struct F16kPlan {
+    const F16kRow* row;           // null: nothing compiled runs this (descriptor, flags)
+    F16kCfg c;                    // geometry, packed and LDS bytes; c.ok: the shape has a configuration at all
+    ConvGeom g[4];
+    int np;                       // phases
+    int msplit, tiles_w, ntiles;
+    dim3 grid;
+};
+
+F16kPlan plan_f16k(const masic_conv_desc_t& d, int flags) {
+    F16kPlan p{};
+    p.np = build_geoms(d, p.g);
+    const F16kCfg& c = p.c = choose_f16k(d, p.g, p.np);
+    const bool gdn = flags & MASIC_F16K_GDN, nosplit = flags & MASIC_F16K_NOSPLIT, multi = flags & MASIC_F16K_MULTI;
+    const bool f8 = d.prec == MASIC_PREC_FP8;
+    if (!c.ok) return p;
+    // the fused GDN contracts one 128-channel block; the multi-output epilogue stands alone and has no activation
+    if (gdn && (d.Cout != 128 || d.act != MASIC_ACT_NONE)) return p;
+    if (multi && (gdn || nosplit || d.act != MASIC_ACT_NONE)) return p;
+    p.tiles_w = ceil_div(p.g[0].Wp, c.TW);
+    p.ntiles = p.tiles_w * ceil_div(p.g[0].Hp, c.TH);
+    // Layers whose grid leaves most of the 256 CUs idle (the 128 -> 192 layer at 64^2 -> 32^2, hyper transforms, context models:
+    // 8 ... 128 workgroups): the 128-channel co-block is split over 2 or 4 workgroups of 2 / 1 accumulator tiles each.  The patch and
+    // the slab DMA are repeated per workgroup (they come from L2), the MFMA work is not.
+    p.msplit = 1;
+    if (!f8 && !gdn && !nosplit && c.NP == 1 && d.Cout >= 64) {
+        const long wgs = (long)p.ntiles * p.np * c.ncb * d.B;
+        p.msplit = wgs <= 64 ? 4 : (wgs <= 160 ? 2 : 1);
+    }
+    p.grid = dim3(round_up(p.ntiles, 8) * p.np, c.ncb * p.msplit, d.B);
+    // accumulator tiles per wave: the lite rows hold exactly Cout / 32, a stride-1 walk to <= 32 channels one, the rest 4 / msplit
+    const int nm = c.D == 1 ? d.Cout / 32 : ((c.T == 2 && d.Cout <= 32) ? 1 : 4 / p.msplit);
+    for (const F16kRow& r : F16K_ROWS)
+        if (r.KS == c.KS && r.T == c.T && r.D == c.D && r.L == c.L && r.NP == c.NP && r.NM == nm && r.GDN == gdn && r.F8 == f8 && r.MULTI == multi) {
+            p.row = &r;
+            break;
+        }
+    return p;
+}
+
+// the symbol of a row's kernel as rocprofv3 prints it
+void f16k_row_name(const F16kRow& r, char* buf, size_t n) {
+    if (r.MULTI) snprintf(buf, n, "conv_f16k_multi<%d>", r.NM);
+    else snprintf(buf, n, "conv_f16k<%d, %d, %d, %d, %d, %s, %d, %d, %s>", r.KS, r.T, r.D, r.PSP, r.L, r.GDN ? "true" : "false", r.NM, r.NP, r.F8 ? "true" : "false");
+}
 
 }  // namespace
 
-extern "C" int masic_conv_f16k_supported(const masic_conv_desc_t* d) {
-    if (check_desc(d) != MASIC_OK) return 0;
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    return choose_f16k(*d, g, np).ok;
+extern "C" int masic_conv_f16k_supported(const masic_conv_desc_t* d) { return check_desc(d) == MASIC_OK && plan_f16k(*d, 0).row != nullptr; }
+
+extern "C" int masic_conv_f16k_multi_supported(const masic_conv_desc_t* d) {
+    return check_desc(d) == MASIC_OK && plan_f16k(*d, MASIC_F16K_MULTI).row != nullptr;
 }
 
-extern "C" int masic_conv_f16k_kernel_name(const masic_conv_desc_t* d, int gdn, char* buf, size_t n) {
+extern "C" int masic_conv_f16k_kernel_name(const masic_conv_desc_t* d, int flags, char* buf, size_t n) {
     int rc = check_desc(d);
     if (rc != MASIC_OK) return rc;
-    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "conv_f16k_kernel_name: null buffer");
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const F16kCfg c = choose_f16k(*d, g, np);
-    MASIC_REQUIRE(c.ok, MASIC_ERR_UNSUPPORTED, "conv_f16k: layer shape has no F16K configuration");
-    const int nm = (d->Cout <= 32 && !gdn) ? 1 : 4;
-    if (d->prec == MASIC_PREC_FP8) snprintf(buf, n, "conv_f16k<%d, %d, %d, %d, %d, %s, 4, 1, true>", c.KS, c.T, F16K_D, c.KS == 1 ? 6 : 4, c.L, gdn ? "true" : "false");
-    else if (c.D == 1) snprintf(buf, n, "conv_f16k<2, 2, 1, 3, 1, false, %d, 1, false>", d->Cout <= 32 ? 1 : (d->Cout <= 64 ? 2 : 3));
-    else if (c.NP == 2 && c.KS == 2) snprintf(buf, n, "conv_f16k<2, 2, 2, 5, 1, %s, 4, 2, false>", gdn ? "true" : "false");
-    else if (c.NP > 1) snprintf(buf, n, "conv_f16k<1, 2, %d, %d, 2, %s, %d, %d, false>", F16K_D, c.NP == 4 ? 5 : 3, gdn ? "true" : "false", nm, c.NP);
-    else if (c.KS == 1) snprintf(buf, n, "conv_f16k<1, %d, %d, 6, 1, %s, %d, 1, false>", c.T, c.D, gdn ? "true" : "false", gdn ? 4 : msplit_nm(*d, c, np, g));
-    else snprintf(buf, n, "conv_f16k<2, 2, %d, 4, 2, %s, %d, 1, false>", F16K_D, gdn ? "true" : "false", (gdn || nm == 1) ? nm : msplit_nm(*d, c, np, g));
+    MASIC_REQUIRE(buf && n > 0 && (flags & ~(MASIC_F16K_GDN | MASIC_F16K_NOSPLIT | MASIC_F16K_MULTI)) == 0, MASIC_ERR_ARG,
+                  "conv_f16k_kernel_name: null buffer or unknown flag");
+    const F16kRow* r = plan_f16k(*d, flags).row;
+    MASIC_REQUIRE(r != nullptr, MASIC_ERR_UNSUPPORTED, "conv_f16k: no kernel runs this layer shape in this form");
+    f16k_row_name(*r, buf, n);
+    return MASIC_OK;
+}
+
+// the table itself, for tests and tools: the name of row `row`, MASIC_ERR_ARG past the last one
+extern "C" int masic_conv_f16k_row_name(int row, char* buf, size_t n) {
+    if (!buf || n == 0 || row < 0 || row >= (int)(sizeof(F16K_ROWS) / sizeof(F16K_ROWS[0]))) return MASIC_ERR_ARG;
+    f16k_row_name(F16K_ROWS[row], buf, n);
     return MASIC_OK;
 }
 
 extern "C" size_t masic_conv_f16k_packed_bytes(const masic_conv_desc_t* d) {
     if (check_desc(d) != MASIC_OK) return 0;
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const F16kCfg c = choose_f16k(*d, g, np);
-    return c.ok ? c.packed_bytes : 0;
+    const F16kPlan p = plan_f16k(*d, 0);
+    return p.row ? p.c.packed_bytes : 0;
 }
 
 namespace {
+// The packing kernels' arguments for the layer; nb: blocks for the largest (phase, all co-blocks) stream of `unit`-byte elements.
+int pack_stream_args(const masic_conv_desc_t* d, const float* w, int unit, PackStreamArgs& a, int& nb, int& np) {
+    const F16kPlan p = plan_f16k(*d, 0);
+    MASIC_REQUIRE(p.row != nullptr, MASIC_ERR_UNSUPPORTED, "conv_f16k: layer shape has no F16K configuration");
+    const F16kCfg& c = p.c;
+    a = PackStreamArgs{w, d->Cin, d->Cout, d->KH, d->KW, d->transposed, c.KS, c.T, c.Cin16 / c.KS, c.ncb, {}, {}};
+    size_t tot = 0;
+    for (int i = 0; i < p.np; ++i) {
+        a.gs[i] = p.g[i];
+        a.phase_offs[i] = c.phase_off[i];
+        const size_t t = (size_t)c.stream_bytes[i] / unit * c.ncb;
+        tot = tot > t ? tot : t;
+    }
+    nb = (int)((tot + 255) / 256);
+    if (nb > 8192) nb = 8192;
+    np = p.np;
+    return MASIC_OK;
+}
+
 int pack_stream_job(const float* w, void* w_packed, const masic_conv_desc_t* d, PackStreamJob& j) {
     int rc = check_desc(d);
     if (rc != MASIC_OK) return rc;
     MASIC_REQUIRE(w && w_packed, MASIC_ERR_ARG, "conv_f16k_pack_weight: null pointer");
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const F16kCfg c = choose_f16k(*d, g, np);
-    MASIC_REQUIRE(c.ok, MASIC_ERR_UNSUPPORTED, "conv_f16k: layer shape has no F16K configuration");
-    j.a = PackStreamArgs{w, d->Cin, d->Cout, d->KH, d->KW, d->transposed, c.KS, c.T, c.Cin16 / c.KS, c.ncb, {}, {}};
-    size_t tot = 0;
-    for (int p = 0; p < np; ++p) {
-        j.a.gs[p] = g[p];
-        j.a.phase_offs[p] = c.phase_off[p];
-        const size_t t = (size_t)c.stream_bytes[p] / 2 * c.ncb;
-        tot = tot > t ? tot : t;
-    }
-    int nb = (int)((tot + 255) / 256);
-    if (nb > 8192) nb = 8192;
     j.wp = (unsigned short*)w_packed;
-    j.nb = nb;
-    j.np = np;
-    return MASIC_OK;
+    return pack_stream_args(d, w, 2, j.a, j.nb, j.np);
 }
 }  // namespace
 
@@ -1603,11 +1694,90 @@ extern "C" int masic_conv_f16k_pack_jobs_run(const void* jobs_dev, int njobs, in
 }
 
 namespace {
-int f16k_launch(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
-                const void* gdn_packed, int gdn_inverse, int d2s, float* y_nchw, void* y_f16k,
-                const masic_conv_desc_t* d, void* stream, const float* wscale = nullptr, void* y_f8k = nullptr, float out_inv_scale = 0.0f,
-                const void* res1 = nullptr, const void* res2 = nullptr, int res_ctot = 0, const float* res32 = nullptr, int cout_store = 0,
-                void* y_pre = nullptr, const void* mask16 = nullptr, float mask_slope = 0.0f, const F16kMulti* multi = nullptr);
+// What an entry point asks of f16k_launch: zero-initialised, then filled by field name.
+struct F16kLaunch {
+    const void* x;                // F16K (F8K with fp8 operands) input, packed weights
+    const void* w;
+    const float* bias;
+    const float* gate;
+    float* y_nchw;                // exactly one of the three outputs -- none with `multi`
+    void* y_f16k;
+    void* y_f8k;
+    float out_inv_scale;          // fp8 output: 1 / scale of the produced tensor
+    const float* wscale;          // fp8 operands: dequantisation scales
+    const void* gdn;              // fused (I)GDN: packed parameters, flags
+    int gdn_inverse;
+    const void* res1;             // F16K output: residuals, act'(mask) factor, the value before the adds (res_ctot channels each)
+    const void* res2;
+    const void* mask;
+    float mask_slope;
+    void* y_pre;
+    int res_ctot;
+    const float* res32;           // few-channel form: float32 residual, channels stored
+    int cout_store;
+    int d2s_c, d2s_ctot, d2s_coff;  // depth-to-space form: real channels (> 0 selects it), channel view of y_nchw
+    const F16kMulti* multi;
+};
+
+int f16k_launch(const F16kLaunch& l, const masic_conv_desc_t* d, void* stream) {
+    int rc = check_desc(d);
+    if (rc != MASIC_OK) return rc;
+    const bool f8 = d->prec == MASIC_PREC_FP8, d2s = l.d2s_c > 0;
+    const int cblk = f8 ? 32 : 16;
+    MASIC_REQUIRE(l.x && l.w && ((l.y_nchw != nullptr) + (l.y_f16k != nullptr) + (l.y_f8k != nullptr) == (l.multi ? 0 : 1)), MASIC_ERR_ARG,
+                  "conv_f16k_fwd: need input, weights and exactly one output");
+    MASIC_REQUIRE(l.y_f8k == nullptr || (d->out_ctot % 32 == 0 && d->out_coff % 32 == 0 && l.gate == nullptr && !d2s), MASIC_ERR_SHAPE,
+                  "conv_f16k: an fp8 output needs a 32-aligned channel view and no gate");
+    MASIC_REQUIRE(!f8 || (l.wscale != nullptr && !d2s), MASIC_ERR_ARG, "conv_f16k: fp8 operands need the dequantisation scales");
+    // the depth-to-space, few-channel and fp8-output epilogues are not compiled for a split co-block
+    const int flags = (l.gdn ? MASIC_F16K_GDN : 0) | ((d2s || l.cout_store != 0 || l.y_f8k) ? MASIC_F16K_NOSPLIT : 0) | (l.multi ? MASIC_F16K_MULTI : 0);
+    const F16kPlan p = plan_f16k(*d, flags);
+    const F16kCfg& c = p.c;
+    MASIC_REQUIRE(c.ok, MASIC_ERR_UNSUPPORTED, "conv_f16k: layer shape has no F16K configuration");
+    MASIC_REQUIRE(d->in_ctot % cblk == 0 && d->in_coff % cblk == 0, MASIC_ERR_SHAPE, "conv_f16k: input channel view must be 16-aligned (32 for fp8)");
+    MASIC_REQUIRE(l.y_f16k == nullptr || (d->out_ctot % 16 == 0 && d->out_coff % 16 == 0 && d->Cout % 4 == 0 && (l.gate == nullptr || l.gdn == nullptr)),
+                  MASIC_ERR_SHAPE, "conv_f16k: F16K output needs a 16-aligned channel view and Cout % 4 == 0 (a gate only without the fused GDN)");
+    MASIC_REQUIRE(p.row != nullptr && (l.gdn == nullptr || l.gate == nullptr), MASIC_ERR_UNSUPPORTED,
+                  "conv_f16k: the fused GDN needs Cout = 128, no activation and no gate; only the strided 5x5 bf16 configuration has the "
+                  "multi-output epilogue");
+    if (p.g[0].Hp <= 0 || p.g[0].Wp <= 0) return MASIC_OK;
+    F16kArgs a{};
+    a.x = (const unsigned short*)l.x, a.w = (const unsigned short*)l.w, a.bias = l.bias, a.gate = l.gate;
+    a.y32 = l.y_nchw, a.y16 = (unsigned short*)l.y_f16k, a.y8 = (unsigned char*)l.y_f8k, a.out_inv_scale = l.out_inv_scale;
+    a.gdn_img = (const uint4*)l.gdn, a.gdn_inverse = l.gdn_inverse, a.wscale = l.wscale, a.stamps = g_f16k_stamps;
+    a.res1 = (const unsigned short*)l.res1, a.res2 = (const unsigned short*)l.res2, a.res_ctot = l.res_ctot;
+    a.y16_pre = (unsigned short*)l.y_pre, a.mask16 = (const unsigned short*)l.mask, a.mask_slope = l.mask_slope;
+    a.res32 = l.res32, a.cout_store = l.cout_store > 0 ? l.cout_store : d->Cout, a.d2s = l.d2s_c;
+    a.in_c16tot = d->in_ctot / cblk, a.in_c16off = d->in_coff / cblk, a.Cin16 = c.Cin16;
+    a.Hi = d->Hi, a.Wi = d->Wi, a.Cout = d->Cout, a.Ho = d->Ho, a.Wo = d->Wo;
+    a.out_ctot = d2s ? l.d2s_ctot : (l.cout_store > 0 ? l.cout_store : d->out_ctot);
+    a.out_coff = d2s ? l.d2s_coff : d->out_coff;
+    a.gate_ctot = d->gate_ctot, a.gate_c = d->gate_c, a.act = d->act;
+    a.TW = c.TW, a.TWlog = c.TWlog, a.SR = c.SR, a.TH = c.TH, a.tiles_w = p.tiles_w, a.ntiles = p.ntiles;
+    a.PH = c.PH, a.PW = c.PW, a.PWh = c.PWh, a.NPIXp = c.NPIXp, a.PB = c.PB;
+    a.mg_PW = (unsigned)((0x100000000ull + c.PW - 1) / c.PW);
+    a.mg_PWh = (unsigned)((0x100000000ull + c.PWh - 1) / c.PWh);
+    a.mg_gpk = (unsigned)((0x100000000ull + c.NPIXp / 32 - 1) / (c.NPIXp / 32));
+    for (int i = 0; i < 4; ++i) a.phase_off[i] = c.phase_off[i], a.stream_bytes[i] = c.stream_bytes[i];
+    a.q = geom_params(*d), a.nphase = p.np, a.xcd_images = d->B % 8 == 0, a.msplit = p.msplit;
+    p.row->launch(p.grid, c.lds_bytes, (hipStream_t)stream, a, l.multi);
+    return masic_launch_status("conv_f16k_fwd");
+}
+}  // namespace
+
+extern "C" int masic_conv_f16k_gdn_fwd(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
+                                       const void* gdn_packed, int gdn_inverse, float* y_nchw, void* y_f16k,
+                                       const masic_conv_desc_t* d, void* stream) {
+    F16kLaunch l{};
+    l.x = x_f16k, l.w = w_packed, l.bias = bias, l.gate = gate;
+    l.gdn = gdn_packed, l.gdn_inverse = gdn_inverse;
+    l.y_nchw = y_nchw, l.y_f16k = y_f16k;
+    return f16k_launch(l, d, stream);
+}
+
+extern "C" int masic_conv_f16k_fwd(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
+                                   float* y_nchw, void* y_f16k, const masic_conv_desc_t* d, void* stream) {
+    return masic_conv_f16k_gdn_fwd(x_f16k, w_packed, bias, gate, nullptr, 0, y_nchw, y_f16k, d, stream);
 }
 
 // Extended residual form for the training step of Independent_EN (masic_amd/autograd.py: EnhancementBlockFn), everything F16K:
@@ -1621,8 +1791,11 @@ extern "C" int masic_conv_f16k_res_ex_fwd(const void* x_f16k, const void* w_pack
     MASIC_REQUIRE(res1 != nullptr || res2 == nullptr, MASIC_ERR_ARG, "conv_f16k_res_ex_fwd: res2 without res1");
     MASIC_REQUIRE((res1 == nullptr && mask == nullptr && y_pre_f16k == nullptr) || (res_ctot % 16 == 0 && res_ctot >= d->Cout), MASIC_ERR_SHAPE,
                   "conv_f16k_res_ex_fwd: residual / mask / pre tensors need >= Cout channels, a multiple of 16");
-    return f16k_launch(x_f16k, w_packed, bias, nullptr, nullptr, 0, 0, nullptr, y_f16k, d, stream, nullptr, nullptr, 0.0f, res1, res2, res_ctot, nullptr, 0,
-                       y_pre_f16k, mask, mask_slope);
+    F16kLaunch l{};
+    l.x = x_f16k, l.w = w_packed, l.bias = bias, l.y_f16k = y_f16k;
+    l.res1 = res1, l.res2 = res2, l.res_ctot = res_ctot;
+    l.mask = mask, l.mask_slope = mask_slope, l.y_pre = y_pre_f16k;
+    return f16k_launch(l, d, stream);
 }
 
 // masic_conv_f16k_gdn_fwd with F16K output that ALSO stores the convolution's result before the GDN (y_pre_f16k, same layout as
@@ -1631,8 +1804,10 @@ extern "C" int masic_conv_f16k_res_ex_fwd(const void* x_f16k, const void* w_pack
 extern "C" int masic_conv_f16k_gdn_dual_fwd(const void* x_f16k, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
                                             void* y_pre_f16k, void* y_f16k, const masic_conv_desc_t* d, void* stream) {
     MASIC_REQUIRE(gdn_packed && y_pre_f16k && y_f16k, MASIC_ERR_ARG, "conv_f16k_gdn_dual_fwd: null pointer");
-    return f16k_launch(x_f16k, w_packed, bias, nullptr, gdn_packed, gdn_inverse, 0, nullptr, y_f16k, d, stream, nullptr, nullptr, 0.0f, nullptr, nullptr, 0,
-                       nullptr, 0, y_pre_f16k);
+    F16kLaunch l{};
+    l.x = x_f16k, l.w = w_packed, l.bias = bias, l.y_f16k = y_f16k;
+    l.gdn = gdn_packed, l.gdn_inverse = gdn_inverse, l.y_pre = y_pre_f16k;
+    return f16k_launch(l, d, stream);
 }
 
 // A layer with few output channels (conv2 of Independent_EN: 96 -> 3, MASIC.py:1492-1496) on the MFMA path: `d` describes the
@@ -1642,7 +1817,10 @@ extern "C" int masic_conv_f16k_few_fwd(const void* x_f16k, const void* w_packed,
                                        int cout_store, const masic_conv_desc_t* d, void* stream) {
     MASIC_REQUIRE(d != nullptr && y_nchw != nullptr && cout_store > 0 && cout_store <= d->Cout && d->Cout == 32 && d->out_coff == 0, MASIC_ERR_ARG,
                   "conv_f16k_few_fwd: needs a 32-channel (zero-padded) descriptor and 0 < cout_store <= 32");
-    return f16k_launch(x_f16k, w_packed, bias, nullptr, nullptr, 0, 0, y_nchw, nullptr, d, stream, nullptr, nullptr, 0.0f, nullptr, nullptr, 0, res32, cout_store);
+    F16kLaunch l{};
+    l.x = x_f16k, l.w = w_packed, l.bias = bias, l.y_nchw = y_nchw;
+    l.res32 = res32, l.cout_store = cout_store;
+    return f16k_launch(l, d, stream);
 }
 
 // F16K in, F16K out (a channel view per d->out_ctot / out_coff) with up to two F16K residual tensors of res_ctot channels added
@@ -1653,7 +1831,10 @@ extern "C" int masic_conv_f16k_res_fwd(const void* x_f16k, const void* w_packed,
     MASIC_REQUIRE(d != nullptr && y_f16k != nullptr, MASIC_ERR_ARG, "conv_f16k_res_fwd: null pointer");
     MASIC_REQUIRE(res1 != nullptr || res2 == nullptr, MASIC_ERR_ARG, "conv_f16k_res_fwd: res2 without res1");
     MASIC_REQUIRE(res1 == nullptr || (res_ctot % 16 == 0 && res_ctot >= d->Cout), MASIC_ERR_SHAPE, "conv_f16k_res_fwd: residual tensors need >= Cout channels, a multiple of 16");
-    return f16k_launch(x_f16k, w_packed, bias, nullptr, nullptr, 0, 0, nullptr, y_f16k, d, stream, nullptr, nullptr, 0.0f, res1, res2, res_ctot);
+    F16kLaunch l{};
+    l.x = x_f16k, l.w = w_packed, l.bias = bias, l.y_f16k = y_f16k;
+    l.res1 = res1, l.res2 = res2, l.res_ctot = res_ctot;
+    return f16k_launch(l, d, stream);
 }
 
 // fp8 (e4m3) operand form (BASELINE configs[4]): d->prec = MASIC_PREC_FP8 -- the input is F8K, weights come from
@@ -1666,7 +1847,11 @@ extern "C" int masic_conv_f8k_fwd(const void* x, const void* w_packed, const flo
     MASIC_REQUIRE(d != nullptr, MASIC_ERR_ARG, "conv_f8k_fwd: null descriptor");
     MASIC_REQUIRE((d->prec == MASIC_PREC_FP8) == (wscale != nullptr), MASIC_ERR_ARG, "conv_f8k_fwd: wscale goes with fp8 operands (prec = MASIC_PREC_FP8)");
     MASIC_REQUIRE(y_f8k == nullptr || out_inv_scale > 0.0f, MASIC_ERR_ARG, "conv_f8k_fwd: an fp8 output needs out_inv_scale > 0");
-    return f16k_launch(x, w_packed, bias, gate, gdn_packed, gdn_inverse, 0, y_nchw, y_f16k, d, stream, wscale, y_f8k, out_inv_scale);
+    F16kLaunch l{};
+    l.x = x, l.w = w_packed, l.wscale = wscale, l.bias = bias, l.gate = gate;
+    l.gdn = gdn_packed, l.gdn_inverse = gdn_inverse;
+    l.y_nchw = y_nchw, l.y_f16k = y_f16k, l.y_f8k = y_f8k, l.out_inv_scale = out_inv_scale;
+    return f16k_launch(l, d, stream);
 }
 
 extern "C" size_t masic_f8k_bytes(int B, int C, int HW) { return (size_t)B * round_up(C, 32) * HW; }
@@ -1675,49 +1860,16 @@ extern "C" int masic_conv_f8k_pack_weight(const float* w, void* w_packed, float*
     int rc = check_desc(d);
     if (rc != MASIC_OK) return rc;
     MASIC_REQUIRE(w && w_packed && wscale && d->prec == MASIC_PREC_FP8, MASIC_ERR_ARG, "conv_f8k_pack_weight: null pointer or prec != MASIC_PREC_FP8");
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const F16kCfg c = choose_f16k(*d, g, np);
-    MASIC_REQUIRE(c.ok, MASIC_ERR_UNSUPPORTED, "conv_f8k: layer shape has no fp8 configuration");
+    PackStreamArgs a;
+    int nb, np;
+    rc = pack_stream_args(d, w, 1, a, nb, np);
+    if (rc != MASIC_OK) return rc;
     hipLaunchKernelGGL(wscale_f8k_kernel, dim3(d->Cout), dim3(256), 0, (hipStream_t)stream, w, wscale, d->Cin, d->Cout, d->KH * d->KW, d->transposed);
-    PackStreamArgs a{w, d->Cin, d->Cout, d->KH, d->KW, d->transposed, c.KS, c.T, c.Cin16 / c.KS, c.ncb, {}, {}};
-    size_t tot = 0;
-    for (int p = 0; p < np; ++p) {
-        a.gs[p] = g[p];
-        a.phase_offs[p] = c.phase_off[p];
-        const size_t t = (size_t)c.stream_bytes[p] * c.ncb;
-        tot = tot > t ? tot : t;
-    }
-    int nb = (int)((tot + 255) / 256);
-    if (nb > 8192) nb = 8192;
     hipLaunchKernelGGL(pack_f8k_stream_kernel, dim3(nb, np), dim3(256), 0, (hipStream_t)stream, a, (const float*)wscale, (unsigned char*)w_packed);
     return masic_launch_status("conv_f8k_pack_weight");
 }
 
-extern "C" int masic_conv_f16k_gdn_fwd(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
-                                       const void* gdn_packed, int gdn_inverse, float* y_nchw, void* y_f16k,
-                                       const masic_conv_desc_t* d, void* stream);
-
-extern "C" int masic_conv_f16k_fwd(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
-                                   float* y_nchw, void* y_f16k, const masic_conv_desc_t* d, void* stream) {
-    return masic_conv_f16k_gdn_fwd(x_f16k, w_packed, bias, gate, nullptr, 0, y_nchw, y_f16k, d, stream);
-}
-
-extern "C" int masic_conv_f16k_gdn_fwd(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
-                                       const void* gdn_packed, int gdn_inverse, float* y_nchw, void* y_f16k,
-                                       const masic_conv_desc_t* d, void* stream) {
-    return f16k_launch(x_f16k, w_packed, bias, gate, gdn_packed, gdn_inverse, 0, y_nchw, y_f16k, d, stream);
-}
-
 // The latent layer of an analysis transform with its result written once, in the layouts its consumers read (include/masic_hip.h).
-extern "C" int masic_conv_f16k_multi_supported(const masic_conv_desc_t* d) {
-    if (check_desc(d) != MASIC_OK || d->prec == MASIC_PREC_FP8 || d->act != MASIC_ACT_NONE || d->Cout % 32 != 0) return 0;
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const F16kCfg c = choose_f16k(*d, g, np);
-    return c.ok && c.NP == 1 && c.KS == 1 && c.T == 5 && c.D == 2;
-}
-
 extern "C" int masic_conv_f16k_multi_fwd(const void* x_f16k, const void* w_packed, const float* bias, const masic_f16k_multi_out_t* out,
                                          const masic_conv_desc_t* d, void* stream) {
     MASIC_REQUIRE(d != nullptr && out != nullptr, MASIC_ERR_ARG, "conv_f16k_multi_fwd: null pointer");
@@ -1731,8 +1883,9 @@ extern "C" int masic_conv_f16k_multi_fwd(const void* x_f16k, const void* w_packe
                   "conv_f16k_multi_fwd: the gate multiplies round16 only; gate channel out of range");
     const F16kMulti mo{out->y32, out->round32, (unsigned short*)out->round16, (unsigned short*)out->abs16, out->gate,
                        out->round16_ctot, out->round16_coff, out->gate_ctot, out->gate_c};
-    return f16k_launch(x_f16k, w_packed, bias, nullptr, nullptr, 0, 0, nullptr, nullptr, d, stream, nullptr, nullptr, 0.0f, nullptr, nullptr, 0, nullptr, 0,
-                       nullptr, nullptr, 0.0f, &mo);
+    F16kLaunch l{};
+    l.x = x_f16k, l.w = w_packed, l.bias = bias, l.multi = &mo;
+    return f16k_launch(l, d, stream);
 }
 
 // ConvTranspose2d(Cin -> C, k5, s2, p2, output_padding 1) weight [Cin][C][5][5] -> the weight [32][Cin][3][3] (+ bias [32]) of the
@@ -1765,136 +1918,11 @@ extern "C" int masic_conv_f16k_d2s_fwd(const void* x_f16k, const void* w_packed,
     MASIC_REQUIRE(d && C > 0 && 4 * C <= 32 && d->Cout == 32 && d->stride == 1 && !d->transposed, MASIC_ERR_UNSUPPORTED,
                   "conv_f16k_d2s: needs a stride-1 convolution to 32 (padded) channels and C <= 8");
     MASIC_REQUIRE(y_coff >= 0 && y_coff + C <= y_ctot, MASIC_ERR_SHAPE, "conv_f16k_d2s: output channel view out of range");
-    return f16k_launch(x_f16k, w_packed, bias, nullptr, nullptr, 0, C | (y_ctot << 8) | (y_coff << 20), y_nchw, nullptr, d, stream);
+    F16kLaunch l{};
+    l.x = x_f16k, l.w = w_packed, l.bias = bias, l.y_nchw = y_nchw;
+    l.d2s_c = C, l.d2s_ctot = y_ctot, l.d2s_coff = y_coff;
+    return f16k_launch(l, d, stream);
 }
-
-namespace {
-int f16k_launch(const void* x_f16k, const void* w_packed, const float* bias, const float* gate,
-                const void* gdn_packed, int gdn_inverse, int d2s, float* y_nchw, void* y_f16k,
-                const masic_conv_desc_t* d, void* stream, const float* wscale, void* y_f8k, float out_inv_scale,
-                const void* res1, const void* res2, int res_ctot, const float* res32, int cout_store, void* y_pre, const void* mask16, float mask_slope,
-                const F16kMulti* multi) {
-    int rc = check_desc(d);
-    if (rc != MASIC_OK) return rc;
-    const bool f8 = d->prec == MASIC_PREC_FP8;
-    const int cblk = f8 ? 32 : 16;
-    MASIC_REQUIRE(x_f16k && w_packed && ((y_nchw != nullptr) + (y_f16k != nullptr) + (y_f8k != nullptr) == (multi ? 0 : 1)), MASIC_ERR_ARG,
-                  "conv_f16k_fwd: need input, weights and exactly one output");
-    MASIC_REQUIRE(y_f8k == nullptr || (d->out_ctot % 32 == 0 && d->out_coff % 32 == 0 && gate == nullptr && d2s == 0), MASIC_ERR_SHAPE,
-                  "conv_f16k: an fp8 output needs a 32-aligned channel view and no gate");
-    MASIC_REQUIRE(!f8 || (wscale != nullptr && d2s == 0), MASIC_ERR_ARG, "conv_f16k: fp8 operands need the dequantisation scales");
-    MASIC_REQUIRE(d->Cout > 32 || d->KH * d->KW > 1, MASIC_ERR_UNSUPPORTED, "conv_f16k: no 1x1 configuration");
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const F16kCfg c = choose_f16k(*d, g, np);
-    MASIC_REQUIRE(c.ok, MASIC_ERR_UNSUPPORTED, "conv_f16k: layer shape has no F16K configuration");
-    MASIC_REQUIRE(d->in_ctot % cblk == 0 && d->in_coff % cblk == 0, MASIC_ERR_SHAPE, "conv_f16k: input channel view must be 16-aligned (32 for fp8)");
-    MASIC_REQUIRE(y_f16k == nullptr || (d->out_ctot % 16 == 0 && d->out_coff % 16 == 0 && d->Cout % 4 == 0 && (gate == nullptr || gdn_packed == nullptr)),
-                  MASIC_ERR_SHAPE, "conv_f16k: F16K output needs a 16-aligned channel view and Cout % 4 == 0 (a gate only without the fused GDN)");
-    MASIC_REQUIRE(gdn_packed == nullptr || (d->Cout == 128 && d->act == MASIC_ACT_NONE && gate == nullptr), MASIC_ERR_UNSUPPORTED,
-                  "conv_f16k: the fused GDN needs Cout = 128, no activation and no gate");
-    if (g[0].Hp <= 0 || g[0].Wp <= 0) return MASIC_OK;
-    const int tiles_w = ceil_div(g[0].Wp, c.TW), ntiles = tiles_w * ceil_div(g[0].Hp, c.TH);
-    F16kArgs a{(const unsigned short*)x_f16k, (const unsigned short*)w_packed, bias, gate, y_nchw, (unsigned short*)y_f16k,
-               (const uint4*)gdn_packed, (const unsigned short*)res1, (const unsigned short*)res2, res_ctot, (unsigned short*)y_pre, g_f16k_stamps, (const unsigned short*)mask16, mask_slope, res32, cout_store > 0 ? cout_store : d->Cout, wscale, (unsigned char*)y_f8k, out_inv_scale, gdn_inverse, d2s & 0xff, d->in_ctot / cblk, d->in_coff / cblk, c.Cin16,
-               d->Hi, d->Wi, d->Cout, d->Ho, d->Wo, d2s ? ((d2s >> 8) & 0xfff) : (cout_store > 0 ? cout_store : d->out_ctot), d2s ? (d2s >> 20) : d->out_coff,
-               d->gate_ctot, d->gate_c, d->act,
-               c.TW, c.TWlog, c.SR, c.TH, tiles_w, ntiles,
-               c.PH, c.PW, c.PWh, c.NPIXp, c.PB,
-               (unsigned)((0x100000000ull + c.PW - 1) / c.PW), (unsigned)((0x100000000ull + c.PWh - 1) / c.PWh),
-               (unsigned)((0x100000000ull + c.NPIXp / 32 - 1) / (c.NPIXp / 32)),
-               {c.phase_off[0], c.phase_off[1], c.phase_off[2], c.phase_off[3]},
-               {c.stream_bytes[0], c.stream_bytes[1], c.stream_bytes[2], c.stream_bytes[3]}, geom_params(*d), np, d->B % 8 == 0, 1};
-    const int msplit = f16k_msplit(*d, c, np, g, gdn_packed != nullptr, d2s != 0 || cout_store != 0 || y_f8k != nullptr);
-    a.msplit = msplit;
-    dim3 grid(round_up(ntiles, 8) * np, c.ncb * msplit, d->B);
-    hipStream_t st = (hipStream_t)stream;
-#define F16K_LAUNCH_D(KSV, TV, DV, PSPV, LV, GDNV, NMV, NPV)                                                                   \
-    do {                                                                                                             \
-        auto kfn = conv_f16k<KSV, TV, DV, PSPV, LV, GDNV, NMV, NPV>;                                                         \
-        static bool attr_set = false;                                                                                \
-        if (!attr_set) {                                                                                             \
-            (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-            attr_set = true;                                                                                         \
-        }                                                                                                            \
-        hipLaunchKernelGGL(kfn, grid, dim3(512), c.lds_bytes, st, a);                                                \
-    } while (0)
-#define F16K_LAUNCH(KSV, TV, PSPV, LV, GDNV, NMV, NPV) F16K_LAUNCH_D(KSV, TV, F16K_D, PSPV, LV, GDNV, NMV, NPV)
-    MASIC_REQUIRE(c.NP == 1 || (d->Cout <= 32) == (c.NP == 4), MASIC_ERR_UNSUPPORTED, "conv_f16k: tile configuration");
-#define F8K_LAUNCH(KSV, TV, PSPV, LV, GDNV)                                                                          \
-    do {                                                                                                             \
-        auto kfn = conv_f16k<KSV, TV, F16K_D, PSPV, LV, GDNV, 4, 1, true>;                                           \
-        static bool attr_set = false;                                                                                \
-        if (!attr_set) {                                                                                             \
-            (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-            attr_set = true;                                                                                         \
-        }                                                                                                            \
-        hipLaunchKernelGGL(kfn, grid, dim3(512), c.lds_bytes, st, a);                                                \
-    } while (0)
-    if (multi) {
-        // the one configuration the multi-output epilogue is compiled for (the 128 -> 192 latent layer); anything else is the caller's
-        // cue to keep the separate launches
-        MASIC_REQUIRE(!f8 && c.NP == 1 && c.KS == 1 && c.T == 5 && c.D == 2 && gdn_packed == nullptr, MASIC_ERR_UNSUPPORTED,
-                      "conv_f16k_multi: only the strided 5x5 bf16 configuration has the multi-output epilogue");
-#define F16K_LAUNCH_MULTI(NMV)                                                                                       \
-    do {                                                                                                             \
-        auto kfn = conv_f16k_multi<NMV>;                                                                             \
-        static bool attr_set = false;                                                                                \
-        if (!attr_set) {                                                                                             \
-            (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-            attr_set = true;                                                                                         \
-        }                                                                                                            \
-        hipLaunchKernelGGL(kfn, grid, dim3(512), c.lds_bytes, st, a, *multi);                                        \
-    } while (0)
-        if (msplit == 4) F16K_LAUNCH_MULTI(1);
-        else if (msplit == 2) F16K_LAUNCH_MULTI(2);
-        else F16K_LAUNCH_MULTI(4);
-#undef F16K_LAUNCH_MULTI
-    } else if (f8) {
-        if (c.KS == 1) {
-            if (gdn_packed) F8K_LAUNCH(1, 4, 6, 1, true);
-            else F8K_LAUNCH(1, 4, 6, 1, false);
-        } else {
-            if (gdn_packed) F8K_LAUNCH(2, 2, 4, 2, true);
-            else F8K_LAUNCH(2, 2, 4, 2, false);
-        }
-    } else
-    if (c.NP == 4) {
-        F16K_LAUNCH(1, 2, 5, 2, false, 1, 4);
-    } else if (c.NP == 2) {
-        if (c.KS == 2) {
-            // (64 / 96 output channels never get here: choose_f16k gives them the lite configuration)
-            if (gdn_packed) F16K_LAUNCH_D(2, 2, 2, 5, 1, true, 4, 2);
-            else F16K_LAUNCH_D(2, 2, 2, 5, 1, false, 4, 2);
-        } else if (gdn_packed) F16K_LAUNCH(1, 2, 3, 2, true, 4, 2);
-        else F16K_LAUNCH(1, 2, 3, 2, false, 4, 2);
-    } else if (c.KS == 1 && c.T == 5) {
-        if (gdn_packed) F16K_LAUNCH_D(1, 5, 2, 6, 1, true, 4, 1);
-        else if (msplit == 4) F16K_LAUNCH_D(1, 5, 2, 6, 1, false, 1, 1);
-        else if (msplit == 2) F16K_LAUNCH_D(1, 5, 2, 6, 1, false, 2, 1);
-        else F16K_LAUNCH_D(1, 5, 2, 6, 1, false, 4, 1);
-    } else if (c.KS == 1) {
-        if (gdn_packed) F16K_LAUNCH(1, 4, 6, 1, true, 4, 1);
-        else if (msplit == 4) F16K_LAUNCH(1, 4, 6, 1, false, 1, 1);
-        else if (msplit == 2) F16K_LAUNCH(1, 4, 6, 1, false, 2, 1);
-        else F16K_LAUNCH(1, 4, 6, 1, false, 4, 1);
-    } else if (c.D == 1) {
-        MASIC_REQUIRE(gdn_packed == nullptr && d->Cout <= 96, MASIC_ERR_UNSUPPORTED, "conv_f16k: lite configuration with GDN / > 96 channels");
-        if (d->Cout <= 32) F16K_LAUNCH_D(2, 2, 1, 3, 1, false, 1, 1);
-        else if (d->Cout <= 64) F16K_LAUNCH_D(2, 2, 1, 3, 1, false, 2, 1);
-        else F16K_LAUNCH_D(2, 2, 1, 3, 1, false, 3, 1);
-    } else {
-        if (gdn_packed) F16K_LAUNCH(2, 2, 4, 2, true, 4, 1);
-        else if (d->Cout <= 32 || msplit == 4) F16K_LAUNCH(2, 2, 4, 2, false, 1, 1);
-        else if (msplit == 2) F16K_LAUNCH(2, 2, 4, 2, false, 2, 1);
-        else F16K_LAUNCH(2, 2, 4, 2, false, 4, 1);
-    }
-#undef F16K_LAUNCH
-#undef F16K_LAUNCH_D
-#undef F8K_LAUNCH
-    return masic_launch_status("conv_f16k_fwd");
-}
-}  // namespace
 
 // First analysis layer: Conv2d(3 -> 128, k5, s2, p2) + GDN -> F16K (conv_a_gdn_f16k above).  x: float32 NCHW channel view.
 extern "C" size_t masic_conv_a_packed_bytes(void) { return CA_WIMG_BYTES; }
@@ -1902,31 +1930,6 @@ extern "C" int masic_conv_a_pack_weight(const float* w, void* w_packed, void* st
     MASIC_REQUIRE(w && w_packed, MASIC_ERR_ARG, "conv_a_pack_weight: null pointer");
     hipLaunchKernelGGL(pack_conv_a_kernel, dim3(4 * CA_KSTEPS * 64 / 256), dim3(256), 0, (hipStream_t)stream, w, (uint4*)w_packed);
     return masic_launch_status("conv_a_pack_weight");
-}
-extern "C" int masic_conv_a_gdn_fwd_ex(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
-                                       void* y_f16k, void* y_f8k, float out_inv_scale, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream);
-namespace { int conv_a_launch(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse, void* y_f16k, void* y_f8k,
-                              float out_inv_scale, void* y_pre, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream); }
-// training-mode form: F16K output plus the pre-GDN result (see masic_conv_f16k_gdn_dual_fwd)
-extern "C" int masic_conv_a_gdn_dual_fwd(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
-                                         void* y_pre_f16k, void* y_f16k, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream) {
-    MASIC_REQUIRE(y_pre_f16k && y_f16k, MASIC_ERR_ARG, "conv_a_gdn_dual_fwd: null pointer");
-    return conv_a_launch(x, w_packed, bias, gdn_packed, gdn_inverse, y_f16k, nullptr, 0.0f, y_pre_f16k, B, Hi, Wi, in_ctot, in_coff, stream);
-}
-extern "C" int masic_conv_a_gdn_fwd(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
-                                    void* y_f16k, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream) {
-    return masic_conv_a_gdn_fwd_ex(x, w_packed, bias, gdn_packed, gdn_inverse, y_f16k, nullptr, 0.0f, B, Hi, Wi, in_ctot, in_coff, stream);
-}
-// the same with the result optionally written as F8K fp8 (y_f8k, quantised with out_inv_scale) for an fp8-operand second layer
-extern "C" int masic_conv_a_gdn_fwd_ex(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
-                                       void* y_f16k, void* y_f8k, float out_inv_scale, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream) {
-    return conv_a_launch(x, w_packed, bias, gdn_packed, gdn_inverse, y_f16k, y_f8k, out_inv_scale, nullptr, B, Hi, Wi, in_ctot, in_coff, stream);
-}
-// the convolution alone (no GDN), F16K out: Conv2d(3 -> 128, k5, s2, p2) on a float32 NCHW channel view
-extern "C" int masic_conv_a_fwd(const float* x, const void* w_packed, const float* bias, void* y_f16k, int B, int Hi, int Wi, int in_ctot, int in_coff,
-                                void* stream) {
-    MASIC_REQUIRE(y_f16k != nullptr, MASIC_ERR_ARG, "conv_a_fwd: null pointer");
-    return conv_a_launch(x, w_packed, bias, nullptr, 0, y_f16k, nullptr, 0.0f, nullptr, B, Hi, Wi, in_ctot, in_coff, stream);
 }
 namespace {
 int conv_a_launch(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse, void* y_f16k, void* y_f8k,
@@ -1941,35 +1944,43 @@ int conv_a_launch(const float* x, const void* w_packed, const float* bias, const
                 Ho, Wo, tiles_w, tiles_per_img, ntiles, (unsigned char*)y_f8k, out_inv_scale, (unsigned short*)y_pre, g_f16k_stamps};
     const size_t lds_bytes = 65536 + CA_WIMG_BYTES + 1024 + 2 * CA_PATCH_BYTES;
     const dim3 grid(ntiles < 256 ? ntiles : 256);
-#define CONV_A_LAUNCH(X3V, OUTV)                                                                                                   \
-    do {                                                                                                                           \
-        auto kfn = conv_a_gdn_f16k<X3V, OUTV>;                                                                                     \
-        static bool attr_set = false;                                                                                              \
-        if (!attr_set) {                                                                                                           \
-            (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                   \
-            attr_set = true;                                                                                                       \
-        }                                                                                                                          \
-        hipLaunchKernelGGL(kfn, grid, dim3(512), lds_bytes, (hipStream_t)stream, a);                                               \
-    } while (0)
+    hipStream_t st = (hipStream_t)stream;
     const bool x3 = (gdn_inverse & 2) != 0;
     const int out = y_f8k != nullptr ? 1 : (y_pre != nullptr ? 2 : 0);
     // the wave-private kernel where it applies; the shared-patch kernel for the rest (no GDN, x3, fp8 or pre-GDN outputs, unaligned input)
-    if (gdn_packed != nullptr && !x3 && out == 0 && Wi % 4 == 0 && ((size_t)x & 15) == 0 && ((size_t)Hi * Wi) % 4 == 0) {
-        static bool attr_w = false;
-        if (!attr_w) {
-            (void)hipFuncSetAttribute((const void*)conv_a_gdn_f16k_w, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_w = true;
-        }
-        hipLaunchKernelGGL(conv_a_gdn_f16k_w, grid, dim3(512), 65536 + CA_WIMG_BYTES + 1024 + 16 * CW_BYTES, (hipStream_t)stream, a);
-        return masic_launch_status("conv_a_gdn_fwd");
-    }
-    if (gdn_packed == nullptr) CONV_A_LAUNCH(false, 3);
-    else if (x3) { if (out == 0) CONV_A_LAUNCH(true, 0); else if (out == 1) CONV_A_LAUNCH(true, 1); else CONV_A_LAUNCH(true, 2); }
-    else { if (out == 0) CONV_A_LAUNCH(false, 0); else if (out == 1) CONV_A_LAUNCH(false, 1); else CONV_A_LAUNCH(false, 2); }
-#undef CONV_A_LAUNCH
+    if (gdn_packed != nullptr && !x3 && out == 0 && Wi % 4 == 0 && ((size_t)x & 15) == 0 && ((size_t)Hi * Wi) % 4 == 0)
+        launch_lds<conv_a_gdn_f16k_w>(grid, 512, 65536 + CA_WIMG_BYTES + 1024 + 16 * CW_BYTES, st, a);
+    else if (gdn_packed == nullptr) launch_lds<conv_a_gdn_f16k<false, 3>>(grid, 512, lds_bytes, st, a);
+    else if (x3 && out == 0) launch_lds<conv_a_gdn_f16k<true, 0>>(grid, 512, lds_bytes, st, a);
+    else if (x3 && out == 1) launch_lds<conv_a_gdn_f16k<true, 1>>(grid, 512, lds_bytes, st, a);
+    else if (x3) launch_lds<conv_a_gdn_f16k<true, 2>>(grid, 512, lds_bytes, st, a);
+    else if (out == 0) launch_lds<conv_a_gdn_f16k<false, 0>>(grid, 512, lds_bytes, st, a);
+    else if (out == 1) launch_lds<conv_a_gdn_f16k<false, 1>>(grid, 512, lds_bytes, st, a);
+    else launch_lds<conv_a_gdn_f16k<false, 2>>(grid, 512, lds_bytes, st, a);
     return masic_launch_status("conv_a_gdn_fwd");
 }
 }  // namespace
+// the same with the result optionally written as F8K fp8 (y_f8k, quantised with out_inv_scale) for an fp8-operand second layer
+extern "C" int masic_conv_a_gdn_fwd_ex(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
+                                       void* y_f16k, void* y_f8k, float out_inv_scale, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream) {
+    return conv_a_launch(x, w_packed, bias, gdn_packed, gdn_inverse, y_f16k, y_f8k, out_inv_scale, nullptr, B, Hi, Wi, in_ctot, in_coff, stream);
+}
+extern "C" int masic_conv_a_gdn_fwd(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
+                                    void* y_f16k, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream) {
+    return conv_a_launch(x, w_packed, bias, gdn_packed, gdn_inverse, y_f16k, nullptr, 0.0f, nullptr, B, Hi, Wi, in_ctot, in_coff, stream);
+}
+// training-mode form: F16K output plus the pre-GDN result (see masic_conv_f16k_gdn_dual_fwd)
+extern "C" int masic_conv_a_gdn_dual_fwd(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
+                                         void* y_pre_f16k, void* y_f16k, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream) {
+    MASIC_REQUIRE(y_pre_f16k && y_f16k, MASIC_ERR_ARG, "conv_a_gdn_dual_fwd: null pointer");
+    return conv_a_launch(x, w_packed, bias, gdn_packed, gdn_inverse, y_f16k, nullptr, 0.0f, y_pre_f16k, B, Hi, Wi, in_ctot, in_coff, stream);
+}
+// the convolution alone (no GDN), F16K out: Conv2d(3 -> 128, k5, s2, p2) on a float32 NCHW channel view
+extern "C" int masic_conv_a_fwd(const float* x, const void* w_packed, const float* bias, void* y_f16k, int B, int Hi, int Wi, int in_ctot, int in_coff,
+                                void* stream) {
+    MASIC_REQUIRE(y_f16k != nullptr, MASIC_ERR_ARG, "conv_a_fwd: null pointer");
+    return conv_a_launch(x, w_packed, bias, nullptr, 0, y_f16k, nullptr, 0.0f, nullptr, B, Hi, Wi, in_ctot, in_coff, stream);
+}
 
 // ------------------------------------------------------------------------------------------ 1x1 layers as DMA-staged GEMMs
 // The nine 1x1 (transposed) convolutions of each GMM head (MASIC.py:330-468) with the K-loop machinery of conv_f16k: the
@@ -2492,23 +2503,12 @@ extern "C" int masic_gemm_f16k_group_fwd(const masic_gemm_group_t* groups, int n
     }
     if (!f8 && !f8_out) {
         const int npx = ceil_div(HW, 256), tiles_per_img = npx * ncb;
-        static bool attr2 = false;
-        if (!attr2) {
-            (void)hipFuncSetAttribute((const void*)gemm_f16k2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr2 = true;
-        }
-        hipLaunchKernelGGL(gemm_f16k2, dim3(B >= 8 ? 8 * tiles_per_img * ceil_div(B, 8) : B * tiles_per_img), dim3(256), G2_NS * G2_STAGE, (hipStream_t)stream, ga, B, npx, tiles_per_img);
+        launch_lds<gemm_f16k2>(dim3(B >= 8 ? 8 * tiles_per_img * ceil_div(B, 8) : B * tiles_per_img), 256, G2_NS * G2_STAGE, (hipStream_t)stream, ga, B, npx, tiles_per_img);
         return masic_launch_status("gemm_f16k_fwd");
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_f16k<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)gemm_f16k<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     const dim3 grid(ceil_div(HW, 256), ncb, B);
-    if (f8) hipLaunchKernelGGL((gemm_f16k<4, true>), grid, dim3(512), 3 * 4 * 12288, (hipStream_t)stream, ga);
-    else hipLaunchKernelGGL(gemm_f16k<2>, grid, dim3(512), 3 * 2 * 12288, (hipStream_t)stream, ga);
+    if (f8) launch_lds<gemm_f16k<4, true>>(grid, 512, 3 * 4 * 12288, (hipStream_t)stream, ga);
+    else launch_lds<gemm_f16k<2>>(grid, 512, 3 * 2 * 12288, (hipStream_t)stream, ga);
     return masic_launch_status("gemm_f16k_fwd");
 }
 
@@ -2834,6 +2834,11 @@ __global__ __launch_bounds__(256) void pack_c3_weights_kernel(const float* __res
 
 }  // namespace
 
+template <int CI, int C>
+static void c3_launch(bool ex, int grid, int lds_bytes, hipStream_t st, const C3Args& a) {
+    if (ex) launch_lds<conv3x3_resident_f16k<CI, C, true>>(dim3(grid), 768, lds_bytes, st, a);
+    else launch_lds<conv3x3_resident_f16k<CI, C, false>>(dim3(grid), 768, lds_bytes, st, a);
+}
 static bool c3_pair_ok(int CI, int C) { return (C == 32 || C == 64) && (CI == 16 || CI == 32 || CI == 64) && (CI <= C || CI == C); }
 
 extern "C" size_t masic_conv3x3_resident_packed_bytes(int Cin, int Cout) {
@@ -2897,30 +2902,15 @@ extern "C" int masic_conv3x3_resident_ex_fwd(const void* x_f16k, const void* w_p
     int grid = 256;                                                  // one persistent workgroup per CU
     if (a.ntiles < grid) grid = round_up(a.ntiles, 8);
     hipStream_t st = (hipStream_t)stream;
-#define C3_LAUNCH_E(CIV, CV, EXV)                                                                                             \
-    do {                                                                                                                       \
-        static bool attr_set = false;                                                                                          \
-        if (!attr_set) {                                                                                                       \
-            (void)hipFuncSetAttribute((const void*)conv3x3_resident_f16k<CIV, CV, EXV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr_set = true;                                                                                                   \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((conv3x3_resident_f16k<CIV, CV, EXV>), dim3(grid), dim3(768), lds_bytes, st, a);                    \
-    } while (0)
-#define C3_LAUNCH(CIV, CV)                                                                                                    \
-    do {                                                                                                                       \
-        if (y2_f16k != nullptr || sum_of) C3_LAUNCH_E(CIV, CV, true);                                                          \
-        else C3_LAUNCH_E(CIV, CV, false);                                                                                      \
-    } while (0)
+    const bool ex = y2_f16k != nullptr || sum_of;
     if (C == 32) {
-        if (CI == 16) C3_LAUNCH(16, 32);
-        else C3_LAUNCH(32, 32);
+        if (CI == 16) c3_launch<16, 32>(ex, grid, lds_bytes, st, a);
+        else c3_launch<32, 32>(ex, grid, lds_bytes, st, a);
     } else {
-        if (CI == 16) C3_LAUNCH(16, 64);
-        else if (CI == 32) C3_LAUNCH(32, 64);
-        else C3_LAUNCH(64, 64);
+        if (CI == 16) c3_launch<16, 64>(ex, grid, lds_bytes, st, a);
+        else if (CI == 32) c3_launch<32, 64>(ex, grid, lds_bytes, st, a);
+        else c3_launch<64, 64>(ex, grid, lds_bytes, st, a);
     }
-#undef C3_LAUNCH
-#undef C3_LAUNCH_E
     if (sum_of) hipLaunchKernelGGL(c3_sum_finish_kernel, dim3(C), dim3(64), 0, st, (const float*)sum_workspace, sum_out, C, grid);
     return masic_launch_status("conv3x3_resident_fwd");
 }

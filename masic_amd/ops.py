@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from .determinism import is_deterministic as _det_mode
 from .fresh import stamp as _stamp
-from ._lib import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SOFTMAX_C, INOP_ABS, INOP_NONE, INOP_ROUND,  # noqa: F401
+from ._lib import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SOFTMAX_C, F16K_GDN, F16K_MULTI, F16K_NOSPLIT, INOP_ABS, INOP_NONE, INOP_ROUND,  # noqa: F401
                    ConvDesc, check, lib)
 
 LIK_BOUND = 1e-9
@@ -172,24 +172,38 @@ def conv_algorithmic_work(desc):
     return 2.0 * macs, float(nbytes)
 
 
+def _timer_open(desc, name_query, launches=1):
+    """The installed KernelTimer's bracket around one wrapper call's launches: names the kernel (name_query(desc_ref, buf, n)), returns None
+    when _timer.only asks for another one, else the record (variant, launches, flops, bytes, e0, e1) with e0 on the stream."""
+    buf = ctypes.create_string_buffer(96)
+    name_query(ctypes.byref(desc), buf, 96)
+    variant = buf.value.decode()
+    if _timer.only is not None and variant != _timer.only:
+        return None
+    rec = (variant, launches) + conv_algorithmic_work(desc) + (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    rec[4].record()
+    return rec
+
+
+def _timer_close(rec):
+    rec[5].record()
+    _timer.records.append(rec)
+
+
+def _f16k_name(flags):
+    return lambda d, buf, n: lib.masic_conv_f16k_kernel_name(d, flags, buf, n)
+
+
 def conv2d(x, packed, bias, desc, out=None, gate=None, res1=None, res2=None):
+    timed = None
     if _timer is not None:
         n = ctypes.c_int(0)
         lib.masic_conv_variant(ctypes.byref(desc), ctypes.byref(n))
-        buf = ctypes.create_string_buffer(96)
-        lib.masic_conv_kernel_name(ctypes.byref(desc), buf, 96)
-        variant = buf.value.decode()
-        if _timer.only is not None and variant != _timer.only:
-            return _conv2d(x, packed, bias, desc, out, gate, res1, res2)
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        y = _conv2d(x, packed, bias, desc, out, gate, res1, res2)
-        e1.record()
-        flops, nbytes = conv_algorithmic_work(desc)
-        _timer.records.append((variant, n.value, flops, nbytes, e0, e1))
-        return y
-    return _conv2d(x, packed, bias, desc, out, gate, res1, res2)
+        timed = _timer_open(desc, lib.masic_conv_kernel_name, n.value)
+    y = _conv2d(x, packed, bias, desc, out, gate, res1, res2)
+    if timed is not None:
+        _timer_close(timed)
+    return y
 
 
 def _conv2d(x, packed, bias, desc, out=None, gate=None, res1=None, res2=None):
@@ -1089,21 +1103,12 @@ def conv2d_f16k(x16, packed, bias, desc, out_nchw=None, want_nchw=False, gate=No
         y16 = torch.empty(desc.B * desc.out_ctot * desc.Ho * desc.Wo, dtype=torch.int16, device=x16.device)
     if gate is not None and tuple(gate.shape) != (desc.B, desc.gate_ctot, desc.Ho, desc.Wo):
         raise RuntimeError("masic_amd.conv2d_f16k: gate does not match descriptor")
-    timed = None
-    if _timer is not None:
-        buf = ctypes.create_string_buffer(96)
-        lib.masic_conv_f16k_kernel_name(ctypes.byref(desc), int(gdn is not None), buf, 96)
-        variant = buf.value.decode()
-        if _timer.only is None or variant == _timer.only:
-            timed = (variant, torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            timed[1].record()
+    timed = None if _timer is None else _timer_open(desc, _f16k_name(F16K_GDN if gdn is not None else 0))
     gp, ginv = (None, 0) if gdn is None else (gdn[0], _gdn_flags(gdn[1]))       # gdn = (pack_gdn_f16k(...), inverse)
     check(lib.masic_conv_f16k_gdn_fwd(_p(x16), _p(packed), _p(bias), _p(gate), _p(gp), ginv, _p(y32), _p(y16), ctypes.byref(desc), _stream()),
           "conv_f16k_fwd")
     if timed is not None:
-        timed[2].record()
-        flops, nbytes = conv_algorithmic_work(desc)
-        _timer.records.append((timed[0], 1, flops, nbytes, timed[1], timed[2]))
+        _timer_close(timed)
     return y32 if y32 is not None else y16
 
 
@@ -1162,7 +1167,10 @@ def conv2d_f16k_multi(x16, packed, bias, desc, want=("y32", "round32", "round16"
         gate_ctot = gate.shape[1]
     mo = _lib.F16kMultiOut(y32=_p(out.get("y32")), round32=_p(out.get("round32")), round16=_p(out.get("round16")), abs16=_p(out.get("abs16")),
                            gate=_p(gate), round16_ctot=round16_ctot, round16_coff=round16_coff, gate_ctot=gate_ctot, gate_c=gate_c)
+    timed = None if _timer is None else _timer_open(desc, _f16k_name(F16K_MULTI))
     check(lib.masic_conv_f16k_multi_fwd(_p(x16), _p(packed), _p(bias), ctypes.byref(mo), ctypes.byref(desc), _stream()), "conv_f16k_multi_fwd")
+    if timed is not None:
+        _timer_close(timed)
     return out
 
 
@@ -1212,8 +1220,11 @@ def conv2d_f16k_d2s(x16, packed, bias32, desc, C, out=None, out_coff=0):
     returns float32 NCHW [B, C, 2Hi, 2Wi] (or writes channels out_coff.. of `out`)."""
     if out is None:
         out = torch.empty((desc.B, C, 2 * desc.Hi, 2 * desc.Wi), dtype=torch.float32, device=x16.device)
+    timed = None if _timer is None else _timer_open(desc, _f16k_name(F16K_NOSPLIT))
     check(lib.masic_conv_f16k_d2s_fwd(_p(x16), _p(packed), _p(bias32), _p(out), C, out.shape[1], out_coff, ctypes.byref(desc), _stream()),
           "conv_f16k_d2s_fwd")
+    if timed is not None:
+        _timer_close(timed)
     return out
 
 
@@ -1398,20 +1409,11 @@ def conv2d_f8k(x, packed, wscale, bias, desc, out="f16k", out_scale=None, out_nc
     else:
         y16 = torch.empty(desc.B * desc.out_ctot * desc.Ho * desc.Wo, dtype=torch.int16, device=x.device)
     gp, ginv = (None, 0) if gdn is None else (gdn[0], _gdn_flags(gdn[1]))
-    timed = None
-    if _timer is not None:
-        buf = ctypes.create_string_buffer(96)
-        lib.masic_conv_f16k_kernel_name(ctypes.byref(desc), int(gdn is not None), buf, 96)
-        variant = buf.value.decode()
-        if _timer.only is None or variant == _timer.only:
-            timed = (variant, torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            timed[1].record()
+    timed = None if _timer is None else _timer_open(desc, _f16k_name((F16K_GDN if gdn is not None else 0) | (F16K_NOSPLIT if y8 is not None else 0)))
     check(lib.masic_conv_f8k_fwd(_p(x), _p(packed), _p(wscale) if f8 else None, _p(bias), _p(gate), _p(gp), ginv, _p(y32), _p(y16), _p(y8),
                                  float(inv), ctypes.byref(desc), _stream()), "conv_f8k_fwd")
     if timed is not None:
-        timed[2].record()
-        flops, nbytes = conv_algorithmic_work(desc)
-        _timer.records.append((timed[0], 1, flops, nbytes, timed[1], timed[2]))
+        _timer_close(timed)
     return y32 if y32 is not None else (y8 if y8 is not None else y16)
 
 
@@ -1521,14 +1523,7 @@ def conv2d_f16k_res(x16, packed, bias, desc, y16=None, res1=None, res2=None, res
     for r in (res1, res2, mask, y_pre):
         if r is not None and (r.dtype != torch.int16 or r.numel() != desc.B * res_ctot * desc.Ho * desc.Wo):
             raise RuntimeError("masic_amd.conv2d_f16k_res: residual / mask / pre buffer does not match (B, res_ctot, Ho, Wo)")
-    timed = None
-    if _timer is not None:
-        buf = ctypes.create_string_buffer(96)
-        lib.masic_conv_f16k_kernel_name(ctypes.byref(desc), 0, buf, 96)
-        variant = buf.value.decode()
-        if _timer.only is None or variant == _timer.only:
-            timed = (variant, torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            timed[1].record()
+    timed = None if _timer is None else _timer_open(desc, _f16k_name(0))
     if mask is None and y_pre is None:
         check(lib.masic_conv_f16k_res_fwd(_p(x16), _p(packed), _p(bias), _p(res1), _p(res2), int(res_ctot), _p(y16), ctypes.byref(desc), _stream()),
               "conv_f16k_res_fwd")
@@ -1536,9 +1531,7 @@ def conv2d_f16k_res(x16, packed, bias, desc, y16=None, res1=None, res2=None, res
         check(lib.masic_conv_f16k_res_ex_fwd(_p(x16), _p(packed), _p(bias), _p(res1), _p(res2), int(res_ctot), _p(mask), float(mask_slope), _p(y_pre),
                                              _p(y16), ctypes.byref(desc), _stream()), "conv_f16k_res_ex_fwd")
     if timed is not None:
-        timed[2].record()
-        flops, nbytes = conv_algorithmic_work(desc)
-        _timer.records.append((timed[0], 1, flops, nbytes, timed[1], timed[2]))
+        _timer_close(timed)
     return y16
 
 
@@ -1643,7 +1636,10 @@ def conv2d_f16k_few(x16, packed, bias32, desc, C, res32=None):
         _dev(res32, "residual")
         if tuple(res32.shape) != tuple(y.shape):
             raise RuntimeError("masic_amd.conv2d_f16k_few: residual shape mismatch")
+    timed = None if _timer is None else _timer_open(desc, _f16k_name(F16K_NOSPLIT))
     check(lib.masic_conv_f16k_few_fwd(_p(x16), _p(packed), _p(bias32), _p(res32), _p(y), int(C), ctypes.byref(desc), _stream()), "conv_f16k_few_fwd")
+    if timed is not None:
+        _timer_close(timed)
     return y
 
 

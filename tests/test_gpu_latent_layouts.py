@@ -35,7 +35,7 @@ def _operator_data(B, H, W, seed):
 
 
 # (B, H, W, accumulator tiles per workgroup = 4 / co-block split): 32 output pixels in a 256-pixel tile, H != W; odd, ragged output;
-# a multiple of 8 images (the per-XCD workgroup order); 72 and 162 workgroups = the two far sides of the split rule of f16k_msplit
+# a multiple of 8 images (the per-XCD workgroup order); 72 and 162 workgroups = the two far sides of the split rule of plan_f16k
 # (<= 64: 4, <= 160: 2, else 1; workgroups = tiles x co-blocks x B, a tile = 8 x 32 output pixels)
 SHAPES = [(2, 8, 16, 1), (1, 34, 18, 1), (8, 8, 16, 1), (4, 48, 192, 2), (9, 48, 192, 4)]
 SUBSETS = [("y32", "round32", "round16", "abs16"), ("y32", "round16", "abs16"), ("gated",)]

@@ -20,6 +20,9 @@ t("x.is_contiguous(); x.shape", lambda: (x.is_contiguous(), x.shape))
 st = ops._stream()
 t("raw lib.masic_elementwise (launch only)", lambda: _lib.lib.masic_elementwise(ops._p(x), None, ops._p(y), 64, int(ops.EW_SQUARE), 0.0, 0.0, st), 5000)
 t("ops.elementwise(EW_SQUARE, x)", lambda: ops.elementwise(ops.EW_SQUARE, x), 5000)
+d16 = ops.make_conv_desc(1, 16, 16, 16, 128, 5, 5, 2, 2, prec=_lib.PREC_BF16); x16 = torch.zeros(16 * 256, dtype=torch.int16, device="cuda")
+wp = ops.pack_conv_f16k_weight(torch.zeros(128, 16, 5, 5, device="cuda"), d16); y16 = torch.empty(128 * 64, dtype=torch.int16, device="cuda")
+t("raw lib.masic_conv_f16k_gdn_fwd (launch only)", lambda: _lib.lib.masic_conv_f16k_gdn_fwd(ops._p(x16), ops._p(wp), None, None, None, 0, None, ops._p(y16), ctypes.byref(d16), st), 5000)
 d = ops.make_conv_desc(2, 32, 16, 16, 32, 3, 3, 1, 1)
 t("make_conv_desc", lambda: ops.make_conv_desc(2, 32, 16, 16, 32, 3, 3, 1, 1))
 t("torch add (aten) x + y", lambda: x + y, 5000)
