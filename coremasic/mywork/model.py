@@ -28,8 +28,8 @@ _PATCH_SIZES = (32, 64, 128)
 
 
 def photometric_loss(delta, img_a, patch_b, corners):
-    raise NotImplementedError("model.photometric_loss: training the homography net is a separate stage (udh/udh/) that this "
-                              "library does not build; Net is inference only")
+    raise NotImplementedError("model.photometric_loss: training the homography net is a separate stage -- use udh/udh/model.py "
+                              "(masic_amd.udh_train: Net, photometric_loss); this Net is inference only")
 
 
 class Flatten(nn.Module):

@@ -639,6 +639,51 @@ int masic_udh_fc_fwd(const float* x, const float* w1, const float* b1, const flo
                      float* hidden, float* out, int B, int K, int N, int M, void* stream);
 int masic_udh_shift_corners(const float* corners, float* out, int B, void* stream);
 
+/* ---- training the UDH homography net (udh/udh/train.py: Net + photometric_loss; masic_amd/csrc/udh_train.hip).  Float32, no float
+ * atomics, every sum in a fixed order.  Masks are uint8 keep-bits (Dropout(0.5): kept values are scaled by 2); a NULL mask = no dropout.
+ *   masic_maxpool2_relu_bwd   gx[planes][H][W]: gy[planes][H/2][W/2] at the first maximum of relu(x) in each 2 x 2 window (scan
+ *                             order, as max_pool2d's backward), times [x > 0]; zeros elsewhere.  x may be the layer's output before or
+ *                             after its ReLU.
+ *   masic_udh_conv1_wgrad     dw[Cout][2][3][3], db[Cout] of masic_udh_conv1_fwd from a, b [B][1][H][W] and dy [B][Cout][H][W] (the
+ *                             gradient in front of the ReLU); Cout a multiple of 4; workspace: ..._workspace_bytes (0 = bad shape).
+ *   masic_udh_dropout_fwd     y = mask ? 2 x : 0 for n floats (n a multiple of 4).
+ *   masic_udh_fc_train_fwd    masic_udh_fc_fwd on the (already dropped) input x, then out = (2 m2 hidden) . w2^T + b2; hidden [B][N] is
+ *                             the activation before its dropout.  Same shapes and workspace as masic_udh_fc_fwd.  The inference
+ *                             entry point runs whole and unchanged, so the second layer is computed twice (B x N x M, negligible) and
+ *                             `out` holds the unmasked value until the masked kernel, next on the stream, overwrites it.
+ *   masic_udh_fc_bwd          from gout [B][M], the dropped input xd [B][K], hidden [B][N], the masks m1 [B][K] / m2 [B][N] (or NULL),
+ *                             w1 [N][K], w2 [M][N]: gw2, gb2, gb1, and in one streaming pass over w1 (per 32 batch rows) gw1 [N][K] and
+ *                             gx [B][K] = 2 m1 (g_h . w1).  K a multiple of 256, N of 16; workspace: masic_udh_fc_bwd_workspace_bytes.
+ *   masic_udh_photo_matrix    S[B][3][3] = inverse(N_dst inverse(h) N_src^-1), h = get_perspective_transform(corners - corners[:, :1],
+ *                             corners + delta) (udh/udh/model.py:18-30), the matrix masic_warp_perspective_fwd samples with; source
+ *                             Hs x Ws, output Hd x Wd; NaN rows for an exactly singular system (a zero pivot or determinant in float64, as
+ *                             masic_homography_from_corners); a quadrilateral degenerate only up to rounding gives huge finite rows.
+ *   masic_udh_photo_matrix_bwd  its adjoint: gS [B][slots][9] (slots added in index order) -> gdelta [B][4][2].
+ *   masic_udh_photo_loss_fwd  loss[0] = mean |warp(img [B][1][Hs][Ws]; S) - patch_b [B][1][Hd][Wd]|, the sampling arithmetic of
+ *                             masic_warp_perspective_fwd (zeros padding, masic_set_warp_align_corners); workspace: B * slots floats,
+ *                             slots = masic_udh_photo_slots(Hd, Wd).
+ *   masic_udh_photo_loss_bwd  gS_part [B][slots][9] from gloss[0] (device memory): sign(diff) gloss / count times grid_sample's
+ *                             coordinate derivative, chained through the homogeneous divide (eps = 1e-8 rule included). */
+int masic_maxpool2_relu_bwd(const float* x, const float* gy, float* gx, int planes, int H, int W, void* stream);
+size_t masic_udh_conv1_wgrad_workspace_bytes(int B, int H, int W, int Cout);
+int masic_udh_conv1_wgrad(const float* a, const float* b, const float* dy, void* workspace, float* dw, float* db, int B, int H, int W,
+                          int Cout, void* stream);
+int masic_udh_dropout_fwd(const float* x, const unsigned char* mask, float* y, size_t n, void* stream);
+int masic_udh_fc_train_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const unsigned char* m2,
+                           void* workspace, float* hidden, float* out, int B, int K, int N, int M, void* stream);
+size_t masic_udh_fc_bwd_workspace_bytes(int B, int N);
+int masic_udh_fc_bwd(const float* gout, const float* xd, const float* hidden, const unsigned char* m1, const unsigned char* m2,
+                     const float* w1, const float* w2, void* workspace, float* gw1, float* gb1, float* gw2, float* gb2, float* gx,
+                     int B, int K, int N, int M, void* stream);
+int masic_udh_photo_matrix(const float* corners, const float* delta, float* S, int B, int Hs, int Ws, int Hd, int Wd, void* stream);
+int masic_udh_photo_matrix_bwd(const float* corners, const float* delta, const float* gS, float* gdelta, int B, int slots, int Hs, int Ws,
+                               int Hd, int Wd, void* stream);
+int masic_udh_photo_slots(int Hd, int Wd);
+int masic_udh_photo_loss_fwd(const float* img, const float* S, const float* patch_b, void* workspace, float* loss, int B, int Hs, int Ws,
+                             int Hd, int Wd, void* stream);
+int masic_udh_photo_loss_bwd(const float* img, const float* S, const float* patch_b, const float* gloss, float* gS_part, int B, int Hs, int Ws,
+                             int Hd, int Wd, void* stream);
+
 /* ---- host data path, SURVEY.md 8(f)-4: one view of a dataset item (compressai/datasets/utils.py:207-285) from the decoded
  * uint8 RGB picture [H][W][3] on the device: pic_chw (nullable) = the crop [start_h : +ph, start_w : +pw] as float32
  * [3][ph][pw] / 255 (ToTensor); homo_patch (nullable) = the [homopatch][homopatch] window at (patch_x, patch_y) of

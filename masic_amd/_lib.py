@@ -91,6 +91,19 @@ SIGNATURES = {
     "masic_udh_fc_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "masic_udh_fc_fwd": (c_int, [_P] * 8 + [c_int] * 4 + [_P]),
     "masic_udh_shift_corners": (c_int, [_P, _P, c_int, _P]),
+    # UDH homography net, training (udh_train.hip)
+    "masic_maxpool2_relu_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "masic_udh_conv1_wgrad_workspace_bytes": (c_size_t, [c_int] * 4),
+    "masic_udh_conv1_wgrad": (c_int, [_P] * 6 + [c_int] * 4 + [_P]),
+    "masic_udh_dropout_fwd": (c_int, [_P, _P, _P, c_size_t, _P]),
+    "masic_udh_fc_train_fwd": (c_int, [_P] * 9 + [c_int] * 4 + [_P]),
+    "masic_udh_fc_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "masic_udh_fc_bwd": (c_int, [_P] * 13 + [c_int] * 4 + [_P]),
+    "masic_udh_photo_matrix": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P]),
+    "masic_udh_photo_matrix_bwd": (c_int, [_P, _P, _P, _P] + [c_int] * 6 + [_P]),
+    "masic_udh_photo_slots": (c_int, [c_int, c_int]),
+    "masic_udh_photo_loss_fwd": (c_int, [_P] * 5 + [c_int] * 5 + [_P]),
+    "masic_udh_photo_loss_bwd": (c_int, [_P] * 5 + [c_int] * 5 + [_P]),
     "masic_rans_encode_freqs": (c_int, [_P, c_size_t, _P, c_size_t, _P]),
     "masic_skinny_ctx_packed_bytes": (c_size_t, [c_int, c_int]),
     "masic_skinny_ctx_pack_weight": (c_int, [_P, _P, c_int, c_int, _P]),

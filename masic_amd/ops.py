@@ -488,6 +488,164 @@ def udh_shift_corners(corners):
     return out
 
 
+# ---- training the homography net (masic_amd/csrc/udh_train.hip; masic_amd/udh_train.py is the caller)
+def _mask(m, shape, name):
+    if m is None:
+        return None
+    if not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.uint8 and m.is_contiguous() and tuple(m.shape) == tuple(shape)):
+        raise RuntimeError(f"masic_amd: {name} must be a contiguous uint8 CUDA (HIP) tensor of shape {tuple(shape)}")
+    return m
+
+
+def maxpool2_relu_bwd(x, gy):
+    """Gradient of max_pool2d(relu(x), 2, 2) with respect to x [B,C,H,W] from gy [B,C,H/2,W/2]: gy lands on the first maximum of each
+    window (scan order, torch's choice) where x > 0.  x may already be relu(x)."""
+    _dev(x, "pool input"); _dev(gy, "pool gradient")
+    if x.dim() != 4 or tuple(gy.shape) != (x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2):
+        raise RuntimeError(f"masic_amd.maxpool2_relu_bwd: x {tuple(x.shape)} and gy {tuple(gy.shape)} do not match")
+    B, C, H, W = x.shape
+    gx = torch.empty_like(x)
+    check(lib.masic_maxpool2_relu_bwd(_p(x), _p(gy), _p(gx), B * C, H, W, _stream()), "maxpool2_relu_bwd")
+    return gx
+
+
+def udh_conv1_wgrad(a, b, dy):
+    """(dW [Cout,2,3,3], db [Cout]) of udh_conv1 from the two patch tensors and the gradient in front of its ReLU."""
+    _dev(a, "patch a"); _dev(b, "patch b"); _dev(dy, "dy")
+    if a.dim() != 4 or a.shape[1] != 1 or a.shape != b.shape or dy.dim() != 4 or dy.shape[0] != a.shape[0] or dy.shape[2:] != a.shape[2:]:
+        raise RuntimeError(f"masic_amd.udh_conv1_wgrad: patches {tuple(a.shape)} / {tuple(b.shape)} and dy {tuple(dy.shape)} do not match")
+    B, _, H, W = a.shape
+    Cout = dy.shape[1]
+    nbytes = _int_query("masic_udh_conv1_wgrad_workspace_bytes", B, H, W, Cout)
+    if nbytes == 0:
+        check(-1, "udh_conv1_wgrad_workspace_bytes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device)
+    dw = torch.empty((Cout, 2, 3, 3), dtype=torch.float32, device=a.device)
+    db = torch.empty(Cout, dtype=torch.float32, device=a.device)
+    check(lib.masic_udh_conv1_wgrad(_p(a), _p(b), _p(dy), _p(ws), _p(dw), _p(db), B, H, W, Cout, _stream()), "udh_conv1_wgrad")
+    return dw, db
+
+
+def udh_dropout(x, mask):
+    """2 * mask * x for a uint8 keep-mask of x's shape (Dropout(0.5) with a given mask)."""
+    _dev(x, "dropout input"); _mask(mask, x.shape, "dropout mask")
+    y = torch.empty_like(x)
+    check(lib.masic_udh_dropout_fwd(_p(x), _p(mask), _p(y), x.numel(), _stream()), "udh_dropout_fwd")
+    return y
+
+
+def udh_fc_train(x, w1, b1, w2, b2, m1=None, m2=None):
+    """The two linear layers in training: x' = 2 m1 x, hidden = relu(x' . w1^T + b1), out = (2 m2 hidden) . w2^T + b2; a None mask is
+    no dropout.  Returns (x' [B,K], hidden [B,N] before its dropout, out [B,M]) -- what udh_fc_bwd reads."""
+    B = x.shape[0]
+    x = x.reshape(B, -1)
+    N = w1.shape[0]
+    _mask(m2, (B, N), "dropout mask 2")
+    xd = x if m1 is None else udh_dropout(x, _mask(m1, x.shape, "dropout mask 1"))
+    if m2 is None:
+        hidden, out = udh_fc(xd, w1, b1, w2, b2, want_hidden=True)
+        return xd, hidden, out
+    _dev(xd, "fc input"); _dev(w1, "fc weight 1"); _dev(b1, "fc bias 1"); _dev(w2, "fc weight 2"); _dev(b2, "fc bias 2")
+    K, M = w1.shape[1], w2.shape[0]
+    if xd.shape[1] != K or tuple(b1.shape) != (N,) or tuple(w2.shape) != (M, N) or tuple(b2.shape) != (M,):
+        raise RuntimeError(f"masic_amd.udh_fc_train: x {tuple(x.shape)}, w1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, w2 {tuple(w2.shape)}, "
+                           f"b2 {tuple(b2.shape)} do not chain")
+    nbytes = _int_query("masic_udh_fc_workspace_bytes", B, K, N)
+    if nbytes == 0:
+        check(-1, "udh_fc_workspace_bytes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    hidden = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    out = torch.empty((B, M), dtype=torch.float32, device=x.device)
+    check(lib.masic_udh_fc_train_fwd(_p(xd), _p(w1), _p(b1), _p(w2), _p(b2), _p(m2), _p(ws), _p(hidden), _p(out), B, K, N, M, _stream()),
+          "udh_fc_train_fwd")
+    return xd, hidden, out
+
+
+def udh_fc_bwd(gout, xd, hidden, w1, w2, m1=None, m2=None):
+    """Backward of udh_fc_train: (gw1 [N,K], gb1 [N], gw2 [M,N], gb2 [M], gx [B,K]) from gout [B,M] and what the forward returned.  w1
+    is read once and gw1 written once per 32 batch rows; no float atomics."""
+    for t, n in ((gout, "gout"), (xd, "fc input"), (hidden, "hidden"), (w1, "fc weight 1"), (w2, "fc weight 2")):
+        _dev(t, n)
+    B, K = xd.shape
+    N, M = w1.shape[0], w2.shape[0]
+    if tuple(w1.shape) != (N, K) or tuple(w2.shape) != (M, N) or tuple(hidden.shape) != (B, N) or tuple(gout.shape) != (B, M):
+        raise RuntimeError(f"masic_amd.udh_fc_bwd: gout {tuple(gout.shape)}, x {tuple(xd.shape)}, hidden {tuple(hidden.shape)}, "
+                           f"w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)} do not chain")
+    _mask(m1, (B, K), "dropout mask 1"); _mask(m2, (B, N), "dropout mask 2")
+    dev = xd.device
+    ws = torch.empty(_int_query("masic_udh_fc_bwd_workspace_bytes", B, N) // 4, dtype=torch.float32, device=dev)
+    gw1 = torch.empty((N, K), dtype=torch.float32, device=dev)
+    gb1 = torch.empty(N, dtype=torch.float32, device=dev)
+    gw2 = torch.empty((M, N), dtype=torch.float32, device=dev)
+    gb2 = torch.empty(M, dtype=torch.float32, device=dev)
+    gx = torch.empty((B, K), dtype=torch.float32, device=dev)
+    check(lib.masic_udh_fc_bwd(_p(gout), _p(xd), _p(hidden), _p(m1), _p(m2), _p(w1), _p(w2), _p(ws), _p(gw1), _p(gb1), _p(gw2), _p(gb2), _p(gx),
+                               B, K, N, M, _stream()), "udh_fc_bwd")
+    return gw1, gb1, gw2, gb2, gx
+
+
+def _photo_args(corners, delta):
+    _dev(corners, "corners"); _dev(delta, "delta")
+    B = corners.shape[0]
+    if tuple(corners.shape) != (B, 4, 2) or tuple(delta.shape) != (B, 4, 2):
+        raise RuntimeError("masic_amd: corners and delta must be [B,4,2]")
+    return B
+
+
+def udh_photo_matrix(corners, delta, src_hw, dst_hw):
+    """The normalised sampling matrix [B,3,3] of photometric_loss's warp: inverse(N_dst inverse(h) N_src^-1) with
+    h = get_perspective_transform(corners - corners[:, :1], corners + delta); NaN rows for a degenerate quadrilateral."""
+    B = _photo_args(corners, delta)
+    S = torch.empty((B, 3, 3), dtype=torch.float32, device=corners.device)
+    check(lib.masic_udh_photo_matrix(_p(corners), _p(delta), _p(S), B, int(src_hw[0]), int(src_hw[1]), int(dst_hw[0]), int(dst_hw[1]), _stream()),
+          "udh_photo_matrix")
+    return S
+
+
+def udh_photo_matrix_bwd(corners, delta, g_s, src_hw, dst_hw):
+    """g_delta [B,4,2] from g_s [B,9] or [B,slots,9] (slots are added in index order)."""
+    B = _photo_args(corners, delta)
+    _dev(g_s, "g_S")
+    if g_s.shape[0] != B or g_s.shape[-1] != 9 or g_s.numel() % (B * 9) != 0:
+        raise RuntimeError(f"masic_amd.udh_photo_matrix_bwd: g_S {tuple(g_s.shape)}")
+    out = torch.empty((B, 4, 2), dtype=torch.float32, device=corners.device)
+    check(lib.masic_udh_photo_matrix_bwd(_p(corners), _p(delta), _p(g_s), _p(out), B, g_s.numel() // (B * 9), int(src_hw[0]), int(src_hw[1]),
+                                         int(dst_hw[0]), int(dst_hw[1]), _stream()), "udh_photo_matrix_bwd")
+    return out
+
+
+def _photo_shapes(img, S, patch_b):
+    _dev(img, "img_a"); _dev(S, "sampling matrix"); _dev(patch_b, "patch_b")
+    B = img.shape[0]
+    if img.dim() != 4 or img.shape[1] != 1 or patch_b.dim() != 4 or tuple(patch_b.shape[:2]) != (B, 1) or tuple(S.shape) != (B, 3, 3):
+        raise RuntimeError(f"masic_amd: photometric loss takes img_a [B,1,H,W], patch_b [B,1,h,w] and S [B,3,3], got {tuple(img.shape)}, "
+                           f"{tuple(patch_b.shape)}, {tuple(S.shape)}")
+    slots = _int_query("masic_udh_photo_slots", patch_b.shape[2], patch_b.shape[3])
+    if slots <= 0:
+        check(-1, "udh_photo_slots")
+    return B, img.shape[2], img.shape[3], patch_b.shape[2], patch_b.shape[3], slots
+
+
+def udh_photo_loss(img, S, patch_b):
+    """mean |warp(img; S) - patch_b| as a 0-d tensor (the warp of ops.warp_perspective, never materialised)."""
+    B, Hs, Ws, Hd, Wd, slots = _photo_shapes(img, S, patch_b)
+    ws = torch.empty(B * slots, dtype=torch.float32, device=img.device)
+    loss = torch.empty((), dtype=torch.float32, device=img.device)
+    check(lib.masic_udh_photo_loss_fwd(_p(img), _p(S), _p(patch_b), _p(ws), _p(loss), B, Hs, Ws, Hd, Wd, _stream()), "udh_photo_loss_fwd")
+    return loss
+
+
+def udh_photo_loss_bwd(img, S, patch_b, g_loss):
+    """Per-workgroup partial sums [B,slots,9] of the loss gradient with respect to S; g_loss a 0-d device tensor."""
+    B, Hs, Ws, Hd, Wd, slots = _photo_shapes(img, S, patch_b)
+    _dev(g_loss, "g_loss")
+    if g_loss.numel() != 1:
+        raise RuntimeError("masic_amd.udh_photo_loss_bwd: g_loss must hold one value")
+    part = torch.empty((B, slots, 9), dtype=torch.float32, device=img.device)
+    check(lib.masic_udh_photo_loss_bwd(_p(img), _p(S), _p(patch_b), _p(g_loss), _p(part), B, Hs, Ws, Hd, Wd, _stream()), "udh_photo_loss_bwd")
+    return part
+
+
 def set_warp_align_corners(flag):
     """grid_sample convention of every warp of the library: True = kornia 0.5.0's default (the reference's pinned version, and the
     default here), False = kornia <= 0.4.1's.  Process-wide (include/masic_hip.h: masic_set_warp_align_corners); captured HIP graphs
