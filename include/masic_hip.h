@@ -271,10 +271,8 @@ int masic_deconv_s2_as_conv_weight(const float* w, const float* bias, float* w_o
 /* weight gradient of Conv2d(Cin -> Cout, k3, s1, p1) with both operands in F16K (Cin, Cout multiples of 32): the 3x3 layers of
  * Independent_EN in the CQE training step (newtrain_cqe_real.py:128-174).  Pixel-major records become MFMA operands through the
  * hardware transpose read ds_read_b64_tr_b16 (masic_amd/csrc/wgrad_f16k.hip).  dw: float32 [Cout][Cin][3][3]; workspace:
- * masic_conv3x3_wgrad_f16k_workspace_bytes bytes (zeroed by the call). */
+ * masic_conv3x3_wgrad_f16k_workspace_bytes bytes; workspace_clean as masic_conv2d_wgrad_ws (0: zeroed by the call). */
 size_t masic_conv3x3_wgrad_f16k_workspace_bytes(int Cin, int Cout);
-int masic_conv3x3_wgrad_f16k(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
-                             int B, int Cin, int Cout, int H, int W, void* stream);
 int masic_conv3x3_wgrad_f16k_ws(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
                              int B, int Cin, int Cout, int H, int W, int workspace_clean, void* stream);
 /* The same for Conv2d(Cin -> Cout, k5, s1, p2): encode_hyper's first layer and the context model at latent resolution
@@ -294,11 +292,10 @@ int masic_conv5x5_wgrad_f16k_ws(const void* x_f16k, const void* dy_f16k, float* 
 /* Weight gradient of the 1x1 layers (the entropy-parameter stacks, reference MASIC.py:330-468) from F16K operands:
  * dw[a][q] = sum over batch and pixels of rows[b][a][p] * cols[b][q][p]; rows / cols: F16K [B][C/16][HW][16] bf16 with CA / CQ
  * channels (multiples of 16); dw float32 [CA][CQ].  Conv2d weight [Cout][Cin]: rows = dy, cols = x; ConvTranspose2d(k1) weight
- * [Cin][Cout]: rows = x, cols = dy. */
-int masic_gemm_wgrad_f16k(const void* rows_f16k, const void* cols_f16k, float* dw, int B, int CA, int CQ, int HW, void* stream);
-/* ... with the layer's bias gradient in the same launch: bias_of 1: dw[CA*CQ .. CA*CQ + CA) = sums of the rows operand over batch and
+ * [Cin][Cout]: rows = x, cols = dy.
+ * With the layer's bias gradient in the same launch: bias_of 1: dw[CA*CQ .. CA*CQ + CA) = sums of the rows operand over batch and
  * pixels (dy of a Conv2d), 2: dw[CA*CQ .. CA*CQ + CQ) = sums of the columns operand (dy of a ConvTranspose2d); dw then holds that
- * many more floats.  0: masic_gemm_wgrad_f16k. */
+ * many more floats.  0: the weight gradient alone. */
 int masic_gemm_wgrad_bias_f16k(const void* rows_f16k, const void* cols_f16k, float* dw, int bias_of, int B, int CA, int CQ, int HW, void* stream);
 /* F16K in, F16K out with up to two F16K residual tensors added after the activation: out = act(conv(x) + bias) + res1 [+ res2]
  * (ResidualBlock: compressai/layers/layers.py:160-190; Enhancement_Block: MASIC.py:149-164) -- Independent_EN with bf16
@@ -503,14 +500,14 @@ int masic_rd_loss_bwd(const float* x1_hat, const float* x1, const float* x2_hat,
  *   Conv2d:          dW[co,ci,kh,kw] = sum_{b,oh,ow} dy[b,co,oh,ow] * x[b,ci,oh*s+kh-p,ow*s+kw-p]
  *   ConvTranspose2d: dW[ci,co,kh,kw] = sum_{b,ih,iw} x[b,ci,ih,iw] * dy[b,co,ih*s+kh-p,iw*s+kw-p]
  * x is the forward input view (in_ctot/in_coff of desc), dy a contiguous [B,Cout,Ho,Wo] tensor.
- * Pixel tiles are reduced with float atomics into `workspace` (>= masic_conv2d_wgrad_workspace_bytes(d) bytes,
- * zero-filled by the call itself with a stream-ordered memset) and then transposed into dw (weight layout).
+ * Pixel tiles are reduced with float atomics into `workspace` (>= masic_conv2d_wgrad_workspace_bytes(d) bytes)
+ * and then transposed into dw (weight layout).
  * Input gradients need no entry point of their own: dx of a Conv2d is masic_conv2d_fwd with transposed=1 and
  * Cin/Cout swapped on the same weight tensor (and vice versa), see masic_amd/autograd.py. */
 size_t masic_conv2d_wgrad_workspace_bytes(const masic_conv_desc_t* d);
-int masic_conv2d_wgrad(const float* x, const float* dy, float* dw, void* workspace, const masic_conv_desc_t* d, void* stream);
-/* The same with a caller-owned PERSISTENT workspace: workspace_clean != 0 promises zeros on entry and gets zeros back on exit (the
- * last pass of the call re-zeroes what it reads), so a training step's ~80 weight gradients need no fill launch each. */
+/* workspace_clean 0: the call zero-fills the workspace itself (a kernel launch) and leaves it dirty.  != 0: a caller-owned PERSISTENT
+ * workspace -- zeros promised on entry, zeros back on exit (the last pass of the call re-zeroes what it reads), so a training step's
+ * ~80 weight gradients need no fill launch each. */
 int masic_conv2d_wgrad_ws(const float* x, const float* dy, float* dw, void* workspace, const masic_conv_desc_t* d, int workspace_clean,
                           void* stream);
 /* The 5x5 stride-2 layers of the bf16 mode with bf16 NCHW operands (x: [B][in_ctot][Hi][Wi], dy: [B][Cout][Ho][Wo], both bf16): the
@@ -823,12 +820,12 @@ int masic_ssim_bwd(const float* X, const float* Y, const float* gout, int N, int
  * weight gradient makes as many launches as the default call with a clean workspace.  The library keeps no mode of its own: the caller
  * picks the entry point.  0 from a size query: bad shape. */
 size_t masic_conv2d_wgrad_det_workspace_bytes(const masic_conv_desc_t* d);
-/* as masic_conv2d_wgrad / masic_conv2d_wgrad_ws */
+/* as masic_conv2d_wgrad_ws */
 int masic_conv2d_wgrad_det(const float* x, const float* dy, float* dw, void* workspace, const masic_conv_desc_t* d, void* stream);
 /* as masic_conv2d_wgrad_bf16in (only layers masic_conv2d_wgrad_bf16in_supported); workspace: masic_conv2d_wgrad_det_workspace_bytes(d) */
 int masic_conv2d_wgrad_bf16in_det(const void* x_bf16, const void* dy_bf16, float* dw, void* workspace, const masic_conv_desc_t* d,
                                   void* stream);
-/* as masic_conv3x3_wgrad_f16k / masic_conv5x5_wgrad_f16k_ws */
+/* as masic_conv3x3_wgrad_f16k_ws / masic_conv5x5_wgrad_f16k_ws */
 size_t masic_conv3x3_wgrad_f16k_det_workspace_bytes(int B, int Cin, int Cout, int H, int W);
 int masic_conv3x3_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
                                  int B, int Cin, int Cout, int H, int W, void* stream);
@@ -840,6 +837,22 @@ int masic_conv5x5_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float*
 size_t masic_gemm_wgrad_bias_f16k_det_workspace_bytes(int bias_of, int B, int CA, int CQ, int HW);
 int masic_gemm_wgrad_bias_f16k_det(const void* rows_f16k, const void* cols_f16k, float* dw, void* workspace, int bias_of, int B, int CA,
                                    int CQ, int HW, void* stream);
+/* What a weight-gradient call launches, as text: one line per launch in launch order, the zero fill and the finishing pass included,
+ *     kernel<every template argument> | gx,gy,gz | block | dynamic LDS bytes
+ * printed from the plan the launcher itself executes (kernel choice, pixel splits, grids are host-side decisions of the shape alone).
+ * flags name the entry point: 0 the _ws form with workspace_clean = 0, MASIC_WGRAD_CLEAN with workspace_clean = 1, MASIC_WGRAD_DET the
+ * _det form, MASIC_WGRAD_IN16 masic_conv2d_wgrad_bf16in[_det].  A form the launcher refuses: its error code and an empty buffer; a
+ * form without an entry point (DET with CLEAN, ...) or a buffer too small: MASIC_ERR_ARG.
+ * masic_wgrad_f16k_plan_name: kind 3 / 5: masic_conv{3x3,5x5}_wgrad_f16k_{ws,det} with s0 .. s4 = B, Cin, Cout, H, W; kind 1:
+ * masic_gemm_wgrad_bias_f16k[_det] with s0 .. s4 = bias_of, B, CA, CQ, HW.  The _row_name queries list every compiled instantiation of
+ * the tables the plans choose from (rows 0 .., det 0 / 1; MASIC_ERR_ARG past the last row). */
+#define MASIC_WGRAD_DET 1
+#define MASIC_WGRAD_IN16 2
+#define MASIC_WGRAD_CLEAN 4
+int masic_conv2d_wgrad_plan_name(const masic_conv_desc_t* d, int flags, char* buf, size_t n);
+int masic_conv2d_wgrad_row_name(int row, int det, char* buf, size_t n);
+int masic_wgrad_f16k_plan_name(int kind, int s0, int s1, int s2, int s3, int s4, int flags, char* buf, size_t n);
+int masic_wgrad_f16k_row_name(int row, int det, char* buf, size_t n);
 /* as masic_warp_perspective_bwd_gather, but where the gather form raises *flag the fallback is a deterministic store-and-sum (entries
  * grouped by source pixel with integer counting atomics, each group summed in destination-pixel order) instead of the float-atomic
  * scatter; it covers every homography, a horizon inside the picture included.  The flag is still tested on the device.  workspace:

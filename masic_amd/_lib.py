@@ -16,6 +16,7 @@ ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SOFTMAX_C = 0, 1, 2, 3
 INOP_NONE, INOP_ABS, INOP_ROUND = 0, 1, 2
 PREC_F32, PREC_BF16, PREC_FP8 = 0, 1, 2
 F16K_GDN, F16K_NOSPLIT, F16K_MULTI = 1, 2, 4      # masic_conv_f16k_kernel_name flags (MASIC_F16K_*)
+WGRAD_DET, WGRAD_IN16, WGRAD_CLEAN = 1, 2, 4      # masic_*wgrad*_plan_name flags (MASIC_WGRAD_*)
 SSIM_MS, SSIM_SIZE_AVERAGE, SSIM_NONNEG = 1, 2, 4
 
 
@@ -136,8 +137,6 @@ SIGNATURES = {
     "masic_conv_a_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "masic_deconv_s2_as_conv_weight": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
     "masic_conv3x3_wgrad_f16k_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "masic_conv3x3_wgrad_f16k": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    "masic_gemm_wgrad_f16k": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "masic_gemm_wgrad_bias_f16k": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "masic_conv3x3_wgrad_f16k_ws": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "masic_pic_wgrad_f16k_workspace_bytes": (c_size_t, []),
@@ -203,7 +202,6 @@ SIGNATURES = {
     "masic_rd_loss_bwd": (c_int, [_P, _P, _P, _P, c_size_t, _P, _P, c_int, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P]),
     # backward
     "masic_conv2d_wgrad_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
-    "masic_conv2d_wgrad": (c_int, [_P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),
     "masic_conv2d_wgrad_ws": (c_int, [_P, _P, _P, _P, ctypes.POINTER(ConvDesc), c_int, _P]),
     "masic_conv2d_wgrad_bf16in_supported": (c_int, [ctypes.POINTER(ConvDesc)]),
     "masic_conv2d_wgrad_bf16in": (c_int, [_P, _P, _P, _P, ctypes.POINTER(ConvDesc), c_int, _P]),
@@ -238,6 +236,10 @@ SIGNATURES = {
     "masic_conv5x5_wgrad_f16k_det": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "masic_gemm_wgrad_bias_f16k_det_workspace_bytes": (c_size_t, [c_int] * 5),
     "masic_gemm_wgrad_bias_f16k_det": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "masic_conv2d_wgrad_plan_name": (c_int, [ctypes.POINTER(ConvDesc), c_int, ctypes.c_char_p, c_size_t]),
+    "masic_conv2d_wgrad_row_name": (c_int, [c_int, c_int, ctypes.c_char_p, c_size_t]),
+    "masic_wgrad_f16k_plan_name": (c_int, [c_int] * 7 + [ctypes.c_char_p, c_size_t]),
+    "masic_wgrad_f16k_row_name": (c_int, [c_int, c_int, ctypes.c_char_p, c_size_t]),
     "masic_warp_perspective_bwd_gather_det_workspace_bytes": (c_size_t, [c_int] * 5),
     "masic_warp_perspective_bwd_gather_det": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 6 + [_P]),
     # SSIM / MS-SSIM

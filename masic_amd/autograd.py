@@ -38,7 +38,7 @@ def _fwd_f16k(mod, x, act):
 class ConvFn(Function):
     """y = act(conv(x, W) + b) for the module's Conv2d / ConvTranspose2d / MaskedConv2d.
     dx: the forward kernel run as the opposite layer kind on the same weight tensor (a Conv2d's input gradient is a
-    ConvTranspose2d with Cin/Cout swapped and vice versa); dW: masic_conv2d_wgrad; db: per-channel sum."""
+    ConvTranspose2d with Cin/Cout swapped and vice versa); dW: masic_conv2d_wgrad_ws; db: per-channel sum."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod, act):
@@ -50,7 +50,7 @@ class ConvFn(Function):
             x16 = ops.nchw_to_f16k(x)
             y = ops.gemm_f16k(x16, mod.packed_gemm_dma_weight(), None if bias is None else bias.detach(), B, mod.in_channels,
                               mod.out_channels, H, W, act, want_nchw=True)
-            ctx.x16 = x16 if _WGRAD1_F16K else None          # kept for the weight gradient (masic_gemm_wgrad_f16k)
+            ctx.x16 = x16 if _WGRAD1_F16K else None          # kept for the weight gradient (masic_gemm_wgrad_bias_f16k)
         elif _fwd_f16k(mod, x, act):
             # bf16 mode, the hyper transforms and context models (3x3 / 5x5, 128 ... 384 channels at latent resolution): the DMA-staged
             # F16K kernel of inference (x converted once; the 3x3 weight gradient reads the same F16K copy) instead of the NCHW
@@ -668,7 +668,7 @@ class GmmHeadsFn(Function):
       forward   x -> F16K once (read by the three stacks); layer i of the three stacks is one grouped GEMM launch (ops.gemm_f16k_group);
                 the last layer writes float32 NCHW.  Saved: x and the six intermediate activations in F16K, the three outputs.
       backward  per level, last to first: act' mask (float32 elementwise on the outputs' gradients, F16K masks below), bias gradient
-                (channel sums), weight gradient from the two F16K operands (masic_gemm_wgrad_f16k), input gradients of the three stacks as
+                (channel sums), weight gradient from the two F16K operands (masic_gemm_wgrad_bias_f16k), input gradients of the three stacks as
                 one grouped GEMM on the transposed weights; the three stacks' input gradients are summed at the end.
     Against one ConvFn per layer: 4 forward launches instead of 36, no float32 NCHW round trip between layers, 3 conversions of a
     gradient instead of 18.  Gradients travel between the layers in bf16, as the operands of the per-layer GEMMs do anyway."""

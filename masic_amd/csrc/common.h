@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <stdio.h>
+#include <string.h>
 #include "masic_hip.h"
 
 void masic_set_error(const char* fmt, ...);
@@ -32,13 +33,36 @@ static inline int masic_launch_status(const char* what) {
 __global__ static void masic_zero_kernel(unsigned* __restrict__ p, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
 }
+// workgroups of the fill of `bytes` bytes (0: nothing to launch)
+static inline unsigned masic_zero_blocks(size_t bytes) {
+    const size_t nb = (bytes / 4 + 255) / 256;
+    return nb > 2048 ? 2048u : (unsigned)nb;
+}
 static inline hipError_t masic_zero_async(void* ptr, size_t bytes, hipStream_t st) {
-    const size_t n = bytes / 4;
-    if (n == 0) return hipSuccess;
-    size_t nb = (n + 255) / 256;
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(masic_zero_kernel, dim3((unsigned)nb), dim3(256), 0, st, (unsigned*)ptr, n);
+    const unsigned nb = masic_zero_blocks(bytes);
+    if (nb == 0) return hipSuccess;
+    hipLaunchKernelGGL(masic_zero_kernel, dim3(nb), dim3(256), 0, st, (unsigned*)ptr, bytes / 4);
     return hipGetLastError();
+}
+
+// Raise the dynamic-LDS limit of kernel K once (the flag is K's own), then launch it.
+template <auto K, class... Args>
+void launch_lds(dim3 grid, int block, size_t lds_bytes, hipStream_t st, const Args&... args) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(K, grid, dim3(block), lds_bytes, st, args...);
+}
+
+// One line of a *_plan_name answer, appended to buf: "kernel | gx,gy,gz | block | lds-bytes"; false when it does not fit.
+static inline bool masic_plan_line(char* buf, size_t n, const char* kernel, dim3 grid, int block, size_t lds) {
+    const size_t used = strlen(buf);
+    return (size_t)snprintf(buf + used, n - used, "%s | %u,%u,%u | %d | %zu\n", kernel, grid.x, grid.y, grid.z, block, lds) < n - used;
+}
+static inline bool masic_plan_fill_line(char* buf, size_t n, size_t bytes) {      // masic_zero_async's launch, if it makes one
+    return masic_zero_blocks(bytes) == 0 || masic_plan_line(buf, n, "masic_zero_kernel", dim3(masic_zero_blocks(bytes)), 256, 0);
 }
 
 // ---- plane copy: B x C planes of HW floats from a channel view of one NCHW buffer into a channel view of another, float4 per lane, four

@@ -1500,17 +1500,6 @@ F16kCfg choose_f16k(const masic_conv_desc_t& d, const ConvGeom* g, int nphase) {
     return c;
 }
 
-// Raise the dynamic-LDS limit of kernel K once (the flag is K's own), then launch it.
-template <auto K, class... Args>
-void launch_lds(dim3 grid, int block, size_t lds_bytes, hipStream_t st, const Args&... args) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(K, grid, dim3(block), lds_bytes, st, args...);
-}
-
 // One row per compiled instantiation of conv_f16k / conv_f16k_multi: its template parameters (what the kernel's name is printed
 // from) and its launcher.  plan_f16k below is the only place a row is chosen; a new instantiation is a new row.
 typedef void (*F16kLaunchFn)(dim3 grid, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti* mo);

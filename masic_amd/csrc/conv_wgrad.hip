@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wgrad_slab.h"
 
 namespace {
 
@@ -819,100 +820,11 @@ __global__ __launch_bounds__(256) void wgrad_transpose_kernel(float* __restrict_
     }
 }
 
-
-// deterministic finishing pass: slabs [nsplit][T][AQ] -> dw [AQ][T], dw = slab 0 + slab 1 + ... in split order (float32); T = 1: the plain
-// sum of [nsplit][AQ] slabs.  Threads walk the slab layout (coalesced reads) and keep 8 slab loads in flight; the adds stay in split order.
-// Slab contents are left as they are (the deterministic workspace is irrelevant on entry and exit).
-__global__ __launch_bounds__(256) void wgrad_slab_transpose_kernel(const float* __restrict__ ws, float* __restrict__ dw, int T, int AQ, int nsplit) {
-    const size_t total = (size_t)T * AQ;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int t = (int)(i / AQ);
-        const size_t aq = i - (size_t)t * AQ;
-        const float* src = ws + i;
-        float s = 0.0f;
-        int z = 0;
-        for (; z + 8 <= nsplit; z += 8) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = src[(size_t)(z + k) * total];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; z < nsplit; ++z) s += src[(size_t)z * total];
-        dw[aq * T + t] = s;
-    }
-}
-
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ host side: one plan, one table
 namespace {
 constexpr int SMALL_WGS = 512;       // workgroups of conv_wgrad_small_s1 (two per CU), each with one partial of 150 floats in the workspace
-// the 5x5 stride-1 layers with 3 / 6 channels on either side (pre_conv, after_conv) take conv_wgrad_small_s1
-bool small_path(const masic_conv_desc_t* d) {
-    if (d->stride != 1 || d->KH != 5 || d->KW != 5 || d->pad != 2 || d->Wi % 4 != 0 || d->Hi != d->Ho || d->Wi != d->Wo) return false;
-    const int CA = d->transposed ? d->Cin : d->Cout, CQ = d->transposed ? d->Cout : d->Cin;
-    return (CQ == 6 || CQ == 3) && CA <= 8;
-}
-}  // namespace
-
-extern "C" size_t masic_conv2d_wgrad_workspace_bytes(const masic_conv_desc_t* d) {
-    if (!d) return 0;
-    const size_t w = (size_t)d->Cin * d->Cout * d->KH * d->KW * sizeof(float);
-    const size_t small = small_path(d) ? (size_t)SMALL_WGS * 150 * sizeof(float) : 0;
-    return w > small ? w : small;
-}
-
-extern "C" int masic_conv2d_wgrad(const float* x, const float* dy, float* dw, void* workspace,
-                                  const masic_conv_desc_t* d, void* stream) {
-    return masic_conv2d_wgrad_ws(x, dy, dw, workspace, d, 0, stream);
-}
-
-// workspace_clean != 0: `workspace` holds zeros on entry (a persistent buffer: zeroed once by its owner) and holds zeros again when the
-// call's last kernel has run -- no fill launch per weight gradient (a training step computes ~80 of them; a launch costs the device
-// ~10 us whatever it does).  0: contents unknown, zeroed here, left dirty (the behaviour of masic_conv2d_wgrad).
-namespace {
-int wgrad_launch(const void* x, const void* dy, float* dw, void* workspace, const masic_conv_desc_t* d, int workspace_clean, int in16, void* stream,
-                 int det = 0, size_t* det_bytes = nullptr);
-}
-extern "C" int masic_conv2d_wgrad_ws(const float* x, const float* dy, float* dw, void* workspace,
-                                     const masic_conv_desc_t* d, int workspace_clean, void* stream) {
-    return wgrad_launch(x, dy, dw, workspace, d, workspace_clean, 0, stream);
-}
-
-// the deterministic mode (include/masic_hip.h): per-split partial slabs, no float atomics, bitwise reproducible
-extern "C" size_t masic_conv2d_wgrad_det_workspace_bytes(const masic_conv_desc_t* d) {
-    size_t bytes = 0;
-    if (!d || wgrad_launch(nullptr, nullptr, nullptr, nullptr, d, 0, 0, nullptr, 1, &bytes) != MASIC_OK) return 0;
-    return bytes;
-}
-
-extern "C" int masic_conv2d_wgrad_det(const float* x, const float* dy, float* dw, void* workspace, const masic_conv_desc_t* d, void* stream) {
-    return wgrad_launch(x, dy, dw, workspace, d, 0, 0, stream, 1);
-}
-
-extern "C" int masic_conv2d_wgrad_bf16in_det(const void* x_bf16, const void* dy_bf16, float* dw, void* workspace, const masic_conv_desc_t* d,
-                                             void* stream) {
-    MASIC_REQUIRE(masic_conv2d_wgrad_bf16in_supported(d), MASIC_ERR_UNSUPPORTED, "conv2d_wgrad_bf16in_det: not a 5x5 stride-2 layer of the bf16 mode");
-    return wgrad_launch(x_bf16, dy_bf16, dw, workspace, d, 0, 1, stream, 1);
-}
-
-// 1 if masic_conv2d_wgrad_bf16in takes this layer: the 5x5 stride-2 layers of the analysis / synthesis / hyper transforms in bf16 mode
-extern "C" int masic_conv2d_wgrad_bf16in_supported(const masic_conv_desc_t* d) {
-    if (d == nullptr || d->prec != MASIC_PREC_BF16 || d->KH != 5 || d->KW != 5 || d->stride != 2 || d->pad != 2) return 0;
-    const int CQ = d->transposed ? d->Cout : d->Cin, Hf = d->transposed ? d->Ho : d->Hi, Wf = d->transposed ? d->Wo : d->Wi;
-    const int Hc = d->transposed ? d->Hi : d->Ho, Wc = d->transposed ? d->Wi : d->Wo;
-    return CQ > 8 && Wf % 8 == 0 && Wf == 2 * Wc && Hf == 2 * Hc;
-}
-
-// x, dy: bf16 NCHW tensors (x: [B][in_ctot][Hi][Wi] with the channel view of d, dy: [B][Cout][Ho][Wo]); only layers for which
-// masic_conv2d_wgrad_bf16in_supported(d); workspace as masic_conv2d_wgrad_ws.
-extern "C" int masic_conv2d_wgrad_bf16in(const void* x_bf16, const void* dy_bf16, float* dw, void* workspace,
-                                         const masic_conv_desc_t* d, int workspace_clean, void* stream) {
-    MASIC_REQUIRE(masic_conv2d_wgrad_bf16in_supported(d), MASIC_ERR_UNSUPPORTED, "conv2d_wgrad_bf16in: not a 5x5 stride-2 layer of the bf16 mode");
-    return wgrad_launch(x_bf16, dy_bf16, dw, workspace, d, workspace_clean, 1, stream);
-}
-
-namespace {
 // slab count cap of the deterministic mode: one layer's slabs stay within 64 MiB
 constexpr size_t DET_SLAB_BYTES = (size_t)64 << 20;
 int det_cap(size_t wbytes) {
@@ -920,29 +832,78 @@ int det_cap(size_t wbytes) {
     return c < 1 ? 1 : (c > (1 << 20) ? (1 << 20) : (int)c);
 }
 
-// det: the deterministic form (slabs of the workspace, no fill, no atomics); det_bytes != null: only report the deterministic workspace
-// size through it, launch nothing (the pointers may then be null)
-int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, const masic_conv_desc_t* d, int workspace_clean, int in16, void* stream,
-                 int det, size_t* det_bytes) {
-    const float* x = (const float*)xv;
-    const float* dy = (const float*)dyv;
-    MASIC_REQUIRE(d && (det_bytes || (x && dy && dw && workspace)), MASIC_ERR_ARG, "conv2d_wgrad: null pointer");
-    MASIC_REQUIRE(d->KH * d->KW == 1 || d->KH * d->KW <= 28, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: kernel %dx%d", d->KH, d->KW);
-    MASIC_REQUIRE(d->stride == 1 || d->stride == 2, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: stride %d", d->stride);
-    MASIC_REQUIRE(d->in_coff >= 0 && d->in_coff + d->Cin <= d->in_ctot, MASIC_ERR_SHAPE, "conv2d_wgrad: input view out of range");
-    hipStream_t st = (hipStream_t)stream;
-    const bool bf16 = d->prec == MASIC_PREC_BF16;      // operands rounded to bf16, float32 accumulate (training in the bf16-operand mode)
-    WgradArgs a{};
-    a.ws = (float*)workspace;
-    a.B = d->B; a.s = d->stride; a.pad = d->pad; a.KH = d->KH;
+enum { WG_GEMM1, WG_K5S2, WG_SMALL, WG_PACKED, WG_GENERAL };      // 1x1-bf16, 5x5 stride-2 bf16, 5x5 stride-1 with 3 / 6 channels, packed, general
+enum { FILL_WS, FILL_DW };                                       // FILL_WS: the workspace unless it is clean; FILL_DW: dw itself
+enum { FIN_NONE, FIN_TRANSPOSE, FIN_SLAB, FIN_SMALL };
+
+// One row per compiled instantiation of the main kernels: its template parameters (what the name is printed from) and its launcher,
+// the default form in column 0 and the DET form in column 1.  plan_wgrad below is the only place a row is chosen.
+struct WgradPlan;
+typedef void (*WgradLaunchFn)(const WgradPlan& p, hipStream_t st);
+struct WgradRow {
+    int path, p0, p1, flag;      // GENERAL: QT, TPW, BF16; PACKED: TPW, -, BF16; K5S2: -, -, IN16; SMALL: NA, CQ, -
+    WgradLaunchFn launch[2];
+};
+struct WgradPlan {
+    int rc;                      // MASIC_OK, or the launcher's refusal (then only path and wbytes are meaningful)
+    WgradArgs a;                 // geometry; the three pointers are the launcher's to fill
+    Wgrad1x1Args g;              // ... of the 1x1-bf16 path
+    int bf16, path;
+    const WgradRow* row;
+    dim3 grid;
+    int block, nsplit, fill, finish, fin_grid;
+    size_t lds, wbytes, det_bytes;
+};
+template <auto K> void wg_run(const WgradPlan& p, hipStream_t st) { hipLaunchKernelGGL(K, p.grid, dim3(p.block), p.lds, st, p.a); }
+template <auto K> void wg_run_gemm1(const WgradPlan& p, hipStream_t st) { hipLaunchKernelGGL(K, p.grid, dim3(p.block), p.lds, st, p.g); }
+template <auto K> void wg_run_small(const WgradPlan& p, hipStream_t st) { hipLaunchKernelGGL(K, p.grid, dim3(p.block), p.lds, st, p.a, p.a.ws, p.bf16); }
+#define ROW_F32(QT, TPW, BF) {WG_GENERAL, QT, TPW, BF, {wg_run<conv_wgrad_f32<QT, TPW, BF, false>>, wg_run<conv_wgrad_f32<QT, TPW, BF, true>>}}
+#define ROW_PACKED(TPW, BF) {WG_PACKED, TPW, 0, BF, {wg_run<conv_wgrad_packed_f32<TPW, BF, false>>, wg_run<conv_wgrad_packed_f32<TPW, BF, true>>}}
+#define ROW_K5S2(IN16) {WG_K5S2, 0, 0, IN16, {wg_run<conv_wgrad_k5s2_bf16<IN16, false>>, wg_run<conv_wgrad_k5s2_bf16<IN16, true>>}}
+#define ROW_SMALL(NA, CQ) {WG_SMALL, NA, CQ, 0, {wg_run_small<conv_wgrad_small_s1<NA, CQ>>, wg_run_small<conv_wgrad_small_s1<NA, CQ>>}}
+const WgradRow WGRAD_ROWS[] = {
+    ROW_F32(4, 1, false), ROW_F32(4, 1, true),          // 1x1: four q sub-tiles per block
+    ROW_F32(1, 3, false), ROW_F32(1, 3, true),          // up to 12 taps; BF16: the register-staged form (8 pixel groups per channel patch)
+    ROW_F32(1, 7, false), ROW_F32(1, 7, true),          // up to 28 taps
+    ROW_PACKED(1, false), ROW_PACKED(1, true),          // few fine-side channels: up to 4 column tiles; BF16: 8 (channel, group) pairs per wave
+    ROW_PACKED(2, false), ROW_PACKED(2, true),          // up to 8
+    ROW_K5S2(false), ROW_K5S2(true),
+    {WG_GEMM1, 0, 0, 0, {wg_run_gemm1<conv_wgrad_1x1_bf16<false>>, wg_run_gemm1<conv_wgrad_1x1_bf16<true>>}},
+    ROW_SMALL(1, 6), ROW_SMALL(2, 3),                   // (already deterministic: both columns are the same kernel)
+};
+constexpr int WGRAD_NROWS = sizeof(WGRAD_ROWS) / sizeof(WGRAD_ROWS[0]);
+const WgradRow* wgrad_row(int path, int p0, int p1, int flag) {
+    for (const WgradRow& r : WGRAD_ROWS)
+        if (r.path == path && r.p0 == p0 && r.p1 == p1 && r.flag == flag) return &r;
+    return nullptr;
+}
+void wgrad_row_name(const WgradRow& r, bool det, char* buf, size_t n) {
+    const char *f = r.flag ? "true" : "false", *dt = det ? "true" : "false";
+    if (r.path == WG_GENERAL) snprintf(buf, n, "conv_wgrad_f32<%d, %d, %s, %s>", r.p0, r.p1, f, dt);
+    else if (r.path == WG_PACKED) snprintf(buf, n, "conv_wgrad_packed_f32<%d, %s, %s>", r.p0, f, dt);
+    else if (r.path == WG_K5S2) snprintf(buf, n, "conv_wgrad_k5s2_bf16<%s, %s>", f, dt);
+    else if (r.path == WG_GEMM1) snprintf(buf, n, "conv_wgrad_1x1_bf16<%s>", dt);
+    else snprintf(buf, n, "conv_wgrad_small_s1<%d, %d>", r.p0, r.p1);
+}
+
+#define PLAN_REQUIRE(cond, code, ...) \
+    do { if (!(cond)) { masic_set_error(__VA_ARGS__); p.rc = (code); return p; } } while (0)
+
+// Everything the launcher decides for one layer: path, table row, grid, pixel splits, fill and finishing pass, workspace sizes.
+// det: the deterministic form (per-split slabs of the workspace, no fill, no atomics).  The path is classified before the refusals, so
+// that masic_conv2d_wgrad_bf16in_supported can ask for it.
+WgradPlan plan_wgrad(const masic_conv_desc_t* d, bool in16, bool det) {
+    WgradPlan p{};
+    WgradArgs& a = p.a;
+    p.bf16 = d->prec == MASIC_PREC_BF16;      // operands rounded to bf16, float32 accumulate (training in the bf16-operand mode)
+    a.B = d->B; a.s = d->stride; a.pad = d->pad; a.KH = d->KH; a.KW = d->KW;
     if (!d->transposed) {   // P = dy (coarse, contiguous), Q = x (fine, view)
-        a.P = dy; a.p_ctot = d->Cout; a.p_coff = 0; a.CA = d->Cout; a.Hc = d->Ho; a.Wc = d->Wo;
-        a.Q = x; a.q_ctot = d->in_ctot; a.q_coff = d->in_coff; a.CQ = d->Cin; a.Hf = d->Hi; a.Wf = d->Wi;
+        a.p_ctot = d->Cout; a.p_coff = 0; a.CA = d->Cout; a.Hc = d->Ho; a.Wc = d->Wo;
+        a.q_ctot = d->in_ctot; a.q_coff = d->in_coff; a.CQ = d->Cin; a.Hf = d->Hi; a.Wf = d->Wi;
     } else {                // P = x (coarse, view), Q = dy (fine, contiguous)
-        a.P = x; a.p_ctot = d->in_ctot; a.p_coff = d->in_coff; a.CA = d->Cin; a.Hc = d->Hi; a.Wc = d->Wi;
-        a.Q = dy; a.q_ctot = d->Cout; a.q_coff = 0; a.CQ = d->Cout; a.Hf = d->Ho; a.Wf = d->Wo;
+        a.p_ctot = d->in_ctot; a.p_coff = d->in_coff; a.CA = d->Cin; a.Hc = d->Hi; a.Wc = d->Wi;
+        a.q_ctot = d->Cout; a.q_coff = 0; a.CQ = d->Cout; a.Hf = d->Ho; a.Wf = d->Wo;
     }
-    a.KW = d->KW;
     a.tiles_w = ceil_div(a.Wc, 32); a.tiles_h = ceil_div(a.Hc, 2);
     a.ntiles = a.tiles_w * a.tiles_h * a.B;
     const int Tt = d->KH * d->KW;
@@ -951,144 +912,177 @@ int wgrad_launch(const void* xv, const void* dyv, float* dw, void* workspace, co
     a.QPIX = a.QROWS * a.PWq;
     a.QG = ceil_div(a.QPIX, 64);
     a.QS = a.QPIX | 1;
-    const size_t wbytes = masic_conv2d_wgrad_workspace_bytes(d);
-    if (bf16 && Tt == 1 && a.s == 1 && a.pad == 0 && (a.Hc * a.Wc) % 64 == 0) {
-        Wgrad1x1Args g{};
-        g.P = a.P; g.Q = a.Q; g.dw = dw; g.CA = a.CA; g.CQ = a.CQ;
-        g.p_ctot = a.p_ctot; g.p_coff = a.p_coff; g.q_ctot = a.q_ctot; g.q_coff = a.q_coff;
+    const int a_tiles = ceil_div(a.CA, 64), ncol_tiles = ceil_div(Tt * a.CQ, 32);
+    const bool k5 = d->KH == 5 && d->KW == 5 && a.pad == 2;
+    if (p.bf16 && Tt == 1 && a.s == 1 && a.pad == 0 && (a.Hc * a.Wc) % 64 == 0) p.path = WG_GEMM1;
+    // the 5x5 stride-2 layers of the analysis / synthesis / hyper transforms in bf16 mode (the one path with a bf16-input kernel)
+    else if (p.bf16 && k5 && a.s == 2 && a.CQ > 8 && a.Wf % 8 == 0 && a.Wf == 2 * a.Wc && a.Hf == 2 * a.Hc) p.path = WG_K5S2;
+    // the 5x5 stride-1 layers with 3 / 6 channels on either side (pre_conv, after_conv)
+    else if (k5 && a.s == 1 && a.Wf % 4 == 0 && a.Hf == a.Hc && a.Wf == a.Wc && (a.CQ == 6 || a.CQ == 3) && a.CA <= 8) p.path = WG_SMALL;
+    // few fine-side channels: (tap, q) pairs packed into the 32 MFMA columns
+    else if (a.CQ <= 8 && Tt > 1 && ncol_tiles <= 8) p.path = WG_PACKED;
+    else p.path = WG_GENERAL;
+    const size_t w = (size_t)d->Cin * d->Cout * Tt * sizeof(float), small = p.path == WG_SMALL ? (size_t)SMALL_WGS * 150 * sizeof(float) : 0;
+    p.wbytes = w > small ? w : small;
+
+    PLAN_REQUIRE(Tt == 1 || Tt <= 28, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: kernel %dx%d", d->KH, d->KW);
+    PLAN_REQUIRE(d->stride == 1 || d->stride == 2, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: stride %d", d->stride);
+    PLAN_REQUIRE(d->in_coff >= 0 && d->in_coff + d->Cin <= d->in_ctot, MASIC_ERR_SHAPE, "conv2d_wgrad: input view out of range");
+    PLAN_REQUIRE(a.CA > 0 && a.CQ > 0, MASIC_ERR_SHAPE, "conv2d_wgrad: no channels");
+    PLAN_REQUIRE(!in16 || p.path == WG_K5S2, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad_bf16in: layer shape without a bf16-input kernel");
+    const int cap = det ? det_cap(p.wbytes) : 1 << 30;
+    p.block = 512;
+    p.finish = det ? FIN_SLAB : FIN_TRANSPOSE;
+    int row[3] = {0, 0, 0};
+    if (p.path == WG_GEMM1) {
+        Wgrad1x1Args& g = p.g;
+        g.CA = a.CA; g.CQ = a.CQ; g.p_ctot = a.p_ctot; g.p_coff = a.p_coff; g.q_ctot = a.q_ctot; g.q_coff = a.q_coff;
         g.HW = a.Hc * a.Wc; g.ntk = a.B * (g.HW / 64);
         g.q_tiles = ceil_div(a.CQ, 128);
         const int base = ceil_div(a.CA, 128) * g.q_tiles;
-        int nsplit = ceil_div(512, base);
-        if (nsplit > g.ntk) nsplit = g.ntk;
-        g.nsplit = nsplit < 1 ? 1 : nsplit;
-        if (det) {
-            if (g.nsplit > det_cap(wbytes)) g.nsplit = det_cap(wbytes);
-            if (det_bytes) { *det_bytes = (size_t)g.nsplit * wbytes; return MASIC_OK; }
-            g.dw = (float*)workspace;
-            hipLaunchKernelGGL(conv_wgrad_1x1_bf16<true>, dim3(base, 1, g.nsplit), dim3(256), 0, st, g);
-            const size_t n1 = (size_t)a.CA * a.CQ;
-            hipLaunchKernelGGL(wgrad_slab_transpose_kernel, dim3((int)(n1 + 255) / 256 < 4096 ? (int)(n1 + 255) / 256 : 4096), dim3(256), 0, st,
-                               (const float*)workspace, dw, 1, (int)n1, g.nsplit);
-            return masic_launch_status("conv2d_wgrad_det");
-        }
-        if (masic_zero_async(dw, wbytes, st) != hipSuccess) {
-            masic_set_error("conv2d_wgrad: memset failed");
-            return MASIC_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL(conv_wgrad_1x1_bf16<false>, dim3(base, 1, g.nsplit), dim3(256), 0, st, g);
-        return masic_launch_status("conv2d_wgrad");
-    }
-    if (!det && !workspace_clean && masic_zero_async(workspace, wbytes, st) != hipSuccess) {
-        masic_set_error("conv2d_wgrad: workspace memset failed");
-        return MASIC_ERR_LAUNCH;
-    }
-    const int a_tiles = ceil_div(a.CA, 64);
-    const int ncol_tiles = ceil_div(Tt * a.CQ, 32);
-    if (bf16 && d->KH == 5 && d->KW == 5 && a.s == 2 && a.pad == 2 && a.CQ > 8 && a.Wf % 8 == 0 && a.Wf == 2 * a.Wc && a.Hf == 2 * a.Hc) {
+        p.nsplit = ceil_div(512, base);
+        if (p.nsplit > g.ntk) p.nsplit = g.ntk;
+        if (p.nsplit < 1) p.nsplit = 1;
+        if (p.nsplit > cap) p.nsplit = cap;
+        g.nsplit = p.nsplit;
+        p.grid = dim3(base, 1, p.nsplit);
+        p.block = 256;
+        p.fill = FILL_DW;            // (the default form adds straight into dw)
+        if (!det) p.finish = FIN_NONE;
+    } else if (p.path == WG_K5S2) {
         a.q_tiles = ceil_div(a.CQ, 32);
         const int ncombo = a_tiles * a.q_tiles;
         // pixel splits: a multiple of 8 (dealt round-robin to the XCDs); one workgroup per CU at a time, each ends with
         // 51 200 float atomics (~4 tile times), so: rounds over the 256 CUs x (tiles per workgroup + 4), minimised
-        int nsplit = 8;
+        p.nsplit = 8;
         long best = -1;
         for (int ns = 8; ns <= 128; ns += 8) {
             if (ns > round_up(a.ntiles, 8)) break;
             const long cost = (long)ceil_div(ncombo * ns, 256) * (ceil_div(a.ntiles, ns) + 4);
-            if (best < 0 || cost < best) { best = cost; nsplit = ns; }
+            if (best < 0 || cost < best) { best = cost; p.nsplit = ns; }
         }
-        a.nsplit = nsplit;
-        const size_t total5 = (size_t)Tt * a.CA * a.CQ;
-        int tb5 = (int)((total5 + 255) / 256);
-        if (tb5 > 4096) tb5 = 4096;
-        if (det) {         // (a multiple of 8 splits, as above: at least 8 whatever the cap)
-            const int cap8 = det_cap(wbytes) / 8 * 8;
-            if (a.nsplit > cap8) a.nsplit = cap8 < 8 ? 8 : cap8;
-            if (det_bytes) { *det_bytes = (size_t)a.nsplit * wbytes; return MASIC_OK; }
-            if (in16) hipLaunchKernelGGL((conv_wgrad_k5s2_bf16<true, true>), dim3(ncombo * a.nsplit), dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((conv_wgrad_k5s2_bf16<false, true>), dim3(ncombo * a.nsplit), dim3(512), 0, st, a);
-            hipLaunchKernelGGL(wgrad_slab_transpose_kernel, dim3(tb5), dim3(256), 0, st, (const float*)workspace, dw, Tt, a.CA * a.CQ, a.nsplit);
-            return masic_launch_status("conv2d_wgrad_det");
-        }
-        if (in16) hipLaunchKernelGGL(conv_wgrad_k5s2_bf16<true>, dim3(ncombo * nsplit), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL(conv_wgrad_k5s2_bf16<false>, dim3(ncombo * nsplit), dim3(512), 0, st, a);
-        hipLaunchKernelGGL(wgrad_transpose_kernel, dim3(tb5), dim3(256), 0, st, (float*)workspace, dw, Tt, a.CA * a.CQ, workspace_clean);
-        return masic_launch_status("conv2d_wgrad");
-    }
-    MASIC_REQUIRE(!in16, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad_bf16in: layer shape without a bf16-input kernel");
-    if (small_path(d)) {
-        // pre_conv / after_conv: plain float32 FMAs, one partial per workgroup in the workspace, summed (and zeroed again) by the finishing pass
+        if (det && p.nsplit > cap / 8 * 8) p.nsplit = cap / 8 * 8 < 8 ? 8 : cap / 8 * 8;      // (still a multiple of 8: at least 8 whatever the cap)
+        p.grid = dim3(ncombo * p.nsplit);
+        row[2] = in16;
+    } else if (p.path == WG_SMALL) {
+        // plain float32 FMAs, one partial per workgroup in the workspace, summed in a fixed order (and zeroed again) by the finishing
+        // pass: already deterministic, the same launches in both modes
         const int ntl = ceil_div(a.Wc, 64) * ceil_div(a.Hc, 32) * a.B;
         const int NA = a.CQ == 6 ? 1 : 2, gy = ceil_div(a.CA, NA), NV = NA * a.CQ * 25;
-        int gx = SMALL_WGS / gy;
-        if (gx > ntl) gx = ntl;
-        if (det_bytes) {   // (already deterministic: one partial per workgroup, summed in a fixed order; the size in whole weights)
-            const size_t w = (size_t)a.CA * a.CQ * 25;
-            *det_bytes = (((size_t)SMALL_WGS * 150 + w - 1) / w) * w * sizeof(float);
-            return MASIC_OK;
-        }
-        if (a.CQ == 6) hipLaunchKernelGGL((conv_wgrad_small_s1<1, 6>), dim3(gx, gy), dim3(256), 0, st, a, (float*)workspace, (int)bf16);
-        else hipLaunchKernelGGL((conv_wgrad_small_s1<2, 3>), dim3(gx, gy), dim3(256), 0, st, a, (float*)workspace, (int)bf16);
-        hipLaunchKernelGGL(wgrad_small_finish, dim3(gy * NV), dim3(64), 0, st, (float*)workspace, dw, gx, gy, NV, a.CA * a.CQ * 25);
-        return masic_launch_status("conv2d_wgrad");
-    }
-    if (a.CQ <= 8 && Tt > 1 && ncol_tiles <= 8) {          // few fine-side channels: (tap, q) pairs packed into the 32 MFMA columns
-        a.q_tiles = 1;
-        int nsplit = ceil_div(512, a_tiles);
-        if (nsplit > a.ntiles) nsplit = a.ntiles;
-        a.nsplit = nsplit < 1 ? 1 : nsplit;
-        if (det && a.nsplit > det_cap(wbytes)) a.nsplit = det_cap(wbytes);
-        if (det_bytes) { *det_bytes = (size_t)a.nsplit * wbytes; return MASIC_OK; }
-        const size_t lds = (size_t)2 * (64 * PS + a.CQ * a.QS) * sizeof(float);
-        dim3 grid(a_tiles, 1, a.nsplit);
-        if (det) {
-            if (bf16 && a.CQ * a.QG <= 64) {
-                if (ncol_tiles <= 4) hipLaunchKernelGGL((conv_wgrad_packed_f32<1, true, true>), grid, dim3(512), lds, st, a);
-                else hipLaunchKernelGGL((conv_wgrad_packed_f32<2, true, true>), grid, dim3(512), lds, st, a);
-            } else if (ncol_tiles <= 4) hipLaunchKernelGGL((conv_wgrad_packed_f32<1, false, true>), grid, dim3(512), lds, st, a);
-            else hipLaunchKernelGGL((conv_wgrad_packed_f32<2, false, true>), grid, dim3(512), lds, st, a);
-        } else if (bf16 && a.CQ * a.QG <= 64) {                    // (the register-staged form holds 8 (channel, group) pairs per wave)
-            if (ncol_tiles <= 4) hipLaunchKernelGGL((conv_wgrad_packed_f32<1, true>), grid, dim3(512), lds, st, a);
-            else hipLaunchKernelGGL((conv_wgrad_packed_f32<2, true>), grid, dim3(512), lds, st, a);
-        } else if (ncol_tiles <= 4) hipLaunchKernelGGL((conv_wgrad_packed_f32<1, false>), grid, dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((conv_wgrad_packed_f32<2, false>), grid, dim3(512), lds, st, a);
+        p.grid = dim3(SMALL_WGS / gy > ntl ? ntl : SMALL_WGS / gy, gy);
+        p.block = 256;
+        p.finish = FIN_SMALL;
+        p.fin_grid = gy * NV;
+        p.det_bytes = (((size_t)SMALL_WGS * 150 + w / 4 - 1) / (w / 4)) * w;       // (in whole weights)
+        row[0] = NA; row[1] = a.CQ;
     } else {
-        const int QT = Tt == 1 ? 4 : 1;                     // 1x1: four q sub-tiles per block; else four tap groups
-        a.q_tiles = ceil_div(a.CQ, 32 * QT);
+        const int QT = p.path == WG_GENERAL && Tt == 1 ? 4 : 1;      // general, 1x1: four q sub-tiles per block; else four tap groups
+        a.q_tiles = p.path == WG_PACKED ? 1 : ceil_div(a.CQ, 32 * QT);
         const int base = a_tiles * a.q_tiles;
-        int nsplit = ceil_div(512, base);
-        if (nsplit > a.ntiles) nsplit = a.ntiles;
-        a.nsplit = nsplit < 1 ? 1 : nsplit;
-        if (det && a.nsplit > det_cap(wbytes)) a.nsplit = det_cap(wbytes);
-        const size_t lds = (size_t)2 * (64 * PS + 32 * QT * a.QS) * sizeof(float);
-        MASIC_REQUIRE(lds <= 160 * 1024, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: tile does not fit LDS");
-        if (det_bytes) { *det_bytes = (size_t)a.nsplit * wbytes; return MASIC_OK; }
-        dim3 grid(a_tiles * a.q_tiles, 1, a.nsplit);
-        if (det) {
-            if (bf16 && a.QG <= 8) {
-                if (Tt == 1) hipLaunchKernelGGL((conv_wgrad_f32<4, 1, true, true>), grid, dim3(512), lds, st, a);
-                else if (Tt <= 12) hipLaunchKernelGGL((conv_wgrad_f32<1, 3, true, true>), grid, dim3(512), lds, st, a);
-                else hipLaunchKernelGGL((conv_wgrad_f32<1, 7, true, true>), grid, dim3(512), lds, st, a);
-            } else if (Tt == 1) hipLaunchKernelGGL((conv_wgrad_f32<4, 1, false, true>), grid, dim3(512), lds, st, a);
-            else if (Tt <= 12) hipLaunchKernelGGL((conv_wgrad_f32<1, 3, false, true>), grid, dim3(512), lds, st, a);
-            else hipLaunchKernelGGL((conv_wgrad_f32<1, 7, false, true>), grid, dim3(512), lds, st, a);
-        } else if (bf16 && a.QG <= 8) {                            // (the register-staged form holds 8 pixel groups per channel patch)
-            if (Tt == 1) hipLaunchKernelGGL((conv_wgrad_f32<4, 1, true>), grid, dim3(512), lds, st, a);
-            else if (Tt <= 12) hipLaunchKernelGGL((conv_wgrad_f32<1, 3, true>), grid, dim3(512), lds, st, a);
-            else hipLaunchKernelGGL((conv_wgrad_f32<1, 7, true>), grid, dim3(512), lds, st, a);
-        } else if (Tt == 1) hipLaunchKernelGGL((conv_wgrad_f32<4, 1, false>), grid, dim3(512), lds, st, a);
-        else if (Tt <= 12) hipLaunchKernelGGL((conv_wgrad_f32<1, 3, false>), grid, dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((conv_wgrad_f32<1, 7, false>), grid, dim3(512), lds, st, a);
+        p.nsplit = ceil_div(512, base);
+        if (p.nsplit > a.ntiles) p.nsplit = a.ntiles;
+        if (p.nsplit < 1) p.nsplit = 1;
+        if (p.nsplit > cap) p.nsplit = cap;
+        p.lds = (size_t)2 * (64 * PS + (p.path == WG_PACKED ? a.CQ : 32 * QT) * a.QS) * sizeof(float);
+        PLAN_REQUIRE(p.lds <= 160 * 1024, MASIC_ERR_UNSUPPORTED, "conv2d_wgrad: tile does not fit LDS");
+        p.grid = dim3(base, 1, p.nsplit);
+        if (p.path == WG_PACKED) { row[0] = ncol_tiles <= 4 ? 1 : 2; row[2] = p.bf16 && a.CQ * a.QG <= 64; }
+        else { row[0] = QT; row[1] = Tt == 1 ? 1 : (Tt <= 12 ? 3 : 7); row[2] = p.bf16 && a.QG <= 8; }
     }
-    const int T = d->KH * d->KW, AQ = a.CA * a.CQ;
-    const size_t total = (size_t)T * AQ;
-    int tb = (int)((total + 255) / 256);
-    if (tb > 4096) tb = 4096;
-    if (det) {
-        hipLaunchKernelGGL(wgrad_slab_transpose_kernel, dim3(tb), dim3(256), 0, st, (const float*)workspace, dw, T, AQ, a.nsplit);
-        return masic_launch_status("conv2d_wgrad_det");
+    a.nsplit = p.nsplit;
+    p.row = wgrad_row(p.path, row[0], row[1], row[2]);
+    if (p.finish == FIN_TRANSPOSE || p.finish == FIN_SLAB) {
+        const size_t blocks = ((size_t)Tt * a.CA * a.CQ + 255) / 256;
+        p.fin_grid = blocks > 4096 ? 4096 : (int)blocks;
     }
-    hipLaunchKernelGGL(wgrad_transpose_kernel, dim3(tb), dim3(256), 0, st, (float*)workspace, dw, T, AQ, workspace_clean);
-    return masic_launch_status("conv2d_wgrad");
+    if (p.path != WG_SMALL) p.det_bytes = (size_t)p.nsplit * p.wbytes;
+    return p;
+}
+
+// plan, optional zero fill, the row's kernel, the finishing pass.
+// workspace_clean != 0: `workspace` holds zeros on entry (a persistent buffer: zeroed once by its owner) and holds zeros again when the
+// call's last kernel has run -- no fill launch per weight gradient (a training step computes ~80 of them; a launch costs the device
+// ~10 us whatever it does).  0: contents unknown, zeroed here, left dirty.
+int wgrad_launch(const void* x, const void* dy, float* dw, void* workspace, const masic_conv_desc_t* d, int workspace_clean, bool in16, bool det,
+                 void* stream) {
+    const char* what = det ? "conv2d_wgrad_det" : "conv2d_wgrad";
+    MASIC_REQUIRE(d && x && dy && dw && workspace, MASIC_ERR_ARG, "%s: null pointer", what);
+    WgradPlan p = plan_wgrad(d, in16, det);
+    if (p.rc != MASIC_OK) return p.rc;
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    p.a.P = p.g.P = (const float*)(d->transposed ? x : dy);
+    p.a.Q = p.g.Q = (const float*)(d->transposed ? dy : x);
+    p.a.ws = ws;
+    p.g.dw = det ? ws : dw;
+    void* fill = det ? nullptr : (p.fill == FILL_DW ? (void*)dw : (workspace_clean ? nullptr : workspace));
+    if (fill && masic_zero_async(fill, p.wbytes, st) != hipSuccess) {
+        masic_set_error("%s: zero fill failed", what);
+        return MASIC_ERR_LAUNCH;
+    }
+    p.row->launch[det](p, st);
+    const int T = d->KH * d->KW, AQ = p.a.CA * p.a.CQ;
+    if (p.finish == FIN_TRANSPOSE) hipLaunchKernelGGL(wgrad_transpose_kernel, dim3(p.fin_grid), dim3(256), 0, st, ws, dw, T, AQ, workspace_clean);
+    else if (p.finish == FIN_SLAB) hipLaunchKernelGGL(wgrad_slab_transpose_kernel, dim3(p.fin_grid), dim3(256), 0, st, (const float*)ws, dw, T, AQ, p.nsplit);
+    else if (p.finish == FIN_SMALL)
+        hipLaunchKernelGGL(wgrad_small_finish, dim3(p.fin_grid), dim3(64), 0, st, ws, dw, (int)p.grid.x, (int)p.grid.y, p.fin_grid / (int)p.grid.y, AQ * 25);
+    return masic_launch_status(what);
 }
 }  // namespace
+
+extern "C" size_t masic_conv2d_wgrad_workspace_bytes(const masic_conv_desc_t* d) { return d ? plan_wgrad(d, false, false).wbytes : 0; }
+
+extern "C" int masic_conv2d_wgrad_ws(const float* x, const float* dy, float* dw, void* workspace,
+                                     const masic_conv_desc_t* d, int workspace_clean, void* stream) {
+    return wgrad_launch(x, dy, dw, workspace, d, workspace_clean, false, false, stream);
+}
+
+// 1 if masic_conv2d_wgrad_bf16in takes this layer: the 5x5 stride-2 layers of the analysis / synthesis / hyper transforms in bf16 mode
+extern "C" int masic_conv2d_wgrad_bf16in_supported(const masic_conv_desc_t* d) { return d && plan_wgrad(d, false, false).path == WG_K5S2; }
+
+// x, dy: bf16 NCHW tensors (x: [B][in_ctot][Hi][Wi] with the channel view of d, dy: [B][Cout][Ho][Wo]); only layers for which
+// masic_conv2d_wgrad_bf16in_supported(d); workspace as masic_conv2d_wgrad_ws.
+extern "C" int masic_conv2d_wgrad_bf16in(const void* x_bf16, const void* dy_bf16, float* dw, void* workspace,
+                                         const masic_conv_desc_t* d, int workspace_clean, void* stream) {
+    MASIC_REQUIRE(masic_conv2d_wgrad_bf16in_supported(d), MASIC_ERR_UNSUPPORTED, "conv2d_wgrad_bf16in: not a 5x5 stride-2 layer of the bf16 mode");
+    return wgrad_launch(x_bf16, dy_bf16, dw, workspace, d, workspace_clean, true, false, stream);
+}
+
+// the deterministic mode (include/masic_hip.h): per-split partial slabs, no float atomics, bitwise reproducible
+extern "C" size_t masic_conv2d_wgrad_det_workspace_bytes(const masic_conv_desc_t* d) { return d ? plan_wgrad(d, false, true).det_bytes : 0; }
+
+extern "C" int masic_conv2d_wgrad_det(const float* x, const float* dy, float* dw, void* workspace, const masic_conv_desc_t* d, void* stream) {
+    return wgrad_launch(x, dy, dw, workspace, d, 0, false, true, stream);
+}
+
+extern "C" int masic_conv2d_wgrad_bf16in_det(const void* x_bf16, const void* dy_bf16, float* dw, void* workspace, const masic_conv_desc_t* d,
+                                             void* stream) {
+    MASIC_REQUIRE(masic_conv2d_wgrad_bf16in_supported(d), MASIC_ERR_UNSUPPORTED, "conv2d_wgrad_bf16in_det: not a 5x5 stride-2 layer of the bf16 mode");
+    return wgrad_launch(x_bf16, dy_bf16, dw, workspace, d, 0, true, true, stream);
+}
+
+// the launches of the call `flags` names (MASIC_WGRAD_*), one line each, as the launcher issues them
+extern "C" int masic_conv2d_wgrad_plan_name(const masic_conv_desc_t* d, int flags, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "conv2d_wgrad_plan_name: no buffer");
+    buf[0] = 0;
+    const bool det = flags & MASIC_WGRAD_DET, in16 = flags & MASIC_WGRAD_IN16, clean = flags & MASIC_WGRAD_CLEAN;
+    MASIC_REQUIRE(d && !(flags & ~7) && !(det && clean), MASIC_ERR_ARG, "conv2d_wgrad_plan_name: no such form (flags %d)", flags);
+    MASIC_REQUIRE(!in16 || masic_conv2d_wgrad_bf16in_supported(d), MASIC_ERR_UNSUPPORTED, "conv2d_wgrad_plan_name: not a 5x5 stride-2 layer of the bf16 mode");
+    const WgradPlan p = plan_wgrad(d, in16, det);
+    if (p.rc != MASIC_OK) return p.rc;
+    char name[64];
+    wgrad_row_name(*p.row, det, name, sizeof name);
+    const bool fill = !det && (p.fill == FILL_DW || !clean);
+    const char* fin = p.finish == FIN_TRANSPOSE ? "wgrad_transpose_kernel" : (p.finish == FIN_SLAB ? "wgrad_slab_transpose_kernel" : "wgrad_small_finish");
+    const bool ok = (!fill || masic_plan_fill_line(buf, n, p.wbytes)) && masic_plan_line(buf, n, name, p.grid, p.block, p.lds) &&
+                    (p.finish == FIN_NONE || masic_plan_line(buf, n, fin, dim3(p.fin_grid), p.finish == FIN_SMALL ? 64 : 256, 0));
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "conv2d_wgrad_plan_name: buffer of %zu bytes too small", n);
+    return MASIC_OK;
+}
+// every compiled main kernel: rows 0 .., det 0 / 1; MASIC_ERR_ARG past the last row
+extern "C" int masic_conv2d_wgrad_row_name(int row, int det, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && row >= 0 && row < WGRAD_NROWS && (det == 0 || det == 1), MASIC_ERR_ARG, "conv2d_wgrad_row_name: row %d", row);
+    wgrad_row_name(WGRAD_ROWS[row], det, buf, n);
+    return MASIC_OK;
+}

@@ -22,6 +22,7 @@
 // tiles and add their partial dW into a [tap][co][ci] workspace with float atomics (ci contiguous: full 128-byte segments);
 // a last pass transposes it into the weight layout.
 #include "common.h"
+#include "wgrad_slab.h"
 
 namespace {
 
@@ -75,7 +76,7 @@ __device__ __forceinline__ bf16x8 frag(const v2u& lo, const v2u& hi) {
 }
 
 // DET (masic_conv3x3_wgrad_f16k_det): workgroup x of every channel group stores its partial tile into slab x ([gridDim.x][T][CA][CQ]) with plain
-// stores; wgrad3_slab_transpose_kernel sums the slabs in that order
+// stores; wgrad_slab_transpose_kernel (wgrad_slab.h) sums the slabs in that order
 template <int MA, int NQ, int KS, bool DET = false>
 __global__ __launch_bounds__(NQ * KS * 64) void wgrad3x3_f16k(const Wg3Args a) {
     constexpr int XR = XGeom<KS>::XR, XROW = XGeom<KS>::XROW, XP = XGeom<KS>::XP;
@@ -232,27 +233,6 @@ __global__ __launch_bounds__(256) void wgrad3_transpose_kernel(float* __restrict
         const size_t aq = i - (size_t)t * AQ;
         dw[aq * T + t] = ws[i];
         if (rezero) ws[i] = 0.0f;          // a persistent workspace is clean again (masic_conv3x3_wgrad_f16k_ws)
-    }
-}
-
-// deterministic finishing pass: slabs [nsplit][T][AQ] -> dw [AQ][T], summed in slab order (float32; 8 slab loads in flight per thread, the
-// adds in slab order); the slabs are left as they are
-__global__ __launch_bounds__(256) void wgrad3_slab_transpose_kernel(const float* __restrict__ ws, float* __restrict__ dw, int AQ, int T, int nsplit) {
-    const size_t total = (size_t)T * AQ;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int t = (int)(i / AQ);
-        const size_t aq = i - (size_t)t * AQ;
-        float s = 0.0f;
-        int z = 0;
-        for (; z + 8 <= nsplit; z += 8) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = ws[(size_t)(z + k) * total + i];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; z < nsplit; ++z) s += ws[(size_t)z * total + i];
-        dw[aq * T + t] = s;
     }
 }
 
@@ -647,190 +627,189 @@ __global__ __launch_bounds__(256) void wgrad_pic_finish(const float* __restrict_
     if (sl == 0 && o < WP_NOUT) dw[o] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
 }
 
-template <int MA, int NQ, int KS = 3, bool DET = false>
-void launch(const Wg3Args& a, int grid, int groups, hipStream_t st) {
-    auto kfn = wgrad3x3_f16k<MA, NQ, KS, DET>;
-    static bool attr_set = false;
-    constexpr size_t lds = 3 * (size_t)(2 * MA * GP + 2 * NQ * XGeom<KS>::XP) + 1024;
-    static_assert(lds <= 160 * 1024, "three tile buffers must fit the LDS");
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(grid, groups), dim3(NQ * KS * 64), lds, st, a);
+// ------------------------------------------------------------------------------------------------ host side, 3x3 / 5x5
+// One row per compiled wgrad3x3_f16k<MA, NQ, KS, DET>: the default form in column 0, the DET form in column 1.
+typedef void (*Wg3LaunchFn)(const Wg3Args& a, dim3 grid, hipStream_t st);
+struct Wg3Row { int ma, nq, ks; size_t lds; Wg3LaunchFn launch[2]; };
+template <int MA, int NQ, int KS> constexpr size_t wg3_lds = 3 * (size_t)(2 * MA * GP + 2 * NQ * XGeom<KS>::XP) + 1024;
+template <int MA, int NQ, int KS, bool DET>
+void wg3_launch(const Wg3Args& a, dim3 grid, hipStream_t st) {
+    static_assert(wg3_lds<MA, NQ, KS> <= 160 * 1024, "three tile buffers must fit the LDS");
+    launch_lds<wgrad3x3_f16k<MA, NQ, KS, DET>>(grid, NQ * KS * 64, wg3_lds<MA, NQ, KS>, st, a);
 }
+#define WG3_ROW(MA, NQ, KS) {MA, NQ, KS, wg3_lds<MA, NQ, KS>, {wg3_launch<MA, NQ, KS, false>, wg3_launch<MA, NQ, KS, true>}}
+const Wg3Row WG3_ROWS[] = {WG3_ROW(1, 1, 3), WG3_ROW(1, 2, 3), WG3_ROW(2, 1, 3), WG3_ROW(2, 2, 3), WG3_ROW(3, 1, 3), WG3_ROW(3, 2, 3),
+                           WG3_ROW(1, 1, 5), WG3_ROW(2, 1, 5)};
+constexpr int WG3_NROWS = sizeof(WG3_ROWS) / sizeof(WG3_ROWS[0]);
 
-// slab count of the deterministic 3x3 / 5x5 forms: ONE workgroup count for every channel group of the layer (the default's rule with all
-// the groups in one round of the CUs), capped so that the slabs stay within 64 MiB
-int det3_splits(int B, int Cin, int Cout, int H, int W, int KS) {
-    const int ntiles = ceil_div(W, TC) * ceil_div(H, TR) * B;
-    const int groups = KS == 3 ? ceil_div(Cout, 96) * ceil_div(Cin, 64) : ceil_div(Cout, 64) * (Cin / 32);
+// Workgroups per channel group: 256 where the picture has that many tiles (Independent_EN); at latent resolution (64 tiles, up to
+// 16 groups: the hyper transforms) one round of the CUs over `groups` groups -- every workgroup ends with a full group tile of float
+// atomics (55 296 of them), and 1024 single-tile workgroups spent 190 us of which ~150 were those atomics.  The default form counts
+// the groups of ONE launch; the deterministic form counts all groups of the layer (one slab count for every launch) and keeps the
+// slabs (det_wbytes each) within 64 MiB.
+int wg3_splits(int ntiles, int groups, size_t det_wbytes) {
     int grid = ntiles < 256 ? ntiles : 256;
     if (ntiles < 256 && grid * groups > 256) grid = 256 / groups > 0 ? 256 / groups : 1;
-    const size_t w = (size_t)KS * KS * Cin * Cout * sizeof(float), cap = ((size_t)64 << 20) / w;
-    if ((size_t)grid > cap) grid = cap < 1 ? 1 : (int)cap;
+    const size_t cap = det_wbytes ? ((size_t)64 << 20) / det_wbytes : (size_t)grid;
+    if ((size_t)grid > cap) grid = (int)cap;
     return grid < 1 ? 1 : grid;
 }
+int wg3_det_splits(int KS, int B, int Cin, int Cout, int H, int W) {
+    const int groups = KS == 3 ? ceil_div(Cout, 96) * ceil_div(Cin, 64) : ceil_div(Cout, 64) * (Cin / 32);
+    return wg3_splits(ceil_div(W, TC) * ceil_div(H, TR) * B, groups, (size_t)KS * KS * Cin * Cout * sizeof(float));
+}
 
-int wgrad_k3k5_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace, int B, int Cin, int Cout, int H, int W, int KS, void* stream) {
-    const char* what = KS == 3 ? "conv3x3_wgrad_f16k_det" : "conv5x5_wgrad_f16k_det";
-    MASIC_REQUIRE(x_f16k && dy_f16k && dw && workspace, MASIC_ERR_ARG, "%s: null pointer", what);
-    MASIC_REQUIRE(B > 0 && H > 0 && W > 0 && Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0, MASIC_ERR_UNSUPPORTED,
-                  "%s: needs Cin, Cout multiples of 32", what);
-    MASIC_REQUIRE((long)B * (Cin > Cout ? Cin : Cout) * H * W * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "%s: tensor too large for 32-bit offsets", what);
+// Channel groups of up to 96 output x 64 input channels for 3x3 (6 waves: at most two per SIMD, so the 9 accumulator tiles of a wave
+// fit its register budget), 64 x 32 for 5x5 (5 waves, 10 accumulator tiles each); each group: workgroups taking a strided share of
+// the pixel tiles.  Equally shaped groups -- (full, full), (remainder, full), (full, remainder), (remainder, remainder) -- go out as
+// ONE launch each (blockIdx.y).
+struct Wg3Launch { int a0, q0, gq, groups, grid; const Wg3Row* row; };
+struct Wg3Plan { int rc, n, fin_grid, nsplit; Wg3Args a; Wg3Launch l[4]; };
+Wg3Plan plan_wg3(int KS, bool det, int B, int Cin, int Cout, int H, int W) {
+    Wg3Plan p{};
+    p.rc = MASIC_ERR_UNSUPPORTED;
+    if (!(B > 0 && H > 0 && W > 0 && Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0)) {
+        masic_set_error("conv%dx%d_wgrad_f16k: needs Cin, Cout multiples of 32", KS, KS);
+        return p;
+    }
+    if (!((long)B * (Cin > Cout ? Cin : Cout) * H * W * 2 < (1l << 31))) {
+        masic_set_error("conv%dx%d_wgrad_f16k: tensor too large for 32-bit offsets", KS, KS);
+        return p;
+    }
+    p.rc = MASIC_OK;
+    const int SA = KS == 3 ? 96 : 64, SQ = KS == 3 ? 64 : 32;
+    p.a = Wg3Args{nullptr, nullptr, nullptr, B, H, W, Cout / 16, Cin / 16, Cout, Cin, 0, 0, SA, SQ, ceil_div(W, TC), ceil_div(H, TR), 0};
+    p.a.ntiles = p.a.tiles_w * p.a.tiles_h * B;
+    p.nsplit = det ? wg3_det_splits(KS, B, Cin, Cout, H, W) : 0;
+    const int na = Cout / SA, ra = (Cout % SA) / 32, nq = Cin / SQ, rq = (Cin % SQ) / 32, MQ = SQ / 32;
+    auto add = [&](int a0, int q0, int ma, int mq, int ga, int gq) {
+        if (ga <= 0 || gq <= 0 || ma <= 0 || mq <= 0) return;
+        const Wg3Row* row = WG3_ROWS;
+        while (row->ma != ma || row->nq != mq || row->ks != KS) ++row;
+        p.l[p.n++] = Wg3Launch{a0, q0, gq, ga * gq, det ? p.nsplit : wg3_splits(p.a.ntiles, ga * gq, 0), row};
+    };
+    add(0, 0, SA / 32, MQ, na, nq);
+    add(SA * na, 0, ra, MQ, 1, nq);
+    add(0, SQ * nq, SA / 32, rq, na, 1);
+    add(SA * na, SQ * nq, ra, rq, 1, 1);
+    const int blocks = (KS * KS * Cin * Cout + 255) / 256;
+    p.fin_grid = blocks > 2048 ? 2048 : blocks;
+    return p;
+}
+
+// the 3x3 and 5x5 entry points: default (workspace zeroed here, left dirty), clean workspace (zeros on entry, zeros again on exit, no
+// fill launch: as masic_conv2d_wgrad_ws) and deterministic (per-split slabs, no float atomics, workspace contents irrelevant)
+int wg3_run(int KS, bool det, int workspace_clean, const void* x_f16k, const void* dy_f16k, float* dw, void* workspace, int B, int Cin, int Cout,
+            int H, int W, void* stream) {
+    MASIC_REQUIRE(x_f16k && dy_f16k && dw && workspace, MASIC_ERR_ARG, "conv%dx%d_wgrad_f16k: null pointer", KS, KS);
+    Wg3Plan p = plan_wg3(KS, det, B, Cin, Cout, H, W);
+    if (p.rc != MASIC_OK) return p.rc;
     hipStream_t st = (hipStream_t)stream;
-    Wg3Args a{(const unsigned short*)dy_f16k, (const unsigned short*)x_f16k, (float*)workspace, B, H, W, Cout / 16, Cin / 16, Cout, Cin, 0, 0,
-              KS == 3 ? 96 : 64, KS == 3 ? 64 : 32, ceil_div(W, TC), ceil_div(H, TR), 0};
-    a.ntiles = a.tiles_w * a.tiles_h * B;
-    const int grid = det3_splits(B, Cin, Cout, H, W, KS);
-    if (KS == 3) {       // the channel groups of masic_conv3x3_wgrad_f16k_ws, every one with the same `grid`
-        const int na = Cout / 96, ra = (Cout % 96) / 32, nqf = Cin / 64, rq = (Cin % 64) / 32;
-        auto go = [&](int a0, int q0, int ma, int nq, int ga, int gq) {
-            if (ga <= 0 || gq <= 0 || ma <= 0 || nq <= 0) return;
-            a.a0 = a0; a.q0 = q0; a.gq = gq;
-            switch (ma * 4 + nq) {
-                case 1 * 4 + 1: launch<1, 1, 3, true>(a, grid, ga * gq, st); break;
-                case 1 * 4 + 2: launch<1, 2, 3, true>(a, grid, ga * gq, st); break;
-                case 2 * 4 + 1: launch<2, 1, 3, true>(a, grid, ga * gq, st); break;
-                case 2 * 4 + 2: launch<2, 2, 3, true>(a, grid, ga * gq, st); break;
-                case 3 * 4 + 1: launch<3, 1, 3, true>(a, grid, ga * gq, st); break;
-                default: launch<3, 2, 3, true>(a, grid, ga * gq, st); break;
-            }
-        };
-        go(0, 0, 3, 2, na, nqf);
-        go(96 * na, 0, ra, 2, 1, nqf);
-        go(0, 64 * nqf, 3, rq, na, 1);
-        go(96 * na, 64 * nqf, ra, rq, 1, 1);
-    } else {             // masic_conv5x5_wgrad_f16k_ws's groups
-        const int na = Cout / 64, ra = (Cout % 64) / 32, nq = Cin / 32;
-        auto go = [&](int a0, int ma, int ga) {
-            if (ga <= 0 || ma <= 0) return;
-            a.a0 = a0; a.q0 = 0; a.gq = nq;
-            if (ma == 2) launch<2, 1, 5, true>(a, grid, ga * nq, st);
-            else launch<1, 1, 5, true>(a, grid, ga * nq, st);
-        };
-        go(0, 2, na);
-        go(64 * na, ra, 1);
+    if (!det && !workspace_clean && masic_zero_async(workspace, (size_t)KS * KS * Cin * Cout * sizeof(float), st) != hipSuccess) {
+        masic_set_error("conv%dx%d_wgrad_f16k: workspace memset failed", KS, KS);
+        return MASIC_ERR_LAUNCH;
+    }
+    p.a.g16 = (const unsigned short*)dy_f16k; p.a.x16 = (const unsigned short*)x_f16k; p.a.ws = (float*)workspace;
+    for (int i = 0; i < p.n; ++i) {
+        p.a.a0 = p.l[i].a0; p.a.q0 = p.l[i].q0; p.a.gq = p.l[i].gq;
+        p.l[i].row->launch[det](p.a, dim3(p.l[i].grid, p.l[i].groups), st);
     }
     const int T = KS * KS, AQ = Cin * Cout;
-    int tb = (T * AQ + 255) / 256;
-    if (tb > 2048) tb = 2048;
-    hipLaunchKernelGGL(wgrad3_slab_transpose_kernel, dim3(tb), dim3(256), 0, st, (const float*)workspace, dw, AQ, T, grid);
-    return masic_launch_status(what);
+    if (det) hipLaunchKernelGGL(wgrad_slab_transpose_kernel, dim3(p.fin_grid), dim3(256), 0, st, (const float*)workspace, dw, T, AQ, p.nsplit);
+    else hipLaunchKernelGGL(wgrad3_transpose_kernel, dim3(p.fin_grid), dim3(256), 0, st, (float*)workspace, dw, AQ, T, workspace_clean);
+    return masic_launch_status(KS == 3 ? "conv3x3_wgrad_f16k" : "conv5x5_wgrad_f16k");
 }
 
+// ------------------------------------------------------------------------------------------------ host side, 1x1
+// pixel splits: as many as keep the grid within ONE round of the 256 CUs -- every split adds a full output tile of float atomics
+// (64 KiB per workgroup, ~13 us at the chip's atomic rate), which outweighs a second co-resident workgroup: 55 us per layer at
+// 540 workgroups, 40 at 216 (1152 x 768 x 8192).  det: capped so that the weight slabs stay within 64 MiB.
+int wg1_splits(bool det, int B, int CA, int CQ, int HW) {
+    const int base = ceil_div(CA, 128) * ceil_div(CQ, 128), ntk = B * ceil_div(HW, W1_PX);
+    int nsplit = 256 / base;
+    if (nsplit > ntk) nsplit = ntk;
+    const size_t cap = ((size_t)64 << 20) / ((size_t)CA * CQ * sizeof(float));
+    if (det && (size_t)nsplit > cap) nsplit = (int)cap;
+    return nsplit < 1 ? 1 : nsplit;
+}
+int wg1_slots(int bias_of, int CA, int CQ) { return bias_of == 1 ? 2 * ceil_div(CQ, 128) : (bias_of == 2 ? 2 * ceil_div(CA, 128) : 0); }   // bias slots per split: duty_n x 2
+
+struct Wg1Plan { int rc, nb, fin_grid; dim3 grid; Wg1Args a; };
+Wg1Plan plan_wg1(bool det, int bias_of, int B, int CA, int CQ, int HW) {
+    Wg1Plan p{};
+    if (bias_of < 0 || bias_of > 2) {
+        masic_set_error("gemm_wgrad_f16k: bias_of %d", bias_of);
+        p.rc = MASIC_ERR_ARG;
+    } else if (!(B > 0 && HW > 0 && CA > 0 && CQ > 0 && CA % 16 == 0 && CQ % 16 == 0)) {
+        masic_set_error("gemm_wgrad_f16k: channel counts must be multiples of 16");
+        p.rc = MASIC_ERR_UNSUPPORTED;
+    } else if (!((long)B * (CA > CQ ? CA : CQ) * HW * 2 < (1l << 31))) {
+        masic_set_error("gemm_wgrad_f16k: tensor too large for 32-bit offsets");
+        p.rc = MASIC_ERR_UNSUPPORTED;
+    }
+    if (p.rc != MASIC_OK) return p;
+    p.nb = bias_of == 1 ? CA : (bias_of == 2 ? CQ : 0);
+    p.a = Wg1Args{nullptr, nullptr, nullptr, B, HW, CA / 16, CQ / 16, CA, CQ, ceil_div(CQ, 128), ceil_div(HW, W1_PX), 0, 0, nullptr, bias_of};
+    p.a.ntk = B * p.a.tpi;
+    p.a.nsplit = wg1_splits(det, B, CA, CQ, HW);
+    p.grid = dim3(ceil_div(CA, 128) * p.a.q_tiles, 1, p.a.nsplit);
+    const size_t blocks = ((size_t)CA * CQ + p.nb + 255) / 256;
+    p.fin_grid = blocks > 2048 ? 2048 : (int)blocks;
+    return p;
+}
+
+// default: dw (and the bias sums behind it) zeroed here, partial tiles added with float atomics; det: slabs [nsplit][CA][CQ], then the
+// bias partials [nsplit][slots][nb] in the workspace, summed in a fixed order by wgrad1x1_finish
+int wg1_run(bool det, const void* rows_f16k, const void* cols_f16k, float* dw, float* ws, int bias_of, int B, int CA, int CQ, int HW, void* stream) {
+    MASIC_REQUIRE(rows_f16k && cols_f16k && dw && (ws || !det), MASIC_ERR_ARG, "gemm_wgrad_f16k: null pointer");
+    Wg1Plan p = plan_wg1(det, bias_of, B, CA, CQ, HW);
+    if (p.rc != MASIC_OK) return p.rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!det && masic_zero_async(dw, ((size_t)CA * CQ + p.nb) * sizeof(float), st) != hipSuccess) {
+        masic_set_error("gemm_wgrad_f16k: zero fill failed");
+        return MASIC_ERR_LAUNCH;
+    }
+    p.a.g16 = (const unsigned short*)rows_f16k; p.a.x16 = (const unsigned short*)cols_f16k;
+    p.a.dw = det ? ws : dw;
+    p.a.db = p.a.dw + (size_t)(det ? p.a.nsplit : 1) * CA * CQ;
+    if (det) {
+        launch_lds<wgrad1x1_f16k<true>>(p.grid, 256, 2 * W1_BUF, st, p.a);
+        hipLaunchKernelGGL(wgrad1x1_finish, dim3(p.fin_grid), dim3(256), 0, st, (const float*)ws, dw, CA * CQ, p.a.nsplit, p.nb, wg1_slots(bias_of, CA, CQ));
+    } else launch_lds<wgrad1x1_f16k<false>>(p.grid, 256, 2 * W1_BUF, st, p.a);
+    return masic_launch_status("gemm_wgrad_f16k");
+}
 }  // namespace
 
-// the deterministic mode (include/masic_hip.h): per-split slabs, no float atomics, workspace contents irrelevant on entry and exit
+// dW [Cout][Cin][KS][KS] (float32) of Conv2d(Cin -> Cout, KS, s1, p KS/2) from x and dy in F16K (Cin, Cout multiples of 32).  5x5: the
+// stride-1 layers at latent resolution -- encode_hyper's first layer (MASIC.py:222) and the context model (MaskedConv2d, :627; its
+// masked taps get their dense gradient like everywhere else: the reference masks weight.data, not the gradient) -- on the 3x3 kernel
+// with five kernel-row waves per 32 input channels.
+extern "C" size_t masic_conv3x3_wgrad_f16k_workspace_bytes(int Cin, int Cout) { return (size_t)9 * Cin * Cout * sizeof(float); }
+extern "C" size_t masic_conv5x5_wgrad_f16k_workspace_bytes(int Cin, int Cout) { return (size_t)25 * Cin * Cout * sizeof(float); }
+extern "C" int masic_conv3x3_wgrad_f16k_ws(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
+                                           int B, int Cin, int Cout, int H, int W, int workspace_clean, void* stream) {
+    return wg3_run(3, false, workspace_clean, x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, stream);
+}
+extern "C" int masic_conv5x5_wgrad_f16k_ws(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
+                                           int B, int Cin, int Cout, int H, int W, int workspace_clean, void* stream) {
+    return wg3_run(5, false, workspace_clean, x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, stream);
+}
+// the deterministic mode (include/masic_hip.h)
 extern "C" size_t masic_conv3x3_wgrad_f16k_det_workspace_bytes(int B, int Cin, int Cout, int H, int W) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)det3_splits(B, Cin, Cout, H, W, 3) * 9 * Cin * Cout * sizeof(float);
-}
-extern "C" int masic_conv3x3_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
-                                            int B, int Cin, int Cout, int H, int W, void* stream) {
-    return wgrad_k3k5_det(x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, 3, stream);
+    return (size_t)wg3_det_splits(3, B, Cin, Cout, H, W) * 9 * Cin * Cout * sizeof(float);
 }
 extern "C" size_t masic_conv5x5_wgrad_f16k_det_workspace_bytes(int B, int Cin, int Cout, int H, int W) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)det3_splits(B, Cin, Cout, H, W, 5) * 25 * Cin * Cout * sizeof(float);
+    return (size_t)wg3_det_splits(5, B, Cin, Cout, H, W) * 25 * Cin * Cout * sizeof(float);
+}
+extern "C" int masic_conv3x3_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
+                                            int B, int Cin, int Cout, int H, int W, void* stream) {
+    return wg3_run(3, true, 0, x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, stream);
 }
 extern "C" int masic_conv5x5_wgrad_f16k_det(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
                                             int B, int Cin, int Cout, int H, int W, void* stream) {
-    return wgrad_k3k5_det(x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, 5, stream);
-}
-
-extern "C" size_t masic_conv3x3_wgrad_f16k_workspace_bytes(int Cin, int Cout) { return (size_t)9 * Cin * Cout * sizeof(float); }
-
-// dW [Cout][Cin][3][3] (float32) of Conv2d(Cin -> Cout, k3, s1, p1) from x and dy in F16K (Cin, Cout multiples of 32).
-extern "C" int masic_conv3x3_wgrad_f16k(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
-                                        int B, int Cin, int Cout, int H, int W, void* stream) {
-    return masic_conv3x3_wgrad_f16k_ws(x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, 0, stream);
-}
-
-// workspace_clean: as masic_conv2d_wgrad_ws -- zeros on entry, zeros again on exit, no fill launch
-extern "C" int masic_conv3x3_wgrad_f16k_ws(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
-                                           int B, int Cin, int Cout, int H, int W, int workspace_clean, void* stream) {
-    MASIC_REQUIRE(x_f16k && dy_f16k && dw && workspace, MASIC_ERR_ARG, "conv3x3_wgrad_f16k: null pointer");
-    MASIC_REQUIRE(B > 0 && H > 0 && W > 0 && Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0, MASIC_ERR_UNSUPPORTED,
-                  "conv3x3_wgrad_f16k: needs Cin, Cout multiples of 32");
-    MASIC_REQUIRE((long)B * (Cin > Cout ? Cin : Cout) * H * W * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "conv3x3_wgrad_f16k: tensor too large for 32-bit offsets");
-    hipStream_t st = (hipStream_t)stream;
-    if (!workspace_clean && masic_zero_async(workspace, masic_conv3x3_wgrad_f16k_workspace_bytes(Cin, Cout), st) != hipSuccess) {
-        masic_set_error("conv3x3_wgrad_f16k: workspace memset failed");
-        return MASIC_ERR_LAUNCH;
-    }
-    Wg3Args a{(const unsigned short*)dy_f16k, (const unsigned short*)x_f16k, (float*)workspace, B, H, W, Cout / 16, Cin / 16, Cout, Cin, 0, 0, 96, 64,
-              ceil_div(W, TC), ceil_div(H, TR), 0};
-    a.ntiles = a.tiles_w * a.tiles_h * B;
-    // channel groups of up to 96 output x 64 input channels (6 waves: at most two per SIMD, so the 9 accumulator tiles of a wave
-    // fit its register budget); each group: one workgroup per CU taking a strided share of the pixel tiles.  Equally shaped groups
-    // -- (full, full), (remainder, full), (full, remainder), (remainder, remainder) -- go out as ONE launch each (blockIdx.y).
-    const int na = Cout / 96, ra = (Cout % 96) / 32, nqf = Cin / 64, rq = (Cin % 64) / 32;
-    auto go = [&](int a0, int q0, int ma, int nq, int ga, int gq) {
-        if (ga <= 0 || gq <= 0 || ma <= 0 || nq <= 0) return;
-        a.a0 = a0; a.q0 = q0; a.gq = gq;
-        // workgroups per channel group: 256 where the picture has that many tiles (Independent_EN); at latent resolution (64 tiles,
-        // up to 16 groups: the hyper transforms) one round of the CUs over ALL groups -- every workgroup ends with a full group tile
-        // of float atomics (55 296 of them), and 1024 single-tile workgroups spent 190 us of which ~150 were those atomics
-        int grid = a.ntiles < 256 ? a.ntiles : 256;
-        if (a.ntiles < 256 && grid * ga * gq > 256) grid = 256 / (ga * gq) > 0 ? 256 / (ga * gq) : 1;
-        switch (ma * 4 + nq) {
-            case 1 * 4 + 1: launch<1, 1>(a, grid, ga * gq, st); break;
-            case 1 * 4 + 2: launch<1, 2>(a, grid, ga * gq, st); break;
-            case 2 * 4 + 1: launch<2, 1>(a, grid, ga * gq, st); break;
-            case 2 * 4 + 2: launch<2, 2>(a, grid, ga * gq, st); break;
-            case 3 * 4 + 1: launch<3, 1>(a, grid, ga * gq, st); break;
-            default: launch<3, 2>(a, grid, ga * gq, st); break;
-        }
-    };
-    go(0, 0, 3, 2, na, nqf);
-    go(96 * na, 0, ra, 2, 1, nqf);
-    go(0, 64 * nqf, 3, rq, na, 1);
-    go(96 * na, 64 * nqf, ra, rq, 1, 1);
-    const int AQ = Cin * Cout;
-    int tb = (9 * AQ + 255) / 256;
-    if (tb > 2048) tb = 2048;
-    hipLaunchKernelGGL(wgrad3_transpose_kernel, dim3(tb), dim3(256), 0, st, (float*)workspace, dw, AQ, 9, workspace_clean);
-    return masic_launch_status("conv3x3_wgrad_f16k");
-}
-
-extern "C" size_t masic_conv5x5_wgrad_f16k_workspace_bytes(int Cin, int Cout) { return (size_t)25 * Cin * Cout * sizeof(float); }
-
-// dW [Cout][Cin][5][5] (float32) of Conv2d(Cin -> Cout, k5, s1, p2) from x and dy in F16K (Cin, Cout multiples of 32): the 5x5
-// stride-1 layers at latent resolution -- encode_hyper's first layer (MASIC.py:222) and the context model (MaskedConv2d, :627; its
-// masked taps get their dense gradient like everywhere else: the reference masks weight.data, not the gradient).  The 3x3 kernel
-// with five kernel-row waves per 32 input channels: workgroup = 64 output x 32 input channels x 25 taps (5 waves, 10 accumulator
-// tiles each).  workspace: masic_conv5x5_wgrad_f16k_workspace_bytes; workspace_clean as masic_conv3x3_wgrad_f16k_ws.
-extern "C" int masic_conv5x5_wgrad_f16k_ws(const void* x_f16k, const void* dy_f16k, float* dw, void* workspace,
-                                           int B, int Cin, int Cout, int H, int W, int workspace_clean, void* stream) {
-    MASIC_REQUIRE(x_f16k && dy_f16k && dw && workspace, MASIC_ERR_ARG, "conv5x5_wgrad_f16k: null pointer");
-    MASIC_REQUIRE(B > 0 && H > 0 && W > 0 && Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0, MASIC_ERR_UNSUPPORTED,
-                  "conv5x5_wgrad_f16k: needs Cin, Cout multiples of 32");
-    MASIC_REQUIRE((long)B * (Cin > Cout ? Cin : Cout) * H * W * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "conv5x5_wgrad_f16k: tensor too large for 32-bit offsets");
-    hipStream_t st = (hipStream_t)stream;
-    if (!workspace_clean && masic_zero_async(workspace, masic_conv5x5_wgrad_f16k_workspace_bytes(Cin, Cout), st) != hipSuccess) {
-        masic_set_error("conv5x5_wgrad_f16k: workspace memset failed");
-        return MASIC_ERR_LAUNCH;
-    }
-    Wg3Args a{(const unsigned short*)dy_f16k, (const unsigned short*)x_f16k, (float*)workspace, B, H, W, Cout / 16, Cin / 16, Cout, Cin, 0, 0, 64, 32,
-              ceil_div(W, TC), ceil_div(H, TR), 0};
-    a.ntiles = a.tiles_w * a.tiles_h * B;
-    const int na = Cout / 64, ra = (Cout % 64) / 32, nq = Cin / 32;
-    auto go = [&](int a0, int ma, int ga) {
-        if (ga <= 0 || ma <= 0) return;
-        a.a0 = a0; a.q0 = 0; a.gq = nq;
-        int grid = a.ntiles < 256 ? a.ntiles : 256;          // (one round of the CUs over all groups at latent resolution, as the 3x3 layers)
-        if (a.ntiles < 256 && grid * ga * nq > 256) grid = 256 / (ga * nq) > 0 ? 256 / (ga * nq) : 1;
-        if (ma == 2) launch<2, 1, 5>(a, grid, ga * nq, st);
-        else launch<1, 1, 5>(a, grid, ga * nq, st);
-    };
-    go(0, 2, na);
-    go(64 * na, ra, 1);
-    const int AQ = Cin * Cout;
-    int tb = (25 * AQ + 255) / 256;
-    if (tb > 2048) tb = 2048;
-    hipLaunchKernelGGL(wgrad3_transpose_kernel, dim3(tb), dim3(256), 0, st, (float*)workspace, dw, AQ, 25, workspace_clean);
-    return masic_launch_status("conv5x5_wgrad_f16k");
+    return wg3_run(5, true, 0, x_f16k, dy_f16k, dw, workspace, B, Cin, Cout, H, W, stream);
 }
 
 constexpr int WP_MAX_WGS = 512;
@@ -849,12 +828,7 @@ extern "C" int masic_pic_wgrad_f16k(const void* p_f16k, const float* q, float* d
     WgPicArgs a{(const unsigned short*)p_f16k, q, (float*)workspace, B, Hc, Wc, q_ctot, q_coff, ceil_div(Hc * Wc, 64), 0};
     a.ntk = a.B * a.tpi;
     const int grid = a.ntk < WP_MAX_WGS ? a.ntk : WP_MAX_WGS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_pic_f16k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(wgrad_pic_f16k, dim3(grid), dim3(256), WP_LDS, st, a);
+    launch_lds<wgrad_pic_f16k>(dim3(grid), 256, WP_LDS, st, a);
     hipLaunchKernelGGL(wgrad_pic_finish, dim3(ceil_div(WP_NOUT, 64)), dim3(256), 0, st, (const float*)workspace, dw, grid);
     return masic_launch_status("pic_wgrad_f16k");
 }
@@ -862,90 +836,58 @@ extern "C" int masic_pic_wgrad_f16k(const void* p_f16k, const float* q, float* d
 // dw [CA][CQ] (float32) = sum over batch and pixels of rows[b][a][p] * cols[b][q][p], both operands F16K ([B][C/16][HW][16] bf16),
 // CA, CQ multiples of 16.  For a Conv2d(Cin -> Cout, k1) weight [Cout][Cin]: rows = dy, cols = x; for the ConvTranspose2d(k1) form
 // [Cin][Cout] (reference MASIC.py:338-376): rows = x, cols = dy.
-extern "C" int masic_gemm_wgrad_f16k(const void* rows_f16k, const void* cols_f16k, float* dw, int B, int CA, int CQ, int HW, void* stream) {
-    return masic_gemm_wgrad_bias_f16k(rows_f16k, cols_f16k, dw, 0, B, CA, CQ, HW, stream);
-}
-
 // bias_of: 0 none; 1: dw[CA*CQ .. CA*CQ + CA) = sums of the rows operand over batch and pixels; 2: dw[CA*CQ .. + CQ) = sums of the
 // columns operand -- the bias gradient of the layer (dy = rows of a Conv2d, columns of a ConvTranspose2d), in the same launch
 extern "C" int masic_gemm_wgrad_bias_f16k(const void* rows_f16k, const void* cols_f16k, float* dw, int bias_of, int B, int CA, int CQ, int HW,
                                           void* stream) {
-    MASIC_REQUIRE(rows_f16k && cols_f16k && dw, MASIC_ERR_ARG, "gemm_wgrad_f16k: null pointer");
-    MASIC_REQUIRE(bias_of >= 0 && bias_of <= 2, MASIC_ERR_ARG, "gemm_wgrad_f16k: bias_of %d", bias_of);
-    MASIC_REQUIRE(B > 0 && HW > 0 && CA > 0 && CQ > 0 && CA % 16 == 0 && CQ % 16 == 0, MASIC_ERR_UNSUPPORTED, "gemm_wgrad_f16k: channel counts must be multiples of 16");
-    MASIC_REQUIRE((long)B * (CA > CQ ? CA : CQ) * HW * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "gemm_wgrad_f16k: tensor too large for 32-bit offsets");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t nb = bias_of == 1 ? CA : (bias_of == 2 ? CQ : 0);
-    if (masic_zero_async(dw, ((size_t)CA * CQ + nb) * sizeof(float), st) != hipSuccess) {
-        masic_set_error("gemm_wgrad_f16k: zero fill failed");
-        return MASIC_ERR_LAUNCH;
-    }
-    Wg1Args a{(const unsigned short*)rows_f16k, (const unsigned short*)cols_f16k, dw, B, HW, CA / 16, CQ / 16, CA, CQ, ceil_div(CQ, 128), ceil_div(HW, W1_PX), 0, 0,
-               dw + (size_t)CA * CQ, bias_of};
-    a.ntk = a.B * a.tpi;
-    const int base = ceil_div(CA, 128) * a.q_tiles;
-    // pixel splits: as many as keep the grid within ONE round of the 256 CUs -- every split adds a full output tile of float atomics
-    // (64 KiB per workgroup, ~13 us at the chip's atomic rate), which outweighs a second co-resident workgroup: 55 us per layer at
-    // 540 workgroups, 40 at 216 (1152 x 768 x 8192)
-    constexpr int target_wgs = 256;
-    int nsplit = target_wgs / base;
-    if (nsplit > a.ntk) nsplit = a.ntk;
-    a.nsplit = nsplit < 1 ? 1 : nsplit;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad1x1_f16k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(wgrad1x1_f16k<false>, dim3(base, 1, a.nsplit), dim3(256), 2 * W1_BUF, st, a);
-    return masic_launch_status("gemm_wgrad_f16k");
+    return wg1_run(false, rows_f16k, cols_f16k, dw, nullptr, bias_of, B, CA, CQ, HW, stream);
 }
-
-namespace {
-// the deterministic 1x1 form's splits: the default's, capped so that the weight slabs stay within 64 MiB; bias slots per split: duty_n x 2
-int det1_splits(int B, int CA, int CQ, int HW) {
-    const int base = ceil_div(CA, 128) * ceil_div(CQ, 128), ntk = B * ceil_div(HW, W1_PX);
-    int nsplit = 256 / base;
-    if (nsplit > ntk) nsplit = ntk;
-    const size_t cap = ((size_t)64 << 20) / ((size_t)CA * CQ * sizeof(float));
-    if ((size_t)nsplit > cap) nsplit = (int)cap;
-    return nsplit < 1 ? 1 : nsplit;
-}
-int det1_slots(int bias_of, int CA, int CQ) { return bias_of == 1 ? 2 * ceil_div(CQ, 128) : (bias_of == 2 ? 2 * ceil_div(CA, 128) : 0); }
-}  // namespace
-
 // slabs [nsplit][CA][CQ], then the bias partials [nsplit][slots][nb]; the total rounded up to whole weights
 extern "C" size_t masic_gemm_wgrad_bias_f16k_det_workspace_bytes(int bias_of, int B, int CA, int CQ, int HW) {
     if (B <= 0 || CA <= 0 || CQ <= 0 || HW <= 0 || bias_of < 0 || bias_of > 2) return 0;
     const size_t w = (size_t)CA * CQ, nb = bias_of == 1 ? CA : (bias_of == 2 ? CQ : 0);
-    const int ns = det1_splits(B, CA, CQ, HW);
-    const size_t n = (size_t)ns * w + (size_t)ns * det1_slots(bias_of, CA, CQ) * nb;
+    const int ns = wg1_splits(true, B, CA, CQ, HW);
+    const size_t n = (size_t)ns * w + (size_t)ns * wg1_slots(bias_of, CA, CQ) * nb;
     return (n + w - 1) / w * w * sizeof(float);
 }
-
 extern "C" int masic_gemm_wgrad_bias_f16k_det(const void* rows_f16k, const void* cols_f16k, float* dw, void* workspace, int bias_of, int B, int CA,
                                               int CQ, int HW, void* stream) {
-    MASIC_REQUIRE(rows_f16k && cols_f16k && dw && workspace, MASIC_ERR_ARG, "gemm_wgrad_f16k_det: null pointer");
-    MASIC_REQUIRE(bias_of >= 0 && bias_of <= 2, MASIC_ERR_ARG, "gemm_wgrad_f16k_det: bias_of %d", bias_of);
-    MASIC_REQUIRE(B > 0 && HW > 0 && CA > 0 && CQ > 0 && CA % 16 == 0 && CQ % 16 == 0, MASIC_ERR_UNSUPPORTED, "gemm_wgrad_f16k_det: channel counts must be multiples of 16");
-    MASIC_REQUIRE((long)B * (CA > CQ ? CA : CQ) * HW * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "gemm_wgrad_f16k_det: tensor too large for 32-bit offsets");
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = bias_of == 1 ? CA : (bias_of == 2 ? CQ : 0);
-    float* ws = (float*)workspace;
-    Wg1Args a{(const unsigned short*)rows_f16k, (const unsigned short*)cols_f16k, ws, B, HW, CA / 16, CQ / 16, CA, CQ, ceil_div(CQ, 128), ceil_div(HW, W1_PX), 0, 0,
-              nullptr, bias_of};
-    a.ntk = a.B * a.tpi;
-    a.nsplit = det1_splits(B, CA, CQ, HW);
-    a.db = ws + (size_t)a.nsplit * CA * CQ;
-    const int base = ceil_div(CA, 128) * a.q_tiles;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad1x1_f16k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
+    return wg1_run(true, rows_f16k, cols_f16k, dw, (float*)workspace, bias_of, B, CA, CQ, HW, stream);
+}
+
+// the launches of the call that (kind, flags) names, one line each (include/masic_hip.h)
+extern "C" int masic_wgrad_f16k_plan_name(int kind, int s0, int s1, int s2, int s3, int s4, int flags, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "wgrad_f16k_plan_name: no buffer");
+    buf[0] = 0;
+    const bool det = flags & MASIC_WGRAD_DET, clean = flags & MASIC_WGRAD_CLEAN;
+    MASIC_REQUIRE((kind == 1 || kind == 3 || kind == 5) && !(flags & ~5) && !(clean && (det || kind == 1)), MASIC_ERR_ARG,
+                  "wgrad_f16k_plan_name: no such form (kind %d, flags %d)", kind, flags);
+    bool ok = true;
+    char name[64];
+    if (kind == 1) {
+        const Wg1Plan p = plan_wg1(det, s0, s1, s2, s3, s4);
+        if (p.rc != MASIC_OK) return p.rc;
+        ok = (det || masic_plan_fill_line(buf, n, ((size_t)s2 * s3 + p.nb) * sizeof(float))) &&
+             masic_plan_line(buf, n, det ? "wgrad1x1_f16k<true>" : "wgrad1x1_f16k<false>", p.grid, 256, 2 * W1_BUF) &&
+             (!det || masic_plan_line(buf, n, "wgrad1x1_finish", dim3(p.fin_grid), 256, 0));
+    } else {
+        const Wg3Plan p = plan_wg3(kind, det, s0, s1, s2, s3, s4);
+        if (p.rc != MASIC_OK) return p.rc;
+        ok = det || clean || masic_plan_fill_line(buf, n, (size_t)kind * kind * s1 * s2 * sizeof(float));
+        for (int i = 0; i < p.n && ok; ++i) {
+            const Wg3Row& r = *p.l[i].row;
+            snprintf(name, sizeof name, "wgrad3x3_f16k<%d, %d, %d, %s>", r.ma, r.nq, r.ks, det ? "true" : "false");
+            ok = masic_plan_line(buf, n, name, dim3(p.l[i].grid, p.l[i].groups), r.nq * r.ks * 64, r.lds);
+        }
+        ok = ok && masic_plan_line(buf, n, det ? "wgrad_slab_transpose_kernel" : "wgrad3_transpose_kernel", dim3(p.fin_grid), 256, 0);
     }
-    hipLaunchKernelGGL(wgrad1x1_f16k<true>, dim3(base, 1, a.nsplit), dim3(256), 2 * W1_BUF, st, a);
-    const size_t total = (size_t)CA * CQ + nb;
-    int tb = (int)((total + 255) / 256);
-    if (tb > 2048) tb = 2048;
-    hipLaunchKernelGGL(wgrad1x1_finish, dim3(tb), dim3(256), 0, st, (const float*)ws, dw, CA * CQ, a.nsplit, nb, det1_slots(bias_of, CA, CQ));
-    return masic_launch_status("gemm_wgrad_f16k_det");
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "wgrad_f16k_plan_name: buffer of %zu bytes too small", n);
+    return MASIC_OK;
+}
+// every compiled wgrad3x3_f16k: rows 0 .., det 0 / 1; MASIC_ERR_ARG past the last row
+extern "C" int masic_wgrad_f16k_row_name(int row, int det, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && row >= 0 && row < WG3_NROWS && (det == 0 || det == 1), MASIC_ERR_ARG, "wgrad_f16k_row_name: row %d", row);
+    snprintf(buf, n, "wgrad3x3_f16k<%d, %d, %d, %s>", WG3_ROWS[row].ma, WG3_ROWS[row].nq, WG3_ROWS[row].ks, det ? "true" : "false");
+    return MASIC_OK;
 }

@@ -708,14 +708,24 @@ def copy_view(x, out, out_coff):
     return out
 
 
-_ws = {}
+_WS = {}
+
+
+def _cached_ws(kind, device, nbytes, zeroed=False):
+    """Persistent workspace of nbytes bytes for the kernels of `kind`.  One buffer per (kind, device, stream, bytes): launches on one
+    stream are ordered, two streams never share a buffer -- their kernels must not share partial sums.  zeroed: filled with zeros ONCE;
+    the weight-gradient kernels accumulate into it with float atomics and their last pass puts the zeros back (masic_conv2d_wgrad_ws), so
+    a step's ~80 weight gradients need no fill launch each.  Otherwise the contents are irrelevant on entry and exit."""
+    key = (kind, device, int(_stream().value or 0), int(nbytes))
+    ws = _WS.get(key)
+    if ws is None:
+        n = (int(nbytes) + 3) // 4
+        ws = _WS[key] = zeros(n, torch.float32, device) if zeroed else torch.empty(n, dtype=torch.float32, device=device)
+    return ws
 
 
 def _workspace(device):
-    key = (device.type, device.index, int(_stream().value or 0))
-    if key not in _ws:
-        _ws[key] = torch.empty(lib.masic_reduce_workspace_bytes() // 8, dtype=torch.float64, device=device)
-    return _ws[key]
+    return _cached_ws("reduce", device, lib.masic_reduce_workspace_bytes())
 
 
 def sum_log(x):
@@ -736,9 +746,6 @@ def sse(a, b):
     return out[0]
 
 
-_RD_WS = {}
-
-
 def _rd_ptrs(liks):
     n = len(liks)
     arr = (ctypes.c_void_p * max(n, 1))(*[l.data_ptr() for l in liks])
@@ -754,10 +761,7 @@ def rd_loss(x1_hat, x1, x2_hat, x2, liks, cb, cm):
     if not (x1_hat.numel() == x1.numel() == x2_hat.numel() == x2.numel()) or len(liks) > 4:
         raise RuntimeError("masic_amd.rd_loss: pictures of one size and at most four likelihood tensors")
     dev = x1.device
-    key = (dev, int(_stream().value or 0))
-    ws = _RD_WS.get(key)
-    if ws is None:
-        ws = _RD_WS[key] = torch.empty(lib.masic_rd_loss_workspace_bytes() // 8, dtype=torch.float64, device=dev)
+    ws = _cached_ws("rd_loss", dev, lib.masic_rd_loss_workspace_bytes())
     loss = torch.empty((), dtype=torch.float32, device=dev)
     vals = [torch.empty((), dtype=torch.float64, device=dev) for _ in range(3 + len(liks))]
     arr, cnt = _rd_ptrs(liks)
@@ -844,22 +848,13 @@ def gdn_bwd_post(x, s, u):
     return dx
 
 
-_GDN_BWD_WS = {}
-
-
-_GDN_BWD_SMALL_WS = {}
-
-
 def gdn_bwd_small(x, g, beta, gamma, inverse=False, beta_min=1e-6):
     """(dx, d beta, d gamma) of GDN / inverse GDN with C <= 4 channels in one pass (float32; masic_gdn_bwd_small)."""
     _dev(x, "x"); _dev(g, "g")
     B, C, H, W = x.shape
     if g.shape != x.shape or not (x.is_contiguous() and g.is_contiguous()):
         raise RuntimeError("masic_amd.gdn_bwd_small: x and g must be contiguous and of one shape")
-    key = (x.device, int(_stream().value or 0))
-    ws = _GDN_BWD_SMALL_WS.get(key)
-    if ws is None:
-        ws = _GDN_BWD_SMALL_WS[key] = torch.empty(lib.masic_gdn_bwd_small_workspace_bytes(), dtype=torch.uint8, device=x.device)
+    ws = _cached_ws("gdn_bwd_small", x.device, lib.masic_gdn_bwd_small_workspace_bytes())
     gx = torch.empty_like(x)
     g_beta = torch.empty(C, dtype=torch.float32, device=x.device)
     g_gamma = torch.empty(C, C, dtype=torch.float32, device=x.device)
@@ -874,10 +869,7 @@ def gdn_bwd_fused(x, g, beta, gamma, inverse=False, beta_min=1e-6):
     B, C, H, W = x.shape
     if g.shape != x.shape or not (x.is_contiguous() and g.is_contiguous()):
         raise RuntimeError("masic_amd.gdn_bwd_fused: x and g must be contiguous and of one shape")
-    key = (x.device, int(_stream().value or 0))        # per stream: two streams' kernels must not share the partial sums
-    ws = _GDN_BWD_WS.get(key)
-    if ws is None:
-        ws = _GDN_BWD_WS[key] = torch.empty(lib.masic_gdn_bwd_fused_workspace_bytes(), dtype=torch.uint8, device=x.device)
+    ws = _cached_ws("gdn_bwd", x.device, lib.masic_gdn_bwd_fused_workspace_bytes())
     gx = torch.empty_like(x)
     g_beta = torch.empty(C, dtype=torch.float32, device=x.device)
     g_gamma = torch.empty(C, C, dtype=torch.float32, device=x.device)
@@ -902,10 +894,7 @@ def gdn_bwd_fused_ex(x, g, shape, beta, gamma, inverse=False, beta_min=1e-6, wan
     if not (want_nchw or want_f16k or want_b16):
         raise RuntimeError("masic_amd.gdn_bwd_fused_ex: no output requested")
     dev = x.device
-    key = (dev, int(_stream().value or 0))
-    ws = _GDN_BWD_WS.get(key)
-    if ws is None:
-        ws = _GDN_BWD_WS[key] = torch.empty(lib.masic_gdn_bwd_fused_workspace_bytes(), dtype=torch.uint8, device=dev)
+    ws = _cached_ws("gdn_bwd", dev, lib.masic_gdn_bwd_fused_workspace_bytes())
     gx = torch.empty(shape, dtype=torch.float32, device=dev) if (want_nchw and not want_b16) else None
     gxb = torch.empty(shape, dtype=torch.bfloat16, device=dev) if want_b16 else None
     gx16 = torch.empty(B * C * H * W, dtype=torch.int16, device=dev) if want_f16k else None
@@ -942,59 +931,38 @@ def conv2d_wgrad(x, dy, desc, weight_shape):
     nbytes = _desc_query("masic_conv2d_wgrad_workspace_bytes", desc)
     if desc.Cin * desc.Cout * desc.KH * desc.KW != dw.numel() or nbytes < dw.numel() * 4:
         raise RuntimeError("masic_amd.conv2d_wgrad: weight shape does not match the descriptor")
-    if _det_mode():
-        ws = _det_workspace(x.device, _desc_query("masic_conv2d_wgrad_det_workspace_bytes", desc))
-        fn = lib.masic_conv2d_wgrad_bf16in_det if b16 else lib.masic_conv2d_wgrad_det
-        check(fn(_p(x), _p(dy), _p(dw), _p(ws), ctypes.byref(desc), _stream()), "conv2d_wgrad_det")
-        return dw
-    ws = _clean_workspace(x.device, nbytes // 4)       # (>= the weight: the few-channel 5x5 kernel keeps per-workgroup partials in it)
-    try:
-        fn = lib.masic_conv2d_wgrad_bf16in if b16 else lib.masic_conv2d_wgrad_ws
-        check(fn(_p(x), _p(dy), _p(dw), _p(ws), ctypes.byref(desc), 1, _stream()), "conv2d_wgrad")
-    except Exception:
-        _drop_workspace(x.device, nbytes // 4)         # an error part-way may have left it dirty
-        raise
+    fn, fn_det = (lib.masic_conv2d_wgrad_bf16in, lib.masic_conv2d_wgrad_bf16in_det) if b16 else (lib.masic_conv2d_wgrad_ws, lib.masic_conv2d_wgrad_det)
+    _wgrad_call(lambda ws: fn(_p(x), _p(dy), _p(dw), ws, ctypes.byref(desc), 1, _stream()),       # (nbytes >= the weight: the few-channel
+                lambda ws: fn_det(_p(x), _p(dy), _p(dw), ws, ctypes.byref(desc), _stream()),      #  5x5 kernel keeps per-workgroup partials)
+                x.device, nbytes, lambda: _desc_query("masic_conv2d_wgrad_det_workspace_bytes", desc), "conv2d_wgrad")
     return dw
 
 
-_CLEAN_WS = {}
-
-
-def _clean_workspace(device, numel):
-    """Persistent float32 workspace of the weight-gradient kernels, zeroed ONCE: the kernels accumulate into it with float atomics and
-    their last pass puts the zeros back (masic_conv2d_wgrad_ws), so a step's ~80 weight gradients need no fill launch each.  One buffer
-    per (device, stream, size): launches on one stream are ordered, two streams never share a buffer."""
-    key = (device, int(_stream().value or 0), int(numel))
-    ws = _CLEAN_WS.get(key)
-    if ws is None:
-        ws = _CLEAN_WS[key] = zeros(numel, torch.float32, device)
-    return ws
-
-
-def _drop_workspace(device, numel):
-    _CLEAN_WS.pop((device, int(_stream().value or 0), int(numel)), None)
-
-
-_DET_WS = {}
-
-
-def _det_workspace(device, nbytes):
-    """Slab workspace of the deterministic weight-gradient kernels (masic_amd/determinism.py): contents irrelevant on entry and exit, so
-    it is never filled.  One buffer per (device, stream, size), as _clean_workspace: two streams never share one."""
+def _det_ws(device, nbytes):
     if nbytes <= 0:
         raise RuntimeError("masic_amd: the deterministic workspace query rejected the shape")
-    key = (device, int(_stream().value or 0), int(nbytes))
-    ws = _DET_WS.get(key)
-    if ws is None:
-        ws = _DET_WS[key] = torch.empty((int(nbytes) + 3) // 4, dtype=torch.float32, device=device)
-    return ws
+    return _cached_ws("det", device, nbytes)
+
+
+def _wgrad_call(fn_clean, fn_det, device, nbytes, det_bytes, what):
+    """One weight gradient with its cached workspace: fn_det(ws) on the slab workspace (det_bytes() bytes) in deterministic mode
+    (masic_amd/determinism.py), else fn_clean(ws) on the zeroed persistent one (nbytes bytes), which is dropped if the call fails -- an
+    error part-way may have left it dirty."""
+    if _det_mode():
+        return check(fn_det(_p(_det_ws(device, det_bytes()))), what + "_det")
+    try:
+        check(fn_clean(_p(_cached_ws("clean", device, nbytes, zeroed=True))), what)
+    except Exception:
+        _WS.pop(("clean", device, int(_stream().value or 0), int(nbytes)), None)
+        raise
 
 
 def det_workspace_bytes():
     """Bytes held by the deterministic mode's cached workspaces: {(device, stream): bytes}."""
     out = {}
-    for (dev, st, n), ws in _DET_WS.items():
-        out[(dev, st)] = out.get((dev, st), 0) + ws.numel() * 4
+    for (kind, dev, st, n), ws in _WS.items():
+        if kind == "det":
+            out[(dev, st)] = out.get((dev, st), 0) + ws.numel() * 4
     return out
 
 
@@ -1849,7 +1817,7 @@ def deconv_s2_as_conv_weight_dev(weight, bias=None):
 
 
 def gemm_wgrad_f16k(rows16, cols16, B, CA, CQ, HW, bias_of=0):
-    """dw [CA, CQ] = sum_{b,p} rows[b, a, p] * cols[b, q, p] from F16K operands (masic_gemm_wgrad_f16k): the weight gradient of a 1x1
+    """dw [CA, CQ] = sum_{b,p} rows[b, a, p] * cols[b, q, p] from F16K operands (masic_gemm_wgrad_bias_f16k): the weight gradient of a 1x1
     layer -- Conv2d: (dy, x) -> [Cout, Cin]; ConvTranspose2d(k=1): (x, dy) -> [Cin, Cout].
     bias_of = 1 / 2: also the sums over batch and pixels of the rows / columns operand (the layer's bias gradient when that operand is
     dy) from the same launch; returns (dw, sums) -- two views of one buffer."""
@@ -1858,15 +1826,12 @@ def gemm_wgrad_f16k(rows16, cols16, B, CA, CQ, HW, bias_of=0):
     nb = CA if bias_of == 1 else (CQ if bias_of == 2 else 0)
     out = torch.empty(CA * CQ + nb, dtype=torch.float32, device=rows16.device)
     if _det_mode():
-        ws = _det_workspace(rows16.device, _int_query("masic_gemm_wgrad_bias_f16k_det_workspace_bytes", int(bias_of), B, CA, CQ, HW))
+        ws = _det_ws(rows16.device, _int_query("masic_gemm_wgrad_bias_f16k_det_workspace_bytes", int(bias_of), B, CA, CQ, HW))
         check(lib.masic_gemm_wgrad_bias_f16k_det(_p(rows16), _p(cols16), _p(out), _p(ws), int(bias_of), B, CA, CQ, HW, _stream()), "gemm_wgrad_f16k_det")
     else:
         check(lib.masic_gemm_wgrad_bias_f16k(_p(rows16), _p(cols16), _p(out), int(bias_of), B, CA, CQ, HW, _stream()), "gemm_wgrad_f16k")
     dw = out[:CA * CQ].view(CA, CQ)
     return (dw, out[CA * CQ:]) if nb else dw
-
-
-_PIC_WGRAD_WS = {}
 
 
 def pic_wgrad_f16k(p16, q, B, Hc, Wc, q_coff=0):
@@ -1876,51 +1841,33 @@ def pic_wgrad_f16k(p16, q, B, Hc, Wc, q_coff=0):
     if p16.dtype != torch.int16 or p16.numel() != B * 128 * Hc * Wc or q.dim() != 4 or q.shape[0] != B or tuple(q.shape[2:]) != (2 * Hc, 2 * Wc) \
             or q_coff + 3 > q.shape[1]:
         raise RuntimeError("masic_amd.pic_wgrad_f16k: operand shapes do not match (B, 128, Hc, Wc) / (B, >= 3, 2 Hc, 2 Wc)")
-    key = (q.device, int(_stream().value or 0))
-    ws = _PIC_WGRAD_WS.get(key)
-    if ws is None:
-        ws = _PIC_WGRAD_WS[key] = torch.empty(lib.masic_pic_wgrad_f16k_workspace_bytes() // 4, dtype=torch.float32, device=q.device)
+    ws = _cached_ws("pic_wgrad", q.device, lib.masic_pic_wgrad_f16k_workspace_bytes())
     dw = torch.empty(128 * 75, dtype=torch.float32, device=q.device)
     check(lib.masic_pic_wgrad_f16k(_p(p16), _p(q), _p(dw), _p(ws), B, Hc, Wc, q.shape[1], q_coff, _stream()), "pic_wgrad_f16k")
     return dw
 
 
+def _conv_wgrad_f16k(KS, x16, dy16, B, Cin, Cout, H, W):
+    name = f"conv{KS}x{KS}_wgrad_f16k"
+    if x16.dtype != torch.int16 or dy16.dtype != torch.int16 or x16.numel() != B * Cin * H * W or dy16.numel() != B * Cout * H * W:
+        raise RuntimeError(f"masic_amd.{name}: F16K buffer sizes do not match (B, C, H, W)")
+    dw = torch.empty((Cout, Cin, KS, KS), dtype=torch.float32, device=x16.device)
+    fn, fn_det = getattr(lib, f"masic_{name}_ws"), getattr(lib, f"masic_{name}_det")
+    _wgrad_call(lambda ws: fn(_p(x16), _p(dy16), _p(dw), ws, B, Cin, Cout, H, W, 1, _stream()),
+                lambda ws: fn_det(_p(x16), _p(dy16), _p(dw), ws, B, Cin, Cout, H, W, _stream()),
+                x16.device, _int_query(f"masic_{name}_workspace_bytes", Cin, Cout),
+                lambda: _int_query(f"masic_{name}_det_workspace_bytes", B, Cin, Cout, H, W), name)
+    return dw
+
+
 def conv5x5_wgrad_f16k(x16, dy16, B, Cin, Cout, H, W):
     """dW [Cout, Cin, 5, 5] (float32) of Conv2d(k5, s1, p2) from x and dy in F16K (bf16 operands, float32 accumulate)."""
-    if x16.dtype != torch.int16 or dy16.dtype != torch.int16 or x16.numel() != B * Cin * H * W or dy16.numel() != B * Cout * H * W:
-        raise RuntimeError("masic_amd.conv5x5_wgrad_f16k: F16K buffer sizes do not match (B, C, H, W)")
-    dw = torch.empty((Cout, Cin, 5, 5), dtype=torch.float32, device=x16.device)
-    if _det_mode():
-        ws = _det_workspace(x16.device, _int_query("masic_conv5x5_wgrad_f16k_det_workspace_bytes", B, Cin, Cout, H, W))
-        check(lib.masic_conv5x5_wgrad_f16k_det(_p(x16), _p(dy16), _p(dw), _p(ws), B, Cin, Cout, H, W, _stream()), "conv5x5_wgrad_f16k_det")
-        return dw
-    n = _int_query("masic_conv5x5_wgrad_f16k_workspace_bytes", Cin, Cout) // 4
-    ws = _clean_workspace(x16.device, n)
-    try:
-        check(lib.masic_conv5x5_wgrad_f16k_ws(_p(x16), _p(dy16), _p(dw), _p(ws), B, Cin, Cout, H, W, 1, _stream()), "conv5x5_wgrad_f16k")
-    except Exception:
-        _drop_workspace(x16.device, n)
-        raise
-    return dw
+    return _conv_wgrad_f16k(5, x16, dy16, B, Cin, Cout, H, W)
 
 
 def conv3x3_wgrad_f16k(x16, dy16, B, Cin, Cout, H, W):
     """dW [Cout, Cin, 3, 3] (float32) of Conv2d(k3, s1, p1) from x and dy in F16K (bf16 operands, float32 accumulate)."""
-    if x16.dtype != torch.int16 or dy16.dtype != torch.int16 or x16.numel() != B * Cin * H * W or dy16.numel() != B * Cout * H * W:
-        raise RuntimeError("masic_amd.conv3x3_wgrad_f16k: F16K buffer sizes do not match (B, C, H, W)")
-    dw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=x16.device)
-    if _det_mode():
-        ws = _det_workspace(x16.device, _int_query("masic_conv3x3_wgrad_f16k_det_workspace_bytes", B, Cin, Cout, H, W))
-        check(lib.masic_conv3x3_wgrad_f16k_det(_p(x16), _p(dy16), _p(dw), _p(ws), B, Cin, Cout, H, W, _stream()), "conv3x3_wgrad_f16k_det")
-        return dw
-    n = _int_query("masic_conv3x3_wgrad_f16k_workspace_bytes", Cin, Cout) // 4
-    ws = _clean_workspace(x16.device, n)
-    try:
-        check(lib.masic_conv3x3_wgrad_f16k_ws(_p(x16), _p(dy16), _p(dw), _p(ws), B, Cin, Cout, H, W, 1, _stream()), "conv3x3_wgrad_f16k")
-    except Exception:
-        _drop_workspace(x16.device, n)
-        raise
-    return dw
+    return _conv_wgrad_f16k(3, x16, dy16, B, Cin, Cout, H, W)
 
 
 # ------------------------------------------------------------------------------------------ SSIM / MS-SSIM (masic_amd/ssim.py)

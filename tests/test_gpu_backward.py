@@ -254,7 +254,7 @@ def test_gdn_backward_fused_f16k_operands(B, H, W, inverse):
 
 @pytest.mark.parametrize("B,Cout,Cin,H,W", [(2, 1152, 768, 16, 24), (3, 96, 160, 7, 9), (1, 768, 960, 32, 32), (2, 32, 48, 5, 3)])
 def test_gemm_wgrad_f16k_1x1_layers(B, Cout, Cin, H, W):
-    """masic_gemm_wgrad_f16k -- the weight gradient of the 1x1 layers of the entropy-parameter stacks (reference MASIC.py:330-468) from
+    """masic_gemm_wgrad_bias_f16k -- the weight gradient of the 1x1 layers of the entropy-parameter stacks (reference MASIC.py:330-468) from
     F16K operands -- against a float64 contraction of the bf16-rounded operands the kernel sees (ragged pixel counts: partial 64-pixel
     tiles; channel counts that are not multiples of 128: partial output tiles), for the Conv2d orientation [Cout, Cin] and the
     ConvTranspose2d(k=1) orientation [Cin, Cout]; and through ConvFn in the bf16 mode against the float32 NCHW kernel's result."""

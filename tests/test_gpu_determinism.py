@@ -123,8 +123,10 @@ def test_conv_wgrad_f16k_det(KS, B, Cin, Cout, H, W):
     assert_close(got, w.grad, f"conv{KS}x{KS}_wgrad_f16k_det {Cin}->{Cout}", 1e-5)
 
 
-@pytest.mark.parametrize("B,Cout,Cin,H,W", [(2, 1152, 768, 16, 24), (3, 96, 160, 7, 9), (1, 768, 960, 32, 32), (2, 32, 48, 5, 3),
-                                            (8, 384, 256, 32, 32)])
+GEMM1_CASES = [(2, 1152, 768, 16, 24), (3, 96, 160, 7, 9), (1, 768, 960, 32, 32), (2, 32, 48, 5, 3), (8, 384, 256, 32, 32)]
+
+
+@pytest.mark.parametrize("B,Cout,Cin,H,W", GEMM1_CASES)
 def test_gemm_wgrad_f16k_det(B, Cout, Cin, H, W):
     """masic_gemm_wgrad_bias_f16k_det, both orientations and both bias modes, against float64 on the bf16-rounded operands (2e-5 of the
     peak, as the default kernel's test), repeatable to the bit, bias sums included."""
@@ -152,6 +154,25 @@ def test_gemm_wgrad_f16k_det(B, Cout, Cin, H, W):
     assert float((b2[:n].view(Cin, Cout).cpu().double() - want.t()).abs().max()) <= 2e-5 * peak
     for db in (b1[n:], b2[n:]):
         assert float((db.cpu().double() - bsum).abs().max()) <= 2e-5 * float(q(dy).abs().sum(dim=(0, 2, 3)).max())
+
+
+def test_det_digests_are_the_recorded():
+    """Every deterministic weight gradient of the three case lists above has the bits recorded in tests/golden/wgrad_det_digest.json
+    (tests/golden/make_wgrad_det_digest.py: written before the host side became a plan and a table) -- same kernels, same grids, same
+    split counts, same order of the sums."""
+    import importlib.util
+    import json
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    spec = importlib.util.spec_from_file_location("make_wgrad_det_digest", os.path.join(here, "golden", "make_wgrad_det_digest.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(here, "golden", "wgrad_det_digest.json")) as f:
+        want = json.load(f)
+    got = gen.digests(NCHW_CASES, K3_CASES, GEMM1_CASES, DEV)
+    assert got.keys() == want.keys() and len(got) >= len(NCHW_CASES) + len(K3_CASES) + 3 * len(GEMM1_CASES)
+    bad = [k for k in want if got[k] != want[k]]
+    assert not bad, f"{len(bad)} of {len(want)} digests differ: {bad[:8]}"
 
 
 def _warp_case(kind, B=2, H=48, W=64):

@@ -20,7 +20,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "coremasic", "mywork"))
 
 WGRAD = ("conv_wgrad", "wgrad3x3_f16k", "wgrad1x1_f16k", "wgrad_pic", "wgrad_small", "wgrad_transpose", "wgrad3_transpose",
-         "wgrad_slab_transpose", "wgrad3_slab_transpose", "wgrad1x1_finish", "warp_bwd", "warp_det")
+         "wgrad_slab_transpose", "wgrad1x1_finish", "warp_bwd", "warp_det")
 
 
 def timed(fn, steps, warmup):
@@ -103,14 +103,14 @@ def main():
         for mode in ("default", "det"):
             if a.only not in (None, mode):
                 continue
-            ops._DET_WS.clear()
+            ops._WS.clear()
             torch.cuda.empty_cache()
             with deterministic(mode == "det"):
                 row[mode + "_ms"] = round(timed(fns[name], a.steps, a.warmup), 2)
             if mode == "det":
                 per = ops.det_workspace_bytes()
                 row["det_workspace_MiB_per_stream"] = {str(k[1]): round(v / 2 ** 20, 1) for k, v in per.items()}
-                row["det_largest_layer_MiB"] = round(max(ws.numel() * 4 for ws in ops._DET_WS.values()) / 2 ** 20, 1)
+                row["det_largest_layer_MiB"] = round(max(ws.numel() * 4 for k, ws in ops._WS.items() if k[0] == "det") / 2 ** 20, 1)
         if "default_ms" in row and "det_ms" in row:
             row["det_over_default"] = round(row["det_ms"] / row["default_ms"], 3)
         print(json.dumps(row), flush=True)

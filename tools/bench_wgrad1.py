@@ -1,4 +1,4 @@
-"""Times masic_gemm_wgrad_f16k against the float32 NCHW 1x1 weight-gradient kernel at the head-layer shapes (8 x 32 x 32 latents)."""
+"""Times masic_gemm_wgrad_bias_f16k (ops.gemm_wgrad_f16k) against the float32 NCHW 1x1 weight-gradient kernel at the head-layer shapes (8 x 32 x 32 latents)."""
 import sys, os, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -10,7 +10,7 @@ def t(name, fn, n=20000):
     for _ in range(n): fn()
     dt = (time.perf_counter() - t0) / n * 1e6
     torch.cuda.synchronize()
-    print(f"{name:44s} {dt:7.2f} us")
+    print(f"{name:50s} {dt:7.2f} us")
 t("ops._stream()", ops._stream)
 t("torch.cuda.current_stream().cuda_stream", lambda: torch.cuda.current_stream().cuda_stream)
 t("torch.empty_like(x)", lambda: torch.empty_like(x))
@@ -23,6 +23,11 @@ t("ops.elementwise(EW_SQUARE, x)", lambda: ops.elementwise(ops.EW_SQUARE, x), 50
 d16 = ops.make_conv_desc(1, 16, 16, 16, 128, 5, 5, 2, 2, prec=_lib.PREC_BF16); x16 = torch.zeros(16 * 256, dtype=torch.int16, device="cuda")
 wp = ops.pack_conv_f16k_weight(torch.zeros(128, 16, 5, 5, device="cuda"), d16); y16 = torch.empty(128 * 64, dtype=torch.int16, device="cuda")
 t("raw lib.masic_conv_f16k_gdn_fwd (launch only)", lambda: _lib.lib.masic_conv_f16k_gdn_fwd(ops._p(x16), ops._p(wp), None, None, None, 0, None, ops._p(y16), ctypes.byref(d16), st), 5000)
+dwg = ops.make_conv_desc(1, 32, 16, 16, 32, 3, 3, 1, 1); xw = torch.zeros(1, 32, 16, 16, device="cuda"); dw = torch.empty(32, 32, 3, 3, device="cuda")
+wsw = torch.zeros(32 * 32 * 9, device="cuda")      # a clean workspace: zeros on entry, zeros again after every call
+t("raw lib.masic_conv2d_wgrad_ws (launch only)", lambda: _lib.lib.masic_conv2d_wgrad_ws(ops._p(xw), ops._p(xw), ops._p(dw), ops._p(wsw), ctypes.byref(dwg), 1, st), 5000)
+xk = torch.zeros(32 * 256, dtype=torch.int16, device="cuda")
+t("raw lib.masic_conv3x3_wgrad_f16k_ws (launch only)", lambda: _lib.lib.masic_conv3x3_wgrad_f16k_ws(ops._p(xk), ops._p(xk), ops._p(dw), ops._p(wsw), 1, 32, 32, 16, 16, 1, st), 5000)
 d = ops.make_conv_desc(2, 32, 16, 16, 32, 3, 3, 1, 1)
 t("make_conv_desc", lambda: ops.make_conv_desc(2, 32, 16, 16, 32, 3, 3, 1, 1))
 t("torch add (aten) x + y", lambda: x + y, 5000)
