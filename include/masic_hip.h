@@ -72,14 +72,20 @@ typedef struct {
  * version into the K-major, Cout-contiguous order the implicit-GEMM kernel stages into LDS) */
 size_t masic_conv_packed_bytes(const masic_conv_desc_t* d);
 int masic_conv_pack_weight(const float* w, void* w_packed, const masic_conv_desc_t* d, void* stream);
-/* which kernel (and how many launches of it) masic_conv2d_fwd issues for this layer -- used by
- * bench.py to attribute HIP-event timings to kernel symbols:
- *   variant 0/1: conv_direct_f32<3>/<8>; 2/3/4/5/7: conv_igemm_f32<2 waves x {1x1,1x2,1x4,2x4,2x2} tiles>; 8/9: conv_igemm_f32<1 wave x {1x2,3x2}>;
- *   6: deconv5s2_small_cout; launches = phases (1, or
- *   stride^2 for transposed convs). Returns variant, writes *launches if non-NULL; <0 on bad desc. */
-int masic_conv_variant(const masic_conv_desc_t* d, int* launches);
-/* the kernel symbol (as rocprofv3 prints it, without namespace/arguments) that this layer launches */
+/* the kernel masic_conv2d_fwd launches for this layer (one launch, all phases of a transposed conv included), as rocprofv3 prints
+ * it without namespace and arguments -- bench.py attributes HIP-event timings to these symbols.  MASIC_ERR_* and an empty string for
+ * a layer masic_conv2d_fwd refuses. */
 int masic_conv_kernel_name(const masic_conv_desc_t* d, char* buf, size_t n);
+/* The launch of one call, for tests and tools: form = the optional operands of the call (MASIC_CONV_GATE, _RES1, _RES2 for
+ * masic_conv2d_fwd_ex; MASIC_CONV_F16K_OUT alone for masic_conv2d_f16k_out_fwd).  Writes "kernel | gx,gy,gz | block | lds bytes |
+ * integers\n" -- the kernel with every template argument, then what it is handed beside the descriptor's own fields (implicit GEMM:
+ * Cin_pad Cout_pad KC TW TH SR PH PW PSZ buf_sz vec4 nphase; conv_direct_f32: nphase; deconv5s2_small_cout: Cin_pad tiles_w;
+ * conv5s1_small: tiles_w) -- and returns what the call returns; the string is empty when the call is refused or launches nothing.
+ * masic_conv_row_name enumerates the compiled kernels the launcher chooses from: rows 0 .., columns in_op 0 .. 2 x flag 0 / 1
+ * (VEC4 of conv_igemm_f32, PF of conv_igemm_bf16); MASIC_ERR_ARG past the last row and for a column the row lacks. */
+enum { MASIC_CONV_GATE = 1, MASIC_CONV_RES1 = 2, MASIC_CONV_RES2 = 4, MASIC_CONV_F16K_OUT = 8 };
+int masic_conv_plan_name(const masic_conv_desc_t* d, int form, char* buf, size_t n);
+int masic_conv_row_name(int row, int in_op, int flag, char* buf, size_t n);
 /* y = act(conv(in_op(x), w) + bias) [* gate].  bias may be NULL. */
 int masic_conv2d_fwd(const float* x, const void* w_packed, const float* bias, const float* gate,
                      float* y, const masic_conv_desc_t* d, void* stream);

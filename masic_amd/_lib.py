@@ -17,6 +17,7 @@ INOP_NONE, INOP_ABS, INOP_ROUND = 0, 1, 2
 PREC_F32, PREC_BF16, PREC_FP8 = 0, 1, 2
 F16K_GDN, F16K_NOSPLIT, F16K_MULTI = 1, 2, 4      # masic_conv_f16k_kernel_name flags (MASIC_F16K_*)
 WGRAD_DET, WGRAD_IN16, WGRAD_CLEAN = 1, 2, 4      # masic_*wgrad*_plan_name flags (MASIC_WGRAD_*)
+CONV_GATE, CONV_RES1, CONV_RES2, CONV_F16K_OUT = 1, 2, 4, 8      # masic_conv_plan_name forms (MASIC_CONV_*)
 SSIM_MS, SSIM_SIZE_AVERAGE, SSIM_NONNEG = 1, 2, 4
 
 
@@ -55,8 +56,9 @@ SIGNATURES = {
     "masic_version": (c_int, []),
     "masic_last_error": (ctypes.c_char_p, []),
     "masic_conv_packed_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
-    "masic_conv_variant": (c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int)]),
     "masic_conv_kernel_name": (c_int, [ctypes.POINTER(ConvDesc), ctypes.c_char_p, c_size_t]),
+    "masic_conv_plan_name": (c_int, [ctypes.POINTER(ConvDesc), c_int, ctypes.c_char_p, c_size_t]),
+    "masic_conv_row_name": (c_int, [c_int, c_int, c_int, ctypes.c_char_p, c_size_t]),
     "masic_conv_pack_weight": (c_int, [_P, _P, ctypes.POINTER(ConvDesc), _P]),
     "masic_conv2d_fwd": (c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),
     "masic_conv2d_fwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),

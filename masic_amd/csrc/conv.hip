@@ -44,6 +44,7 @@ struct ConvCfg {
 };
 
 int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+constexpr int patch_bound(int TH, int TW) { return ((TH - 1) * 2 + 5) * ((TW - 1) * 2 + 5); }      // largest patch of a TH x TW tile: stride 2, 5 taps
 
 ConvCfg choose_cfg(const masic_conv_desc_t& d, const ConvGeom* g, int nphase) {
     ConvCfg c{};
@@ -91,21 +92,18 @@ ConvCfg choose_cfg(const masic_conv_desc_t& d, const ConvGeom* g, int nphase) {
     const int wvn = 4 / c.wvm;
     const int BM = 32 * c.wm * c.wvm;
     c.Cout_pad = round_up(d.Cout, BM);
-    // the per-channel patch must fit 24 DMA wave-instructions (MAXE = 6 per wave)
-    while (c.wvm == 2 && c.wn > 1 && ((c.SR * wvn * c.wn - 1) * is + span_h) * ((c.TW - 1) * is + span_w) > 24 * 64) c.wn >>= 1;
+    // The per-channel patch must fit 24 DMA wave-instructions (MAXE = 6 per wave: 1536 floats), the bf16 patch MAXP * 256 = 1536 pixels.
+    // Every tile does: TH * TW = 32 * wvn * wn <= 256 with TW = 8, 16 or 32, and check_desc admits stride <= 2 and kernels <= 5, so
+    // PH * PW <= (2 (TH - 1) + 5) * (2 (TW - 1) + 5), which is largest for the 8 x 32 and 32 x 8 tiles: 19 * 67 = 1273.
+    static_assert(patch_bound(8, 32) == 1273 && patch_bound(32, 8) == 1273 && patch_bound(16, 16) <= 1273 && 1273 <= 24 * 64 && 1273 <= 6 * 256,
+                  "a 256-pixel tile's patch fits the DMA and the bf16 staging limits without shrinking the tile");
     c.TH = c.SR * wvn * c.wn;
     c.PH = (c.TH - 1) * is + span_h;
     c.PW = (c.TW - 1) * is + span_w;
     c.PWp = c.PW;                                       // LDS-DMA writes 64 consecutive floats: no row padding
     if (d.prec == MASIC_PREC_BF16) {
-        // [pixel][KC+8] bf16 patch in one LDS buffer (two workgroups per CU overlap staging and MFMA);
-        // the whole patch must fit MAXP*256 pixels
+        // [pixel][KC+8] bf16 patch in one LDS buffer (two workgroups per CU overlap staging and MFMA)
         c.bf16 = 1;
-        while (c.wn > 1 && c.PH * c.PW > 6 * 256) {
-            c.wn >>= 1;
-            c.TH = c.SR * wvn * c.wn;
-            c.PH = (c.TH - 1) * is + span_h;
-        }
         int KC = 32;
         while (KC > 16 && ((size_t)c.PH * c.PW * (KC + 8) * 2 > 64 * 1024 || KC > round_up(d.Cin, 16))) KC >>= 1;
         c.KC = KC; c.KClog = ilog2(KC);
@@ -1073,220 +1071,219 @@ __global__ void pack_conv5s1_kernel(const float* __restrict__ w, float* __restri
     wp[i] = v;
 }
 
+// ------------------------------------------------------------------------------------------ host side: table, plan, launcher
+enum { CF_IGEMM_F32, CF_IGEMM_BF16, CF_DIRECT, CF_DECONV4, CF_CONV5S1 };      // family: one argument struct and one kernel signature each
+typedef void (*ConvKernelFn)();                // a kernel of any family; conv_run casts it back to its signature
+template <class... A> void conv_run(ConvKernelFn k, dim3 grid, size_t lds, void* stream, const A&... a) {
+    const auto fn = reinterpret_cast<void (*)(A...)>(k);
+    hipLaunchKernelGGL(fn, grid, dim3(256), lds, (hipStream_t)stream, a...);
+}
+// One row per compiled tile shape; the igemm rows hold their in_op x VEC4 (f32) / PF (bf16) instantiations as columns.  plan_conv below
+// is the only place a row is chosen; a (row, column) that is not in the table is not compiled.
+struct ConvRow {
+    int family;
+    int t[3];                    // igemm: WVM, WM, WN; conv_direct_f32 / conv5s1_small: CO
+    ConvKernelFn k[3][2];        // igemm: [in_op][VEC4 or PF] (VEC4 stages untransformed input only); the others: k[0][0]
+};
+#define KFN(...) reinterpret_cast<ConvKernelFn>(&__VA_ARGS__)
+#define K1(K, V, M, N, OP) {KFN(K<V, M, N, OP, false>), nullptr}
+#define K2(K, V, M, N, OP) {KFN(K<V, M, N, OP, false>), KFN(K<V, M, N, OP, true>)}
+#define ROW_F32(V, M, N) {CF_IGEMM_F32, {V, M, N}, {K2(conv_igemm_f32, V, M, N, 0), K1(conv_igemm_f32, V, M, N, 1), K1(conv_igemm_f32, V, M, N, 2)}}
+#define ROW_BF16(V, M, N) {CF_IGEMM_BF16, {V, M, N}, {K2(conv_igemm_bf16, V, M, N, 0), K2(conv_igemm_bf16, V, M, N, 1), K2(conv_igemm_bf16, V, M, N, 2)}}
+const ConvRow CONV_ROWS[] = {
+    ROW_F32(1, 1, 2), ROW_F32(1, 3, 2),                                        // one wave along the channels: 32 x 256 and 96 x 256 tiles
+    ROW_F32(2, 1, 1), ROW_F32(2, 1, 2), ROW_F32(2, 1, 4),                      // 64 x 64 / 128 / 256
+    ROW_F32(2, 2, 2), ROW_F32(2, 2, 4),                                        // 128 x 128 / 256
+    ROW_BF16(1, 1, 2), ROW_BF16(1, 3, 2), ROW_BF16(2, 1, 1), ROW_BF16(2, 1, 2), ROW_BF16(2, 1, 4), ROW_BF16(2, 2, 2), ROW_BF16(2, 2, 4),
+    {CF_DIRECT, {3, 0, 0}, {{KFN(conv_direct_f32<3>), nullptr}}}, {CF_DIRECT, {8, 0, 0}, {{KFN(conv_direct_f32<8>), nullptr}}},
+    {CF_DECONV4, {0, 0, 0}, {{KFN(deconv5s2_small_cout), nullptr}}},
+    {CF_CONV5S1, {4, 0, 0}, {{KFN(conv5s1_small<4>), nullptr}}}, {CF_CONV5S1, {8, 0, 0}, {{KFN(conv5s1_small<8>), nullptr}}},
+};
+constexpr int CONV_NROWS = sizeof(CONV_ROWS) / sizeof(CONV_ROWS[0]);
+const ConvRow* conv_row(int family, int t0, int t1, int t2) {
+    for (const ConvRow& r : CONV_ROWS)
+        if (r.family == family && r.t[0] == t0 && r.t[1] == t1 && r.t[2] == t2) return &r;
+    return nullptr;
+}
+// symbol: as masic_conv_kernel_name has always printed it -- conv5s1_small without its template argument
+void conv_row_name(const ConvRow& r, int op, int col, bool symbol, char* buf, size_t n) {
+    const char* f = col ? "true" : "false";
+    if (r.family == CF_IGEMM_F32) snprintf(buf, n, "conv_igemm_f32<%d, %d, %d, %d, %s>", r.t[0], r.t[1], r.t[2], op, f);
+    else if (r.family == CF_IGEMM_BF16) snprintf(buf, n, "conv_igemm_bf16<%d, %d, %d, %d, %s>", r.t[0], r.t[1], r.t[2], op, f);
+    else if (r.family == CF_DIRECT) snprintf(buf, n, "conv_direct_f32<%d>", r.t[0]);
+    else if (r.family == CF_DECONV4) snprintf(buf, n, "deconv5s2_small_cout");
+    else if (symbol) snprintf(buf, n, "conv5s1_small");
+    else snprintf(buf, n, "conv5s1_small<%d>", r.t[0]);
+}
 
+// Everything the launcher decides for one (layer, form); form: which optional operands the call has (MASIC_CONV_*).
+struct ConvPlan {
+    int rc;                      // MASIC_OK, or the launcher's refusal of this descriptor and form
+    bool desc_ok;                // check_desc passed: geometry, configuration and packed_bytes are set whatever rc says (the weight pack reads them)
+    bool empty;                  // no output pixels: MASIC_OK and no launch
+    ConvGeom g[4];
+    ConvCfg c;
+    const ConvRow* row;
+    int nphase, op, col, tiles_w;      // op, col: the row's column
+    dim3 grid;
+    size_t packed_bytes;
+};
+#define PLAN_REQUIRE(cond, code, ...) \
+    do { if (!(cond)) { masic_set_error(__VA_ARGS__); p.rc = (code); return p; } } while (0)
+
+ConvPlan plan_conv(const masic_conv_desc_t* d, int form) {
+    ConvPlan p{};
+    const bool f16k = form & MASIC_CONV_F16K_OUT, gate = form & MASIC_CONV_GATE, res1 = form & MASIC_CONV_RES1, res2 = form & MASIC_CONV_RES2;
+    const char* const no_f16k = "conv2d_f16k_out_fwd: needs bf16 operands on the implicit-GEMM kernel, Cout % 32 == 0 and a 16-aligned output view";
+    p.rc = check_desc(d);
+    if (p.rc != MASIC_OK) {      // (the F16K-output form answers every descriptor it cannot take, a malformed one included, with its one refusal)
+        if (f16k && d) { masic_set_error("%s", no_f16k); p.rc = MASIC_ERR_UNSUPPORTED; }
+        return p;
+    }
+    p.desc_ok = true;
+    p.nphase = build_geoms(*d, p.g);
+    const ConvCfg& c = p.c = choose_cfg(*d, p.g, p.nphase);
+    p.op = d->in_op == MASIC_INOP_ABS ? 1 : (d->in_op == MASIC_INOP_ROUND ? 2 : 0);
+    int taps = 0;
+    for (int i = 0; i < p.nphase; ++i) taps += p.g[i].ntaps;
+    p.packed_bytes = (size_t)taps * c.Cin_pad * c.Cout_pad * (c.bf16 ? sizeof(unsigned short) : sizeof(float));
+    if (c.direct == 2) { p.row = conv_row(CF_DECONV4, 0, 0, 0); p.packed_bytes = (size_t)c.Cin_pad * 100 * sizeof(float); }
+    else if (c.direct == 3) { p.row = conv_row(CF_CONV5S1, c.Cout_pad, 0, 0); p.packed_bytes = (size_t)c.Cin_pad * 25 * c.Cout_pad * sizeof(float); }
+    else if (c.direct) p.row = conv_row(CF_DIRECT, d->Cout <= 3 ? 3 : 8, 0, 0);
+    else { p.row = conv_row(c.bf16 ? CF_IGEMM_BF16 : CF_IGEMM_F32, c.wvm, c.wm, c.wn); p.col = c.bf16 ? c.pf : c.vec4; }
+    if (c.direct) p.op = 0;      // (conv_direct_f32 takes in_op as an argument; the other two have none)
+    PLAN_REQUIRE(!f16k || (c.bf16 && d->Cout % 32 == 0 && d->out_ctot % 16 == 0 && d->out_coff % 16 == 0), MASIC_ERR_UNSUPPORTED, "%s", no_f16k);
+    PLAN_REQUIRE(d->prec != MASIC_PREC_FP8, MASIC_ERR_UNSUPPORTED, "conv2d_fwd: fp8 operands exist on the F8K entry points only (masic_conv_f8k_fwd)");
+    PLAN_REQUIRE(p.row && p.row->k[p.op][p.col], MASIC_ERR_UNSUPPORTED, "conv2d_fwd: no kernel compiled for tile <%d, %d, %d>, in_op %d, column %d",
+                 c.wvm, c.wm, c.wn, p.op, p.col);
+    if (p.g[0].Hp <= 0 || p.g[0].Wp <= 0) { p.empty = true; return p; }
+    PLAN_REQUIRE(c.direct != 2 || (!gate && !res1 && !res2), MASIC_ERR_UNSUPPORTED, "conv2d_fwd: gate/residual on the small-Cout deconv path");
+    PLAN_REQUIRE(c.direct != 2 || d->Wo % 2 == 0, MASIC_ERR_SHAPE, "conv2d_fwd: odd output width");
+    PLAN_REQUIRE(c.direct != 3 || !res2, MASIC_ERR_UNSUPPORTED, "conv2d_fwd: two residuals on the small 5x5 path");
+    p.tiles_w = c.direct ? ceil_div(d->Wi, 16) : ceil_div(p.g[0].Wp, c.TW);      // (conv_direct_f32 has no tiles)
+    if (c.direct == 1) p.grid = dim3(ceil_div(p.g[0].Hp * p.g[0].Wp, 256) * p.nphase, d->B);
+    else if (c.direct) p.grid = dim3(p.tiles_w * ceil_div(d->Hi, 16), d->B);
+    else p.grid = dim3(p.tiles_w * ceil_div(p.g[0].Hp, c.TH) * p.nphase, c.Cout_pad / (32 * c.wm * c.wvm), d->B);
+    return p;
+}
+
+// plan, refuse or return, fill the argument struct of the row's family, launch the row
+int conv2d_launch(const float* x, const void* w_packed, const float* bias, const float* gate, const float* res1, const float* res2, float* y,
+                  void* y_f16k, const masic_conv_desc_t* d, void* stream) {
+    const ConvPlan p = plan_conv(d, (gate ? MASIC_CONV_GATE : 0) | (res1 ? MASIC_CONV_RES1 : 0) | (res2 ? MASIC_CONV_RES2 : 0) | (y_f16k ? MASIC_CONV_F16K_OUT : 0));
+    if (p.rc != MASIC_OK || p.empty) return p.rc;
+    const ConvCfg& c = p.c;
+    const ConvKernelFn k = p.row->k[p.op][p.col];
+    if (p.row->family == CF_DECONV4) {
+        const Deconv4Args a{x, (const float*)w_packed, bias, y, d->Cin, c.Cin_pad, d->Hi, d->Wi, d->in_ctot, d->in_coff,
+                            d->Cout, d->Ho, d->Wo, d->out_ctot, d->out_coff, d->act, p.tiles_w};
+        conv_run(k, p.grid, 0, stream, a, (const float*)w_packed);
+    } else if (p.row->family == CF_CONV5S1) {
+        const Conv5s1Args a{x, bias, gate, res1, y, d->Cin, d->Hi, d->Wi, d->in_ctot, d->in_coff, d->Cout, d->out_ctot, d->out_coff,
+                            d->act, p.tiles_w, d->gate_ctot, d->gate_c, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, 0.0f, 0.0f, 0.0f};
+        conv_run(k, p.grid, 0, stream, a, (const float*)w_packed);
+    } else if (p.row->family == CF_DIRECT) {
+        const DirectArgs a{x, (const float*)w_packed, bias, gate, res1, res2, y, d->Cin, d->Hi, d->Wi, d->in_ctot, d->in_coff,
+                           d->Cout, d->Ho, d->Wo, d->out_ctot, d->out_coff, d->in_op, d->act, d->gate_ctot, d->gate_c, geom_params(*d), p.nphase};
+        conv_run(k, p.grid, 0, stream, a);
+    } else {
+        const IgemmArgs a{x, (const float*)w_packed, bias, gate, res1, res2, y,
+                          d->Cin, d->Hi, d->Wi, d->in_ctot, d->in_coff, d->Cout, d->Ho, d->Wo, d->out_ctot, d->out_coff,
+                          c.Cin_pad, c.Cout_pad, c.KC, c.KClog, c.TW, c.TWlog, c.SR, c.TH, p.tiles_w,
+                          c.PH, c.PW, c.PWp, c.PSZ, c.buf_sz, c.vec4,
+                          d->in_op, d->act, d->gate_ctot, d->gate_c, geom_params(*d), p.nphase, (unsigned short*)y_f16k};
+        if (p.row->family == CF_IGEMM_BF16) conv_run(k, p.grid, c.lds_bytes, stream, a, (const unsigned short*)w_packed);
+        else conv_run(k, p.grid, c.lds_bytes, stream, a);
+    }
+    return masic_launch_status("conv2d_fwd");
+}
 }  // namespace
 
-extern "C" size_t masic_conv_packed_bytes(const masic_conv_desc_t* d) {
-    if (check_desc(d) != MASIC_OK) return 0;
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const ConvCfg c = choose_cfg(*d, g, np);
-    int taps = 0;
-    for (int p = 0; p < np; ++p) taps += g[p].ntaps;
-    if (c.direct == 2) return (size_t)c.Cin_pad * 100 * sizeof(float);
-    if (c.direct == 3) return (size_t)c.Cin_pad * 25 * c.Cout_pad * sizeof(float);
-    if (c.bf16) return (size_t)taps * c.Cin_pad * c.Cout_pad * sizeof(unsigned short);
-    return (size_t)taps * c.Cin_pad * c.Cout_pad * sizeof(float);
-}
+extern "C" size_t masic_conv_packed_bytes(const masic_conv_desc_t* d) { return plan_conv(d, 0).packed_bytes; }
 
-extern "C" int masic_conv_variant(const masic_conv_desc_t* d, int* launches) {
-    int rc = check_desc(d);
-    if (rc != MASIC_OK) return rc;
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const ConvCfg c = choose_cfg(*d, g, np);
-    if (launches) *launches = 1;   // all phases ride in one launch
-    if (c.direct == 2) return 6;
-    if (c.direct == 3) return 11;
-    if (c.direct) return d->Cout <= 3 ? 0 : 1;
-    if (c.bf16) return 10;
-    if (c.wvm == 1) return c.wm == 1 ? 8 : 9;
-    if (c.wm == 2) return c.wn == 4 ? 5 : 7;
-    return c.wn == 4 ? 4 : (c.wn == 2 ? 3 : 2);
-}
-
+// the kernel of the plain form (no gate, no residual, float32 NCHW output); MASIC_ERR_* and an empty string where the launcher refuses it
 extern "C" int masic_conv_kernel_name(const masic_conv_desc_t* d, char* buf, size_t n) {
-    int rc = check_desc(d);
-    if (rc != MASIC_OK) return rc;
     MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "conv_kernel_name: null buffer");
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const ConvCfg c = choose_cfg(*d, g, np);
-    if (c.direct == 2) snprintf(buf, n, "deconv5s2_small_cout");
-    else if (c.direct == 3) snprintf(buf, n, "conv5s1_small");
-    else if (c.direct) snprintf(buf, n, "conv_direct_f32<%d>", d->Cout <= 3 ? 3 : 8);
-    else if (c.bf16) snprintf(buf, n, "conv_igemm_bf16<%d, %d, %d, %d, %s>", c.wvm, c.wm, c.wn, d->in_op, c.pf ? "true" : "false");
-    else snprintf(buf, n, "conv_igemm_f32<%d, %d, %d, %d, %s>", c.wvm, c.wm, c.wn, d->in_op, c.vec4 ? "true" : "false");
-    return MASIC_OK;
+    buf[0] = 0;
+    const ConvPlan p = plan_conv(d, 0);
+    if (p.rc == MASIC_OK) conv_row_name(*p.row, p.op, p.col, true, buf, n);
+    return p.rc;
 }
 
 extern "C" int masic_conv_pack_weight(const float* w, void* w_packed, const masic_conv_desc_t* d, void* stream) {
-    int rc = check_desc(d);
-    if (rc != MASIC_OK) return rc;
     MASIC_REQUIRE(w && w_packed, MASIC_ERR_ARG, "conv_pack_weight: null pointer");
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const ConvCfg c = choose_cfg(*d, g, np);
-    if (c.direct == 2) {
-        hipLaunchKernelGGL(pack_deconv4_kernel, dim3(ceil_div(c.Cin_pad * 100, 256)), dim3(256), 0, (hipStream_t)stream,
-                           w, (float*)w_packed, d->Cin, c.Cin_pad, d->Cout);
-        return masic_launch_status("conv_pack_weight");
-    }
-    if (c.direct == 3) {
-        hipLaunchKernelGGL(pack_conv5s1_kernel, dim3(ceil_div(d->Cin * 25 * c.Cout_pad, 256)), dim3(256), 0, (hipStream_t)stream,
-                           w, (float*)w_packed, d->Cin, d->Cout, d->transposed, c.Cout_pad);
+    const ConvPlan p = plan_conv(d, 0);
+    if (!p.desc_ok) return p.rc;
+    const ConvCfg& c = p.c;
+    if (c.direct == 2 || c.direct == 3) {
+        if (c.direct == 2) hipLaunchKernelGGL(pack_deconv4_kernel, dim3(ceil_div(c.Cin_pad * 100, 256)), dim3(256), 0, (hipStream_t)stream,
+                                              w, (float*)w_packed, d->Cin, c.Cin_pad, d->Cout);
+        else hipLaunchKernelGGL(pack_conv5s1_kernel, dim3(ceil_div(d->Cin * 25 * c.Cout_pad, 256)), dim3(256), 0, (hipStream_t)stream,
+                                w, (float*)w_packed, d->Cin, d->Cout, d->transposed, c.Cout_pad);
         return masic_launch_status("conv_pack_weight");
     }
     PackArgs a{w, (float*)w_packed, d->Cin, d->Cout, d->KH, d->KW, c.Cin_pad, c.Cout_pad, d->transposed, {}};
     int max_taps = 0;
-    for (int p = 0; p < np; ++p) {
-        a.gs[p] = g[p];
-        max_taps = max_taps > g[p].ntaps ? max_taps : g[p].ntaps;
+    for (int i = 0; i < p.nphase; ++i) {
+        a.gs[i] = p.g[i];
+        max_taps = max_taps > p.g[i].ntaps ? max_taps : p.g[i].ntaps;
     }
     const size_t total = (size_t)max_taps * c.Cin_pad * c.Cout_pad;           // the largest phase sizes the grid (grid-stride loops)
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    if (c.bf16) hipLaunchKernelGGL(pack_weight_bf16_kernel, dim3(blocks, np), dim3(256), 0, (hipStream_t)stream, a, (unsigned short*)w_packed);
-    else hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks, np), dim3(256), 0, (hipStream_t)stream, a);
+    const int blocks = total > 4096 * 256 ? 4096 : (int)((total + 255) / 256);
+    if (c.bf16) hipLaunchKernelGGL(pack_weight_bf16_kernel, dim3(blocks, p.nphase), dim3(256), 0, (hipStream_t)stream, a, (unsigned short*)w_packed);
+    else hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks, p.nphase), dim3(256), 0, (hipStream_t)stream, a);
     return masic_launch_status("conv_pack_weight");
 }
 
 extern "C" int masic_conv2d_fwd_ex(const float* x, const void* w_packed, const float* bias, const float* gate,
-                                   const float* res1, const float* res2, float* y, const masic_conv_desc_t* d, void* stream);
+                                   const float* res1, const float* res2, float* y, const masic_conv_desc_t* d, void* stream) {
+    MASIC_REQUIRE(x && w_packed && y, MASIC_ERR_ARG, "conv2d_fwd: null pointer");
+    return conv2d_launch(x, w_packed, bias, gate, res1, res2, y, nullptr, d, stream);
+}
 
 extern "C" int masic_conv2d_fwd(const float* x, const void* w_packed, const float* bias, const float* gate,
                                 float* y, const masic_conv_desc_t* d, void* stream) {
     return masic_conv2d_fwd_ex(x, w_packed, bias, gate, nullptr, nullptr, y, d, stream);
 }
 
-namespace {
-int conv2d_launch(const float* x, const void* w_packed, const float* bias, const float* gate,
-                  const float* res1, const float* res2, float* y, void* y_f16k, const masic_conv_desc_t* d, void* stream);
-}
-
-extern "C" int masic_conv2d_fwd_ex(const float* x, const void* w_packed, const float* bias, const float* gate,
-                                   const float* res1, const float* res2, float* y, const masic_conv_desc_t* d, void* stream) {
-    MASIC_REQUIRE(y != nullptr, MASIC_ERR_ARG, "conv2d_fwd: null pointer");
-    return conv2d_launch(x, w_packed, bias, gate, res1, res2, y, nullptr, d, stream);
-}
-
 // 1 when masic_conv2d_f16k_out_fwd has a kernel for the layer: bf16 operands on the implicit-GEMM kernel, whole 32-channel tiles
-extern "C" int masic_conv2d_f16k_out_supported(const masic_conv_desc_t* d) {
-    if (check_desc(d) != MASIC_OK || d->prec != MASIC_PREC_BF16 || d->Cout % 32 != 0 || d->out_ctot % 16 != 0 || d->out_coff % 16 != 0) return 0;
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const ConvCfg c = choose_cfg(*d, g, np);
-    return !c.direct && c.bf16;
-}
+extern "C" int masic_conv2d_f16k_out_supported(const masic_conv_desc_t* d) { return d && plan_conv(d, MASIC_CONV_F16K_OUT).rc == MASIC_OK; }
 
 extern "C" int masic_conv2d_f16k_out_fwd(const float* x, const void* w_packed, const float* bias, void* y_f16k,
                                          const masic_conv_desc_t* d, void* stream) {
-    MASIC_REQUIRE(y_f16k != nullptr && d != nullptr, MASIC_ERR_ARG, "conv2d_f16k_out_fwd: null pointer");
-    MASIC_REQUIRE(masic_conv2d_f16k_out_supported(d), MASIC_ERR_UNSUPPORTED,
-                  "conv2d_f16k_out_fwd: needs bf16 operands on the implicit-GEMM kernel, Cout % 32 == 0 and a 16-aligned output view");
+    MASIC_REQUIRE(x && w_packed && y_f16k && d, MASIC_ERR_ARG, "conv2d_f16k_out_fwd: null pointer");
     return conv2d_launch(x, w_packed, bias, nullptr, nullptr, nullptr, nullptr, y_f16k, d, stream);
 }
 
-namespace {
-int conv2d_launch(const float* x, const void* w_packed, const float* bias, const float* gate,
-                  const float* res1, const float* res2, float* y, void* y_f16k, const masic_conv_desc_t* d, void* stream) {
-    int rc = check_desc(d);
-    if (rc != MASIC_OK) return rc;
-    MASIC_REQUIRE(d->prec != MASIC_PREC_FP8, MASIC_ERR_UNSUPPORTED, "conv2d_fwd: fp8 operands exist on the F8K entry points only (masic_conv_f8k_fwd)");
-    MASIC_REQUIRE(x && w_packed && (y || y_f16k), MASIC_ERR_ARG, "conv2d_fwd: null pointer");
-    ConvGeom g[4];
-    const int np = build_geoms(*d, g);
-    const ConvCfg c = choose_cfg(*d, g, np);
-    MASIC_REQUIRE(y_f16k == nullptr || (!c.direct && c.bf16), MASIC_ERR_UNSUPPORTED, "conv2d_fwd: F16K output exists on conv_igemm_bf16 only");
-    hipStream_t st = (hipStream_t)stream;
-    const GeomParams q = geom_params(*d);
-    if (g[0].Hp <= 0 || g[0].Wp <= 0) return MASIC_OK;
-    if (c.direct == 2) {
-        MASIC_REQUIRE(gate == nullptr && res1 == nullptr && res2 == nullptr, MASIC_ERR_UNSUPPORTED, "conv2d_fwd: gate/residual on the small-Cout deconv path");
-        MASIC_REQUIRE(d->Wo % 2 == 0, MASIC_ERR_SHAPE, "conv2d_fwd: odd output width");
-        Deconv4Args a{x, (const float*)w_packed, bias, y, d->Cin, c.Cin_pad, d->Hi, d->Wi, d->in_ctot, d->in_coff,
-                      d->Cout, d->Ho, d->Wo, d->out_ctot, d->out_coff, d->act, ceil_div(d->Wi, 16)};
-        hipLaunchKernelGGL(deconv5s2_small_cout, dim3(ceil_div(d->Wi, 16) * ceil_div(d->Hi, 16), d->B), dim3(256), 0, st, a,
-                           (const float*)w_packed);
-        return masic_launch_status("conv2d_fwd");
-    }
-    if (c.direct == 3) {
-        MASIC_REQUIRE(res2 == nullptr, MASIC_ERR_UNSUPPORTED, "conv2d_fwd: two residuals on the small 5x5 path");
-        Conv5s1Args a{x, bias, gate, res1, y, d->Cin, d->Hi, d->Wi, d->in_ctot, d->in_coff, d->Cout, d->out_ctot, d->out_coff,
-                      d->act, ceil_div(d->Wi, 16), d->gate_ctot, d->gate_c, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, 0.0f, 0.0f, 0.0f};
-        if (c.Cout_pad == 4) hipLaunchKernelGGL(conv5s1_small<4>, dim3(ceil_div(d->Wi, 16) * ceil_div(d->Hi, 16), d->B), dim3(256), 0, st, a,
-                                                (const float*)w_packed);
-        else hipLaunchKernelGGL(conv5s1_small<8>, dim3(ceil_div(d->Wi, 16) * ceil_div(d->Hi, 16), d->B), dim3(256), 0, st, a,
-                                (const float*)w_packed);
-        return masic_launch_status("conv2d_fwd");
-    }
-    if (c.direct) {
-        DirectArgs a{x, (const float*)w_packed, bias, gate, res1, res2, y,
-                     d->Cin, d->Hi, d->Wi, d->in_ctot, d->in_coff,
-                     d->Cout, d->Ho, d->Wo, d->out_ctot, d->out_coff,
-                     d->in_op, d->act, d->gate_ctot, d->gate_c, q, np};
-        dim3 grid(ceil_div(g[0].Hp * g[0].Wp, 256) * np, d->B);
-        if (d->Cout <= 3) hipLaunchKernelGGL(conv_direct_f32<3>, grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(conv_direct_f32<8>, grid, dim3(256), 0, st, a);
-        return masic_launch_status("conv2d_fwd");
-    }
-    {
-        IgemmArgs a{x, (const float*)w_packed, bias, gate, res1, res2, y,
-                    d->Cin, d->Hi, d->Wi, d->in_ctot, d->in_coff,
-                    d->Cout, d->Ho, d->Wo, d->out_ctot, d->out_coff,
-                    c.Cin_pad, c.Cout_pad, c.KC, c.KClog,
-                    c.TW, c.TWlog, c.SR, c.TH, ceil_div(g[0].Wp, c.TW),
-                    c.PH, c.PW, c.PWp, c.PSZ, c.buf_sz, c.vec4,
-                    d->in_op, d->act, d->gate_ctot, d->gate_c, q, np, (unsigned short*)y_f16k};
-        dim3 grid(ceil_div(g[0].Wp, c.TW) * ceil_div(g[0].Hp, c.TH) * np, c.Cout_pad / (32 * c.wm * c.wvm), d->B);
-        if (c.bf16) {
-#define BF16_LAUNCH(WV, WMV, WNV, OPV)                                                                                            \
-    do {                                                                                                                          \
-        if (c.pf) hipLaunchKernelGGL((conv_igemm_bf16<WV, WMV, WNV, OPV, true>), grid, dim3(256), c.lds_bytes, st, a,             \
-                                     (const unsigned short*)w_packed);                                                           \
-        else hipLaunchKernelGGL((conv_igemm_bf16<WV, WMV, WNV, OPV, false>), grid, dim3(256), c.lds_bytes, st, a,                 \
-                                (const unsigned short*)w_packed);                                                                 \
-    } while (0)
-#define BF16_BY_OP(WV, WMV, WNV)                                                       \
-    do {                                                                               \
-        if (d->in_op == MASIC_INOP_ABS) BF16_LAUNCH(WV, WMV, WNV, MASIC_INOP_ABS);     \
-        else if (d->in_op == MASIC_INOP_ROUND) BF16_LAUNCH(WV, WMV, WNV, MASIC_INOP_ROUND); \
-        else BF16_LAUNCH(WV, WMV, WNV, MASIC_INOP_NONE);                               \
-    } while (0)
-            if (c.wvm == 1 && c.wm == 1) BF16_BY_OP(1, 1, 2);
-            else if (c.wvm == 1) BF16_BY_OP(1, 3, 2);
-            else if (c.wm == 2 && c.wn == 4) BF16_BY_OP(2, 2, 4);
-            else if (c.wm == 2 && c.wn == 2) BF16_BY_OP(2, 2, 2);
-            else if (c.wm == 2) BF16_BY_OP(2, 2, 1);
-            else if (c.wn == 4) BF16_BY_OP(2, 1, 4);
-            else if (c.wn == 2) BF16_BY_OP(2, 1, 2);
-            else BF16_BY_OP(2, 1, 1);
-#undef BF16_BY_OP
-#undef BF16_LAUNCH
-            return masic_launch_status("conv2d_fwd");
-        }
-#define IGEMM_LAUNCH(WV, WMV, WNV, OPV, V4) \
-    hipLaunchKernelGGL((conv_igemm_f32<WV, WMV, WNV, OPV, V4>), grid, dim3(256), c.lds_bytes, st, a)
-#define IGEMM_BY_OP(WV, WMV, WNV)                                                               \
-    do {                                                                                        \
-        if (d->in_op == MASIC_INOP_ABS) IGEMM_LAUNCH(WV, WMV, WNV, MASIC_INOP_ABS, false);      \
-        else if (d->in_op == MASIC_INOP_ROUND) IGEMM_LAUNCH(WV, WMV, WNV, MASIC_INOP_ROUND, false); \
-        else if (c.vec4) IGEMM_LAUNCH(WV, WMV, WNV, MASIC_INOP_NONE, true);                     \
-        else IGEMM_LAUNCH(WV, WMV, WNV, MASIC_INOP_NONE, false);                                \
-    } while (0)
-        if (c.wvm == 1 && c.wm == 1) IGEMM_BY_OP(1, 1, 2);
-        else if (c.wvm == 1) IGEMM_BY_OP(1, 3, 2);
-        else if (c.wm == 2 && c.wn == 4) IGEMM_BY_OP(2, 2, 4);
-        else if (c.wm == 2) IGEMM_BY_OP(2, 2, 2);
-        else if (c.wn == 4) IGEMM_BY_OP(2, 1, 4);
-        else if (c.wn == 2) IGEMM_BY_OP(2, 1, 2);
-        else IGEMM_BY_OP(2, 1, 1);
-#undef IGEMM_BY_OP
-#undef IGEMM_LAUNCH
-    }
-    return masic_launch_status("conv2d_fwd");
+// the launch of the call `form` names (MASIC_CONV_*): "kernel | gx,gy,gz | block | lds | integers", the integers being what the kernel is
+// handed beside the descriptor's own -- igemm: Cin_pad Cout_pad KC TW TH SR PH PW PSZ buf_sz vec4 nphase; conv_direct_f32: nphase;
+// deconv5s2_small_cout: Cin_pad tiles_w; conv5s1_small: tiles_w.  Returns the launcher's code; an empty string when it refuses or launches nothing.
+extern "C" int masic_conv_plan_name(const masic_conv_desc_t* d, int form, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "conv_plan_name: no buffer");
+    buf[0] = 0;
+    MASIC_REQUIRE(d && !(form & ~15) && !((form & MASIC_CONV_F16K_OUT) && (form & ~MASIC_CONV_F16K_OUT)), MASIC_ERR_ARG,
+                  "conv_plan_name: no such form (flags %d)", form);
+    const ConvPlan p = plan_conv(d, form);
+    if (p.rc != MASIC_OK || p.empty) return p.rc;
+    const ConvCfg& c = p.c;
+    char name[64], ints[128];
+    conv_row_name(*p.row, p.op, p.col, false, name, sizeof name);
+    if (p.row->family == CF_DECONV4) snprintf(ints, sizeof ints, "%d %d", c.Cin_pad, p.tiles_w);
+    else if (p.row->family == CF_CONV5S1) snprintf(ints, sizeof ints, "%d", p.tiles_w);
+    else if (p.row->family == CF_DIRECT) snprintf(ints, sizeof ints, "%d", p.nphase);
+    else snprintf(ints, sizeof ints, "%d %d %d %d %d %d %d %d %d %d %d %d", c.Cin_pad, c.Cout_pad, c.KC, c.TW, c.TH, c.SR, c.PH, c.PW, c.PSZ, c.buf_sz, c.vec4, p.nphase);
+    const bool ok = (size_t)snprintf(buf, n, "%s | %u,%u,%u | %d | %zu | %s\n", name, p.grid.x, p.grid.y, p.grid.z, 256, c.lds_bytes, ints) < n;
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "conv_plan_name: buffer of %zu bytes too small", n);
+    return MASIC_OK;
 }
-}  // namespace
+// every compiled kernel of the table: rows 0 .., columns in_op 0 .. 2 x flag 0 / 1; MASIC_ERR_ARG past the last row and for a column the row lacks
+extern "C" int masic_conv_row_name(int row, int in_op, int flag, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0 && row >= 0 && row < CONV_NROWS && in_op >= 0 && in_op < 3 && (flag == 0 || flag == 1) && CONV_ROWS[row].k[in_op][flag],
+                  MASIC_ERR_ARG, "conv_row_name: row %d, column %d, %d", row, in_op, flag);
+    conv_row_name(CONV_ROWS[row], in_op, flag, false, buf, n);
+    return MASIC_OK;
+}
 
 // encoder2.pre_conv + pre_gdn and decoder2.after_gdn + cat + after_conv (MASIC.py:559-560, :574-576, :599-600, :617-621) as one
 // launch each: Conv2d / ConvTranspose2d(6 -> 3, k5, s1, p2) whose six input channels come from two 3-channel tensors (no

@@ -197,9 +197,7 @@ def _f16k_name(flags):
 def conv2d(x, packed, bias, desc, out=None, gate=None, res1=None, res2=None):
     timed = None
     if _timer is not None:
-        n = ctypes.c_int(0)
-        lib.masic_conv_variant(ctypes.byref(desc), ctypes.byref(n))
-        timed = _timer_open(desc, lib.masic_conv_kernel_name, n.value)
+        timed = _timer_open(desc, lib.masic_conv_kernel_name, 1)      # one launch, every phase of a transposed conv included
     y = _conv2d(x, packed, bias, desc, out, gate, res1, res2)
     if timed is not None:
         _timer_close(timed)

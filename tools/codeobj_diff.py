@@ -3,7 +3,8 @@
     python tools/codeobj_diff.py <dirA>/conv_f16k-hip-amdgcn-amd-amdhsa-gfx950.s <dirB>/conv_f16k-hip-amdgcn-amd-amdhsa-gfx950.s
 A kernel is "identical" when its assembly from .type to .end_amdhsa_kernel (instruction stream and the .amdhsa_ kernel descriptor:
 VGPRs, SGPRs, LDS, scratch, kernarg size) and its .amdgpu_metadata entry are equal after the function's index in the module is taken out
-of its local labels (.LBB<n>_, .Lfunc_end<n>).  The order of the kernels in the module is free."""
+of its local labels (.LBB<n>_, .Lfunc_end<n>) and the IR block names are taken out of the labels' comments (numbered per module: they
+move when another instantiation of the same template comes or goes).  The order of the kernels in the module is free."""
 import re, sys, hashlib
 
 def norm(ls):
@@ -13,6 +14,7 @@ def norm(ls):
         l = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", l)
         l = re.sub(r"\.Ltmp\d+", ".Ltmp", l)
         l = re.sub(r"\$local\d*", "$local", l)
+        l = re.sub(r"^(\.LBB_\d+:|; %bb\.\d+:)\s*; %.*$", r"\1", l)      # the IR block name a label's comment repeats: numbered per module
         out.append(l)
     return out
 

@@ -28,6 +28,8 @@ wsw = torch.zeros(32 * 32 * 9, device="cuda")      # a clean workspace: zeros on
 t("raw lib.masic_conv2d_wgrad_ws (launch only)", lambda: _lib.lib.masic_conv2d_wgrad_ws(ops._p(xw), ops._p(xw), ops._p(dw), ops._p(wsw), ctypes.byref(dwg), 1, st), 5000)
 xk = torch.zeros(32 * 256, dtype=torch.int16, device="cuda")
 t("raw lib.masic_conv3x3_wgrad_f16k_ws (launch only)", lambda: _lib.lib.masic_conv3x3_wgrad_f16k_ws(ops._p(xk), ops._p(xk), ops._p(dw), ops._p(wsw), 1, 32, 32, 16, 16, 1, st), 5000)
+dcv = ops.make_conv_desc(1, 32, 16, 16, 32, 3, 3, 1, 1); wcv = ops.pack_conv_weight(torch.zeros(32, 32, 3, 3, device="cuda"), dcv); ycv = torch.empty(1, 32, 16, 16, device="cuda")
+t("raw lib.masic_conv2d_fwd (launch only)", lambda: _lib.lib.masic_conv2d_fwd(ops._p(xw), ops._p(wcv), None, None, ops._p(ycv), ctypes.byref(dcv), st), 5000)
 d = ops.make_conv_desc(2, 32, 16, 16, 32, 3, 3, 1, 1)
 t("make_conv_desc", lambda: ops.make_conv_desc(2, 32, 16, 16, 32, 3, 3, 1, 1))
 t("torch add (aten) x + y", lambda: x + y, 5000)
