@@ -117,7 +117,7 @@ int masic_gemm1x1_pack_weight(const float* w, void* wp, int Cin, int Cout, int t
 int masic_gemm1x1_bf16_fwd(const void* x_f16k, const void* w_packed, const float* bias, void* y_f16k, float* y_nchw,
                            int B, int Cin, int Cout, int HW, int out_ctot, int out_coff, int act, void* stream);
 
-/* The same 1x1 layers with both operands staged by DMA (masic_amd/csrc/conv_f16k.hip: gemm_f16k), Cin % 16 == 0 and
+/* The same 1x1 layers with both operands staged by DMA (masic_amd/csrc/gemm_f16k.hip: gemm_f16k), Cin % 16 == 0 and
  * Cout % 32 == 0; own weight pack (per 128-channel block, 64-channel chunks in LDS-image order). */
 size_t masic_gemm_f16k_packed_bytes(int Cin, int Cout);
 int masic_gemm_f16k_pack_weight(const float* w, void* wp, int Cin, int Cout, int transposed, void* stream);
@@ -236,7 +236,7 @@ int masic_conv_f16k_d2s_fwd(const void* x_f16k, const void* w_packed, const floa
  * oracle in tests/test_gpu_fp8.py.  Activations: F8K = [B][C/32][H*W][32] fp8, stored as fp8(x / scale) with one scale per
  * tensor; weights: one scale per output channel, written by the pack calls.  Contraction:
  * v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales, float32 accumulate; dequantisation (wscale[co] = weight scale x
- * input scale) in the epilogue (masic_amd/csrc/conv_f16k.hip, fp8.hip).
+ * input scale) in the epilogue (masic_amd/csrc/conv_f16k.hip, gemm_f16k.hip, fp8.hip).
  *   masic_nchw_to_f8k            float32 NCHW channel view -> F8K (in_op as masic_nchw_to_f16k_op), x * inv_scale, saturating
  *   masic_absmax                 *out = max(*out, max|x|) over n float32 (bf16 = 0) or bf16 (bf16 = 1) values: calibration
  *   masic_conv_f8k_pack_weight   d->prec = MASIC_PREC_FP8: fp8 slab stream + wscale[Cout] (max|W[co]| / 448)

@@ -44,7 +44,7 @@ class ConvFn(Function):
     def forward(ctx, x, weight, bias, mod, act):
         x = _c(x)
         if _gemm_1x1(mod, act):
-            # bf16-operand mode, 1x1 layers of the entropy-parameter stacks: the DMA-staged GEMM of the inference path (conv_f16k.hip:
+            # bf16-operand mode, 1x1 layers of the entropy-parameter stacks: the DMA-staged GEMM of the inference path (gemm_f16k.hip:
             # gemm_f16k, 4x the rate of the NCHW implicit-GEMM kernel at these shapes); x is converted once to F16K
             B, _, H, W = x.shape
             x16 = ops.nchw_to_f16k(x)
@@ -448,7 +448,7 @@ class AddFn(Function):
 
 class EnhancementBlockFn(Function):
     """Enhancement_Block -- three residual blocks and the skip over all of them (reference MASIC.py:149-164) -- as ONE node of the CQE
-    training step in bf16 mode, forward AND backward on F16K buffers (conv_f16k.hip, wgrad_f16k.hip, f16k_ops.hip):
+    training step in bf16 mode, forward AND backward on F16K buffers (conv_f16k.hip, conv3x3_resident.hip, wgrad_f16k.hip, f16k_ops.hip):
 
       (with `tail`: Independent_EN.conv2 + the residual image, reference :1487-1488, run on the block's F16K output in the same node)
       forward   x -> F16K once; per block  t = L(c1(x)),  u = L(c2(t)) (stored by the same launch as `y_pre`),  o = u + x (+ x0 on
@@ -640,7 +640,7 @@ _RD_FUSED = True             # the criterion as two launches; tests set False fo
 
 # ------------------------------------------------------------------------------------------ fused transforms (bf16-operand training)
 # In the bf16-operand mode the training step runs the SAME DMA-staged kernels as inference for the analysis / synthesis transforms
-# (conv_f16k.hip: both operands by DMA, (I)GDN in the epilogue) instead of one NCHW float32 launch per convolution and per GDN: the
+# (conv_f16k.hip, conv_a.hip: both operands by DMA, (I)GDN in the epilogue) instead of one NCHW float32 launch per convolution and per GDN: the
 # kernels store, per layer, the convolution's result before the GDN and the GDN's result, both F16K bf16 -- half the bytes of the
 # float32 activations the per-layer nodes keep -- and the backward converts each to float32 NCHW right before the kernel that
 # needs it (weight gradient: the layer's input; GDN backward: the GDN's input).  Gradients are those of the same function evaluated

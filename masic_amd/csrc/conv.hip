@@ -24,6 +24,7 @@
 // all output channels in registers, weights through scalar loads.
 #include "common.h"
 #include "conv_geom.h"
+#include "f16k_device.h"      // bf16x8
 
 namespace {
 struct ConvCfg {
@@ -237,7 +238,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, const ConvGeo
 // ---- F16K output (conv_igemm_bf16, a.y16): bf16(act(acc + bias)) as 32-byte channel records for an F16K consumer -- what
 // nchw_to_f16k_kernel makes of the float32 result of igemm_epilogue, bit for bit (that epilogue computes act(..) * 1.0f + 0.0f when there
 // is no gate and no residual: the + 0.0f turns -0 into +0 and is kept here).  Lane (j, h) holds channels 8q + 4h + i of pixel j, the
-// accumulator layout of conv_f16k.hip: the halves of the wave swap their middle quarters (v_permlane32_swap) and each lane writes the 8
+// accumulator layout of conv_f16k.hip (f16k_device.h: store_f16k_tile): the halves of the wave swap their middle quarters (v_permlane32_swap) and each lane writes the 8
 // consecutive channels 8h .. 8h+7 of a record with one 16-byte store.  Cout % 32 == 0: a 32-channel tile is valid or not as a whole.
 template <int WM, int WN>
 __device__ __forceinline__ void igemm_epilogue_f16k(const IgemmArgs& a, const ConvGeom& g, f32x16 (&acc)[WM][WN], int b, int m0w,
@@ -647,7 +648,6 @@ __global__ void pack_deconv4_kernel(const float* __restrict__ w, float* __restri
 //     [tap][ci/16][co][16 ci] bf16, so a wave's fragment load is 1 KiB contiguous -- prefetched one k-step ahead.
 //     Keeping the 25-tap weights out of LDS is what lets the whole 5x5 patch of a 128 x 256 tile fit.
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int MAXP = 6;    // pixel tasks per thread per 8-channel group (patch <= 1536 pixels)
 
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {

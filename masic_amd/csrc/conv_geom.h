@@ -1,4 +1,4 @@
-// conv_geom.h -- phase geometry of the convolution family (shared by conv.hip and conv_f16k.hip); see conv.hip header.
+// conv_geom.h -- phase geometry of the convolution family (shared by conv.hip and conv_f16k.hip; the other F16K families -- conv_a.hip, gemm_f16k.hip, conv3x3_resident.hip -- have fixed geometry); see conv.hip header.
 #pragma once
 #include "common.h"
 

@@ -1,7 +1,7 @@
 // f16k_ops.hip -- layout-side helpers of the F16K ([B][C/16][H*W][16] bf16) chains of Independent_EN (gfx950 / MI355X).
 //
 // The CQE network (reference coremasic/mywork/MASIC.py:1436-1501) works at full picture resolution on 32 / 64 / 96 channels;
-// with bf16 operands its 3x3 convolutions run on conv_f16k.hip with the activations in F16K between them.  What the reference
+// with bf16 operands its 3x3 convolutions run on conv_f16k.hip and conv3x3_resident.hip with the activations in F16K between them.  What the reference
 // writes as `torch.cat((a * w[:, 1:2], warp(b) * w[:, 0:1]), dim=-3)` (:1470-1482) is done here by writing each operand
 // straight into its channel slice of the concatenated F16K buffer:
 //   f16k_gate_kernel   dst[:, coff : coff+C] = (warp?)(src) * gate[:, gc]    (src F16K; gate float32 [B, G, H, W] or none;

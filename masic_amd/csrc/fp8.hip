@@ -1,10 +1,10 @@
 // fp8.hip -- layout / calibration helpers of the fp8 (OCP e4m3fn) operand path (BASELINE configs[4]; gfx950 / MI355X).
 //
 // F8K = [B][C/32][H*W][32] fp8: a pixel's 32 channels are one 32-byte record -- the same record size as F16K
-// ([B][C/16][H*W][16] bf16), so the DMA-staged kernels of conv_f16k.hip move both formats with the same code and one
+// ([B][C/16][H*W][16] bf16), so the DMA-staged kernels of conv_f16k.hip and gemm_f16k.hip move both formats with the same code and one
 // v_mfma_scale_f32_32x32x64_f8f6f4 (K = 64) consumes two records per pixel.  A tensor x is stored as fp8(x / scale) with ONE
 // scale per tensor, fixed at calibration (masic_amd/fp8.py: scale = recorded max|x| x margin / 448); weights carry one scale
-// per output channel (conv_f16k.hip: wscale_*).  No reference counterpart: the reference computes in float32; what this
+// per output channel (conv_f16k.hip, gemm_f16k.hip: wscale_*).  No reference counterpart: the reference computes in float32; what this
 // path costs in rate / PSNR / symbols is declared and gated against the oracle in tests/test_gpu_fp8.py.
 #include "common.h"
 

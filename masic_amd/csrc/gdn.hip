@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void gdn_bf16x3_c128(const float* __restric
     }
 }
 
-// gamma^ (bf16 hi, lo) in MFMA A-fragment order and beta^ for the GDN epilogue of conv_f16k.hip:
+// gamma^ (bf16 hi, lo) in MFMA A-fragment order and beta^ for the GDN epilogue of conv_f16k.hip and conv_a.hip (f16k_device.h: gdn_in_registers):
 //   img[((m*8 + s)*2 + hl)*64 + lane] = 8 bf16: gamma^[32m + (lane & 31)][chan(s, lane >> 5, c)], c = 0..7;  then beta^[128] floats
 __global__ void gdn_pack_f16k_kernel(const float* __restrict__ beta, const float* __restrict__ gamma, uint4* __restrict__ img,
                                      float beta_bound, float gamma_bound, float pedestal) {

@@ -27,7 +27,7 @@
 //         records through v_permlane32_swap) next to -- or instead of -- the float32 NCHW tensor the weight gradient reads,
 //   and the per-channel sums of dx (the bias gradient of the convolution in front of the GDN) ride along: per-lane float32
 //   sums over the workgroup's tiles, reduced across lanes and waves once at the end, one more row of the partial slot.
-#include "common.h"
+#include "f16k_device.h"      // pack2bf
 
 namespace {
 
@@ -75,14 +75,6 @@ struct GdnBwdArgs {
     long long npix;              // B * HW
     int HW, ntiles, inverse, want_sum;
 };
-
-__device__ __forceinline__ unsigned gb_pack2bf(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (__bf16)lo;
-    v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
 
 // lane (j, h) of a wave holds channels 32m + 8q + 4h + i (registers [m][4q + i]) of its pixel: 4 consecutive bf16 of record
 // 2m + (q >> 1), elements 8(q & 1) + 4h ...  rec: address of the pixel in record 0 (+ 4h elements); rs: elements between records
@@ -233,7 +225,7 @@ __global__ __launch_bounds__(256, 1) void gdn_bwd_c128(const GdnBwdArgs a) {
                 }
         }
         if (a.gx16 != nullptr) {
-            // as conv_f16k.hip: store_f16k_tile -- the two halves of the wave swap their middle quarters so that lane (j, h) writes
+            // as f16k_device.h: store_f16k_tile -- the two halves of the wave swap their middle quarters so that lane (j, h) writes
             // the 8 consecutive channels 8h .. 8h+7 of each 16-channel record with one 16-byte store (every lane takes part in
             // the swap; only valid pixels store)
             unsigned short* rec = a.gx16 + ((size_t)b * 8 * hw + pix) * 16 + 8 * h;
@@ -241,8 +233,8 @@ __global__ __launch_bounds__(256, 1) void gdn_bwd_c128(const GdnBwdArgs a) {
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
-                    const unsigned a0 = gb_pack2bf(uv[m][8 * r + 0], uv[m][8 * r + 1]), a1 = gb_pack2bf(uv[m][8 * r + 2], uv[m][8 * r + 3]);
-                    const unsigned b0 = gb_pack2bf(uv[m][8 * r + 4], uv[m][8 * r + 5]), b1 = gb_pack2bf(uv[m][8 * r + 6], uv[m][8 * r + 7]);
+                    const unsigned a0 = pack2bf(uv[m][8 * r + 0], uv[m][8 * r + 1]), a1 = pack2bf(uv[m][8 * r + 2], uv[m][8 * r + 3]);
+                    const unsigned b0 = pack2bf(uv[m][8 * r + 4], uv[m][8 * r + 5]), b1 = pack2bf(uv[m][8 * r + 6], uv[m][8 * r + 7]);
                     const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
                     const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
                     uint4 st;
@@ -483,8 +475,8 @@ __global__ __launch_bounds__(1024 / NML, 1) void gdn_bwd_c128_wn(const GdnBwdArg
             for (int ml = 0; ml < NML; ++ml)
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
-                    const unsigned a0 = gb_pack2bf(uv[ml][8 * r + 0], uv[ml][8 * r + 1]), a1 = gb_pack2bf(uv[ml][8 * r + 2], uv[ml][8 * r + 3]);
-                    const unsigned b0 = gb_pack2bf(uv[ml][8 * r + 4], uv[ml][8 * r + 5]), b1 = gb_pack2bf(uv[ml][8 * r + 6], uv[ml][8 * r + 7]);
+                    const unsigned a0 = pack2bf(uv[ml][8 * r + 0], uv[ml][8 * r + 1]), a1 = pack2bf(uv[ml][8 * r + 2], uv[ml][8 * r + 3]);
+                    const unsigned b0 = pack2bf(uv[ml][8 * r + 4], uv[ml][8 * r + 5]), b1 = pack2bf(uv[ml][8 * r + 6], uv[ml][8 * r + 7]);
                     const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
                     const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
                     uint4 st;

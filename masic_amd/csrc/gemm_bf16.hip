@@ -11,11 +11,9 @@
 // issues v_mfma_f32_32x32x16_bf16 into a 64(co) x 128(pixel) accumulator tile; the 4 waves of a workgroup share
 // operands through L1.  Epilogue: bias + ReLU/LeakyReLU, then either F16K bf16 for the next layer of the stack or
 // float32 NCHW for the consumer (the GMM likelihood kernel).
-#include "common.h"
+#include "f16k_device.h"      // bf16x8
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ unsigned pack2(float lo, float hi) {
     typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));

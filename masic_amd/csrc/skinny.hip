@@ -21,30 +21,9 @@
 // b = q / HW, pixel p = q % HW of a batch of nimg images: every buffer is [nimg][image] with its own per-image stride, the masked taps
 // stay inside image b (out-of-range rows / columns read zeros as at the picture edge), so a pixel's result still depends on its own
 // operands alone -- batched and one-image launches, in any list order and split, give the same bits.  One image: entries are p.
-#include "common.h"
-
-#include <type_traits>
+#include "f16k_device.h"      // bf16x8, v4u, static_for, pack2bf
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (__bf16)lo;
-    v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
 
 struct SkGroup {
     const unsigned short* x;      // F16K [nimg][Cin16][HW][16]

@@ -21,14 +21,10 @@
 // (mod 256) apart so that the two 16-lane groups of a half wave never share a bank.  Workgroups take a strided share of the
 // tiles and add their partial dW into a [tap][co][ci] workspace with float atomics (ci contiguous: full 128-byte segments);
 // a last pass transposes it into the weight layout.
-#include "common.h"
+#include "f16k_device.h"      // bf16x8, v2u, v4u
 #include "wgrad_slab.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 constexpr int TR = 4, TC = 32;                       // tile: output rows x columns
 constexpr int GP = TR * TC * 32 + 128;               // bytes per 16-channel plane of the dy tile (+128: bank offset between planes)

@@ -270,7 +270,7 @@ class _PackedWeightMixin:
         oc = (self.out_channels + 15) // 16 * 16 if out_ctot is None else out_ctot
         bias = None if self.bias is None else self.bias.detach()
         if self.resident_supported(B, Hi, Wi) and act in (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LEAKY):
-            # 32 -> 32 3x3 layers: weights resident in LDS, persistent workgroups (conv_f16k.hip: conv3x3_resident_f16k)
+            # 32 -> 32 3x3 layers: weights resident in LDS, persistent workgroups (conv3x3_resident.hip: conv3x3_resident_f16k)
             w = self.weight
             wp = _cached(self, "_packed_c3_cache", weight_key(w), (), lambda: ops.pack_conv3x3_resident_weight(w.detach()))
             return ops.conv3x3_resident(x16, wp, bias, B, self.in_channels, self.out_channels, Hi, Wi, act=act, y16=out16, out_ctot=oc, out_coff=out_coff,
@@ -309,7 +309,7 @@ class _PackedWeightMixin:
         return ops.conv2d_f16k_few(x16, wp, bp, desc, self.out_channels, res32=res32)
 
     def packed_gemm_dma_weight(self):
-        """Per-128-channel-block k16-major pack of a 1x1 layer for the DMA-staged GEMM (conv_f16k.hip: gemm_f16k)."""
+        """Per-128-channel-block k16-major pack of a 1x1 layer for the DMA-staged GEMM (gemm_f16k.hip: gemm_f16k)."""
         w = self.weight
         key = weight_key(w)
         cache = self.__dict__.get("_packed_gemm_dma_cache")

@@ -1693,7 +1693,7 @@ def pack_conv3x3_resident_weight(weight, transposed=False):
 
 def conv3x3_resident(x16, packed, bias, B, Cin, Cout, H, W, act=ACT_NONE, y16=None, out_ctot=None, out_coff=0, in_ctot=None, in_coff=0,
                      res1=None, res2=None, res_ctot=0, mask=None, mask_slope=0.0, y_pre=None, mask2=None, mask2_slope=0.0, sum_of=0):
-    """y = act(conv3x3(x) + bias) * act'(mask) + res1 + res2 on F16K buffers with LDS-resident weights (csrc/conv_f16k.hip:
+    """y = act(conv3x3(x) + bias) * act'(mask) + res1 + res2 on F16K buffers with LDS-resident weights (csrc/conv3x3_resident.hip:
     conv3x3_resident_f16k); operands as conv2d_f16k_res.  The input buffer holds ceil16(Cin) channels per pixel.
     mask2: also y2 = y * act'(mask2) (the next layer's dy of a backward chain); sum_of = 1 / 2: also the per-channel sums of the value
     before the residual adds / of y2 (a bias gradient).  Returns y, or (y, y2, sums) -- None where not asked -- when either is given."""

@@ -515,7 +515,7 @@ def test_conv5s1_pair_with_fused_gdn3(transposed, where):
 
 @pytest.mark.parametrize("B,Cin,Cmid,Cout,H,W,tr", [(2, 768, 1152, 960, 16, 24, True), (1, 960, 1152, 768, 8, 12, False), (3, 64, 96, 32, 5, 7, False)])
 def test_gemm_f16k_dma_stack(B, Cin, Cmid, Cout, H, W, tr):
-    """The DMA-staged GEMM of the head layers (conv_f16k.hip: gemm_f16k, both chunk sizes): two chained layers against the
+    """The DMA-staged GEMM of the head layers (gemm_f16k.hip: gemm_f16k, both chunk sizes): two chained layers against the
     float32 oracle on bf16-rounded operands, and bit-identical to the register-streamed kernel."""
     ops = _ops()
     x = _rand(B, Cin, H, W, seed=1, scale=2.0)

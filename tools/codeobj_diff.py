@@ -1,10 +1,14 @@
-"""Compare the device code of two builds of one source file kernel by kernel, keyed by symbol:
-    hipcc <the Makefile's FLAGS> -save-temps=obj -c conv_f16k.hip -o <dir>/conv_f16k.o       (once per commit)
+"""Compare the device code of two builds kernel by kernel, keyed by symbol.  A side is one module or several (a source file that was split:
+the union of their kernels is compared, and a symbol that several modules of a side hold must be the same kernel in each of them):
+    hipcc <the Makefile's FLAGS> -save-temps=obj -c conv_f16k.hip -o <dir>/conv_f16k.o       (once per commit and source file)
     python tools/codeobj_diff.py <dirA>/conv_f16k-hip-amdgcn-amd-amdhsa-gfx950.s <dirB>/conv_f16k-hip-amdgcn-amd-amdhsa-gfx950.s
+    python tools/codeobj_diff.py <dirA>/conv_f16k-hip-*.s -- <dirB>/conv_f16k-hip-*.s <dirB>/conv_a-hip-*.s <dirB>/gemm_f16k-hip-*.s <dirB>/conv3x3_resident-hip-*.s
 A kernel is "identical" when its assembly from .type to .end_amdhsa_kernel (instruction stream and the .amdhsa_ kernel descriptor:
 VGPRs, SGPRs, LDS, scratch, kernarg size) and its .amdgpu_metadata entry are equal after the function's index in the module is taken out
 of its local labels (.LBB<n>_, .Lfunc_end<n>) and the IR block names are taken out of the labels' comments (numbered per module: they
-move when another instantiation of the same template comes or goes).  The order of the kernels in the module is free."""
+move when another instantiation of the same template comes or goes) and the blanks between a local label and the comment after it are
+collapsed (the comment is padded to a column, so the padding changes with the number of digits of the index).  The order of the kernels in
+a module is free."""
 import re, sys, hashlib
 
 def norm(ls):
@@ -15,6 +19,7 @@ def norm(ls):
         l = re.sub(r"\.Ltmp\d+", ".Ltmp", l)
         l = re.sub(r"\$local\d*", "$local", l)
         l = re.sub(r"^(\.LBB_\d+:|; %bb\.\d+:)\s*; %.*$", r"\1", l)      # the IR block name a label's comment repeats: numbered per module
+        l = re.sub(r"^(\.LBB_\d+:)\s+;", r"\1 ;", l)                        # any other comment after a label is padded to a column: .LBB3_2: and .LBB10_2: pad differently
         out.append(l)
     return out
 
@@ -56,9 +61,31 @@ def kernels(path):
         i += 1
     return ks
 
-pa, pb = sys.argv[1], sys.argv[2]
-ka, kb, ma, mb = kernels(pa), kernels(pb), metadata(pa), metadata(pb)
-print(f"parent: {len(ka)} kernel symbols ({len(ma)} metadata entries); branch: {len(kb)} kernel symbols ({len(mb)} metadata entries)")
+def side(paths):
+    """the union of the kernels and metadata entries of a side's modules; a symbol in several of them (the common.h / conv_geom.h kernels
+    every module instantiates for itself) must be the same kernel in each"""
+    ks, ms, copies = {}, {}, 0
+    for p in paths:
+        k, m = kernels(p), metadata(p)
+        for s in k:
+            if s in ks:
+                copies += 1
+                if norm(k[s]) != norm(ks[s]) or m.get(s) != ms.get(s):
+                    sys.exit(f"{s}: differs between {p} and an earlier module of the same side")
+        ks.update(k)
+        ms.update(m)
+    return ks, ms, copies
+
+args = sys.argv[1:]
+if "--" in args:
+    pa, pb = args[:args.index("--")], args[args.index("--") + 1:]
+else:
+    pa, pb = args[:1], args[1:]
+if not pa or not pb:
+    sys.exit("usage: codeobj_diff.py PARENT.s [PARENT.s ...] -- BRANCH.s [BRANCH.s ...]      (one file per side: the `--` may be left out)")
+(ka, ma, ca), (kb, mb, cb) = side(pa), side(pb)
+print(f"parent: {len(ka)} kernel symbols ({len(ma)} metadata entries) in {len(pa)} module(s), {ca} repeated; "
+      f"branch: {len(kb)} kernel symbols ({len(mb)} metadata entries) in {len(pb)} module(s), {cb} repeated")
 print("removed:", sorted(set(ka) - set(kb)))
 print("added:  ", sorted(set(kb) - set(ka)))
 ndiff = 0

@@ -23,6 +23,10 @@ t("ops.elementwise(EW_SQUARE, x)", lambda: ops.elementwise(ops.EW_SQUARE, x), 50
 d16 = ops.make_conv_desc(1, 16, 16, 16, 128, 5, 5, 2, 2, prec=_lib.PREC_BF16); x16 = torch.zeros(16 * 256, dtype=torch.int16, device="cuda")
 wp = ops.pack_conv_f16k_weight(torch.zeros(128, 16, 5, 5, device="cuda"), d16); y16 = torch.empty(128 * 64, dtype=torch.int16, device="cuda")
 t("raw lib.masic_conv_f16k_gdn_fwd (launch only)", lambda: _lib.lib.masic_conv_f16k_gdn_fwd(ops._p(x16), ops._p(wp), None, None, None, 0, None, ops._p(y16), ctypes.byref(d16), st), 5000)
+wpg = ops.pack_gemm_f16k_weight(torch.zeros(32, 16, device="cuda"), 16, 32, False); yg = torch.empty(32 * 256, dtype=torch.int16, device="cuda")
+t("raw lib.masic_gemm_f16k_fwd (launch only)", lambda: _lib.lib.masic_gemm_f16k_fwd(ops._p(x16), ops._p(wpg), None, ops._p(yg), None, 1, 16, 32, 256, 32, 0, 0, st), 5000)
+x3 = torch.zeros(32 * 512, dtype=torch.int16, device="cuda"); wp3 = ops.pack_conv3x3_resident_weight(torch.zeros(32, 32, 3, 3, device="cuda")); y3 = torch.empty_like(x3)
+t("raw lib.masic_conv3x3_resident_fwd (launch only)", lambda: _lib.lib.masic_conv3x3_resident_fwd(ops._p(x3), ops._p(wp3), None, None, None, 0, None, 0.0, None, ops._p(y3), 1, 32, 32, 16, 32, 32, 0, 32, 0, 0, st), 5000)
 dwg = ops.make_conv_desc(1, 32, 16, 16, 32, 3, 3, 1, 1); xw = torch.zeros(1, 32, 16, 16, device="cuda"); dw = torch.empty(32, 32, 3, 3, device="cuda")
 wsw = torch.zeros(32 * 32 * 9, device="cuda")      # a clean workspace: zeros on entry, zeros again after every call
 t("raw lib.masic_conv2d_wgrad_ws (launch only)", lambda: _lib.lib.masic_conv2d_wgrad_ws(ops._p(xw), ops._p(xw), ops._p(dw), ops._p(wsw), ctypes.byref(dwg), 1, st), 5000)
