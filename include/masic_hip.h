@@ -816,6 +816,33 @@ int masic_ssim_bwd(const float* X, const float* Y, const float* gout, int N, int
                    const float* weights, float C1, float C2, int flags, const void* ws, void* bws, float* dX, float* dY, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LPIPS, AlexNet trunk (masic_amd/csrc/lpips.hip; the schedule is masic_amd/lpips.py): what the implicit-GEMM convolution does not
+ * cover of `lpips.LPIPS(net='alex')` as the reference's evaluators call it (coremasic/mywork/test2_real.py:105-112).  Float32, fixed
+ * summation orders, no float atomics, no fills, no host synchronisation (capturable into a HIP graph); a picture's result does not
+ * depend on which other pictures share the launch.  The two pictures of comparison n are images 2n and 2n + 1 of every batch.
+ *   masic_lpips_conv1_pack_weight  w [64][3][11][11] -> the A-fragment image of masic_lpips_conv1_fwd (masic_lpips_conv1_packed_bytes).
+ *   masic_lpips_conv1_fwd   y[2N][64][Ho][Wo] = relu(Conv2d(3 -> 64, k11, s4, p2)(s(x)) + bias), Ho = (H - 7) / 4 + 1; image 2n is
+ *                           in0[n], image 2n + 1 is in1[n] (both [N][3][H][W], no concat copy); s(x) = ((normalize ? 2x - 1 : x) -
+ *                           shift[c]) / scale[c] on in-image pixels, padding is zero after s.  shift, scale: 3 floats each, device
+ *                           memory.  H, W >= 11.  Weights at the twelfth row / column of the 12 x 12 tap grid are zeros that multiply
+ *                           in-image pixels, so a non-finite pixel reaches outputs one row / column further than in Conv2d.
+ *   masic_maxpool3s2_fwd    MaxPool2d(3, 2) (floor mode) of `planes` planes of H x W (>= 3) -> ((H - 3) / 2 + 1) x ((W - 3) / 2 + 1);
+ *                           NaN propagates, the first of equal values wins (torch's scan).
+ *   masic_lpips_dist_fwd    f [2N][C][HW], lin [C]: per pixel the norms na = sqrt(sum_c a_c^2) + 1e-10 and nb first, then
+ *                           sum_c lin_c (a_c / na - b_c / nb)^2; part[n][chunk] (double) = the sum over the chunk's pixels,
+ *                           masic_lpips_dist_chunks(HW) chunks per picture.
+ *   masic_lpips_finish      out[1 + t][n] = (float)(sum_chunk part_t[n][chunk] / hw[t]) for the five taps, out[0][n] their float32 sum in
+ *                           tap order; part holds the taps' [N][nchunks[t]] blocks back to back; nchunks, hw: 5 ints each, host memory. */
+size_t masic_lpips_conv1_packed_bytes(void);
+int masic_lpips_conv1_pack_weight(const float* w, float* w_packed, void* stream);
+int masic_lpips_conv1_fwd(const float* in0, const float* in1, const float* w_packed, const float* bias, const float* shift,
+                          const float* scale, float* y, int N, int H, int W, int normalize, void* stream);
+int masic_maxpool3s2_fwd(const float* x, float* y, int planes, int H, int W, void* stream);
+int masic_lpips_dist_chunks(int HW);
+int masic_lpips_dist_fwd(const float* f, const float* lin, double* part, int N, int C, int HW, void* stream);
+int masic_lpips_finish(const double* part, const int* nchunks, const int* hw, int N, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Deterministic mode (masic_amd/determinism.py).  Siblings of the weight-gradient and warp-backward entry points
  * above with the same arguments and the same results up to summation order, but NO float atomics: each pixel split stores its partial
  * tile with plain stores into its own slab of `workspace` ([split][...], indexed by split number), and a finishing launch sums the slabs

@@ -249,6 +249,14 @@ SIGNATURES = {
     "masic_ssim_fwd": (c_int, [_P, _P] + [c_int] * 5 + [_P, c_float, c_float, _P, _P]),
     "masic_ssim_finish": (c_int, [_P] + [c_int] * 5 + [_P, c_int, _P, _P]),
     "masic_ssim_bwd": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P, _P, c_float, c_float, c_int, _P, _P, _P, _P, _P]),
+    # LPIPS (AlexNet trunk)
+    "masic_lpips_conv1_packed_bytes": (c_size_t, []),
+    "masic_lpips_conv1_pack_weight": (c_int, [_P, _P, _P]),
+    "masic_lpips_conv1_fwd": (c_int, [_P] * 7 + [c_int] * 4 + [_P]),
+    "masic_maxpool3s2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "masic_lpips_dist_chunks": (c_int, [c_int]),
+    "masic_lpips_dist_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "masic_lpips_finish": (c_int, [_P, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, _P, _P]),
 }
 
 

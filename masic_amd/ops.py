@@ -1906,3 +1906,83 @@ def ssim_bwd(X, Y, ws, gout, taps, weights, C1, C2, flags, need_x=True, need_y=F
     check(lib.masic_ssim_bwd(_p(X), _p(Y), _p(gout), N, C, H, W, levels, _f32_array(taps, 11), w, float(C1), float(C2), int(flags),
                              _p(ws), _p(bws), _p(dX), _p(dY), _stream()), "ssim_bwd")
     return dX, dY
+
+
+# ------------------------------------------------------------------------------------------ LPIPS, AlexNet trunk (masic_amd/lpips.py)
+def pack_lpips_conv1_weight(weight):
+    """The fragment-order image of a Conv2d(3, 64, 11, stride 4, padding 2) weight for lpips_conv1."""
+    _dev(weight, "weight")
+    if tuple(weight.shape) != (64, 3, 11, 11):
+        raise RuntimeError(f"masic_amd.pack_lpips_conv1_weight: weight {tuple(weight.shape)} is not a Conv2d(3, 64, 11)")
+    packed = torch.empty(lib.masic_lpips_conv1_packed_bytes() // 4, dtype=torch.float32, device=weight.device)
+    check(lib.masic_lpips_conv1_pack_weight(_p(weight), _p(packed), _stream()), "lpips_conv1_pack_weight")
+    return packed
+
+
+def lpips_conv1(in0, in1, packed, bias, shift, scale, normalize=False):
+    """relu(Conv2d(3 -> 64, k11, s4, p2)(((2x - 1 if normalize else x) - shift) / scale) + bias) of two [N,3,H,W] pictures read in
+    place: [2N,64,Ho,Wo] with in0[n] as image 2n and in1[n] as image 2n + 1."""
+    _dev(in0, "in0"); _dev(in1, "in1"); _dev(packed, "packed weight"); _dev(bias, "bias"); _dev(shift, "shift"); _dev(scale, "scale")
+    if in0.dim() != 4 or in0.shape[1] != 3 or in0.shape != in1.shape:
+        raise RuntimeError(f"masic_amd.lpips_conv1: pictures must be two [N,3,H,W] tensors, got {tuple(in0.shape)} and {tuple(in1.shape)}")
+    if bias.numel() != 64 or shift.numel() != 3 or scale.numel() != 3 or packed.numel() * 4 != lib.masic_lpips_conv1_packed_bytes():
+        raise RuntimeError("masic_amd.lpips_conv1: bias [64], shift [3], scale [3] and the pack of pack_lpips_conv1_weight expected")
+    N, _, H, W = in0.shape
+    y = torch.empty((2 * N, 64, (H - 7) // 4 + 1, (W - 7) // 4 + 1), dtype=torch.float32, device=in0.device)
+    check(lib.masic_lpips_conv1_fwd(_p(in0), _p(in1), _p(packed), _p(bias), _p(shift), _p(scale), _p(y), N, H, W, int(bool(normalize)), _stream()),
+          "lpips_conv1_fwd")
+    return y
+
+
+def maxpool3s2(x):
+    """MaxPool2d(3, 2) (floor mode) of a float32 NCHW tensor."""
+    _dev(x, "maxpool input")
+    if x.dim() != 4 or x.shape[2] < 3 or x.shape[3] < 3:
+        raise RuntimeError(f"masic_amd.maxpool3s2: input must be [B,C,H,W] with H, W >= 3, got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    y = torch.empty((B, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1), dtype=torch.float32, device=x.device)
+    check(lib.masic_maxpool3s2_fwd(_p(x), _p(y), B * C, H, W, _stream()), "maxpool3s2_fwd")
+    return y
+
+
+def lpips_distance(feats, lins):
+    """The LPIPS head on five feature taps [2N,C_t,h_t,w_t] (pictures 2n, 2n + 1 compared) with lin weights [.., C_t ..]: float32 [6,N],
+    row 0 the value, rows 1..5 the taps' spatial means of sum_c lin_c (a_c / |a| - b_c / |b|)^2."""
+    if len(feats) != 5 or len(lins) != 5:
+        raise RuntimeError("masic_amd.lpips_distance: five taps expected")
+    N = feats[0].shape[0] // 2
+    hw, nch = [], []
+    for f, w in zip(feats, lins):
+        _dev(f, "feature tap"); _dev(w, "lin weight")
+        if f.dim() != 4 or f.shape[0] != 2 * N or w.numel() != f.shape[1]:
+            raise RuntimeError(f"masic_amd.lpips_distance: tap {tuple(f.shape)} with lin weight {tuple(w.shape)}")
+        hw.append(f.shape[2] * f.shape[3])
+        nch.append(_int_query("masic_lpips_dist_chunks", hw[-1]))
+    part = torch.empty(N * sum(nch), dtype=torch.float64, device=feats[0].device)
+    out = torch.empty((6, N), dtype=torch.float32, device=feats[0].device)
+    st, off = _stream(), 0
+    for f, w, m, k in zip(feats, lins, hw, nch):
+        check(lib.masic_lpips_dist_fwd(_p(f), _p(w), ctypes.c_void_p(part.data_ptr() + 8 * off), N, f.shape[1], m, st), "lpips_dist_fwd")
+        off += N * k
+    check(lib.masic_lpips_finish(_p(part), (ctypes.c_int * 5)(*nch), (ctypes.c_int * 5)(*hw), N, _p(out), st), "lpips_finish")
+    return out
+
+
+def conv_plan_signature(desc):
+    """What fixes the summation order of one output of an implicit-GEMM convolution besides its operands: the kernel family and, from
+    masic_conv_plan_name's configuration, the padded input channels, the K chunk, the 16-byte staging form and the phase count -- k runs
+    over (chunk, tap, channel pair of the chunk).  The tile shape (the template arguments, TW / TH, the grid) only says which workgroup
+    computes an output.  Two descriptors that differ in B only and agree here give every image the same bits."""
+    sig = desc.__dict__.get("_plan_sig")
+    if sig is None:
+        buf = ctypes.create_string_buffer(512)
+        check(lib.masic_conv_plan_name(ctypes.byref(desc), 0, buf, 512), "conv_plan_name")
+        fields = [s.strip() for s in buf.value.decode().split("|")]
+        family, ints = fields[0].split("<")[0], fields[4].split()
+        if family not in ("conv_igemm_f32", "conv_igemm_bf16") or len(ints) != 12:
+            sig = tuple(fields[:1] + fields[2:])          # another family: only an identical plan counts as the same order
+        else:
+            cin_pad, _, kc, _, _, _, _, _, _, _, vec4, nphase = ints
+            sig = (family, cin_pad, kc, vec4, nphase)
+        desc.__dict__["_plan_sig"] = sig
+    return sig
