@@ -842,6 +842,41 @@ int masic_lpips_dist_chunks(int HW);
 int masic_lpips_dist_fwd(const float* f, const float* lin, double* part, int N, int C, int HW, void* stream);
 int masic_lpips_finish(const double* part, const int* nchunks, const int* hw, int N, float* out, void* stream);
 
+/* LPIPS input gradients (masic_amd/csrc/lpips_bwd.hip; the schedule is masic_amd/lpips.py): with the float32 implicit-GEMM convolution
+ * run as the opposite layer kind for layers 2-5, the backward of the forward above with respect to the pictures -- in0, in1 or both;
+ * no weight gradients.  The rules of the forward hold (float32, fixed summation orders, no float atomics, no fills, no host
+ * synchronisation, an image's result independent of the rest of the launch).  `f` is always a tap of the forward, [2N][C][HW] with
+ * images 2n and 2n + 1 compared.  A gradient tensor holds the images of ONE side, [N][..] (sides = 1: in0's, sides = 2: in1's), or
+ * the interleaved [2N][..] of the forward (sides = 3).  Everything is written, not accumulated.
+ *   masic_lpips_dist_bwd    g_pre = (g_dist + g_in) * [f > 0]: the gradient of the tap's PRE-activation.  g_dist is the gradient of
+ *                           G[n] * mean_pixels sum_c lin_c (a_c / na - b_c / nb)^2 with G[n] = g_val[n] + g_res[n] read from device
+ *                           memory (the upstream gradients of the value and of this tap's per-layer value): with u = a / na,
+ *                           v = b / nb, d = u - v, d/da_c = (2 G / HW) (lin_c d_c / na - a_c (sum_k lin_k d_k a_k) / (na^2 sqrt(sum a^2))),
+ *                           the mirror image with the opposite sign for b; d and the sum are formed from the normalised values.
+ *                           DEVIATION from lpips's autograd, on purpose: at a pixel whose squares sum to 0 the second term is DEFINED
+ *                           as 0 (d/da_c = 2 G lin_c d_c / (HW 1e-10) with u = 0), matching the forward's 0 / 1e-10 = 0; torch
+ *                           computes 0 / 0 = NaN in sqrt's backward there.  (With the ReLU mask that pixel's own g_pre is 0 either
+ *                           way; the other picture's gradient at the pixel is the regular formula with u = 0.)  g_in (nullable): what
+ *                           arrives from the layer above, laid out as g_pre; g_pre may be g_in itself (in place).
+ *   masic_maxpool3s2_bwd    gx [B][C][H][W] from gy [B][C][Ho][Wo] of MaxPool2d(3, 2): a gather over the <= 2 x 2 windows covering a
+ *                           pixel in row-major window order, each window's winner recomputed with the forward's scan -- bit-equal to
+ *                           torch's max_pool2d backward; rows / columns under no window get 0.  The forward input of image b is image
+ *                           b * img_stride + img_off of x (x: a saved tap; stride 2, offset = side for a one-sided chain, else 1, 0).
+ *   masic_lpips_conv1_bwd_pack_weight  w [64][3][11][11] -> the image [row phase][co][tap][c][column phase] read by masic_lpips_conv1_bwd
+ *                           (masic_lpips_conv1_bwd_packed_bytes).
+ *   masic_lpips_conv1_bwd   the input gradient of masic_lpips_conv1_fwd's convolution (g: the gradient of its pre-activation,
+ *                           [B][64][Ho][Wo]) through the scaling layer and `normalize`: d[.][3][H][W] = convT(g) / scale[c] (* 2 under
+ *                           normalize), every pixel written (exactly 0 where no window reaches).  d0 and d1 both given: B = 2N
+ *                           interleaved images, image 2n goes to d0[n], image 2n + 1 to d1[n]; one of them null: B images to the other. */
+int masic_lpips_dist_bwd(const float* f, const float* lin, const float* g_val, const float* g_res, const float* g_in, float* g_pre,
+                         int N, int C, int HW, int sides, void* stream);
+int masic_maxpool3s2_bwd(const float* x, const float* gy, float* gx, int B, int C, int H, int W, int img_stride, int img_off,
+                         void* stream);
+size_t masic_lpips_conv1_bwd_packed_bytes(void);
+int masic_lpips_conv1_bwd_pack_weight(const float* w, float* w_packed, void* stream);
+int masic_lpips_conv1_bwd(const float* g, const float* w_packed, const float* scale, float* d0, float* d1, int B, int H, int W,
+                          int normalize, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Deterministic mode (masic_amd/determinism.py).  Siblings of the weight-gradient and warp-backward entry points
  * above with the same arguments and the same results up to summation order, but NO float atomics: each pixel split stores its partial

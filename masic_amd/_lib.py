@@ -257,6 +257,11 @@ SIGNATURES = {
     "masic_lpips_dist_chunks": (c_int, [c_int]),
     "masic_lpips_dist_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "masic_lpips_finish": (c_int, [_P, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, _P, _P]),
+    "masic_lpips_dist_bwd": (c_int, [_P] * 6 + [c_int] * 4 + [_P]),
+    "masic_maxpool3s2_bwd": (c_int, [_P] * 3 + [c_int] * 6 + [_P]),
+    "masic_lpips_conv1_bwd_packed_bytes": (c_size_t, []),
+    "masic_lpips_conv1_bwd_pack_weight": (c_int, [_P, _P, _P]),
+    "masic_lpips_conv1_bwd": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
 }
 
 

@@ -25,13 +25,29 @@ comparison n travel as images 2n and 2n + 1 of one batch of 2N.  A picture's val
 reused convolution picks its K chunk (hence its summation order) from the batch size among other things, so a layer whose launch
 plan for 2N images would sum in another order than the plan for 2 (ops.conv_plan_signature) runs once per picture pair instead.
 
-Not built (each raises): other trunks, version != '0.1', `spatial=True`, `lpips=False`, `pnet_tune=True`, training mode (Dropout in
-the lin layers), gradients (the evaluators run under no_grad; no parameter of this module requires grad), CPU tensors.
+**As a loss.**  `loss_fn(x_hat, x).mean().backward()`: when grad is enabled and a picture on the device requires grad, the same 13
+launches run inside one `torch.autograd.Function` that keeps the five taps, and its backward is a second schedule of 12 launches
+(masic_amd/csrc/lpips_bwd.hip, conv.hip): per tap, from the last to the first, one launch that forms the gradient of the normalised
+distance (under the upstream gradients of `val` and of the per-layer values, read on the device), adds what arrives from the layer
+above and applies the tap's ReLU mask; between the taps the input gradient of layers 5-2 as the float32 implicit-GEMM convolution run
+as the opposite layer kind on the same weight, and the max-pool backward as a gather; last the input gradient of the first layer with
+the scaling layer, `normalize` and the split into the two pictures' gradients folded into its store.  With one picture requiring grad
+(the training case: the other is the target) the chain runs on that side's N images, with both on the 2N interleaved ones.  Float32,
+no float atomics, fixed summation orders, capturable; picture n's gradient does not depend on the rest of the batch, and the
+one-sided chain gives the bits of the two-sided one: a layer's input gradient runs as one launch only if its plan sums in the order of
+the ONE-image plan, else per pair if the two-image plan does, else per image.  Once differentiable.  Deliberate deviation from lpips's
+autograd: at a feature pixel that is zero in every channel torch's sqrt backward is 0 / 0 = NaN; here the norm's derivative is
+defined as 0 there, in line with the forward's 0 / 1e-10 = 0 (include/masic_hip.h, masic_lpips_dist_bwd).
+
+Not built (each raises): other trunks, version != '0.1', `spatial=True`, `lpips=False`, `pnet_tune=True` and any other weight gradient
+(no parameter of this module requires grad, and one flipped to requires_grad raises in forward), training mode (Dropout in the lin
+layers), double backward, CPU tensors (with or without grad).
 """
 import os
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import nn as _mnn
 from . import ops as _hip
@@ -139,13 +155,78 @@ def _conv_relu(conv, x):
     return y
 
 
+def _conv_dgrad(conv, g, unit):
+    """The input gradient of a stride-1 layer of the trunk (pad = k // 2: the map keeps its size) from the gradient g [B,Cout,h,w] of its
+    pre-activation: the float32 implicit GEMM as the opposite layer kind on the same weight.  `unit`: the images one call on a single
+    comparison holds (1 for a one-sided chain, 2 for both sides).  One launch when its plan sums in the order of the one-image plan, else
+    one per `unit` images if that plan does, else one per image -- image n gets the arithmetic of a one-image launch in every case, so
+    the one-sided and the two-sided chain agree bit for bit."""
+    B, _, H, W = g.shape
+    k, p = conv.kernel_size[0], conv.padding[0]
+    w = conv.weight
+
+    def desc(b):
+        return _hip.make_conv_desc(b, conv.out_channels, H, W, conv.in_channels, k, k, 1, p, transposed=True, prec=_F32)
+
+    def run(gv, out=None):
+        d = desc(gv.shape[0])
+        packed = _mnn._cached(conv, "_packed_dgrad_cache", _mnn.weight_key(w), (gv.shape[0], H, W, _F32),
+                              lambda: _hip.pack_conv_weight(w.detach().contiguous(), d))
+        return _hip.conv2d(gv, packed, None, d, out=out)
+
+    one = _hip.conv_plan_signature(desc(1))
+    step = next(u for u in (B, unit, 1) if u == 1 or (B % u == 0 and _hip.conv_plan_signature(desc(u)) == one))
+    if step == B:
+        return run(g)
+    y = torch.empty((B, conv.in_channels, H, W), dtype=torch.float32, device=g.device)
+    for n in range(0, B, step):
+        run(g[n:n + step], out=y[n:n + step])
+    return y
+
+
+class _LpipsFn(torch.autograd.Function):
+    """out [6,N] (row 0 the value, rows 1-5 the per-layer values) of LPIPS._run with the five taps kept for the backward schedule."""
+
+    @staticmethod
+    def forward(ctx, in0, in1, mod, normalize):
+        taps, lins, out = mod._run(in0, in1, normalize)
+        ctx.mod, ctx.normalize, ctx.hw = mod, normalize, tuple(in0.shape[2:])
+        ctx.save_for_backward(*taps, *lins)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        taps, lins = ctx.saved_tensors[:5], ctx.saved_tensors[5:]
+        mod = ctx.mod
+        sides = (1 if ctx.needs_input_grad[0] else 0) | (2 if ctx.needs_input_grad[1] else 0)
+        if not sides:
+            return None, None, None, None
+        unit, stride, off = (2, 1, 0) if sides == 3 else (1, 2, sides - 1)
+        gout = gout.contiguous()
+        g = None
+        for t in range(4, -1, -1):
+            g = _hip.lpips_dist_bwd(taps[t], lins[t], gout, t, sides, g_in=g, out=g)
+            if t:
+                s, *_, pool = _CONVS[t]
+                g = _conv_dgrad(mod.net.conv(s), g, unit)
+                if pool:
+                    g = _hip.maxpool3s2_bwd(taps[t - 1], g, stride, off)
+        c1 = mod.net.conv(1)
+        w = c1.weight
+        packed = _mnn._cached(c1, "_packed_lpips_bwd_cache", _mnn.weight_key(w), (),
+                              lambda: _hip.pack_lpips_conv1_bwd_weight(w.detach().contiguous()))
+        d0, d1 = _hip.lpips_conv1_bwd(g, packed, mod.scaling_layer.scale, ctx.hw[0], ctx.hw[1], ctx.normalize, sides)
+        return d0, d1, None, None
+
+
 class LPIPS(nn.Module):
     def __init__(self, pretrained=True, net='alex', version='0.1', lpips=True, spatial=False, pnet_rand=False, pnet_tune=False,
                  use_dropout=True, model_path=None, eval_mode=True, verbose=True):
         super().__init__()
         for what, bad in ((f"net={net!r} (only 'alex')", net != 'alex'), (f"version={version!r} (only '0.1')", version != '0.1'),
                           ("spatial=True", bool(spatial)), ("lpips=False (the unweighted baseline)", not lpips),
-                          ("pnet_tune=True (no backward)", bool(pnet_tune))):
+                          ("pnet_tune=True (no weight gradients)", bool(pnet_tune))):
             if bad:
                 raise NotImplementedError(f"lpips.LPIPS: {what} is not built on the HIP path")
         if verbose:
@@ -185,7 +266,7 @@ class LPIPS(nn.Module):
                 if verbose:
                     print('Loading model from: %s' % lin_path)
                 self.load_state_dict(torch.load(lin_path, map_location="cpu"), strict=False)
-        for prm in self.parameters():          # inference only: no backward exists for any of them
+        for prm in self.parameters():          # no weight gradient exists for any of them
             prm.requires_grad = False
         if eval_mode:
             self.eval()
@@ -203,31 +284,50 @@ class LPIPS(nn.Module):
         if in0.shape[0] < 1 or min(in0.shape[2:]) < _MIN_SIDE:
             raise ValueError(f"lpips.LPIPS: {tuple(in0.shape)}: at least one picture with sides >= {_MIN_SIDE} (the second max-pool "
                              "would have no window)")
-        if torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad):
-            raise NotImplementedError("lpips.LPIPS: no backward is built -- call under torch.no_grad() or detach the inputs")
+        grad = torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad)
+        if grad and not (in0.is_cuda and in1.is_cuda):
+            raise NotImplementedError("lpips.LPIPS: no backward is built for CPU tensors -- the gradients run on the MI355X path only")
+        if torch.is_grad_enabled() and any(prm.requires_grad for prm in self.parameters()):
+            raise NotImplementedError("lpips.LPIPS: a parameter requires grad, but no weight gradient is built (only the pictures' "
+                                      "gradients) -- keep the parameters at requires_grad=False or call under torch.no_grad()")
         for t, name in ((in0, "in0"), (in1, "in1")):
             if not t.is_cuda:
                 raise RuntimeError(f"lpips.LPIPS: {name} must be a CUDA (HIP) tensor -- the MI355X path has no CPU fallback")
+        return grad
 
-    def features(self, in0, in1, normalize=False):
-        """The five taps [2N,C,h,w] (float32 NCHW), in0[n] as image 2n and in1[n] as image 2n + 1."""
-        self._check(in0, in1)
-        with torch.no_grad():
-            c1 = self.net.conv(1)
-            w = c1.weight
-            packed = _mnn._cached(c1, "_packed_lpips_cache", _mnn.weight_key(w), (),
-                                  lambda: _hip.pack_lpips_conv1_weight(w.detach().contiguous()))
-            sl = self.scaling_layer
-            taps = [_hip.lpips_conv1(in0.contiguous(), in1.contiguous(), packed, c1.bias.detach(), sl.shift, sl.scale, normalize)]
-            for s, *_, pool in _CONVS[1:]:
-                x = _hip.maxpool3s2(taps[-1]) if pool else taps[-1]
-                taps.append(_conv_relu(self.net.conv(s), x))
+    def _taps(self, in0, in1, normalize):
+        c1 = self.net.conv(1)
+        w = c1.weight
+        packed = _mnn._cached(c1, "_packed_lpips_cache", _mnn.weight_key(w), (),
+                              lambda: _hip.pack_lpips_conv1_weight(w.detach().contiguous()))
+        sl = self.scaling_layer
+        taps = [_hip.lpips_conv1(in0.detach().contiguous(), in1.detach().contiguous(), packed, c1.bias.detach(), sl.shift, sl.scale, normalize)]
+        for s, *_, pool in _CONVS[1:]:
+            x = _hip.maxpool3s2(taps[-1]) if pool else taps[-1]
+            taps.append(_conv_relu(self.net.conv(s), x))
         return taps
 
-    def forward(self, in0, in1, retPerLayer=False, normalize=False):
-        taps = self.features(in0, in1, normalize)
+    def _run(self, in0, in1, normalize):
+        """The 13 launches: (taps, lin weights, out [6,N])."""
+        taps = self._taps(in0, in1, normalize)
+        lins = [self.lins[i].weight.detach() for i in range(self.L)]
+        return taps, lins, _hip.lpips_distance(taps, lins)
+
+    def features(self, in0, in1, normalize=False):
+        """The five taps [2N,C,h,w] (float32 NCHW), in0[n] as image 2n and in1[n] as image 2n + 1.  Not differentiable: gradients flow
+        through `forward` only."""
+        if self._check(in0, in1):
+            raise NotImplementedError("lpips.LPIPS.features: the taps carry no gradient -- differentiate forward(), or call under "
+                                      "torch.no_grad()")
         with torch.no_grad():
-            out = _hip.lpips_distance(taps, [self.lins[i].weight.detach() for i in range(self.L)])
+            return self._taps(in0, in1, normalize)
+
+    def forward(self, in0, in1, retPerLayer=False, normalize=False):
+        if self._check(in0, in1):
+            out = _LpipsFn.apply(in0, in1, self, bool(normalize))
+        else:
+            with torch.no_grad():
+                out = self._run(in0, in1, normalize)[2]
         N = in0.shape[0]
         val = out[0].view(N, 1, 1, 1)
         if retPerLayer:

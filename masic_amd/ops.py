@@ -1968,6 +1968,71 @@ def lpips_distance(feats, lins):
     return out
 
 
+def lpips_dist_bwd(f, lin, gout, tap, sides, g_in=None, out=None):
+    """The gradient of the pre-activation of a tap f [2N,C,h,w] (images 2n, 2n + 1 compared): (g_dist + g_in) * [f > 0], where g_dist is
+    the gradient of the tap's normalised distance under the upstream gradients gout [6,N] (row 0 of the value, row 1 + tap of the
+    per-layer value; read on the device) and g_in what arrives from the layer above.  sides: 1 in0's images [N,C,h,w], 2 in1's, 3 both,
+    interleaved [2N,C,h,w] -- the layout of g_in and of the result.  out may be g_in (in place)."""
+    _dev(f, "feature tap"); _dev(lin, "lin weight"); _dev(gout, "upstream gradient")
+    if f.dim() != 4 or f.shape[0] % 2 or lin.numel() != f.shape[1] or sides not in (1, 2, 3):
+        raise RuntimeError(f"masic_amd.lpips_dist_bwd: tap {tuple(f.shape)} with lin weight {tuple(lin.shape)}, sides {sides}")
+    N, C, h, w = f.shape[0] // 2, f.shape[1], f.shape[2], f.shape[3]
+    if tuple(gout.shape) != (6, N) or not 0 <= tap < 5:
+        raise RuntimeError(f"masic_amd.lpips_dist_bwd: upstream gradient {tuple(gout.shape)} for {N} comparisons, tap {tap}")
+    shape = (2 * N if sides == 3 else N, C, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=f.device)
+    for t, name in ((g_in, "incoming gradient"), (out, "gradient buffer")):
+        if t is not None:
+            _dev(t, name)
+            if tuple(t.shape) != shape:
+                raise RuntimeError(f"masic_amd.lpips_dist_bwd: {name} {tuple(t.shape)}, expected {shape}")
+    gv = ctypes.c_void_p(gout.data_ptr())
+    gr = ctypes.c_void_p(gout.data_ptr() + 4 * (1 + tap) * N)
+    check(lib.masic_lpips_dist_bwd(_p(f), _p(lin), gv, gr, _p(g_in), _p(out), N, C, h * w, sides, _stream()), "lpips_dist_bwd")
+    return out
+
+
+def maxpool3s2_bwd(x, gy, img_stride=1, img_off=0):
+    """The input gradient [B,C,H,W] of MaxPool2d(3, 2) from gy [B,C,Ho,Wo]; the forward input of image b is x[b * img_stride + img_off]
+    (x: [B * img_stride,C,H,W]).  Bit-equal to torch's max_pool2d backward."""
+    _dev(x, "maxpool input"); _dev(gy, "maxpool output gradient")
+    if x.dim() != 4 or gy.dim() != 4 or x.shape[2] < 3 or x.shape[3] < 3 or img_stride < 1 or not 0 <= img_off < img_stride:
+        raise RuntimeError(f"masic_amd.maxpool3s2_bwd: input {tuple(x.shape)}, gradient {tuple(gy.shape)}, stride {img_stride}, offset {img_off}")
+    B, C, H, W = gy.shape[0], x.shape[1], x.shape[2], x.shape[3]
+    if x.shape[0] != B * img_stride or tuple(gy.shape) != (B, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1):
+        raise RuntimeError(f"masic_amd.maxpool3s2_bwd: gradient {tuple(gy.shape)} does not belong to input {tuple(x.shape)} (image stride {img_stride})")
+    gx = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+    check(lib.masic_maxpool3s2_bwd(_p(x), _p(gy), _p(gx), B, C, H, W, img_stride, img_off, _stream()), "maxpool3s2_bwd")
+    return gx
+
+
+def pack_lpips_conv1_bwd_weight(weight):
+    """The image of a Conv2d(3, 64, 11, stride 4, padding 2) weight that lpips_conv1_bwd reads."""
+    _dev(weight, "weight")
+    if tuple(weight.shape) != (64, 3, 11, 11):
+        raise RuntimeError(f"masic_amd.pack_lpips_conv1_bwd_weight: weight {tuple(weight.shape)} is not a Conv2d(3, 64, 11)")
+    packed = torch.empty(lib.masic_lpips_conv1_bwd_packed_bytes() // 4, dtype=torch.float32, device=weight.device)
+    check(lib.masic_lpips_conv1_bwd_pack_weight(_p(weight), _p(packed), _stream()), "lpips_conv1_bwd_pack_weight")
+    return packed
+
+
+def lpips_conv1_bwd(g, packed, scale, H, W, normalize=False, sides=3):
+    """The picture gradients of lpips_conv1 from the gradient g [B,64,Ho,Wo] of its pre-activation: (d in0, d in1), each [N,3,H,W] or
+    None.  sides = 3: g holds the 2N interleaved images; sides = 1 / 2: the N images of in0 / in1 alone."""
+    _dev(g, "first-layer gradient"); _dev(packed, "packed weight"); _dev(scale, "scale")
+    B = g.shape[0]
+    if (g.dim() != 4 or tuple(g.shape[1:]) != (64, (H - 7) // 4 + 1, (W - 7) // 4 + 1) or sides not in (1, 2, 3) or (sides == 3 and B % 2)
+            or scale.numel() != 3 or packed.numel() * 4 != lib.masic_lpips_conv1_bwd_packed_bytes()):
+        raise RuntimeError(f"masic_amd.lpips_conv1_bwd: gradient {tuple(g.shape)} for {H} x {W} pictures, sides {sides}; scale [3] and the "
+                           "pack of pack_lpips_conv1_bwd_weight expected")
+    N = B // 2 if sides == 3 else B
+    d0 = torch.empty((N, 3, H, W), dtype=torch.float32, device=g.device) if sides & 1 else None
+    d1 = torch.empty((N, 3, H, W), dtype=torch.float32, device=g.device) if sides & 2 else None
+    check(lib.masic_lpips_conv1_bwd(_p(g), _p(packed), _p(scale), _p(d0), _p(d1), B, H, W, int(bool(normalize)), _stream()), "lpips_conv1_bwd")
+    return d0, d1
+
+
 def conv_plan_signature(desc):
     """What fixes the summation order of one output of an implicit-GEMM convolution besides its operands: the kernel family and, from
     masic_conv_plan_name's configuration, the padded input channels, the K chunk, the 16-byte staging form and the phase count -- k runs

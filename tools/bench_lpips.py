@@ -6,7 +6,12 @@ layers 2-5, the five distance launches + the finishing launch) and the whole for
 [2N, ...] tensors (scaling ops + F.conv2d + relu, F.max_pool2d, F.conv2d + relu, normalise / square / 1x1 convolution / mean), and
 the whole sequence.  Device events around `--steps` calls after `--warmup` calls; the median of five windows; microseconds.
 Weights are torch's default initialisation (`pnet_rand=True`, `pretrained=False`): no trained weights ship with the repository, and
-the times do not depend on them.  `--only hip|torch` runs one side (for a kernel trace of it)."""
+the times do not depend on them.  `--only hip|torch` runs one side (for a kernel trace of it).
+
+Then the loss: forward + backward (`net(y, x).sum().backward()`) with only `x` requiring grad (the training case, a chain of N images)
+and with both pictures requiring grad (2N images), beside torch autograd through the same float32 restatement run as lpips runs it
+(the trunk once per picture tensor, so autograd prunes the side that needs no gradient); and the 12 launches of the backward schedule
+one by one for both chains."""
 import argparse
 import json
 import os
@@ -52,6 +57,66 @@ def torch_distance(taps, lins):
     return val
 
 
+def backward_rows(a, net, convs, lins, y, x, taps, row, torch_taps, conv1_flop):
+    """Forward + backward of the loss for both chains beside torch autograd, then the backward schedule launch by launch."""
+    sl, N = net.scaling_layer, y.shape[0]
+
+    def hip_loss(need0):
+        yy, xx = y.detach().requires_grad_(need0), x.detach().requires_grad_(True)
+        net(yy, xx).sum().backward()
+        return yy.grad, xx.grad
+
+    def torch_loss(need0):
+        yy, xx = y.detach().requires_grad_(need0), x.detach().requires_grad_(True)
+        with torch.set_grad_enabled(need0):
+            t0 = torch_taps(yy)
+        t1, val = torch_taps(xx), 0
+        for f0, f1, w in zip(t0, t1, lins):
+            val = val + F.conv2d((torch_normalize(f0) - torch_normalize(f1)) ** 2, w).mean([2, 3], keepdim=True)
+        val.sum().backward()
+        return yy.grad, xx.grad
+
+    print(f"{'forward + backward':<34}{'hip us':>10}{'torch us':>10}{'torch/hip':>10}")
+    for name, need0 in (("fwd + bwd, x requires grad", False), ("fwd + bwd, both require grad", True)):
+        th = timed(lambda: hip_loss(need0), a.steps, a.warmup) if a.only in (None, "hip") else None
+        tt = timed(lambda: torch_loss(need0), a.steps, a.warmup) if a.only in (None, "torch") else None
+        row[name] = {"hip_us": th and round(th, 1), "torch_us": tt and round(tt, 1)}
+        ratio = f"{tt / th:10.2f}" if th and tt else f"{'':>10}"
+        print(f"{name:<34}{(f'{th:10.1f}' if th else f'{chr(45):>10}')}{(f'{tt:10.1f}' if tt else f'{chr(45):>10}')}{ratio}", flush=True)
+        if a.only is None:
+            gh, gt = hip_loss(need0)[1], torch_loss(need0)[1]
+            row[name]["hip_vs_torch_relative"] = float((gh - gt).abs().max() / gt.abs().max())
+    if a.only == "torch":
+        return
+    gout = torch.full((6, N), 0.5, device="cuda")
+    packedb = ops.pack_lpips_conv1_bwd_weight(convs[0].weight.detach())
+    H, W = y.shape[2:]
+    cols = {}
+    for sides in (2, 3):
+        unit, stride, off = (2, 1, 0) if sides == 3 else (1, 2, sides - 1)
+        stages, g = [], None
+        for t in range(4, -1, -1):
+            fn = lambda t=t, gin=g: ops.lpips_dist_bwd(taps[t], lins[t], gout, t, sides, g_in=gin)      # noqa: E731
+            g = fn()
+            stages.append((f"distance bwd tap {t} ({row['taps'][t]})", fn))
+            if t:
+                fn = lambda t=t, gi=g: L._conv_dgrad(convs[t], gi, unit)                                  # noqa: E731
+                g = fn()
+                stages.append((f"conv{t + 1} input gradient", fn))
+                if t in (1, 2):
+                    fn = lambda t=t, gi=g: ops.maxpool3s2_bwd(taps[t - 1], gi, stride, off)               # noqa: E731
+                    g = fn()
+                    stages.append((f"maxpool bwd ({taps[t - 1].shape[1]} ch)", fn))
+        stages.append(("conv1 input gradient (+scaling)", lambda gi=g: ops.lpips_conv1_bwd(gi, packedb, sl.scale, H, W, False, sides)))
+        cols[sides] = [(name, timed(fn, a.steps, a.warmup)) for name, fn in stages]
+    print(f"{'backward launch':<38}{'N images us':>12}{'2N images us':>13}")
+    for (name, one), (_, two) in zip(cols[2], cols[3]):
+        row["bwd " + name] = {"one_sided_us": round(one, 1), "two_sided_us": round(two, 1)}
+        print(f"{'  ' + name:<38}{one:12.1f}{two:13.1f}", flush=True)
+    print(f"{'  sum':<38}{sum(v for _, v in cols[2]):12.1f}{sum(v for _, v in cols[3]):13.1f}")
+    row["conv1_bwd_TFLOPs_useful"] = round(conv1_flop / cols[3][-1][1] / 1e6, 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -80,14 +145,17 @@ def main():
                 c = convs[i]
                 return F.relu(F.conv2d(t, c.weight, c.bias, stride=c.stride, padding=c.padding))
 
-            def torch_forward():
-                t, out = (both - sl.shift) / sl.scale, []
+            def torch_taps(pictures):
+                t, out = (pictures - sl.shift) / sl.scale, []
                 for i in range(5):
                     if i in (1, 2):
                         t = F.max_pool2d(t, 3, 2)
                     t = tconv(i, t)
                     out.append(t)
-                return torch_distance(out, lins)
+                return out
+
+            def torch_forward():
+                return torch_distance(torch_taps(both), lins)
 
             hip = (lambda: ops.lpips_conv1(y, x, packed1, convs[0].bias.detach(), sl.shift, sl.scale, False),
                    lambda: ops.maxpool3s2(taps[0]), lambda: L._conv_relu(convs[1], pools[0]),
@@ -131,7 +199,8 @@ def main():
             conv1_flop = 2.0 * 2 * shape[0] * 64 * 363 * taps[0].shape[2] * taps[0].shape[3]
             if a.only in (None, "hip"):
                 row["conv1_TFLOPs_useful"] = round(conv1_flop / row[STAGES[0]]["hip_us"] / 1e6, 1)
-            print(json.dumps(row), flush=True)
+        backward_rows(a, net, convs, lins, y, x, taps, row, torch_taps, conv1_flop)
+        print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":
