@@ -149,6 +149,50 @@ def test_conv_wgrad_bf16_operands(case):
     assert float((got - full).abs().max()) <= 1e-2 * peak, name
 
 
+# conv_wgrad_packed_f32<2, bf16, det> (5 .. 8 column tiles of (tap, fine-side channel) pairs: 5x5 kernels with 6 .. 8 fine-side channels).
+# A list of its own: tests/test_gpu_determinism.py records digests over CONV_BWD_CASES.  tests/test_cpu_conv_rows.py holds the cases
+# to the four instantiations.
+WGRAD_PACKED2_CASES = [
+    # name,          B, Cin, H,  W,  Cout, k, s, transposed
+    ("pre_conv_w50", 2, 6,   32, 50, 3,    5, 1, False),      # pre_conv at a width that is no multiple of 4 (else conv_wgrad_small_s1)
+    ("conv6to128",   2, 6,   36, 44, 128,  5, 2, False),
+    ("deconv128to6", 2, 128, 18, 22, 6,    5, 2, True),
+    ("ragged_b1",    1, 7,   19, 37, 70,   5, 2, False),      # one image, odd sizes, 64 + 6 coarse-side channels, 7 fine-side ones
+]
+
+
+@pytest.mark.parametrize("det", [False, True], ids=["default", "det"])
+@pytest.mark.parametrize("prec", ["f32", "bf16"])
+@pytest.mark.parametrize("case", WGRAD_PACKED2_CASES, ids=[c[0] for c in WGRAD_PACKED2_CASES])
+def test_conv_wgrad_packed2(case, prec, det):
+    """ops.conv2d_wgrad on the packed kernel's wider instantiations against float64 autograd, as tests/test_gpu_determinism.py::
+    test_conv2d_wgrad_det: GTOL for float32 operands, 2e-5 of the peak + 1e-6 on the bf16-rounded operands for bf16; the deterministic
+    form is run twice and gives the same bits."""
+    import contextlib
+    from masic_amd import ops
+    from masic_amd._lib import PREC_BF16, PREC_F32
+    from masic_amd.determinism import deterministic
+    from tests.test_gpu_determinism import _wgrad_ref      # float64 autograd
+    name, B, Cin, H, W, Cout, k, s, tr = case
+    d = ops.make_conv_desc(B, Cin, H, W, Cout, k, k, s, k // 2, transposed=tr, prec=PREC_BF16 if prec == "bf16" else PREC_F32)
+    x = _rand(B, Cin, H, W, seed=11, scale=2.0)
+    dy = _rand(B, Cout, d.Ho, d.Wo, seed=12)
+    wshape = (Cin, Cout, k, k) if tr else (Cout, Cin, k, k)
+    xd, dyd = x.to(DEV), dy.to(DEV)
+    with (deterministic() if det else contextlib.nullcontext()):
+        got = ops.conv2d_wgrad(xd, dyd, d, wshape)
+        if det:
+            assert torch.equal(ops.conv2d_wgrad(xd, dyd, d, wshape), got), name + ": two deterministic calls differ"
+    if prec == "bf16":
+        want = _wgrad_ref(x.bfloat16().float(), dy.bfloat16().float(), k, s, tr)
+        err, peak = float((got.cpu().double() - want).abs().max()), float(want.abs().max())
+        print(f"{name} {prec} det={det}: |error| {err:.3e}, peak {peak:.3e}, relative {err / peak:.3e}")
+        assert err <= 2e-5 * peak + 1e-6, name
+    else:
+        e = assert_close(got, _wgrad_ref(x, dy, k, s, tr), name + ":dw", GTOL)
+        print(f"{name} {prec} det={det}: relative error {e:.3e}")
+
+
 @pytest.mark.parametrize("C,H,W,inverse", [(128, 16, 32, False), (128, 8, 8, True), (3, 32, 48, False), (3, 24, 40, True), (16, 8, 12, False)])
 def test_gdn_backward(C, H, W, inverse):
     from compressai.layers import GDN
