@@ -747,7 +747,14 @@ class HSIC(CompressionModel):
         # float32 chain (bit-compatible, the float32 parity path keeps it) costs a device -> host copy that makes the host wait for
         # the previous step's last kernel before it may launch this step's first
         from masic_amd import nn as _mnn
-        m_fwd, m_back = _warp_matrices(h_matrix, (H, W), (H, W), want_inverse=True, device=_mnn.reduced_precision())
+        # h_matrix.requires_grad: the sampling matrices and the four warps (x1_warp, x1_mask_R, x1_mask_L, x1_hat_warp) are nodes that
+        # carry the gradient back to h_matrix (kornia.warp_perspective is differentiable in the matrix, reference :638,644,781,821/833);
+        # otherwise -- every driver of the reference detaches it -- exactly the calls below as they were
+        hgrad = h_matrix.requires_grad
+        if hgrad:
+            m_fwd, m_back = _ag.WarpMatricesFn.apply(h_matrix, (H, W), (H, W), _mnn.reduced_precision())
+        else:
+            m_fwd, m_back = _warp_matrices(h_matrix, (H, W), (H, W), want_inverse=True, device=_mnn.reduced_precision())
         y1 = self.encoder1.latent_train(x1)
         # Two branches of the step need nothing of the main chain (encoder1 -> y1 + noise -> decoder1 -> warp -> encoder1 -> heads2 ->
         # decoder2) until late: the left view's entropy chain (only its likelihoods leave it) and the right view up to its entropy
@@ -773,14 +780,18 @@ class HSIC(CompressionModel):
 
         fj.fork(sA)
         with fj.on(sA):
-            x1_warp = _hip.warp_perspective(x1, m_fwd, (H, W))
+            x1_warp = _ag.WarpFn.apply(x1, m_fwd, (H, W)) if hgrad else _hip.warp_perspective(x1, m_fwd, (H, W))
             y2 = self.encoder2(x1_warp, x2)
             z2 = self._h_a2(y2)
             z2_hat, z2_lik = self.entropy_bottleneck2(z2)                                   # draw 4
             params2 = self._hyper_up(self.h_s2_up, z2_hat, None, 0)
             ctx2 = self.context_prediction2.run(self.gaussian2._quantize(y2, "noise"))     # draw 5
-            x1_mask_R = _hip.warp_perspective(None, m_fwd, (H, W), ones_like=(B, H, W))
-            x1_mask_L = _hip.warp_perspective(x1_mask_R, m_back, (H, W))
+            if hgrad:
+                x1_mask_R = _ag.WarpOnesFn.apply(m_fwd, (B, H, W), (H, W))
+                x1_mask_L = _ag.WarpFn.apply(x1_mask_R, m_back, (H, W))
+            else:
+                x1_mask_R = _hip.warp_perspective(None, m_fwd, (H, W), ones_like=(B, H, W))
+                x1_mask_L = _hip.warp_perspective(x1_mask_R, m_back, (H, W))
             gates = self.mask2weights_unit(x1_mask_R)
         x1_hat_warp = _ag.WarpFn.apply(x1_hat, m_fwd, (H, W))
         y1_warp = self.encoder1.latent_train(x1_hat_warp)
@@ -812,6 +823,9 @@ class HSIC(CompressionModel):
         (masic_amd/graph.py), since their host-side float32 evaluation is the only synchronising step."""
         if self._needs_graph():
             return self._forward_graph(x1, x2, h_matrix)
+        if torch.is_grad_enabled() and h_matrix.requires_grad:
+            raise NotImplementedError("HSIC.forward: the gradient with respect to h_matrix exists in the training-mode graph only (.train() with "
+                                      "trainable parameters); this call would leave h_matrix.grad None -- detach h_matrix or call under no_grad")
         M, K = self.M, self.K
         x1 = x1.contiguous()
         x2 = x2.contiguous()
@@ -1574,6 +1588,9 @@ class Independent_EN(nn.Module):
         return all(eb.f16k_supported(B, H, W) for eb in (self.EBl1, self.EBl2, self.EBl3, self.EBr1, self.EBr2, self.EBr3))
 
     def forward(self, x1_hat, x2_hat, h_matrix):
+        if torch.is_grad_enabled() and h_matrix.requires_grad:
+            raise NotImplementedError("Independent_EN.forward: no gradient with respect to h_matrix (its masks and warps treat it as data); "
+                                      "detach h_matrix")
         if self._needs_graph(x1_hat, x2_hat):
             return self._forward_graph(x1_hat, x2_hat, h_matrix)
         x1_hat = x1_hat.contiguous()

@@ -599,6 +599,30 @@ int masic_warp_perspective_bwd(const float* g_dst, const float* minv_norm, float
  * beyond ~2 x) -- the call has then redone the whole tensor with the scatter form above (device-side test of the flag, no host round trip). */
 int masic_warp_perspective_bwd_gather(const float* g_dst, const float* minv_norm, float* g_src, int* flag,
                                       int B, int C, int Hs, int Ws, int Hd, int Wd, void* stream);
+/* ---- the warp differentiated with respect to its matrix (warp_bwd_matrix.hip): kornia.warp_perspective is differentiable in the
+ * homography, and so is HSIC.forward in h_matrix.  No float atomics anywhere: bit-reproducible, and an item's result does not
+ * depend on the batch around it.
+ *   masic_warp_perspective_bwd_matrix  part [B][slots][9] (float64, slots = masic_warp_matrix_slots(Hd, Wd)): per-workgroup partial
+ *                                      sums of d loss / d minv_norm of dst = warp(src; minv_norm) for the incoming gradient g_dst
+ *                                      [B][C][Hd][Wd]; src NULL => the all-ones source (C = 1).  The sampling coordinates are the
+ *                                      forward's own (same float32 operations, masic_set_warp_align_corners included), so the
+ *                                      bilinear derivative is that of the cell the forward sampled (one-sided on cell boundaries);
+ *                                      a destination pixel with non-finite coordinates contributes 0.  g_minv [B][3][3] (or NULL):
+ *                                      the slots added in a fixed order by a second launch (one wave per item), rounded once to float32.
+ *   masic_warp_matrix_bwd              the adjoint of masic_warp_matrix: g_M [B][3][3] from g_fwd [B][slots_fwd][9], the gradient of
+ *                                      inverse(N_dst M N_src^-1), and / or g_inv [B][slots_inv][9], that of the invert_first chain
+ *                                      (either may be NULL); the slots are float64 (slots_f64 = 1) or float32 (0) and are added in
+ *                                      a fixed order (one wave per item: lane l takes slots l, l + 64, ..., then a butterfly); float64 inside, the chain re-evaluated at M.  NaN rows for a singular chain.
+ *   masic_homography_from_corners_bwd  the adjoint of masic_homography_from_corners with respect to delta: g_h [B][3][3] ->
+ *                                      g_delta [B][4][2] (h_adjust's scalings, the cofactor inverse, the 8 x 8 solve by implicit
+ *                                      differentiation); NaN rows where the forward gives NaN. */
+int masic_warp_matrix_slots(int Hd, int Wd);
+int masic_warp_perspective_bwd_matrix(const float* src, const float* minv_norm, const float* g_dst, double* part, float* g_minv,
+                                      int B, int C, int Hs, int Ws, int Hd, int Wd, void* stream);
+int masic_warp_matrix_bwd(const float* M, const void* g_fwd, int slots_fwd, const void* g_inv, int slots_inv, int slots_f64, float* g_M,
+                          int B, int Hs, int Ws, int Hd, int Wd, void* stream);
+int masic_homography_from_corners_bwd(const float* corners, const float* delta, const float* g_h, float* g_delta, int B, float scale_a,
+                                      float scale_b, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side entropy coding (no device work).  Bit-exact replacements of the reference's pybind11

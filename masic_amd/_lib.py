@@ -228,6 +228,11 @@ SIGNATURES = {
     "masic_entropy_bottleneck_aux_step": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P]),
     "masic_warp_perspective_bwd": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
     "masic_warp_perspective_bwd_gather": (c_int, [_P, _P, _P, _P] + [c_int] * 6 + [_P]),
+    # gradients with respect to the warp matrix / h_matrix (warp_bwd_matrix.hip)
+    "masic_warp_matrix_slots": (c_int, [c_int, c_int]),
+    "masic_warp_perspective_bwd_matrix": (c_int, [_P] * 5 + [c_int] * 6 + [_P]),
+    "masic_warp_matrix_bwd": (c_int, [_P, _P, c_int, _P, c_int, c_int, _P] + [c_int] * 5 + [_P]),
+    "masic_homography_from_corners_bwd": (c_int, [_P, _P, _P, _P, c_int, c_float, c_float, _P]),
     # deterministic mode: per-split slabs, no float atomics
     "masic_conv2d_wgrad_det_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
     "masic_conv2d_wgrad_det": (c_int, [_P, _P, _P, _P, ctypes.POINTER(ConvDesc), _P]),

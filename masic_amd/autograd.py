@@ -367,19 +367,80 @@ class AddNoiseFn(Function):
 
 
 class WarpFn(Function):
-    """kornia warp_perspective w.r.t. the source image (h_matrix is detached by every driver)."""
+    """kornia warp_perspective(src, M, dsize) on the normalised sampling matrix `minv` of M (WarpMatricesFn / homography.warp_matrices):
+    the gradient with respect to the source image, and -- when the matrix requires grad, i.e. h_matrix does -- with respect to `minv`
+    (ops.warp_perspective_bwd_matrix; the source is saved only then).  The reference's drivers detach h_matrix
+    (newtrain_codec_real.py:132), so their steps never take the second path and issue exactly the launches they did before it existed."""
 
     @staticmethod
     def forward(ctx, src, minv, dsize):
         src = _c(src)
         ctx.src_shape = tuple(src.shape)
-        ctx.save_for_backward(minv)
+        ctx.save_for_backward(minv, src if ctx.needs_input_grad[1] else None)
         return ops.warp_perspective(src, minv, dsize)
 
     @staticmethod
     def backward(ctx, g):
+        minv, src = ctx.saved_tensors
+        g = _c(g)
+        g_src = ops.warp_perspective_bwd(g, minv, ctx.src_shape) if ctx.needs_input_grad[0] else None
+        g_minv = ops.warp_perspective_bwd_matrix(src, minv, g, want_sum=True)[1] if ctx.needs_input_grad[1] else None
+        return g_src, g_minv, None
+
+
+class WarpOnesFn(Function):
+    """warp_perspective of an all-ones [B,1,H,W] image (the mask of MASIC.py:636-638): a function of the matrix alone."""
+
+    @staticmethod
+    def forward(ctx, minv, ones_like, dsize):
+        ctx.ones_like = tuple(ones_like)
+        ctx.save_for_backward(minv)
+        return ops.warp_perspective(None, minv, dsize, ones_like=ones_like)
+
+    @staticmethod
+    def backward(ctx, g):
         (minv,) = ctx.saved_tensors
-        return ops.warp_perspective_bwd(_c(g), minv, ctx.src_shape), None, None
+        return ops.warp_perspective_bwd_matrix(None, minv, _c(g), ones_like=ctx.ones_like, want_sum=True)[1], None, None
+
+
+class WarpMatricesFn(Function):
+    """h_matrix [B,3,3] -> the normalised sampling matrices (of warp(., h_matrix), of warp(., inverse(h_matrix))): forward =
+    homography.warp_matrices as it is (the reference's float32 chain on the host, or the float64 device kernel with `device`),
+    backward = ops.warp_matrix_bwd -- the float64 adjoint of both chains evaluated at the same h_matrix (the host chain's forward
+    values differ from the float64 ones by rounding only)."""
+
+    @staticmethod
+    def forward(ctx, h_matrix, src_hw, dst_hw, device=False):
+        from . import homography
+        ctx.src_hw, ctx.dst_hw = tuple(src_hw), tuple(dst_hw)
+        ctx.save_for_backward(h_matrix)
+        ctx.set_materialize_grads(False)          # a matrix nobody differentiated through (m_back under a loss without x1_mask_L) arrives as None: its chain is skipped
+        return homography.warp_matrices(h_matrix.detach(), src_hw, dst_hw, want_inverse=True, device=device)
+
+    @staticmethod
+    def backward(ctx, g_fwd, g_back):
+        (h_matrix,) = ctx.saved_tensors
+        g_fwd = None if g_fwd is None else _c(g_fwd)
+        g_back = None if g_back is None else _c(g_back)
+        if g_fwd is None and g_back is None:
+            return None, None, None, None
+        return ops.warp_matrix_bwd(_c(h_matrix), ctx.src_hw, ctx.dst_hw, g_fwd, g_back), None, None, None
+
+
+class HomographyFromCornersFn(Function):
+    """ops.homography_from_corners differentiable in delta (corners are data)."""
+
+    @staticmethod
+    def forward(ctx, corners, delta, ori_hw, patch_hw):
+        corners, delta = _c(corners), _c(delta)
+        ctx.ori_hw, ctx.patch_hw = tuple(ori_hw), tuple(patch_hw)
+        ctx.save_for_backward(corners, delta)
+        return ops.homography_from_corners(corners, delta, ori_hw, patch_hw)
+
+    @staticmethod
+    def backward(ctx, g):
+        corners, delta = ctx.saved_tensors
+        return None, ops.homography_from_corners_bwd(corners, delta, _c(g), ctx.ori_hw, ctx.patch_hw), None, None
 
 
 class CatFn(Function):

@@ -21,6 +21,7 @@
 //   udh_photo_loss        mean |warp_perspective(img_a, inverse(h), (h, w)) - patch_b| with warp.hip's coordinate arithmetic, and its
 //                         backward to g_S (nine partial sums per workgroup, finished per pair in workgroup order).
 #include "common.h"
+#include "homography_math.h"
 
 namespace {
 
@@ -264,52 +265,7 @@ __global__ __launch_bounds__(256) void udh_fc1_bwd_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ photometric loss: the matrix
-// Gaussian elimination with partial pivoting of an 8 x 8 system; false if a pivot is exactly zero.
-__device__ bool solve8(double (&A)[8][9], double (&x)[8]) {
-    for (int c = 0; c < 8; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 8; ++r)
-            if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
-        if (A[piv][c] == 0.0 || A[piv][c] != A[piv][c]) return false;
-        if (piv != c)
-            for (int k = 0; k < 9; ++k) { const double t = A[c][k]; A[c][k] = A[piv][k]; A[piv][k] = t; }
-        for (int r = c + 1; r < 8; ++r) {
-            const double f = A[r][c] / A[c][c];
-            for (int k = c; k < 9; ++k) A[r][k] -= f * A[c][k];
-        }
-    }
-    for (int c = 7; c >= 0; --c) {
-        double s = A[c][8];
-        for (int k = c + 1; k < 8; ++k) s -= A[c][k] * x[k];
-        x[c] = s / A[c][c];
-    }
-    return true;
-}
-
-__device__ bool inv3(const double* a, double* r) {
-    const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
-    const double det = a[0] * c00 + a[1] * c01 + a[2] * c02;
-    if (det == 0.0 || det != det) return false;
-    const double id = 1.0 / det;
-    r[0] = c00 * id; r[1] = (a[2] * a[7] - a[1] * a[8]) * id; r[2] = (a[1] * a[5] - a[2] * a[4]) * id;
-    r[3] = c01 * id; r[4] = (a[0] * a[8] - a[2] * a[6]) * id; r[5] = (a[2] * a[3] - a[0] * a[5]) * id;
-    r[6] = c02 * id; r[7] = (a[1] * a[6] - a[0] * a[7]) * id; r[8] = (a[0] * a[4] - a[1] * a[3]) * id;
-    return true;
-}
-
-__device__ void mul3(const double* a, const double* b, double* c) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-}
-__device__ void mul3_tn(const double* a, const double* b, double* c) {      // a^T b
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) c[3 * i + j] = a[i] * b[j] + a[3 + i] * b[3 + j] + a[6 + i] * b[6 + j];
-}
-__device__ void mul3_nt(const double* a, const double* b, double* c) {      // a b^T
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[3 * j] + a[3 * i + 1] * b[3 * j + 1] + a[3 * i + 2] * b[3 * j + 2];
-}
-
+// (solve8, inv3, mul3, mul3_tn, mul3_nt: homography_math.h)
 struct PhotoChain {
     double px[4], py[4];       // corners - corners[0] (float32 subtraction, as the reference forms it)
     double h[9], m[9], s[9];   // h, inverse(h), S

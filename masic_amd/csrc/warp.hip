@@ -12,6 +12,7 @@
 // HBM-bound gather: one thread per destination pixel computes the source location once and
 // samples every channel (4 taps each); destination stores are coalesced along W.
 #include "common.h"
+#include "warp_sample.h"
 #include <atomic>
 
 namespace {
@@ -59,28 +60,10 @@ __global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ src
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= Hd * Wd) return;
     const int oy = pix / Wd, ox = pix - oy * Wd;
-    const float* m = minv + b * 9;
-    // create_meshgrid(normalized_coordinates=True): (i / (n-1) - 0.5) * 2
-    const float gx = __fmul_rn(__fsub_rn(__fdiv_rn((float)ox, (float)(Wd - 1)), 0.5f), 2.0f);
-    const float gy = __fmul_rn(__fsub_rn(__fdiv_rn((float)oy, (float)(Hd - 1)), 0.5f), 2.0f);
-    const float X = __fadd_rn(__fadd_rn(__fmul_rn(gx, m[0]), __fmul_rn(gy, m[1])), m[2]);
-    const float Y = __fadd_rn(__fadd_rn(__fmul_rn(gx, m[3]), __fmul_rn(gy, m[4])), m[5]);
-    const float Z = __fadd_rn(__fadd_rn(__fmul_rn(gx, m[6]), __fmul_rn(gy, m[7])), m[8]);
-    const float scale = fabsf(Z) > 1e-8f ? __fdiv_rn(1.0f, __fadd_rn(Z, 1e-8f)) : 1.0f;
-    const float nx = __fmul_rn(X, scale), ny = __fmul_rn(Y, scale);
-    const float fx = masic_grid_unnormalize(nx, Ws, align_corners);
-    const float fy = masic_grid_unnormalize(ny, Hs, align_corners);
-    const float x0f = floorf(fx), y0f = floorf(fy);
-    const float wx = __fsub_rn(fx, x0f), wy = __fsub_rn(fy, y0f);
-    const float ex = __fsub_rn(1.0f, wx), ey = __fsub_rn(1.0f, wy);
-    const float w_nw = __fmul_rn(ex, ey), w_ne = __fmul_rn(wx, ey), w_sw = __fmul_rn(ex, wy), w_se = __fmul_rn(wx, wy);
-    // float -> int with saturation so that far-away samples stay out of range instead of wrapping
-    const float lim = 1.0e9f;
-    const int x0 = (int)fminf(fmaxf(x0f, -lim), lim), y0 = (int)fminf(fmaxf(y0f, -lim), lim);
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const bool vx0 = x0 >= 0 && x0 < Ws, vx1 = x1 >= 0 && x1 < Ws;
-    const bool vy0 = y0 >= 0 && y0 < Hs, vy1 = y1 >= 0 && y1 < Hs;
-    const bool finite = (fx == fx) && (fy == fy);
+    const WarpSample ws = masic_warp_sample(minv + b * 9, ox, oy, Hs, Ws, Hd, Wd, align_corners);
+    const float w_nw = __fmul_rn(ws.ex, ws.ey), w_ne = __fmul_rn(ws.wx, ws.ey), w_sw = __fmul_rn(ws.ex, ws.wy), w_se = __fmul_rn(ws.wx, ws.wy);
+    const int x0 = ws.x0, y0 = ws.y0, x1 = x0 + 1, y1 = y0 + 1;
+    const bool vx0 = ws.vx0(Ws), vx1 = ws.vx1(Ws), vy0 = ws.vy0(Hs), vy1 = ws.vy1(Hs), finite = ws.finite();
     const size_t splane = (size_t)Hs * Ws, dplane = (size_t)Hd * Wd;
     float* d = dst + ((size_t)b * out_ctot + out_coff) * dplane + pix;
     if (src == nullptr) {   // warp of an all-ones image (MASIC.py:636-638): the sum of the in-range weights

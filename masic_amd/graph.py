@@ -213,6 +213,7 @@ class GraphedTrainStep:
         from .train import train_step
         if not model.training:
             raise RuntimeError("GraphedTrainStep captures the training-mode step: call model.train() first")
+        self._refuse_h_grad(h_matrix)
         if not _mnn.reduced_precision():
             raise RuntimeError("GraphedTrainStep needs the bf16 / fp8 operand mode (masic_amd.nn.set_precision): the float32 parity path "
                                "evaluates the sampling matrices on the host, which a captured step cannot do")
@@ -248,6 +249,12 @@ class GraphedTrainStep:
             self._crit, self._aux = train_step(model, self.optimizer, self.aux_optimizer, self.d1, self.d2, self.h, lmbda)
         self._touch()
 
+    @staticmethod
+    def _refuse_h_grad(h_matrix):
+        if h_matrix.requires_grad:
+            raise NotImplementedError("GraphedTrainStep: the captured step copies h_matrix into a static buffer and returns no gradient for "
+                                      "it; use the eager step (HSIC.forward in .train() mode) for gradients with respect to h_matrix")
+
     def _touch(self):
         """The replay changes every parameter without Python seeing it: bump the version counters so that the per-version caches of
         weight packs / tables (masic_amd/nn.py) are rebuilt by the next EAGER use of the model instead of serving the packs of the
@@ -266,6 +273,7 @@ class GraphedTrainStep:
         if is_deterministic() != self._deterministic:
             raise RuntimeError(f"GraphedTrainStep: captured with the deterministic mode {'on' if self._deterministic else 'off'}, "
                                f"replayed with it {'on' if is_deterministic() else 'off'}: the graph replays the kernels of its capture")
+        self._refuse_h_grad(h_matrix)
         if d1 is not self.d1:
             self.d1.copy_(d1)
         if d2 is not self.d2:

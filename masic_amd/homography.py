@@ -40,6 +40,15 @@ def warp_matrices(h_matrix, src_hw, dst_hw, want_inverse=False, device=False):
     return fwd.to(h_matrix.device), (back.to(h_matrix.device) if want_inverse else None)
 
 
+def h_matrix_from_corners(corners, delta, ori_hw, patch_hw):
+    """ops.homography_from_corners as a differentiable function of `delta` (the UDH net's output): with it the chain
+    UDH training net -> delta -> h_matrix -> HSIC -> loss backpropagates end to end.  `corners` get no gradient."""
+    if torch.is_grad_enabled() and delta.requires_grad:
+        from .autograd import HomographyFromCornersFn
+        return HomographyFromCornersFn.apply(corners, delta, ori_hw, patch_hw)
+    return ops.homography_from_corners(corners, delta, ori_hw, patch_hw)
+
+
 def warp_matrices_host(m, src_hw, dst_hw, want_inverse=False):
     """The float32 chain itself on a CPU tensor [B,3,3]; returns CPU tensors (callers that pipeline the host step with
     device work -- masic_amd/graph.py -- do their own transfers)."""

@@ -1041,6 +1041,69 @@ def warp_perspective_bwd(g_dst, minv_norm, src_shape, want_flag=False):
     return (g_src, None) if want_flag else g_src
 
 
+def warp_perspective_bwd_matrix(src, minv_norm, g_dst, ones_like=None, want_sum=False):
+    """Per-workgroup partial sums [B,slots,9] (float64) of d loss / d minv_norm of warp_perspective(src, minv_norm, g_dst.shape[-2:]) for the
+    incoming gradient g_dst; src None: the all-ones source of size ones_like=(B,H,W) (g_dst [B,1,Hd,Wd]).  The slots are to be added in
+    a fixed order (warp_matrix_bwd does; want_sum: also return that sum as a float32 [B,3,3], second launch).  No atomics: equal bits on
+    every call, and item n's slots do not depend on the rest of the batch."""
+    _dev(minv_norm, "warp matrix"); _dev(g_dst, "g_dst")
+    if src is not None:
+        _dev(src, "warp source")
+        B, C, Hs, Ws = src.shape
+    else:
+        B, Hs, Ws = ones_like
+        C = 1
+    Hd, Wd = g_dst.shape[-2:]
+    if tuple(minv_norm.shape) != (B, 3, 3) or g_dst.dim() != 4 or tuple(g_dst.shape[:2]) != (B, C):
+        raise RuntimeError(f"masic_amd.warp_perspective_bwd_matrix: matrix {tuple(minv_norm.shape)}, g_dst {tuple(g_dst.shape)} for a {B} x {C} source")
+    slots = _int_query("masic_warp_matrix_slots", Hd, Wd)
+    if slots <= 0:
+        check(-1, "warp_matrix_slots")
+    part = torch.empty((B, slots, 9), dtype=torch.float64, device=g_dst.device)
+    total = torch.empty((B, 3, 3), dtype=torch.float32, device=g_dst.device) if want_sum else None
+    check(lib.masic_warp_perspective_bwd_matrix(_p(src), _p(minv_norm), _p(g_dst), _p(part), _p(total), B, C, Hs, Ws, Hd, Wd, _stream()),
+          "warp_perspective_bwd_matrix")
+    return (part, total) if want_sum else part
+
+
+def warp_matrix_bwd(M, src_hw, dst_hw, g_fwd=None, g_inv=None):
+    """d loss / d M [B,3,3] of warp_matrix: g_fwd is the gradient of warp_matrix(M, ...), g_inv that of warp_matrix(M, ..., invert_first=True);
+    each [B,3,3] or [B,slots,9] (slots added in a fixed order by one wave per item), both float64 or both float32.  float64 inside."""
+    _dev(M, "homography")
+    B = M.shape[0]
+    if tuple(M.shape) != (B, 3, 3):
+        raise RuntimeError("masic_amd.warp_matrix_bwd: homography must be [B,3,3]")
+    given = [g for g in (g_fwd, g_inv) if g is not None]
+    if not given:
+        raise RuntimeError("masic_amd.warp_matrix_bwd: no gradient given")
+    dt = given[0].dtype
+    n = []
+    for g in (g_fwd, g_inv):
+        if g is None:
+            n.append(0)
+            continue
+        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.is_contiguous() and g.dtype == dt and dt in (torch.float32, torch.float64)
+                and g.shape[0] == B and g.numel() % (B * 9) == 0 and g.numel() > 0):
+            raise RuntimeError(f"masic_amd.warp_matrix_bwd: gradient slots must be contiguous HIP tensors [B,slots,9] of one float type, got {tuple(g.shape)} {g.dtype}")
+        n.append(g.numel() // (B * 9))
+    out = torch.empty_like(M)
+    check(lib.masic_warp_matrix_bwd(_p(M), _p(g_fwd), n[0], _p(g_inv), n[1], int(dt == torch.float64), _p(out), B, int(src_hw[0]), int(src_hw[1]),
+                                    int(dst_hw[0]), int(dst_hw[1]), _stream()), "warp_matrix_bwd")
+    return out
+
+
+def homography_from_corners_bwd(corners, delta, g_h, ori_hw, patch_hw):
+    """d loss / d delta [B,4,2] of homography_from_corners from g_h [B,3,3]."""
+    _dev(corners, "corners"); _dev(delta, "delta"); _dev(g_h, "g_h")
+    B = corners.shape[0]
+    if tuple(corners.shape) != (B, 4, 2) or tuple(delta.shape) != (B, 4, 2) or tuple(g_h.shape) != (B, 3, 3):
+        raise RuntimeError("masic_amd.homography_from_corners_bwd: corners and delta must be [B,4,2], g_h [B,3,3]")
+    out = torch.empty((B, 4, 2), dtype=torch.float32, device=corners.device)
+    check(lib.masic_homography_from_corners_bwd(_p(corners), _p(delta), _p(g_h), _p(out), B, float(ori_hw[0]) / float(patch_hw[0]),
+                                                float(ori_hw[1]) / float(patch_hw[1]), _stream()), "homography_from_corners_bwd")
+    return out
+
+
 # --------------------------------------------------------------------------------------------- bf16 1x1 GEMM stacks
 def nchw_to_f16k(x, C=None, coff=0, in_op=INOP_NONE):
     """float32 NCHW (channel view) -> F16K bf16 [B][ceil16(C)/16][HW][16] (include/masic_hip.h); in_op: |x| / round(x) on the way."""
