@@ -160,6 +160,10 @@ int masic_conv_f16k_supported(const masic_conv_desc_t* d);
 #define MASIC_F16K_NOSPLIT 2   /* the forms whose co-block is never split: _d2s_fwd, _few_fwd, an fp8 output of masic_conv_f8k_fwd */
 #define MASIC_F16K_MULTI 4     /* masic_conv_f16k_multi_fwd: conv_f16k_multi<NM> */
 int masic_conv_f16k_kernel_name(const masic_conv_desc_t* d, int flags, char* buf, size_t n);
+/* masic_conv_f16k_plan_name: that kernel's launch as one line "kernel | gx,gy,gz | block | lds | integers" (the format of
+ * masic_conv_plan_name); the integers are  TW TH NP KS T D L  msplit ntiles tiles_w nphase ncb  nchunks  <steps per chunk of each phase>
+ * PW PWh NPIXp  xcd_images.  Refusals and return codes as masic_conv_f16k_kernel_name; the buffer is empty after a refusal. */
+int masic_conv_f16k_plan_name(const masic_conv_desc_t* d, int flags, char* buf, size_t n);
 int masic_conv_f16k_row_name(int row, char* buf, size_t n);   /* every compiled conv_f16k / conv_f16k_multi symbol: rows 0 .., MASIC_ERR_ARG past the last */
 size_t masic_conv_f16k_packed_bytes(const masic_conv_desc_t* d);
 int masic_conv_f16k_pack_weight(const float* w, void* w_packed, const masic_conv_desc_t* d, void* stream);

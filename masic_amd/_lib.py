@@ -74,6 +74,7 @@ SIGNATURES = {
     "masic_gemm_f16k_group_fwd": (c_int, [ctypes.POINTER(GemmGroup), c_int, c_int, c_int, _P]),
     "masic_conv_f16k_supported": (c_int, [_P]),
     "masic_conv_f16k_kernel_name": (c_int, [_P, c_int, ctypes.c_char_p, c_size_t]),
+    "masic_conv_f16k_plan_name": (c_int, [_P, c_int, ctypes.c_char_p, c_size_t]),
     "masic_conv_f16k_row_name": (c_int, [c_int, ctypes.c_char_p, c_size_t]),
     "masic_conv_f16k_packed_bytes": (c_size_t, [_P]),
     "masic_conv_f16k_pack_weight": (c_int, [_P, _P, _P, _P]),

@@ -841,7 +841,7 @@ F16kCfg choose_f16k(const masic_conv_desc_t& d, const ConvGeom* g, int nphase) {
 
 // One row per compiled instantiation of conv_f16k / conv_f16k_multi: its template parameters (what the kernel's name is printed
 // from) and its launcher.  plan_f16k below is the only place a row is chosen; a new instantiation is a new row.
-typedef void (*F16kLaunchFn)(dim3 grid, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti* mo);
+typedef void (*F16kLaunchFn)(dim3 grid, int block, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti* mo);
 struct F16kRow {
     int KS, T, D, PSP, L;
     bool GDN;
@@ -850,12 +850,12 @@ struct F16kRow {
     F16kLaunchFn launch;
 };
 template <int KS, int T, int D, int PSP, int L, bool GDN, int NM, int NP, bool F8>
-void f16k_row_launch(dim3 grid, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti*) {
-    launch_lds<conv_f16k<KS, T, D, PSP, L, GDN, NM, NP, F8>>(grid, 512, lds_bytes, st, a);
+void f16k_row_launch(dim3 grid, int block, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti*) {
+    launch_lds<conv_f16k<KS, T, D, PSP, L, GDN, NM, NP, F8>>(grid, block, lds_bytes, st, a);
 }
 template <int NM>
-void f16k_multi_row_launch(dim3 grid, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti* mo) {
-    launch_lds<conv_f16k_multi<NM>>(grid, 512, lds_bytes, st, a, *mo);
+void f16k_multi_row_launch(dim3 grid, int block, size_t lds_bytes, hipStream_t st, const F16kArgs& a, const F16kMulti* mo) {
+    launch_lds<conv_f16k_multi<NM>>(grid, block, lds_bytes, st, a, *mo);
 }
 #define F16K_ROW(KS, T, D, PSP, L, GDN, NM, NP, F8) {KS, T, D, PSP, L, GDN, NM, NP, F8, false, f16k_row_launch<KS, T, D, PSP, L, GDN, NM, NP, F8>}
 #define F16K_MULTI_ROW(NM) {1, 5, 2, 6, 1, false, NM, 1, false, true, f16k_multi_row_launch<NM>}
@@ -890,7 +890,9 @@ struct F16kPlan {
     ConvGeom g[4];
     int np;                       // phases
     int msplit, tiles_w, ntiles;
+    int xcd_images;               // B % 8 == 0: the block -> tile map that walks image b on XCD b % 8
     dim3 grid;
+    int block;                    // threads per workgroup (8 waves)
 };
 
 F16kPlan plan_f16k(const masic_conv_desc_t& d, int flags) {
@@ -914,6 +916,8 @@ F16kPlan plan_f16k(const masic_conv_desc_t& d, int flags) {
         p.msplit = wgs <= 64 ? 4 : (wgs <= 160 ? 2 : 1);
     }
     p.grid = dim3(round_up(p.ntiles, 8) * p.np, c.ncb * p.msplit, d.B);
+    p.block = 512;
+    p.xcd_images = d.B % 8 == 0;
     // accumulator tiles per wave: the lite rows hold exactly Cout / 32, a stride-1 walk to <= 32 channels one, the rest 4 / msplit
     const int nm = c.D == 1 ? d.Cout / 32 : ((c.T == 2 && d.Cout <= 32) ? 1 : 4 / p.msplit);
     for (const F16kRow& r : F16K_ROWS)
@@ -946,6 +950,33 @@ extern "C" int masic_conv_f16k_kernel_name(const masic_conv_desc_t* d, int flags
     const F16kRow* r = plan_f16k(*d, flags).row;
     MASIC_REQUIRE(r != nullptr, MASIC_ERR_UNSUPPORTED, "conv_f16k: no kernel runs this layer shape in this form");
     f16k_row_name(*r, buf, n);
+    return MASIC_OK;
+}
+
+// The launch of the layer in the form `flags` names, in the format of masic_conv_plan_name: "kernel | gx,gy,gz | block | lds | integers",
+// the integers being what plan_f16k decided and the launcher hands to the kernel:
+//   TW TH NP KS T D L  msplit ntiles tiles_w nphase ncb  nchunks  steps per chunk of each of the nphase phases  PW PWh NPIXp  xcd_images
+// Refusals and return codes are those of masic_conv_f16k_kernel_name; the buffer is empty after a refusal (and for an empty output plane,
+// where the launcher launches nothing).  Host code only: the tests read every property of a case from this line.
+extern "C" int masic_conv_f16k_plan_name(const masic_conv_desc_t* d, int flags, char* buf, size_t n) {
+    if (buf && n > 0) buf[0] = 0;
+    int rc = check_desc(d);
+    if (rc != MASIC_OK) return rc;
+    MASIC_REQUIRE(buf && n > 0 && (flags & ~(MASIC_F16K_GDN | MASIC_F16K_NOSPLIT | MASIC_F16K_MULTI)) == 0, MASIC_ERR_ARG,
+                  "conv_f16k_plan_name: null buffer or unknown flag");
+    const F16kPlan p = plan_f16k(*d, flags);
+    MASIC_REQUIRE(p.row != nullptr, MASIC_ERR_UNSUPPORTED, "conv_f16k: no kernel runs this layer shape in this form");
+    if (p.g[0].Hp <= 0 || p.g[0].Wp <= 0) return MASIC_OK;
+    const F16kCfg& c = p.c;
+    char name[96], spc[64];
+    f16k_row_name(*p.row, name, sizeof name);
+    size_t used = 0;
+    for (int i = 0; i < p.np; ++i) used += (size_t)snprintf(spc + used, sizeof spc - used, "%d ", ceil_div(p.g[i].ntaps, c.T));
+    const bool ok = (size_t)snprintf(buf, n, "%s | %u,%u,%u | %d | %zu | %d %d %d %d %d %d %d %d %d %d %d %d %d %s%d %d %d %d\n", name, p.grid.x, p.grid.y,
+                                     p.grid.z, p.block, c.lds_bytes, c.TW, c.TH, c.NP, c.KS, c.T, c.D, c.L, p.msplit, p.ntiles, p.tiles_w, p.np, c.ncb,
+                                     c.Cin16 / c.KS, spc, c.PW, c.PWh, c.NPIXp, p.xcd_images) < n;
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "conv_f16k_plan_name: buffer of %zu bytes too small", n);
     return MASIC_OK;
 }
 
@@ -1087,8 +1118,8 @@ int f16k_launch(const F16kLaunch& l, const masic_conv_desc_t* d, void* stream) {
     a.mg_PWh = (unsigned)((0x100000000ull + c.PWh - 1) / c.PWh);
     a.mg_gpk = (unsigned)((0x100000000ull + c.NPIXp / 32 - 1) / (c.NPIXp / 32));
     for (int i = 0; i < 4; ++i) a.phase_off[i] = c.phase_off[i], a.stream_bytes[i] = c.stream_bytes[i];
-    a.q = geom_params(*d), a.nphase = p.np, a.xcd_images = d->B % 8 == 0, a.msplit = p.msplit;
-    p.row->launch(p.grid, c.lds_bytes, (hipStream_t)stream, a, l.multi);
+    a.q = geom_params(*d), a.nphase = p.np, a.xcd_images = p.xcd_images, a.msplit = p.msplit;
+    p.row->launch(p.grid, p.block, c.lds_bytes, (hipStream_t)stream, a, l.multi);
     return masic_launch_status("conv_f16k_fwd");
 }
 }  // namespace
