@@ -723,6 +723,18 @@ int masic_udh_photo_loss_bwd(const float* img, const float* S, const float* patc
 int masic_pair_prep(const uint8_t* img_hwc, int H, int W, int start_h, int start_w, int ph, int pw, float* pic_chw,
                     int homopic, int patch_x, int patch_y, int homopatch, float* homo_patch, void* stream);
 
+/* ---- the two ends of the stereo file pipeline (masic_amd/stereofile.py), over a stack of P pictures per launch.
+ *   masic_pairs_prep    uint8 [P][H0][W0][3] -> planes (nullable) float32 [P][3][H][W], H >= H0, W >= W0: u8 / 255 inside the picture
+ *                       (the division of masic_pair_prep's crop), the last row and column replicated outside it; patches (nullable)
+ *                       float32 [P][homopatch][homopatch]: masic_pair_prep's homo_patch of each WHOLE, unpadded picture.  One launch each.
+ *   masic_planes_to_u8  float32 [P][3][H][W] -> uint8 [P][H0][W0][3], H0 <= H, W0 <= W: floor(min(max(x, 0), 1) * 255 + 0.5) in float32
+ *                       (two roundings, no fused multiply-add: torchvision's save_image); NaN -> 0.  Inverts masic_pairs_prep exactly.
+ * Buffers 4-byte aligned (planes 16-byte aligned and W % 4 == 0 for the 16-byte accesses); at most 65535 pictures, rows and columns.
+ * MASIC_ERR_ARG for a null pointer, an empty extent, H0 > H or W0 > W, or a patch that leaves the resized picture. */
+int masic_pairs_prep(const uint8_t* pics_hwc, int P, int H0, int W0, int H, int W, float* planes, int homopic, int patch_x, int patch_y,
+                     int homopatch, float* patches, void* stream);
+int masic_planes_to_u8(const float* planes, int P, int H, int W, int H0, int W0, uint8_t* pics_hwc, void* stream);
+
 /* ---- HSIC.compress / decompress (MASIC.py:855-1408), SURVEY.md 8(f)-1: the y1 / y2 streams.
  * rANS with one table per symbol (host).  The reference drives the third-party `range_coder` package here
  * (MASIC.py:958, :1044, :1221, :1296), which is not part of its tree: the byte stream of this container is this

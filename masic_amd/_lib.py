@@ -89,6 +89,8 @@ SIGNATURES = {
     "masic_rans_decode_with_indexes": (c_int, [_P, c_size_t, _P, c_int, _P, c_int, _P, _P, c_int, _P]),
     "masic_homography_from_corners": (c_int, [_P, _P, _P, c_int, c_float, c_float, _P]),
     "masic_pair_prep": (c_int, [_P] + [c_int] * 6 + [_P] + [c_int] * 4 + [_P, _P]),
+    "masic_pairs_prep": (c_int, [_P] + [c_int] * 5 + [_P] + [c_int] * 4 + [_P, _P]),
+    "masic_planes_to_u8": (c_int, [_P] + [c_int] * 5 + [_P, _P]),
     # UDH homography net
     "masic_udh_conv1_fwd": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
     "masic_maxpool2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),

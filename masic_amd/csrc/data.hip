@@ -7,6 +7,8 @@
 // int32 horizontal pass, (b*(t>>4))>>16 vertical pass, +2 >>2; an exact 2x decimation runs as the rounded 2x2 box mean), and
 // only the patch window of the resized picture is ever computed.  cv2 itself is absent: parity is pinned by the numpy
 // restatement oracle/data_oracle.py.
+// Below that: the two ends of the stereo file pipeline over a stack of pictures per launch -- masic_pairs_prep (uint8 pictures ->
+// float planes padded by edge replication + the patches of the unpadded pictures) and masic_planes_to_u8 (planes -> cropped uint8).
 #include "common.h"
 
 namespace {
@@ -31,11 +33,9 @@ __device__ __forceinline__ void lin_coeff(int d, double scale, int src, int& s, 
     c1 = (int)rintf(f * 2048.0f);
 }
 
-__global__ __launch_bounds__(256) void homo_patch_kernel(const unsigned char* __restrict__ img, int W, int h0, int w0, int ph, int pw,
-                                                         int S, int px0, int py0, int patch, float mean, float stdv,
-                                                         float* __restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= patch * patch) return;
+// Element i of the patch of one picture (img: its first byte); shared by the per-picture and the batched kernel, so the two agree bit for bit.
+__device__ __forceinline__ void homo_patch_element(const unsigned char* __restrict__ img, int W, int h0, int w0, int ph, int pw, int S, int px0,
+                                                   int py0, int patch, float mean, float stdv, float* __restrict__ out, int i) {
     const int dy = py0 + i / patch, dx = px0 + i % patch;              // pixel of the S x S resized crop
     int v[3];
     if (ph == 2 * S && pw == 2 * S) {
@@ -63,6 +63,162 @@ __global__ __launch_bounds__(256) void homo_patch_kernel(const unsigned char* __
     out[i] = __fdiv_rn(__fadd_rn(__fadd_rn(n[0], n[1]), n[2]), 3.0f);
 }
 
+__global__ __launch_bounds__(256) void homo_patch_kernel(const unsigned char* __restrict__ img, int W, int h0, int w0, int ph, int pw,
+                                                         int S, int px0, int py0, int patch, float mean, float stdv,
+                                                         float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < patch * patch) homo_patch_element(img, W, h0, w0, ph, pw, S, px0, py0, patch, mean, stdv, out, i);
+}
+
+// The same patch of each of the P pictures of a stack [P][H0][W0][3] (blockIdx.y = picture), the whole picture being the crop.
+__global__ __launch_bounds__(256) void homo_patches_kernel(const unsigned char* __restrict__ pics, int H0, int W0, int S, int px0, int py0,
+                                                           int patch, float mean, float stdv, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= patch * patch) return;
+    const size_t p = blockIdx.y;
+    homo_patch_element(pics + p * H0 * W0 * 3, W0, 0, 0, H0, W0, S, px0, py0, patch, mean, stdv, out + p * patch * patch, i);
+}
+
+// ---- the two ends of the stereo file pipeline (masic_amd/stereofile.py): P pictures uint8 [P][H0][W0][3] <-> float32 planes [P][3][H][W],
+// H >= H0, W >= W0.  Both stream: 3 bytes a pixel on the interleaved side, 12 on the planar side.  A lane owns FOUR consecutive pixels of a
+// row -- one 16-byte access per plane -- and a workgroup one segment of `segl` lanes of 256 / segl rows (segl a multiple of 64: 64 lanes x 4
+// rows for narrow pictures up to 256 x 1 row).  The 12 interleaved bytes of a lane start at a multiple of 3, so they go through LDS: a row
+// segment's bytes cross the global boundary as aligned 32-bit words, laid out in LDS at the global address's offset within its word, and
+// the lanes pick or place single bytes there (12-byte lane stride: three banks, conflict-free over a wavefront).
+constexpr int PIX_REGION_WORDS = 776;      // rows * (3 * segl + 2) words at most: 4 * 194
+
+struct pix_block {
+    int r, l, y, x, valid;      // row of the block, lane of the segment, picture row, first pixel; lane inside the picture
+    uint32_t* region;
+};
+__device__ __forceinline__ pix_block pix_block_of(uint32_t* lds, int segl, int Hlim) {
+    pix_block b;
+    const int rows = 256 / segl;
+    b.r = threadIdx.x / segl;
+    b.l = threadIdx.x - b.r * segl;
+    b.y = blockIdx.y * rows + b.r;
+    b.x = (blockIdx.x * segl + b.l) * 4;
+    b.valid = b.r < rows && b.y < Hlim;
+    b.region = lds + b.r * (3 * segl + 2);
+    return b;
+}
+
+// planes[p][c][y][x] = pics[p][min(y, H0-1)][min(x, W0-1)][c] / 255 (the division of crop_to_tensor_kernel); vec: W % 4 == 0 and a 16-byte
+// aligned base.  nbytes = P * H0 * W0 * 3; pics is 4-byte aligned, and the one word that may reach past nbytes is read bytewise.
+__global__ __launch_bounds__(256) void pairs_planes_kernel(const unsigned char* __restrict__ pics, size_t nbytes, int H0, int W0, int H, int W,
+                                                           int segl, int vec, float* __restrict__ planes) {
+    __shared__ uint32_t lds[PIX_REGION_WORDS];
+    const int rows = 256 / segl, seg_pix = segl * 4;
+    const size_t p = blockIdx.z;
+    const int x0 = blockIdx.x * seg_pix;
+    const int s0 = min(x0, W0 - 1), s1 = max(min(x0 + seg_pix, W0), s0 + 1);      // source pixels [s0, s1) of this segment, never empty
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(pics);
+    for (int r = 0; r < rows; ++r) {
+        const int y = blockIdx.y * rows + r;
+        if (y >= H) break;
+        const size_t g0 = ((p * H0 + min(y, H0 - 1)) * W0 + s0) * 3;              // first byte of the segment's source pixels
+        const int sh = (int)(g0 & 3), nw = (sh + (s1 - s0) * 3 + 3) >> 2;
+        uint32_t* region = lds + r * (3 * segl + 2);
+        for (int i = threadIdx.x; i < nw; i += 256) {
+            const size_t wi = (g0 >> 2) + i;
+            uint32_t v;
+            if (wi * 4 + 4 <= nbytes) {
+                v = words[wi];
+            } else {
+                v = 0;
+                for (size_t k = wi * 4; k < nbytes; ++k) v |= (uint32_t)pics[k] << (8 * (k - wi * 4));
+            }
+            region[i] = v;
+        }
+    }
+    __syncthreads();
+    const pix_block b = pix_block_of(lds, segl, H);
+    if (!b.valid || b.x >= W) return;
+    const size_t g0 = ((p * H0 + min(b.y, H0 - 1)) * W0 + s0) * 3;
+    const unsigned char* bytes = reinterpret_cast<const unsigned char*>(b.region) + (g0 & 3);
+    float v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int s = (min(b.x + k, W0 - 1) - s0) * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) v[ch][k] = (float)bytes[s + ch] / 255.0f;
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float* o = planes + ((p * 3 + ch) * H + b.y) * W + b.x;
+        if (vec) {
+            *reinterpret_cast<float4*>(o) = make_float4(v[ch][0], v[ch][1], v[ch][2], v[ch][3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (b.x + k < W) o[k] = v[ch][k];
+        }
+    }
+}
+
+// out[p][y][x][c] = floor(clamp(planes[p][c][y][x], 0, 1) * 255 + 0.5), NaN -> 0 (two float32 roundings: torchvision's save_image), for
+// y < H0, x < W0.  out is 4-byte aligned; a word that holds bytes of a neighbouring segment or row is written bytewise.
+__device__ __forceinline__ unsigned char to_u8(float v) {
+    const float c = !(v > 0.0f) ? 0.0f : (v < 1.0f ? v : 1.0f);
+    return (unsigned char)(int)floorf(__fadd_rn(__fmul_rn(c, 255.0f), 0.5f));
+}
+
+__global__ __launch_bounds__(256) void planes_to_u8_kernel(const float* __restrict__ planes, int H, int W, int H0, int W0, int segl, int vec,
+                                                           unsigned char* __restrict__ out) {
+    __shared__ uint32_t lds[PIX_REGION_WORDS];
+    const int rows = 256 / segl, seg_pix = segl * 4;
+    const size_t p = blockIdx.z;
+    const int x0 = blockIdx.x * seg_pix, x1 = min(x0 + seg_pix, W0);             // pixels [x0, x1) of this segment; x0 < W0 by the grid
+    const pix_block b = pix_block_of(lds, segl, H0);
+    if (b.valid && b.x < W0) {
+        const size_t g0 = ((p * H0 + b.y) * W0 + x0) * 3;
+        unsigned char* bytes = reinterpret_cast<unsigned char*>(b.region) + (g0 & 3) + b.l * 12;
+        float v[3][4];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float* s = planes + ((p * 3 + ch) * H + b.y) * W + b.x;
+            if (vec) {
+                const float4 t = *reinterpret_cast<const float4*>(s);
+                v[ch][0] = t.x; v[ch][1] = t.y; v[ch][2] = t.z; v[ch][3] = t.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[ch][k] = b.x + k < W0 ? s[k] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (b.x + k < W0) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) bytes[k * 3 + ch] = to_u8(v[ch][k]);
+            }
+    }
+    __syncthreads();
+    uint32_t* words = reinterpret_cast<uint32_t*>(out);
+    for (int r = 0; r < rows; ++r) {
+        const int y = blockIdx.y * rows + r;
+        if (y >= H0) break;
+        const size_t g0 = ((p * H0 + y) * W0 + x0) * 3;
+        const int sh = (int)(g0 & 3), end = sh + (x1 - x0) * 3, nw = (end + 3) >> 2;      // the segment's bytes are [sh, end) of the region
+        const uint32_t* region = lds + r * (3 * segl + 2);
+        for (int i = threadIdx.x; i < nw; i += 256) {
+            const size_t wi = (g0 >> 2) + i;
+            if (4 * i >= sh && 4 * i + 4 <= end) {
+                words[wi] = region[i];
+            } else {
+                const unsigned char* src = reinterpret_cast<const unsigned char*>(region);
+                for (int k = max(4 * i, sh); k < min(4 * i + 4, end); ++k) out[wi * 4 + (k - 4 * i)] = src[k];
+            }
+        }
+    }
+}
+
+// lanes of a row segment: the row's ceil(W / 4) lanes split evenly over the fewest workgroups, rounded up to whole wavefronts
+inline int pix_segment_lanes(int W) {
+    const int lanes = ceil_div(W, 4);
+    const int segl = round_up(ceil_div(lanes, ceil_div(lanes, 256)), 64);
+    return segl < 256 ? segl : 256;
+}
+
 }  // namespace
 
 extern "C" int masic_pair_prep(const uint8_t* img_hwc, int H, int W, int start_h, int start_w, int ph, int pw, float* pic_chw,
@@ -81,4 +237,42 @@ extern "C" int masic_pair_prep(const uint8_t* img_hwc, int H, int W, int start_h
                            homopic, patch_x, patch_y, homopatch, mean, stdv, homo_patch);
     }
     return masic_launch_status("pair_prep");
+}
+
+extern "C" int masic_pairs_prep(const uint8_t* pics_hwc, int P, int H0, int W0, int H, int W, float* planes, int homopic, int patch_x,
+                                int patch_y, int homopatch, float* patches, void* stream) {
+    MASIC_REQUIRE(pics_hwc && (planes || patches), MASIC_ERR_ARG, "pairs_prep: null pointer");
+    MASIC_REQUIRE(P > 0 && P <= 65535 && H0 > 0 && W0 > 0, MASIC_ERR_ARG, "pairs_prep: %d pictures of %d x %d (1 .. 65535 pictures, no empty extent)", P, H0, W0);
+    MASIC_REQUIRE(((size_t)pics_hwc & 3) == 0, MASIC_ERR_ARG, "pairs_prep: the picture stack must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (planes) {
+        MASIC_REQUIRE(H >= H0 && W >= W0 && H <= 65535 && W <= 65535, MASIC_ERR_ARG,
+                      "pairs_prep: planes of %d x %d for pictures of %d x %d (at least the picture, at most 65535)", H, W, H0, W0);
+        MASIC_REQUIRE(((size_t)planes & 3) == 0, MASIC_ERR_ARG, "pairs_prep: the planes must be 4-byte aligned");
+        const int segl = pix_segment_lanes(W), vec = W % 4 == 0 && ((size_t)planes & 15) == 0;
+        hipLaunchKernelGGL(pairs_planes_kernel, dim3(ceil_div(W, 4 * segl), ceil_div(H, 256 / segl), P), dim3(256), 0, st, pics_hwc,
+                           (size_t)P * H0 * W0 * 3, H0, W0, H, W, segl, vec, planes);
+    }
+    if (patches) {
+        MASIC_REQUIRE(homopic > 0 && homopatch > 0 && patch_x >= 0 && patch_y >= 0 && patch_x + homopatch <= homopic && patch_y + homopatch <= homopic,
+                      MASIC_ERR_ARG, "pairs_prep: patch [%d:%d, %d:%d] of the %d x %d resized picture", patch_y, patch_y + homopatch, patch_x,
+                      patch_x + homopatch, homopic, homopic);
+        MASIC_REQUIRE(homopic <= 16384, MASIC_ERR_ARG, "pairs_prep: resized picture of %d x %d (at most 16384)", homopic, homopic);
+        const float mean = (0.485f + 0.456f + 0.406f) / 3.0f, stdv = (0.229f + 0.224f + 0.225f) / 3.0f;    // utils.py:26-27
+        hipLaunchKernelGGL(homo_patches_kernel, dim3(ceil_div(homopatch * homopatch, 256), P), dim3(256), 0, st, pics_hwc, H0, W0, homopic,
+                           patch_x, patch_y, homopatch, mean, stdv, patches);
+    }
+    return masic_launch_status("pairs_prep");
+}
+
+extern "C" int masic_planes_to_u8(const float* planes, int P, int H, int W, int H0, int W0, uint8_t* pics_hwc, void* stream) {
+    MASIC_REQUIRE(planes && pics_hwc, MASIC_ERR_ARG, "planes_to_u8: null pointer");
+    MASIC_REQUIRE(P > 0 && P <= 65535 && H0 > 0 && W0 > 0 && H0 <= H && W0 <= W && H0 <= 65535 && W0 <= 65535, MASIC_ERR_ARG,
+                  "planes_to_u8: %d pictures of %d x %d out of planes of %d x %d (1 .. 65535 pictures; no empty extent, at most the planes and 65535)",
+                  P, H0, W0, H, W);
+    MASIC_REQUIRE(((size_t)pics_hwc & 3) == 0 && ((size_t)planes & 3) == 0, MASIC_ERR_ARG, "planes_to_u8: both buffers must be 4-byte aligned");
+    const int segl = pix_segment_lanes(W0), vec = W % 4 == 0 && ((size_t)planes & 15) == 0;
+    hipLaunchKernelGGL(planes_to_u8_kernel, dim3(ceil_div(W0, 4 * segl), ceil_div(H0, 256 / segl), P), dim3(256), 0, (hipStream_t)stream, planes,
+                       H, W, H0, W0, segl, vec, pics_hwc);
+    return masic_launch_status("planes_to_u8");
 }

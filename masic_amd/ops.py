@@ -3,6 +3,7 @@ its outputs with torch (device memory is torch's; the library never allocates) a
 C-ABI kernel on torch's current HIP stream.  No function here computes on the CPU and none falls
 back to ATen ops: CPU tensors raise.
 """
+import collections
 import ctypes
 
 import torch
@@ -413,6 +414,43 @@ def pair_prep(img_u8, start_hw, crop_hw, homopic=256, patch_xy=(0, 0), homopatch
     check(lib.masic_pair_prep(_p(img_u8), H, W, int(start_hw[0]), int(start_hw[1]), int(ph), int(pw), _p(pic), int(homopic),
                               int(patch_xy[0]), int(patch_xy[1]), int(homopatch), _p(patch), _stream()), "pair_prep")
     return pic, patch
+
+
+PairsPrep = collections.namedtuple("PairsPrep", "planes patches")
+
+
+def pairs_prep(pics_u8, pad_to=64, homopic=256, patch_xy=(64, 64), homopatch=128):
+    """pair_prep for a stack of P whole pictures, uint8 [P,H0,W0,3] on the device, in two launches -> (planes float32 [P,3,H,W] with
+    H, W = H0, W0 rounded up to pad_to: u8 / 255 inside the picture, the last row and column replicated outside it; patches float32
+    [P,1,homopatch,homopatch]: pair_prep's grey patch of each UNPADDED picture, so a homography estimated from them stays in the
+    picture's own pixel coordinates)."""
+    if not (isinstance(pics_u8, torch.Tensor) and pics_u8.is_cuda and pics_u8.dtype == torch.uint8 and pics_u8.dim() == 4
+            and pics_u8.shape[3] == 3 and pics_u8.is_contiguous()):
+        raise RuntimeError("masic_amd.pairs_prep: the pictures must be a contiguous uint8 [P,H0,W0,3] CUDA (HIP) tensor")
+    if int(pad_to) < 1:
+        raise RuntimeError("masic_amd.pairs_prep: pad_to must be at least 1")
+    if pics_u8.data_ptr() % 4:
+        pics_u8 = pics_u8.clone()
+    P, H0, W0 = pics_u8.shape[:3]
+    H, W = -(-H0 // int(pad_to)) * int(pad_to), -(-W0 // int(pad_to)) * int(pad_to)
+    planes = torch.empty((P, 3, H, W), dtype=torch.float32, device=pics_u8.device)
+    patches = torch.empty((P, 1, homopatch, homopatch), dtype=torch.float32, device=pics_u8.device)
+    check(lib.masic_pairs_prep(_p(pics_u8), P, H0, W0, H, W, _p(planes), int(homopic), int(patch_xy[0]), int(patch_xy[1]), int(homopatch),
+                               _p(patches), _stream()), "pairs_prep")
+    return PairsPrep(planes, patches)
+
+
+def planes_to_u8(x, out_hw):
+    """float32 planes [P,3,H,W] -> uint8 pictures [P,H0,W0,3], out_hw = (H0, W0) the top-left window kept: floor(clamp(x, 0, 1) * 255 +
+    0.5) in float32 (torchvision's save_image), NaN -> 0; the exact inverse of pairs_prep's planes."""
+    _dev(x, "planes")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("masic_amd.planes_to_u8: the planes must be [P,3,H,W]")
+    P, _, H, W = x.shape
+    H0, W0 = int(out_hw[0]), int(out_hw[1])
+    out = torch.empty((P, max(H0, 0), max(W0, 0), 3), dtype=torch.uint8, device=x.device)
+    check(lib.masic_planes_to_u8(_p(x), P, H, W, H0, W0, _p(out), _stream()), "planes_to_u8")
+    return out
 
 
 def homography_from_corners(corners, delta, ori_hw, patch_hw):
