@@ -735,6 +735,26 @@ int masic_pairs_prep(const uint8_t* pics_hwc, int P, int H0, int W0, int H, int 
                      int homopatch, float* patches, void* stream);
 int masic_planes_to_u8(const float* planes, int P, int H, int W, int H0, int W0, uint8_t* pics_hwc, void* stream);
 
+/* ---- the training batch of a device-resident dataset (masic_amd/data.py): masic_pair_prep for P views at once, each view its own crop
+ * of its own picture, in one launch for the crops and one for the patches whatever P is.
+ *   arena      uint8, 4-byte aligned, arena_bytes % 4 == 0: the decoded pictures back to back, picture i as [H_i][W_i][3] from a 16-byte
+ *              aligned offset (so the aligned 32-bit word that holds a picture's last byte lies inside the arena)
+ *   desc_dev   P descriptors in DEVICE memory, 8-byte aligned (filled by an asynchronous copy on `stream` before the call)
+ *   planes     (nullable) float32 [P][3][ph][pw]: masic_pair_prep's pic_chw of view p, bit for bit; 16-byte stores when pw % 4 == 0 and the
+ *              base is 16-byte aligned, scalar stores otherwise
+ *   patches    (nullable) float32 [P][homopatch][homopatch]: masic_pair_prep's homo_patch of view p at (patch_x, patch_y), bit for bit
+ * The library cannot read the descriptors: the caller checks each one on the host (crop inside the picture, picture inside the arena,
+ * patch inside the homopic x homopic resized crop) before the call.  The kernels skip a view whose descriptor fails that check, so a bad
+ * table leaves its outputs unwritten and reads nothing outside the arena.  No view's result depends on the other views of the call. */
+typedef struct masic_view_desc_t {
+    uint64_t offset;               /* first byte of the picture in the arena */
+    int32_t W, H;                  /* the picture's row width and its rows */
+    int32_t start_h, start_w;      /* top-left of the crop */
+    int32_t patch_x, patch_y;      /* top-left of the patch in the resized crop */
+} masic_view_desc_t;
+int masic_views_prep(const uint8_t* arena, size_t arena_bytes, const masic_view_desc_t* desc_dev, int P, int ph, int pw, float* planes,
+                     int homopic, int homopatch, float* patches, void* stream);
+
 /* ---- HSIC.compress / decompress (MASIC.py:855-1408), SURVEY.md 8(f)-1: the y1 / y2 streams.
  * rANS with one table per symbol (host).  The reference drives the third-party `range_coder` package here
  * (MASIC.py:958, :1044, :1221, :1296), which is not part of its tree: the byte stream of this container is this

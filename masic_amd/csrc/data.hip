@@ -9,6 +9,8 @@
 // restatement oracle/data_oracle.py.
 // Below that: the two ends of the stereo file pipeline over a stack of pictures per launch -- masic_pairs_prep (uint8 pictures ->
 // float planes padded by edge replication + the patches of the unpadded pictures) and masic_planes_to_u8 (planes -> cropped uint8).
+// Last: masic_views_prep, the training batch of a device-resident dataset (masic_amd/data.py) -- P views, each its own crop of its own
+// picture of an arena of decoded pictures, one descriptor per view in device memory, two launches for the whole batch.
 #include "common.h"
 
 namespace {
@@ -212,6 +214,86 @@ __global__ __launch_bounds__(256) void planes_to_u8_kernel(const float* __restri
     }
 }
 
+// ---- the batch of a device-resident dataset (masic_amd/data.py): the pictures lie back to back in one uint8 arena, [H_i][W_i][3] each from a
+// 16-byte aligned offset, and view p of a batch is the crop [start_h : +ph, start_w : +pw] of the picture its descriptor names.
+// A descriptor that does not fit its picture or the arena is skipped whole by both kernels (the caller refuses it before it launches; a
+// fault here would be everybody's), so no read leaves the arena whatever the table holds.
+__device__ __forceinline__ bool view_inside(const masic_view_desc_t& d, size_t arena_bytes, int ph, int pw) {
+    return d.W > 0 && d.H > 0 && d.start_h >= 0 && d.start_w >= 0 && d.start_h <= d.H - ph && d.start_w <= d.W - pw && d.offset <= arena_bytes &&
+           (uint64_t)d.H * (uint64_t)d.W * 3u <= arena_bytes - d.offset;
+}
+
+// planes[p][c][y][x] = u8 / 255 of the crop of view p (the division of crop_to_tensor_kernel).  The lane and workgroup shapes are those of
+// pairs_planes_kernel: a lane owns four consecutive pixels of a row, a workgroup one segment of `segl` lanes of 256 / segl rows; blockIdx.x =
+// (p * ysegs + row block) * xsegs + segment, so the number of views is not bound by a grid extent.  A segment's bytes start anywhere --
+// offset + ((start_h + y) * W_i + start_w + x0) * 3, every residue mod 4, another one on the next row when W_i is odd -- and cross the
+// global boundary as the aligned 32-bit words that hold them, each lane fetching the words l, l + segl, ... of its own row: word i of
+// the LDS region is word i of that run.  A lane's 12 bytes then begin `sh` bytes into word 3 l: four LDS words (stride 3 words: no bank
+// is hit twice by a half-wavefront), shifted together, hold them.  arena_bytes % 4 == 0 and the arena is 4-byte aligned, so the last
+// word of a picture lies inside the arena as well.
+__global__ __launch_bounds__(256) void views_planes_kernel(const unsigned char* __restrict__ arena, size_t arena_bytes,
+                                                           const masic_view_desc_t* __restrict__ desc, int ph, int pw, int segl, int xsegs,
+                                                           int ysegs, int vec, float* __restrict__ planes) {
+    __shared__ uint32_t lds[PIX_REGION_WORDS];
+    const int rows = 256 / segl, seg_pix = segl * 4;
+    const int xb = blockIdx.x % xsegs, yb = (blockIdx.x / xsegs) % ysegs;
+    const size_t p = blockIdx.x / xsegs / ysegs;
+    const masic_view_desc_t d = desc[p];
+    if (!view_inside(d, arena_bytes, ph, pw)) return;
+    const int r = threadIdx.x / segl, l = threadIdx.x - r * segl;
+    const int y = yb * rows + r, x0 = xb * seg_pix, x = x0 + 4 * l;
+    const bool row = r < rows && y < ph;
+    const int n = min(seg_pix, pw - x0);                                            // pixels of this segment, > 0 by the grid
+    const size_t g0 = d.offset + ((size_t)(d.start_h + (row ? y : 0)) * d.W + d.start_w + x0) * 3;
+    const int sh = (int)(g0 & 3), nw = (sh + n * 3 + 3) >> 2;
+    uint32_t* region = lds + r * (3 * segl + 2);
+    if (row) {
+        const uint32_t* words = reinterpret_cast<const uint32_t*>(arena) + (g0 >> 2);
+        for (int i = l; i < nw; i += segl) region[i] = words[i];
+    }
+    __syncthreads();
+    if (!row || x >= pw) return;
+    const uint32_t w0 = region[3 * l], w1 = region[3 * l + 1], w2 = region[3 * l + 2], w3 = region[3 * l + 3];
+    const int s8 = 8 * sh;
+    uint32_t w[3];
+    w[0] = (uint32_t)((((uint64_t)w1 << 32) | w0) >> s8);
+    w[1] = (uint32_t)((((uint64_t)w2 << 32) | w1) >> s8);
+    w[2] = (uint32_t)((((uint64_t)w3 << 32) | w2) >> s8);
+    float v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int b = k * 3 + ch;
+            v[ch][k] = (float)((w[b >> 2] >> (8 * (b & 3))) & 0xffu) / 255.0f;
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float* o = planes + ((p * 3 + ch) * ph + y) * pw + x;
+        if (vec) {
+            *reinterpret_cast<float4*>(o) = make_float4(v[ch][0], v[ch][1], v[ch][2], v[ch][3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x + k < pw) o[k] = v[ch][k];
+        }
+    }
+}
+
+// patches[p] = the patch at (patch_x, patch_y) of view p's crop resized to S x S: homo_patch_element itself, so the three resize branches
+// are pair_prep's.  blockIdx.x = p * blocks per patch + block.
+__global__ __launch_bounds__(256) void views_patches_kernel(const unsigned char* __restrict__ arena, size_t arena_bytes,
+                                                            const masic_view_desc_t* __restrict__ desc, int ph, int pw, int S, int patch,
+                                                            int nb, float mean, float stdv, float* __restrict__ out) {
+    const size_t p = blockIdx.x / nb;
+    const int i = (blockIdx.x - (int)p * nb) * 256 + threadIdx.x;
+    if (i >= patch * patch) return;
+    const masic_view_desc_t d = desc[p];
+    if (!view_inside(d, arena_bytes, ph, pw) || d.patch_x < 0 || d.patch_y < 0 || d.patch_x > S - patch || d.patch_y > S - patch) return;
+    homo_patch_element(arena + d.offset, d.W, d.start_h, d.start_w, ph, pw, S, d.patch_x, d.patch_y, patch, mean, stdv, out + p * patch * patch, i);
+}
+
 // lanes of a row segment: the row's ceil(W / 4) lanes split evenly over the fewest workgroups, rounded up to whole wavefronts
 inline int pix_segment_lanes(int W) {
     const int lanes = ceil_div(W, 4);
@@ -275,4 +357,33 @@ extern "C" int masic_planes_to_u8(const float* planes, int P, int H, int W, int 
     hipLaunchKernelGGL(planes_to_u8_kernel, dim3(ceil_div(W0, 4 * segl), ceil_div(H0, 256 / segl), P), dim3(256), 0, (hipStream_t)stream, planes,
                        H, W, H0, W0, segl, vec, pics_hwc);
     return masic_launch_status("planes_to_u8");
+}
+
+extern "C" int masic_views_prep(const uint8_t* arena, size_t arena_bytes, const masic_view_desc_t* desc_dev, int P, int ph, int pw, float* planes,
+                                int homopic, int homopatch, float* patches, void* stream) {
+    MASIC_REQUIRE(arena && desc_dev && (planes || patches), MASIC_ERR_ARG, "views_prep: null pointer");
+    MASIC_REQUIRE(P > 0 && ph > 0 && pw > 0 && ph <= 65535 && pw <= 65535, MASIC_ERR_ARG,
+                  "views_prep: %d views cropped to %d x %d (at least one view, extents 1 .. 65535)", P, ph, pw);
+    MASIC_REQUIRE(((size_t)arena & 3) == 0 && (arena_bytes & 3) == 0 && ((size_t)desc_dev & 7) == 0, MASIC_ERR_ARG,
+                  "views_prep: the arena must be 4-byte aligned and a multiple of 4 bytes long, the descriptors 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (planes) {
+        MASIC_REQUIRE(((size_t)planes & 3) == 0, MASIC_ERR_ARG, "views_prep: the planes must be 4-byte aligned");
+        const int segl = pix_segment_lanes(pw), vec = pw % 4 == 0 && ((size_t)planes & 15) == 0;
+        const int xsegs = ceil_div(pw, 4 * segl), ysegs = ceil_div(ph, 256 / segl);
+        MASIC_REQUIRE((long long)P * xsegs * ysegs <= 0x7fffffffLL, MASIC_ERR_ARG, "views_prep: %d views of %d x %d are more than one grid", P, ph, pw);
+        hipLaunchKernelGGL(views_planes_kernel, dim3((unsigned)(P * xsegs * ysegs)), dim3(256), 0, st, arena, arena_bytes, desc_dev, ph, pw, segl,
+                           xsegs, ysegs, vec, planes);
+    }
+    if (patches) {
+        MASIC_REQUIRE(homopic > 0 && homopatch > 0 && homopatch <= homopic && homopic <= 16384, MASIC_ERR_ARG,
+                      "views_prep: patch of %d x %d of the %d x %d resized crop (patch at most the crop, the crop at most 16384)", homopatch,
+                      homopatch, homopic, homopic);
+        const int nb = ceil_div(homopatch * homopatch, 256);
+        MASIC_REQUIRE((long long)P * nb <= 0x7fffffffLL, MASIC_ERR_ARG, "views_prep: %d patches of %d x %d are more than one grid", P, homopatch, homopatch);
+        const float mean = (0.485f + 0.456f + 0.406f) / 3.0f, stdv = (0.229f + 0.224f + 0.225f) / 3.0f;    // utils.py:26-27
+        hipLaunchKernelGGL(views_patches_kernel, dim3((unsigned)(P * nb)), dim3(256), 0, st, arena, arena_bytes, desc_dev, ph, pw, homopic,
+                           homopatch, nb, mean, stdv, patches);
+    }
+    return masic_launch_status("views_prep");
 }

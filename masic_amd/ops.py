@@ -453,6 +453,83 @@ def planes_to_u8(x, out_hw):
     return out
 
 
+VIEW_DESC_FIELDS = ("offset", "W", "H", "start_h", "start_w", "patch_x", "patch_y")      # masic_view_desc_t, in its order
+_VIEW_DESC = None
+
+
+def _view_desc_dtype():
+    global _VIEW_DESC
+    if _VIEW_DESC is None:
+        import numpy as np
+        _VIEW_DESC = np.dtype([("offset", "<u8")] + [(n, "<i4") for n in VIEW_DESC_FIELDS[1:]])
+        assert _VIEW_DESC.itemsize == 32
+    return _VIEW_DESC
+
+
+def check_view_descriptors(desc, arena_bytes, crop_hw, homopic, homopatch):
+    """The host check masic_views_prep asks of its caller: every row of desc (integers [P,7] in the order of VIEW_DESC_FIELDS) names a
+    picture inside the arena, a crop inside that picture and a patch inside the resized crop.  Returns desc as int64 [P,7]; a bad row
+    raises RuntimeError naming the first one."""
+    import numpy as np
+    d = np.asarray(desc)
+    if d.ndim != 2 or d.shape[1] != 7 or d.shape[0] < 1 or d.dtype.kind not in "iu":
+        raise RuntimeError("masic_amd.views_prep: the descriptors must be integers [P,7] (" + ", ".join(VIEW_DESC_FIELDS) + "), P >= 1")
+    d = d.astype(np.int64)
+    ph, pw = int(crop_hw[0]), int(crop_hw[1])
+    off, W, H, sh, sw, px, py = d.T
+    lim = 1 << 24                         # keeps H * W * 3 far inside int64; no picture has an extent like it
+    bad = (off < 0) | (off % 16 != 0) | (W <= 0) | (H <= 0) | (W >= lim) | (H >= lim)
+    bad |= off + np.where(bad, 0, H * W * 3) > int(arena_bytes)
+    bad |= (sh < 0) | (sw < 0) | (sh + ph > H) | (sw + pw > W)
+    bad |= (px < 0) | (py < 0) | (px + int(homopatch) > int(homopic)) | (py + int(homopatch) > int(homopic))
+    if bad.any():
+        p = int(np.argmax(bad))
+        what = ", ".join(f"{n} {int(v)}" for n, v in zip(VIEW_DESC_FIELDS, d[p]))
+        raise RuntimeError(f"masic_amd.views_prep: view {p} ({what}) does not fit: crop {ph} x {pw}, patch {homopatch} of {homopic}, "
+                           f"arena of {int(arena_bytes)} bytes, pictures at multiples of 16")
+    return d
+
+
+def pack_view_descriptors(d):
+    """checked descriptors int64 [P,7] -> the P masic_view_desc_t records as int32 [P,8]"""
+    import numpy as np
+    rec = np.empty(d.shape[0], dtype=_view_desc_dtype())
+    for i, n in enumerate(VIEW_DESC_FIELDS):
+        rec[n] = d[:, i]
+    return rec.view(np.int32).reshape(d.shape[0], 8)
+
+
+def views_prep(arena, desc, crop_hw, homopic=256, homopatch=128, planes=None, patches=None):
+    """pair_prep for P views at once out of an arena of decoded pictures (masic_amd/data.py; include/masic_hip.h: masic_views_prep) ->
+    (planes float32 [P,3,ph,pw], patches float32 [P,1,homopatch,homopatch]), each view with the bits of pair_prep on its picture.
+    arena: uint8 1-D device tensor, a multiple of 4 bytes.  desc: integers [P,7] on the HOST, one row per view in the order of
+    VIEW_DESC_FIELDS; every row is checked here before anything is launched (RuntimeError, outputs untouched).  The rows reach the device
+    through pinned memory by an asynchronous copy on the current stream: nothing waits for the device.  planes / patches: optional
+    output tensors (contiguous float32 of those shapes)."""
+    if not (isinstance(arena, torch.Tensor) and arena.is_cuda and arena.dtype == torch.uint8 and arena.dim() == 1 and arena.is_contiguous()):
+        raise RuntimeError("masic_amd.views_prep: the arena must be a contiguous uint8 1-D CUDA (HIP) tensor -- the MI355X path has no CPU fallback")
+    if arena.numel() % 4 or arena.data_ptr() % 4:
+        raise RuntimeError("masic_amd.views_prep: the arena must be 4-byte aligned and a multiple of 4 bytes long")
+    ph, pw = int(crop_hw[0]), int(crop_hw[1])
+    homopic, homopatch = int(homopic), int(homopatch)
+    if ph < 1 or pw < 1 or homopatch < 1 or homopic < homopatch:
+        raise RuntimeError(f"masic_amd.views_prep: crop {ph} x {pw}, patch {homopatch} of {homopic}")
+    d = check_view_descriptors(desc, arena.numel(), (ph, pw), homopic, homopatch)
+    P = d.shape[0]
+    for name, t, shape in (("planes", planes, (P, 3, ph, pw)), ("patches", patches, (P, 1, homopatch, homopatch))):
+        if t is not None and (_dev(t, name).device != arena.device or tuple(t.shape) != shape):
+            raise RuntimeError(f"masic_amd.views_prep: {name} must be {shape} on the arena's device")
+    if planes is None:
+        planes = torch.empty((P, 3, ph, pw), dtype=torch.float32, device=arena.device)
+    if patches is None:
+        patches = torch.empty((P, 1, homopatch, homopatch), dtype=torch.float32, device=arena.device)
+    host = torch.empty((P, 8), dtype=torch.int32, pin_memory=True)       # (torch's pinned allocator keeps the block until the copy has run)
+    host.numpy()[...] = pack_view_descriptors(d)
+    table = host.to(arena.device, non_blocking=True)
+    check(lib.masic_views_prep(_p(arena), arena.numel(), _p(table), P, ph, pw, _p(planes), homopic, homopatch, _p(patches), _stream()), "views_prep")
+    return PairsPrep(planes, patches)
+
+
 def homography_from_corners(corners, delta, ori_hw, patch_hw):
     """h_matrix [B,3,3] of udh/udh/model.py:100-111 + h_adjust (newtrain_codec_real.py:49-59, :129) from the patch corners
     [B,4,2] and the predicted offsets [B,4,2]; ori_hw = picture size, patch_hw = the size the homography net saw."""
