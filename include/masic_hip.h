@@ -755,6 +755,35 @@ typedef struct masic_view_desc_t {
 int masic_views_prep(const uint8_t* arena, size_t arena_bytes, const masic_view_desc_t* desc_dev, int P, int ph, int pw, float* planes,
                      int homopic, int homopatch, float* patches, void* stream);
 
+/* ---- the training batch of the homography net (UDH) out of the same arena: the item of the reference's udh/udh/dataset.py
+ * (SyntheticDataset.__getitem__) for P views in one launch.  Element (r, c) of out[p] is pixel (y0 + r, x0 + c) of the
+ * pic_size x pic_size grey picture
+ *     mean_c(Normalize(ToTensor(CenterCrop(pic_size)(Resize(pic_size)(picture)))))
+ * with Resize as PIL does it (Image.resize, BILINEAR, antialiased): a horizontal pass into uint8, then a vertical pass into uint8, each
+ * `(2^21 + sum px * k) >> 22` clipped to 0 .. 255 in int32, the support growing with the scale; an axis that keeps its size gets NO pass
+ * (its bytes are copied; no one-tap table is multiplied).  The grey value has the bits of masic_pair_prep's homo_patch.
+ *   tables     int32 in device memory, 4-byte aligned: the coefficients, computed on the host in float64 as Pillow computes them
+ *              (masic_amd/udh_data.py: pil_bilinear_tables).  One table per axis that is resized, for the pic_size output positions
+ *              that survive the centre crop: xmin[pic_size], n[pic_size], k[pic_size][ksize], ksize = 2 * ceil(in / out) + 1
+ *              (3 when up-scaling), 0 <= xmin, 1 <= n <= ksize, xmin + n <= the axis' input size.  The kernel computes no coefficient.
+ *   desc_dev   P descriptors in DEVICE memory, 8-byte aligned
+ *   out        float32 [P][out_h][out_w], 4-byte aligned; 16-byte stores when out_w % 4 == 0 and the base is 16-byte aligned
+ * ceil(in / out) up to 17 per axis (ksize <= 35): Resize by up to 16 on the shorter side, the longer side's output size being rounded
+ * down.  The library cannot read the descriptors: the caller checks each one on the host
+ * (picture inside the arena, tables inside table_words, rectangle inside pic_size, ksize what the sizes give) before the call.  The kernel
+ * checks the same again and skips a view that fails, and a tile whose table entries leave their ranges: outputs unwritten, nothing read
+ * outside the arena or the tables.  No view's result depends on the other views of the call.
+ * MASIC_ERR_ARG for a null pointer, an empty extent, P > 65535, a rectangle larger than pic_size or a misaligned buffer. */
+typedef struct masic_udh_view_desc_t {
+    uint64_t offset;               /* first byte of the picture in the arena */
+    int32_t W, H;                  /* the picture's row width and its rows */
+    uint32_t h_table, v_table;     /* first word of the horizontal / vertical table in `tables` (ignored when the ksize is 0) */
+    int32_t h_ksize, v_ksize;      /* taps per output position; 0: the axis keeps its size, no pass and no table */
+    int32_t x0, y0;                /* top-left of the out_h x out_w rectangle in the pic_size x pic_size picture */
+} masic_udh_view_desc_t;
+int masic_udh_views_prep(const uint8_t* arena, size_t arena_bytes, const int32_t* tables, size_t table_words,
+                         const masic_udh_view_desc_t* desc_dev, int P, int out_h, int out_w, int pic_size, float* out, void* stream);
+
 /* ---- HSIC.compress / decompress (MASIC.py:855-1408), SURVEY.md 8(f)-1: the y1 / y2 streams.
  * rANS with one table per symbol (host).  The reference drives the third-party `range_coder` package here
  * (MASIC.py:958, :1044, :1221, :1296), which is not part of its tree: the byte stream of this container is this

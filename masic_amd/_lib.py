@@ -92,6 +92,7 @@ SIGNATURES = {
     "masic_pairs_prep": (c_int, [_P] + [c_int] * 5 + [_P] + [c_int] * 4 + [_P, _P]),
     "masic_planes_to_u8": (c_int, [_P] + [c_int] * 5 + [_P, _P]),
     "masic_views_prep": (c_int, [_P, c_size_t, _P] + [c_int] * 3 + [_P, c_int, c_int, _P, _P]),
+    "masic_udh_views_prep": (c_int, [_P, c_size_t, _P, c_size_t, _P] + [c_int] * 4 + [_P, _P]),
     # UDH homography net
     "masic_udh_conv1_fwd": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
     "masic_maxpool2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),

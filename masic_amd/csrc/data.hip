@@ -10,7 +10,10 @@
 // Below that: the two ends of the stereo file pipeline over a stack of pictures per launch -- masic_pairs_prep (uint8 pictures ->
 // float planes padded by edge replication + the patches of the unpadded pictures) and masic_planes_to_u8 (planes -> cropped uint8).
 // Last: masic_views_prep, the training batch of a device-resident dataset (masic_amd/data.py) -- P views, each its own crop of its own
-// picture of an arena of decoded pictures, one descriptor per view in device memory, two launches for the whole batch.
+// picture of an arena of decoded pictures, one descriptor per view in device memory, two launches for the whole batch -- and
+// masic_udh_views_prep, the batch the homography net itself trains on (udh/udh/dataset.py), out of the same arena: PIL's antialiased
+// two-pass bilinear Resize + CenterCrop, bit for bit, from coefficient tables the host computes as Pillow does.  The two resizes differ
+// (cv2: two taps at any scale, 11-bit; PIL: a support that grows with the scale, 22-bit, uint8 between the passes); the grey tail is one.
 #include "common.h"
 
 namespace {
@@ -33,6 +36,15 @@ __device__ __forceinline__ void lin_coeff(int d, double scale, int src, int& s, 
     if (s >= src - 1) { s = src - 1; f = 0.0f; }
     c0 = (int)rintf((1.0f - f) * 2048.0f);
     c1 = (int)rintf(f * 2048.0f);
+}
+
+// mean_c(Normalize(ToTensor(.))) of one resized uint8 pixel with the scalar MEAN / STD: the tail of every grey output of this file (the codec's
+// patches and the UDH batch), so they cannot drift apart.  Each operation is rounded once (no fused multiply-add, no reciprocal).
+__device__ __forceinline__ float grey_value(const int (&v)[3], float mean, float stdv) {
+    float n[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) n[ch] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)v[ch], 255.0f), mean), stdv);
+    return __fdiv_rn(__fadd_rn(__fadd_rn(n[0], n[1]), n[2]), 3.0f);
 }
 
 // Element i of the patch of one picture (img: its first byte); shared by the per-picture and the batched kernel, so the two agree bit for bit.
@@ -59,10 +71,7 @@ __device__ __forceinline__ void homo_patch_element(const unsigned char* __restri
             v[ch] = min(max(o, 0), 255);
         }
     }
-    float n[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) n[ch] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)v[ch], 255.0f), mean), stdv);
-    out[i] = __fdiv_rn(__fadd_rn(__fadd_rn(n[0], n[1]), n[2]), 3.0f);
+    out[i] = grey_value(v, mean, stdv);
 }
 
 __global__ __launch_bounds__(256) void homo_patch_kernel(const unsigned char* __restrict__ img, int W, int h0, int w0, int ph, int pw,
@@ -294,6 +303,167 @@ __global__ __launch_bounds__(256) void views_patches_kernel(const unsigned char*
     homo_patch_element(arena + d.offset, d.W, d.start_h, d.start_w, ph, pw, S, d.patch_x, d.patch_y, patch, mean, stdv, out + p * patch * patch, i);
 }
 
+// ---- the batch of the homography net's own training (udh/udh/dataset.py: SyntheticDataset) out of the same arena: PIL's antialiased
+// bilinear Resize(S) + CenterCrop(S) + the grey tail, of which only the rectangle a view asks for is computed.  PIL resizes in two passes
+// with a uint8 picture between them; both run here in one workgroup, the intermediate in LDS.  A workgroup owns one view and one tile of
+// 16 x 16 output pixels:
+//   1. the tile's table entries (xmin, n per output column / row; the coefficients) go to LDS and are range-checked;
+//   2. the source rows the tile's vertical taps reach, [y_lo, y_hi), are walked in chunks of 32: the bytes of the source columns the
+//      tile's horizontal taps reach, [x_lo, x_hi), cross the global boundary as the aligned 32-bit words that hold them (coalesced, flat
+//      over the chunk), then the horizontal pass writes 16 x 3 uint8 per row into `mid`.  In that pass a lane owns a ROW of the chunk and
+//      a wavefront half one output column at a time, so the coefficients are broadcasts and the byte reads and writes of the 32 lanes go
+//      to 32 rows whose strides (221 and 13 words) are odd: no bank is hit twice;
+//   3. the vertical pass reads `mid` into registers, one lane per output pixel, then grey_value and the store; four neighbours' values
+//      meet in one lane by shuffles for the 16-byte store.
+// An axis that keeps its size has ksize 0 and no table: its bytes are copied (xmin = crop origin + position, one "tap" that is not
+// multiplied).  LDS: 32 x 221 words of source + 291 x 13 words of intermediate + 2 x 16 x 35 coefficients + bounds = 47.0 KiB, sized for
+// the largest scale served: Resize(S) by 16 on the shorter side leaves the longer one, whose output size is rounded down, a scale of up
+// to 17 (256 x 300 -> 16 x 18 is 16.7), so ceil(in / out) <= 17 per axis, ksize <= 35, and a tile's 16 outputs reach at most
+// 15 * 17 + 2 * 17 + 1 = 290 source pixels per axis; three workgroups fit a CU.  All arithmetic is int32 (255 * 2^22 + 2^21 < 2^31) or
+// float32.
+constexpr int UDH_TILE = 16, UDH_KMAX = 35, UDH_CHUNK = 32, UDH_SPAN = 291;
+constexpr int UDH_SRC_WORDS = 221;      // (3 + 291 * 3 + 3) / 4 = 219 and a pad, odd
+constexpr int UDH_MID_WORDS = 13;       // 16 x 3 bytes + 4, odd
+
+__device__ __forceinline__ int round_half_even_half(int d) {      // Python's round(d / 2.0), d >= 0
+    const int m = d >> 1;
+    return (d & 1) ? m + (m & 1) : m;
+}
+
+// ksize of one axis as PIL computes it: 0 stands for "same size, no pass"; -1 for a scale that is not served
+__device__ __forceinline__ int udh_axis_ksize(int in, int out) {
+    if (in == out) return 0;
+    const int s = in > out ? (in + out - 1) / out : 1;
+    return s <= 17 ? 2 * s + 1 : -1;
+}
+
+// The host's check (ops.check_udh_view_descriptors) again; top / left: the centre crop's origin in the resized picture
+__device__ __forceinline__ bool udh_view_inside(const masic_udh_view_desc_t& d, size_t arena_bytes, size_t table_words, int S, int out_h,
+                                                int out_w, int& top, int& left) {
+    if (d.W <= 0 || d.H <= 0 || d.W >= (1 << 24) || d.H >= (1 << 24)) return false;
+    if (d.offset > arena_bytes || (uint64_t)d.H * (uint64_t)d.W * 3u > arena_bytes - d.offset) return false;
+    if (d.x0 < 0 || d.y0 < 0 || d.x0 > S - out_w || d.y0 > S - out_h) return false;
+    long long ow = S, oh = S;                                     // torchvision's Resize(int): the shorter side becomes S
+    if (d.W <= d.H) oh = (long long)S * d.H / d.W; else ow = (long long)S * d.W / d.H;
+    if (ow >= (1 << 24) || oh >= (1 << 24)) return false;
+    const int ksh = udh_axis_ksize(d.W, (int)ow), ksv = udh_axis_ksize(d.H, (int)oh);
+    if (ksh < 0 || ksv < 0 || ksh != d.h_ksize || ksv != d.v_ksize) return false;
+    if (ksh && (d.h_table > table_words || (uint64_t)S * (uint64_t)(2 + ksh) > table_words - d.h_table)) return false;
+    if (ksv && (d.v_table > table_words || (uint64_t)S * (uint64_t)(2 + ksv) > table_words - d.v_table)) return false;
+    top = round_half_even_half((int)oh - S);
+    left = round_half_even_half((int)ow - S);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void udh_views_kernel(const unsigned char* __restrict__ arena, size_t arena_bytes, const int* __restrict__ tables,
+                                                        size_t table_words, const masic_udh_view_desc_t* __restrict__ desc, int S, int out_h,
+                                                        int out_w, int xt, int yt, int vec, float mean, float stdv, float* __restrict__ out) {
+    __shared__ uint32_t src[UDH_CHUNK * UDH_SRC_WORDS];
+    __shared__ uint32_t mid[UDH_SPAN * UDH_MID_WORDS];
+    __shared__ int hk[UDH_TILE * UDH_KMAX], vk[UDH_TILE * UDH_KMAX];
+    __shared__ int hx[UDH_TILE], hn[UDH_TILE], vx[UDH_TILE], vn[UDH_TILE];
+    const int t = threadIdx.x;
+    const int tx = blockIdx.x % xt, ty = (blockIdx.x / xt) % yt;
+    const size_t p = blockIdx.x / xt / yt;
+    const masic_udh_view_desc_t d = desc[p];
+    int top, left;
+    if (!udh_view_inside(d, arena_bytes, table_words, S, out_h, out_w, top, left)) return;
+    const int tw = min(UDH_TILE, out_w - tx * UDH_TILE), th = min(UDH_TILE, out_h - ty * UDH_TILE);      // > 0 by the grid
+    const int X0 = d.x0 + tx * UDH_TILE, Y0 = d.y0 + ty * UDH_TILE;                                       // the tile in the S x S picture
+    const int ksh = d.h_ksize, ksv = d.v_ksize;
+    const int* ht = tables + (ksh ? d.h_table : 0u);
+    const int* vt = tables + (ksv ? d.v_table : 0u);
+
+    // 1. bounds and coefficients of the tile's columns and rows
+    if (t < UDH_TILE) {
+        const int c = min(t, tw - 1);
+        hx[t] = ksh ? ht[X0 + c] : left + X0 + c;
+        hn[t] = ksh ? ht[S + X0 + c] : 1;
+    } else if (t < 2 * UDH_TILE) {
+        const int r = min(t - UDH_TILE, th - 1);
+        vx[t - UDH_TILE] = ksv ? vt[Y0 + r] : top + Y0 + r;
+        vn[t - UDH_TILE] = ksv ? vt[S + Y0 + r] : 1;
+    }
+    for (int i = t; i < tw * ksh; i += 256) hk[i] = ht[2 * S + X0 * ksh + i];
+    for (int i = t; i < th * ksv; i += 256) vk[i] = vt[2 * S + Y0 * ksv + i];
+    __syncthreads();
+    int x_lo = 0x7fffffff, x_hi = 0, y_lo = 0x7fffffff, y_hi = 0;
+    bool good = true;
+#pragma unroll
+    for (int i = 0; i < UDH_TILE; ++i) {
+        const int a = hx[i], an = hn[i], b = vx[i], bn = vn[i];
+        good = good && a >= 0 && an >= 1 && an <= max(ksh, 1) && a <= d.W - an && b >= 0 && bn >= 1 && bn <= max(ksv, 1) && b <= d.H - bn;
+        x_lo = min(x_lo, a); x_hi = max(x_hi, a + an);
+        y_lo = min(y_lo, b); y_hi = max(y_hi, b + bn);
+    }
+    if (!good || x_hi - x_lo > UDH_SPAN || y_hi - y_lo > UDH_SPAN) return;      // the same for every lane: no barrier is left behind
+
+    // 2. source rows [y_lo, y_hi), columns [x_lo, x_hi) -> mid[row - y_lo][16][3] uint8
+    const int row_bytes = (x_hi - x_lo) * 3, nw_max = (row_bytes + 6) >> 2;
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(arena);
+    unsigned char* mid8 = reinterpret_cast<unsigned char*>(mid);
+    for (int base = y_lo; base < y_hi; base += UDH_CHUNK) {
+        const int rows = min(UDH_CHUNK, y_hi - base);
+        for (int i = t; i < rows * nw_max; i += 256) {
+            const int r = i / nw_max, w = i - r * nw_max;
+            const size_t g0 = d.offset + ((size_t)(base + r) * d.W + x_lo) * 3;
+            if (w < (((int)(g0 & 3) + row_bytes + 3) >> 2)) src[r * UDH_SRC_WORDS + w] = words[(g0 >> 2) + w];
+        }
+        __syncthreads();
+        const int r = t & (UDH_CHUNK - 1);
+        if (r < rows) {
+            const size_t g0 = d.offset + ((size_t)(base + r) * d.W + x_lo) * 3;
+            const unsigned char* s8 = reinterpret_cast<const unsigned char*>(src + r * UDH_SRC_WORDS) + (g0 & 3);
+            unsigned char* m8 = mid8 + (base - y_lo + r) * (UDH_MID_WORDS * 4);
+            for (int c = t / UDH_CHUNK; c < tw; c += 256 / UDH_CHUNK) {
+                const unsigned char* q = s8 + (hx[c] - x_lo) * 3;
+                if (ksh) {
+                    const int n = hn[c];
+                    const int* k = hk + c * ksh;
+                    uint32_t a0 = 1u << 21, a1 = a0, a2 = a0;
+                    for (int j = 0; j < n; ++j) {
+                        const uint32_t kj = (uint32_t)k[j];
+                        a0 += q[3 * j] * kj; a1 += q[3 * j + 1] * kj; a2 += q[3 * j + 2] * kj;
+                    }
+                    m8[c * 3] = (unsigned char)min(max((int)a0 >> 22, 0), 255);
+                    m8[c * 3 + 1] = (unsigned char)min(max((int)a1 >> 22, 0), 255);
+                    m8[c * 3 + 2] = (unsigned char)min(max((int)a2 >> 22, 0), 255);
+                } else {
+                    m8[c * 3] = q[0]; m8[c * 3 + 1] = q[1]; m8[c * 3 + 2] = q[2];
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // 3. vertical pass, grey value, store
+    const int r = t / UDH_TILE, c = t % UDH_TILE;
+    const bool valid = r < th && c < tw;
+    const int rr = min(r, th - 1), cc = min(c, tw - 1);
+    const unsigned char* q = mid8 + (vx[rr] - y_lo) * (UDH_MID_WORDS * 4) + cc * 3;
+    int v[3];
+    if (ksv) {
+        const int n = vn[rr];
+        const int* k = vk + rr * ksv;
+        uint32_t a0 = 1u << 21, a1 = a0, a2 = a0;
+        for (int j = 0; j < n; ++j) {
+            const uint32_t kj = (uint32_t)k[j];
+            a0 += q[j * (UDH_MID_WORDS * 4)] * kj; a1 += q[j * (UDH_MID_WORDS * 4) + 1] * kj; a2 += q[j * (UDH_MID_WORDS * 4) + 2] * kj;
+        }
+        v[0] = min(max((int)a0 >> 22, 0), 255); v[1] = min(max((int)a1 >> 22, 0), 255); v[2] = min(max((int)a2 >> 22, 0), 255);
+    } else {
+        v[0] = q[0]; v[1] = q[1]; v[2] = q[2];
+    }
+    const float g = grey_value(v, mean, stdv);
+    const float g1 = __shfl_down(g, 1), g2 = __shfl_down(g, 2), g3 = __shfl_down(g, 3);      // every lane takes part
+    float* o = out + ((p * out_h + ty * UDH_TILE + r) * out_w + tx * UDH_TILE + c);
+    if (vec && r < th && (c | 3) < tw) {
+        if ((c & 3) == 0) *reinterpret_cast<float4*>(o) = make_float4(g, g1, g2, g3);
+    } else if (valid) {
+        *o = g;
+    }
+}
+
 // lanes of a row segment: the row's ceil(W / 4) lanes split evenly over the fewest workgroups, rounded up to whole wavefronts
 inline int pix_segment_lanes(int W) {
     const int lanes = ceil_div(W, 4);
@@ -386,4 +556,21 @@ extern "C" int masic_views_prep(const uint8_t* arena, size_t arena_bytes, const 
                            homopatch, nb, mean, stdv, patches);
     }
     return masic_launch_status("views_prep");
+}
+
+extern "C" int masic_udh_views_prep(const uint8_t* arena, size_t arena_bytes, const int32_t* tables, size_t table_words,
+                                    const masic_udh_view_desc_t* desc_dev, int P, int out_h, int out_w, int pic_size, float* out, void* stream) {
+    MASIC_REQUIRE(arena && desc_dev && out, MASIC_ERR_ARG, "udh_views_prep: null pointer");
+    MASIC_REQUIRE(tables || table_words == 0, MASIC_ERR_ARG, "udh_views_prep: %zu table words at a null pointer", table_words);
+    MASIC_REQUIRE(P > 0 && P <= 65535 && out_h > 0 && out_w > 0 && pic_size <= 16384 && out_h <= pic_size && out_w <= pic_size, MASIC_ERR_ARG,
+                  "udh_views_prep: %d views of %d x %d out of a %d x %d picture (1 .. 65535 views, no empty extent, at most the picture, the picture at most 16384)",
+                  P, out_h, out_w, pic_size, pic_size);
+    MASIC_REQUIRE(((size_t)arena & 3) == 0 && (arena_bytes & 3) == 0 && ((size_t)desc_dev & 7) == 0 && ((size_t)tables & 3) == 0 && ((size_t)out & 3) == 0,
+                  MASIC_ERR_ARG, "udh_views_prep: the arena, the tables and the output must be 4-byte aligned, the arena a multiple of 4 bytes long, the descriptors 8-byte aligned");
+    const int xt = ceil_div(out_w, UDH_TILE), yt = ceil_div(out_h, UDH_TILE), vec = out_w % 4 == 0 && ((size_t)out & 15) == 0;
+    MASIC_REQUIRE((long long)P * xt * yt <= 0x7fffffffLL, MASIC_ERR_ARG, "udh_views_prep: %d views of %d x %d are more than one grid", P, out_h, out_w);
+    const float mean = (0.485f + 0.456f + 0.406f) / 3.0f, stdv = (0.229f + 0.224f + 0.225f) / 3.0f;    // dataset.py:10-11, the scalars of utils.py:26-27
+    hipLaunchKernelGGL(udh_views_kernel, dim3((unsigned)(P * xt * yt)), dim3(256), 0, (hipStream_t)stream, arena, arena_bytes, tables, table_words,
+                       desc_dev, pic_size, out_h, out_w, xt, yt, vec, mean, stdv, out);
+    return masic_launch_status("udh_views_prep");
 }

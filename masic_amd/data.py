@@ -15,6 +15,9 @@ per-item chain.  Drawing a batch never waits for the device.
     for b in ds.batches(8):
         h = b.h_matrix(udh_net)
         train_step(model, opt, aux_opt, b.d1, b.d2, h, lmbda)
+
+The homography net itself trains on another item, that of udh/udh/dataset.py (PIL's antialiased Resize, CenterCrop, grey, one window):
+udh_batch / udh_batches cut it from the same arena (masic_amd/udh_data.py), with draws from a generator of their own.
 """
 import collections
 import glob
@@ -204,6 +207,10 @@ class DeviceStereoFolder:
             raise ValueError(f"homopatch {homopatch} of homopic {homopic}")
         self.max_bytes = int(max_bytes)
         self._rng = random.Random(seed)
+        self._udh_rng = random.Random(seed)      # the UDH batches' own stream: codec and UDH batches draw as if the other were absent
+        self._udh_seed = seed
+        self._udh_gen = None                     # torch.Generator of delta_gt, made when first asked for
+        self._udh_tables = {}                    # pic_size -> udh_data.UDHTables
 
     @staticmethod
     def _threads():
@@ -335,3 +342,75 @@ class DeviceStereoFolder:
             if len(chunk) < int(batch_size) and drop_last:
                 return
             yield self.batch(chunk)
+
+    # ---- the homography net's own training batches (udh/udh/dataset.py: SyntheticDataset)
+    def udh_draw(self, n, pic_size=256, patch_size=128, rho=45):
+        """The reference's window draws for n items from the dataset's UDH generator: [(x, y)] (udh_data.draw_udh_items)"""
+        from .udh_data import draw_udh_items
+        return draw_udh_items(self._udh_rng, n, pic_size, patch_size, rho)
+
+    def udh_tables(self, pic_size):
+        """The coefficient tables of this dataset's distinct picture sizes at pic_size, on the device; built on first use"""
+        from .udh_data import UDHTables
+        key = int(pic_size)
+        if key not in self._udh_tables:
+            self._udh_tables[key] = UDHTables(set(self.sizes), key, self.device)
+        return self._udh_tables[key]
+
+    def udh_batch(self, indices, draws=None, pic_size=256, patch_size=128, rho=45, want_img_b=False, want_delta_gt=False):
+        """UDHBatch of the items `indices`: what the reference's SyntheticDataset collates (masic_amd/udh_data.py), cut from the arena by
+        two launches of ops.udh_views_prep -- the B left views (2B with want_img_b) at pic_size x pic_size, then the 2B windows of
+        patch_size at (x, y); a right view never computes more than its window unless img_b is asked for.  Pictures of different
+        sizes may share a batch.  draws: [(x, y)] per item to place the windows by hand; by default they come from the dataset's UDH
+        generator, a random.Random(seed) of its own, so batch() / batches() draw exactly what they would without any UDH batch.
+        delta_gt (want_delta_gt) is the reference's unused supervised label, drawn on the CPU from a torch.Generator the dataset
+        owns.  Two small asynchronous copies (descriptors, corners) per batch; nothing waits for the device, except that the first
+        batch of a pic_size uploads the coefficient tables.  A greyscale or RGBA file deviates from the reference in the last bit
+        or more (udh_data's docstring): the arena holds three channels."""
+        import torch
+        from . import ops
+        from .udh_data import UDHBatch, corners_of, draw_delta_gt
+        indices = [int(i) for i in indices]
+        if not indices:
+            raise ValueError("an empty batch")
+        for i in indices:
+            if not 0 <= i < len(self):
+                raise IndexError(f"item {i} of a dataset of {len(self)} pairs")
+        S, p, rho = int(pic_size), int(patch_size), int(rho)
+        if not 0 < p <= S:
+            raise ValueError(f"patch_size {patch_size} of pic_size {pic_size}")
+        if draws is None:
+            draws = self.udh_draw(len(indices), S, p, rho)
+        if len(draws) != len(indices):
+            raise ValueError(f"{len(draws)} draws for {len(indices)} items")
+        draws = [(int(x), int(y)) for x, y in draws]
+        B = len(indices)
+        tables = self.udh_tables(S)                                   # ValueError for a picture scaled by more than 16
+        sizes = [self.sizes[i] for i in indices]
+        left, right = [int(self.offsets[i, 0]) for i in indices], [int(self.offsets[i, 1]) for i in indices]
+        with torch.cuda.device(self.device):
+            full = tables.rows(left + (right if want_img_b else []), sizes * (2 if want_img_b else 1), [(0, 0)] * (2 * B if want_img_b else B))
+            imgs = ops.udh_views_prep(self.arena, full, tables.words, (S, S), S)
+            patches = ops.udh_views_prep(self.arena, tables.rows(left + right, sizes * 2, draws * 2), tables.words, (p, p), S)
+            host = torch.empty((B, 4, 2), dtype=torch.float32, pin_memory=True)
+            host.numpy()[...] = corners_of(draws, p)
+            corners = host.to(self.device, non_blocking=True)
+            delta_gt = None
+            if want_delta_gt:
+                if self._udh_gen is None:
+                    self._udh_gen = torch.Generator().manual_seed(int(self._udh_seed))
+                delta_gt = draw_delta_gt(self._udh_gen, B, rho).pin_memory().to(self.device, non_blocking=True)
+        return UDHBatch(imgs[:B], imgs[B:] if want_img_b else None, patches[:B], patches[B:], corners, delta_gt, tuple(indices),
+                        tuple(self.names[i] for i in indices))
+
+    def udh_batches(self, batch_size, shuffle=True, drop_last=True, **kw):
+        """One epoch of UDH batches: every index once, in an order taken from the dataset's UDH generator (as it is if shuffle is False);
+        kw: udh_batch's pic_size, patch_size, rho, want_img_b, want_delta_gt"""
+        order = list(range(len(self)))
+        if shuffle:
+            self._udh_rng.shuffle(order)
+        for i in range(0, len(order), int(batch_size)):
+            chunk = order[i:i + int(batch_size)]
+            if len(chunk) < int(batch_size) and drop_last:
+                return
+            yield self.udh_batch(chunk, **kw)

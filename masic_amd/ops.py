@@ -530,6 +530,95 @@ def views_prep(arena, desc, crop_hw, homopic=256, homopatch=128, planes=None, pa
     return PairsPrep(planes, patches)
 
 
+UDH_VIEW_DESC_FIELDS = ("offset", "W", "H", "h_table", "v_table", "h_ksize", "v_ksize", "x0", "y0")      # masic_udh_view_desc_t, in its order
+_UDH_VIEW_DESC = None
+
+
+def _udh_view_desc_dtype():
+    global _UDH_VIEW_DESC
+    if _UDH_VIEW_DESC is None:
+        import numpy as np
+        kinds = {"offset": "<u8", "h_table": "<u4", "v_table": "<u4"}
+        _UDH_VIEW_DESC = np.dtype([(n, kinds.get(n, "<i4")) for n in UDH_VIEW_DESC_FIELDS])
+        assert _UDH_VIEW_DESC.itemsize == 40
+    return _UDH_VIEW_DESC
+
+
+def check_udh_view_descriptors(desc, arena_bytes, table_words, out_hw, pic_size):
+    """The host check masic_udh_views_prep asks of its caller: every row of desc (integers [P,9] in the order of UDH_VIEW_DESC_FIELDS)
+    names a picture inside the arena, a rectangle of out_hw inside the pic_size x pic_size picture, the ksize its sizes give per axis
+    (udh_data.resize_geometry / axis_ksize; 0 for an axis that keeps its size) and, for each axis that is resized, a table of
+    pic_size * (2 + ksize) words inside table_words.  Returns desc as int64 [P,9].  A scale above 16 raises ValueError (the kernel
+    does not serve it), any other bad row RuntimeError naming the first one."""
+    import numpy as np
+    from .udh_data import axis_ksize, resize_geometry
+    d = np.asarray(desc)
+    if d.ndim != 2 or d.shape[1] != 9 or d.shape[0] < 1 or d.dtype.kind not in "iu":
+        raise RuntimeError("masic_amd.udh_views_prep: the descriptors must be integers [P,9] (" + ", ".join(UDH_VIEW_DESC_FIELDS) + "), P >= 1")
+    d = d.astype(np.int64)
+    oh, ow, S = int(out_hw[0]), int(out_hw[1]), int(pic_size)
+    lim = 1 << 24
+    ksizes = {}
+    for p in range(d.shape[0]):
+        off, W, H, ht, vt, ksh, ksv, x0, y0 = (int(v) for v in d[p])
+        bad = off < 0 or off % 16 != 0 or not (0 < W < lim and 0 < H < lim) or off + H * W * 3 > int(arena_bytes)
+        bad = bad or x0 < 0 or y0 < 0 or x0 + ow > S or y0 + oh > S
+        if not bad:
+            if (H, W) not in ksizes:
+                (rh, rw), _ = resize_geometry((H, W), S)            # ValueError: a scale above 16
+                ksizes[(H, W)] = (axis_ksize(W, rw), axis_ksize(H, rh))
+            want = ksizes[(H, W)]
+            bad = (ksh, ksv) != want
+            for t, ks in ((ht, ksh), (vt, ksv)):
+                bad = bad or (ks != 0 and (t < 0 or t + S * (2 + ks) > int(table_words)))
+        if bad:
+            what = ", ".join(f"{n} {int(v)}" for n, v in zip(UDH_VIEW_DESC_FIELDS, d[p]))
+            raise RuntimeError(f"masic_amd.udh_views_prep: view {p} ({what}) does not fit: rectangle {oh} x {ow} of {S} x {S}, arena of "
+                               f"{int(arena_bytes)} bytes, pictures at multiples of 16, {int(table_words)} table words")
+    return d
+
+
+def pack_udh_view_descriptors(d):
+    """checked descriptors int64 [P,9] -> the P masic_udh_view_desc_t records as int32 [P,10]"""
+    import numpy as np
+    rec = np.empty(d.shape[0], dtype=_udh_view_desc_dtype())
+    for i, n in enumerate(UDH_VIEW_DESC_FIELDS):
+        rec[n] = np.where(d[:, i] < 0, 0, d[:, i]) if n.endswith("_table") else d[:, i]
+    return rec.view(np.int32).reshape(d.shape[0], 10)
+
+
+def udh_views_prep(arena, desc, tables, out_hw, pic_size, out=None):
+    """P views of the homography net's training batch out of an arena of decoded pictures (masic_amd/udh_data.py; include/masic_hip.h:
+    masic_udh_views_prep) -> float32 [P,1,out_h,out_w]: the rectangle at (x0, y0) of the grey pic_size x pic_size picture
+    mean_c(Normalize(ToTensor(CenterCrop(Resize(picture))))), Resize with the bits of PIL's antialiased bilinear.  arena: uint8 1-D
+    device tensor, a multiple of 4 bytes.  tables: int32 1-D device tensor (udh_data.UDHTables.words).  desc: integers [P,9] on the HOST
+    in the order of UDH_VIEW_DESC_FIELDS; every row is checked here before anything is launched (outputs untouched).  The rows reach the
+    device through pinned memory by an asynchronous copy on the current stream: nothing waits for the device."""
+    if not (isinstance(arena, torch.Tensor) and arena.is_cuda and arena.dtype == torch.uint8 and arena.dim() == 1 and arena.is_contiguous()):
+        raise RuntimeError("masic_amd.udh_views_prep: the arena must be a contiguous uint8 1-D CUDA (HIP) tensor -- the MI355X path has no CPU fallback")
+    if arena.numel() % 4 or arena.data_ptr() % 4:
+        raise RuntimeError("masic_amd.udh_views_prep: the arena must be 4-byte aligned and a multiple of 4 bytes long")
+    if not (isinstance(tables, torch.Tensor) and tables.dtype == torch.int32 and tables.dim() == 1 and tables.is_contiguous()
+            and tables.device == arena.device and tables.numel() >= 1):
+        raise RuntimeError("masic_amd.udh_views_prep: the tables must be a contiguous int32 1-D tensor on the arena's device")
+    oh, ow, S = int(out_hw[0]), int(out_hw[1]), int(pic_size)
+    if oh < 1 or ow < 1 or S < max(oh, ow) or S > 16384:
+        raise RuntimeError(f"masic_amd.udh_views_prep: rectangle {oh} x {ow} of a {S} x {S} picture (at most 16384)")
+    d = check_udh_view_descriptors(desc, arena.numel(), tables.numel(), (oh, ow), S)
+    P = d.shape[0]
+    if P > 65535:
+        raise RuntimeError(f"masic_amd.udh_views_prep: {P} views in one call (at most 65535)")
+    if out is not None and (_dev(out, "out").device != arena.device or tuple(out.shape) != (P, 1, oh, ow)):
+        raise RuntimeError(f"masic_amd.udh_views_prep: out must be {(P, 1, oh, ow)} on the arena's device")
+    if out is None:
+        out = torch.empty((P, 1, oh, ow), dtype=torch.float32, device=arena.device)
+    host = torch.empty((P, 10), dtype=torch.int32, pin_memory=True)      # (torch's pinned allocator keeps the block until the copy has run)
+    host.numpy()[...] = pack_udh_view_descriptors(d)
+    table = host.to(arena.device, non_blocking=True)
+    check(lib.masic_udh_views_prep(_p(arena), arena.numel(), _p(tables), tables.numel(), _p(table), P, oh, ow, S, _p(out), _stream()), "udh_views_prep")
+    return out
+
+
 def homography_from_corners(corners, delta, ori_hw, patch_hw):
     """h_matrix [B,3,3] of udh/udh/model.py:100-111 + h_adjust (newtrain_codec_real.py:49-59, :129) from the patch corners
     [B,4,2] and the predicted offsets [B,4,2]; ori_hw = picture size, patch_hw = the size the homography net saw."""
