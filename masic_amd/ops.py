@@ -453,7 +453,7 @@ def planes_to_u8(x, out_hw):
     return out
 
 
-VIEW_DESC_FIELDS = ("offset", "W", "H", "start_h", "start_w", "patch_x", "patch_y")      # masic_view_desc_t, in its order
+VIEW_DESC_FIELDS = tuple(n for n, _ in _lib.STRUCTS["masic_view_desc_t"]._fields_)      # masic_view_desc_t, in its order
 _VIEW_DESC = None
 
 
@@ -461,7 +461,7 @@ def _view_desc_dtype():
     global _VIEW_DESC
     if _VIEW_DESC is None:
         import numpy as np
-        _VIEW_DESC = np.dtype([("offset", "<u8")] + [(n, "<i4") for n in VIEW_DESC_FIELDS[1:]])
+        _VIEW_DESC = np.dtype(_lib.STRUCTS["masic_view_desc_t"])
         assert _VIEW_DESC.itemsize == 32
     return _VIEW_DESC
 
@@ -530,7 +530,7 @@ def views_prep(arena, desc, crop_hw, homopic=256, homopatch=128, planes=None, pa
     return PairsPrep(planes, patches)
 
 
-UDH_VIEW_DESC_FIELDS = ("offset", "W", "H", "h_table", "v_table", "h_ksize", "v_ksize", "x0", "y0")      # masic_udh_view_desc_t, in its order
+UDH_VIEW_DESC_FIELDS = tuple(n for n, _ in _lib.STRUCTS["masic_udh_view_desc_t"]._fields_)      # masic_udh_view_desc_t, in its order
 _UDH_VIEW_DESC = None
 
 
@@ -538,8 +538,7 @@ def _udh_view_desc_dtype():
     global _UDH_VIEW_DESC
     if _UDH_VIEW_DESC is None:
         import numpy as np
-        kinds = {"offset": "<u8", "h_table": "<u4", "v_table": "<u4"}
-        _UDH_VIEW_DESC = np.dtype([(n, kinds.get(n, "<i4")) for n in UDH_VIEW_DESC_FIELDS])
+        _UDH_VIEW_DESC = np.dtype(_lib.STRUCTS["masic_udh_view_desc_t"])
         assert _UDH_VIEW_DESC.itemsize == 40
     return _UDH_VIEW_DESC
 
