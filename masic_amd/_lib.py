@@ -26,19 +26,19 @@ _SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_dou
             "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
 
 
-def _ctype(decl, structs, what, named=True, void_ok=False):
+def _ctype(decl, structs, what, named=True, void_ok=False, header="masic_hip.h"):
     """ctypes type of one C declarator: 'const float* const* liks', 'int32_t B', a return type (named=False)"""
     words = [t for t in decl.replace("*", " ").split() if t != "const"]
     stars = decl.count("*")
     name = words.pop() if named and words else "_"
     base = " ".join(words)
     if not name.isidentifier() or not (base in _SCALARS or base in structs or base == "void"):
-        raise ValueError(f"masic_hip.h: unknown type in '{' '.join(decl.split())}' of {what}")
+        raise ValueError(f"{header}: unknown type in '{' '.join(decl.split())}' of {what}")
     if stars == 0:
         if base == "void" and void_ok:
             return None
         if base not in _SCALARS:
-            raise ValueError(f"masic_hip.h: '{' '.join(decl.split())}' of {what} is passed by value")
+            raise ValueError(f"{header}: '{' '.join(decl.split())}' of {what} is passed by value")
         return _SCALARS[base]
     if stars == 1 and base == "char":
         return ctypes.c_char_p
@@ -47,9 +47,10 @@ def _ctype(decl, structs, what, named=True, void_ok=False):
     return ctypes.c_void_p
 
 
-def parse_header(text):
+def parse_header(text, header="masic_hip.h"):
     """(signatures {name: (restype, [argtypes])}, constants {name: int}, structs {C name: Structure class}) of a C header
-    written as include/masic_hip.h is; ValueError naming the declaration for anything else."""
+    written as include/masic_hip.h is; ValueError naming the declaration for anything else.  `header`: the name its messages start
+    with (a second header of the library, include/masic_align.h, is parsed by masic_amd/align.py)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     constants, structs, signatures = {}, {}, {}
 
@@ -57,7 +58,7 @@ def parse_header(text):
         name, value = m.group(1), m.group(2).strip()
         if value:
             if not name.startswith("MASIC_") or not re.fullmatch(r"-?\d+", value):
-                raise ValueError(f"masic_hip.h: #define {name} {value} is not MASIC_<NAME> <integer>")
+                raise ValueError(f"{header}: #define {name} {value} is not MASIC_<NAME> <integer>")
             constants[name[6:]] = int(value)
         return " "
 
@@ -66,7 +67,7 @@ def parse_header(text):
         for item in filter(None, (s.strip() for s in m.group(1).split(","))):
             e = re.fullmatch(r"MASIC_(\w+)(?:\s*=\s*(-?\d+))?", item)
             if not e:
-                raise ValueError(f"masic_hip.h: enumerator '{item}' is not MASIC_<NAME> [= <integer>]")
+                raise ValueError(f"{header}: enumerator '{item}' is not MASIC_<NAME> [= <integer>]")
             nxt = constants[e.group(1)] = int(e.group(2)) if e.group(2) else nxt
             nxt += 1
         return " "
@@ -75,13 +76,13 @@ def parse_header(text):
         name, fields = m.group(2), []
         for line in filter(None, (s.strip() for s in m.group(1).split(";"))):
             first, *more = line.split(",")
-            ctype = _ctype(first, structs, f"struct {name}")
+            ctype = _ctype(first, structs, f"struct {name}", header=header)
             if "*" in line:
                 ctype = ctypes.c_void_p
             for n in [first] + more:
                 n = n.replace("*", " ").split()
                 if not n or not re.fullmatch(r"[A-Za-z_]\w*", n[-1]) or ("*" in line and more):
-                    raise ValueError(f"masic_hip.h: field '{line}' of struct {name}")
+                    raise ValueError(f"{header}: field '{line}' of struct {name}")
                 fields.append((n[-1], ctype))
         structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": name})
         return " "
@@ -93,7 +94,7 @@ def parse_header(text):
     text = re.sub(r"\btypedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
     def unparsed(s):
         name = re.search(r"\bmasic_\w+(?=\s*\()", s)
-        return ValueError("masic_hip.h: cannot parse " + (f"the declaration of {name.group(0)}" if name else f"'{' '.join(s.split())[:80]}'"))
+        return ValueError(f"{header}: cannot parse " + (f"the declaration of {name.group(0)}" if name else f"'{' '.join(s.split())[:80]}'"))
 
     *statements, tail = text.split(";")                 # what is left: prototypes, each up to its semicolon
     if tail.strip():
@@ -103,8 +104,8 @@ def parse_header(text):
         if not m:
             raise unparsed(s)
         name, params = m.group(2), m.group(3).strip()
-        args = [] if params == "void" else [_ctype(p, structs, name) for p in params.split(",")]
-        signatures[name] = (_ctype(m.group(1), structs, name, named=False, void_ok=True), args)
+        args = [] if params == "void" else [_ctype(p, structs, name, header=header) for p in params.split(",")]
+        signatures[name] = (_ctype(m.group(1), structs, name, named=False, void_ok=True, header=header), args)
     return signatures, constants, structs
 
 

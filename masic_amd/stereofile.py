@@ -126,7 +126,8 @@ def _inner_names(names):
 
 class StereoCodec:
     """encode: B stereo pairs of 8-bit pictures -> B .msf files; decode: the files -> the pictures, from nothing but the files and the
-    weights.  hsic (MASIC.HSIC), udh (model.Net, patch size 128; needed by encode only) and cqe (MASIC.Independent_EN; needed for
+    weights.  hsic (MASIC.HSIC), udh (any eval-mode module mapping two patches to `delta`: model.Net at patch size 128, or
+    masic_amd.align.PatchAligner, which needs no weights; needed by encode only) and cqe (MASIC.Independent_EN; needed for
     decode(enhance=True) only) are modules of this tree on one MI355X device, in eval mode.  The operand mode is
     masic_amd.nn.set_precision's, as for HSIC.compress; the file records it."""
 
