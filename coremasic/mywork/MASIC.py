@@ -32,6 +32,7 @@ from masic_amd.homography import warp_matrices as _warp_matrices
 from masic_amd import autograd as _ag
 from masic_amd.streams import ForkJoin as _ForkJoin
 from masic_amd import fp8 as _fp8
+from masic_amd import deconv as _deconv
 
 _RELU, _LEAKY, _NONE = _hip.ACT_RELU, _hip.ACT_LEAKY, _hip.ACT_NONE
 _CAT_F16K = True           # F16K concat buffers in front of the heads; tests set False for the float32 concat as their reference
@@ -471,7 +472,11 @@ def _synthesis_f16k(dec, y_hat, y16=None, shape=None):
         t16, _, _ = convs[2].run_f8k(t8, sc["d2"], B, *sizes[2], gdn=gdns[2], out="f16k")
         return dec.g_s_conv4.run_f16k_d2s(t16, B, *sizes[3])
     for i in range(3):
-        t16, _, _ = convs[i].run_f16k(t16, B, *sizes[i], gdn=gdns[i])
+        # g_s_conv2 / g_s_conv3 (128 -> 128): deconv_igdn_f16k, the layer's own kernel; conv_f16k's packs, conv_f16k's bits
+        if _deconv.supported(convs[i], gdns[i], B, *sizes[i]):
+            t16, _, _ = _deconv.run(convs[i], gdns[i], t16, B, *sizes[i])
+        else:
+            t16, _, _ = convs[i].run_f16k(t16, B, *sizes[i], gdn=gdns[i])
         if i < 2:
             _fp8.record(dec, "d%d" % (i + 1), t16)
     return dec.g_s_conv4.run_f16k_d2s(t16, B, *sizes[3])

@@ -173,8 +173,11 @@ __device__ __forceinline__ void dma_buf16(__amdgpu_buffer_rsrc_t r, unsigned cha
 // gimg: LDS address of the fragment image + lane * 16;  bet: LDS address of beta^[128] + 4h (read late: no registers held).
 // X3 = false: one product (bf16 gamma^ x bf16 x^2, error ~2^-10 of the result -- the order of the bf16 rounding the result gets
 // anyway when it is stored as F16K / fed to a bf16-operand layer): a third of the MFMAs, half the fragment reads, no lo split.
-template <bool X3>
+// PS: bytes between the hi pieces of consecutive (m, k-step) pairs -- 2048 for the image as gdn_pack_f16k_kernel lays it out (hi and lo
+// pieces alternate), 1024 for a copy that holds the hi pieces alone (one-product form only).
+template <bool X3, int PS = 2048>
 __device__ __forceinline__ void gdn_in_registers(f32x16 (&acc)[4], const unsigned char* gimg, const float* bet, int inverse) {
+    static_assert(PS == 2048 || (PS == 1024 && !X3), "a hi-only image serves the one-product form");
     f32x16 nrm[4];
 #pragma unroll
     for (int m = 0; m < 4; ++m)
@@ -193,9 +196,9 @@ __device__ __forceinline__ void gdn_in_registers(f32x16 (&acc)[4], const unsigne
         }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            const bf16x8 gh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(gimg + ((m * 8 + sx) * 2 + 0) * 1024));
+            const bf16x8 gh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(gimg + (m * 8 + sx) * PS));
             if constexpr (X3) {
-                const bf16x8 gl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(gimg + ((m * 8 + sx) * 2 + 1) * 1024));
+                const bf16x8 gl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(gimg + (m * 8 + sx) * PS + 1024));
                 nrm[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl, bh, nrm[m], 0, 0, 0);
                 nrm[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, blo, nrm[m], 0, 0, 0);
             }
