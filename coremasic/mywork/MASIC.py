@@ -33,6 +33,7 @@ from masic_amd import autograd as _ag
 from masic_amd.streams import ForkJoin as _ForkJoin
 from masic_amd import fp8 as _fp8
 from masic_amd import deconv as _deconv
+from masic_amd.f16k import F16K as _F16K, F8K as _F8K
 
 _RELU, _LEAKY, _NONE = _hip.ACT_RELU, _hip.ACT_LEAKY, _hip.ACT_NONE
 _CAT_F16K = True           # F16K concat buffers in front of the heads; tests set False for the float32 concat as their reference
@@ -140,11 +141,7 @@ def _keep_until(t, stream):
     """Tensor.record_stream for a tensor used on another stream than the one it was allocated on.  Skipped inside a HIP-graph
     capture: there every cross-stream tensor of the forward lives until all streams have joined the capturing one (and
     record_stream with a non-capturing-origin stream ends torch's capture with a fault on this ROCm)."""
-    if isinstance(t, (tuple, list)):              # (F16K buffer, channels) pairs
-        for e in t:
-            _keep_until(e, stream)
-        return
-    if not torch.is_tensor(t):
+    if not (torch.is_tensor(t) or isinstance(t, _F16K)):
         return
     if not torch.cuda.is_current_stream_capturing():
         t.record_stream(stream)
@@ -158,27 +155,21 @@ def _bf16_inference(*tensors):
     return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
 
 
-def _f16k_chain(convs, acts, x, in_op=0, out=None, out_coff=0, gate=None, gate_c=0, out16=None, x16=None, shape=None):
-    """A chain of convolutions on the float32 NCHW tensor `x` with the activations between them in F16K bf16
-    (conv_f16k.hip); |x| / round(x) is applied while converting the input -- or x16 IS that converted input already (written by
-    the layer that produced x, Encoder1.latent_layouts), and x only gives the shape (or is None, with `shape` = its [B, C, H, W]). The last layer writes float32 NCHW (a channel
-    view of `out`, optionally gated) -- or, with out16 = (F16K buffer, its channel count), the same view of an F16K concat buffer.
-    None if a layer shape has no F16K configuration."""
-    B, C, H, W = x.shape if shape is None else shape
-    sizes = [(H, W)]
+def _f16k_chain(convs, acts, x, in_op=0, out=None, out_coff=0, gate=None, gate_c=0):
+    """A chain of convolutions with the activations between them in F16K bf16 (conv_f16k.hip).  x: a float32 NCHW tensor -- |x| /
+    round(x) is applied while converting it -- or the F16K that already holds that converted input (written by the layer that produced
+    it, Encoder1.latent_layouts).  The last layer writes float32 NCHW (channels out_coff.. of the concat buffer `out`, optionally gated)
+    -- or, with `out` an F16K view of a concat buffer, that view.  None if a layer shape has no F16K configuration."""
+    B, _, H, W = x.shape
+    hw = (H, W)
     for cv in convs:
-        if not cv.f16k_supported(B, *sizes[-1]):
+        if not cv.f16k_supported(B, *hw):
             return None
-        d = cv._desc_f16k(B, *sizes[-1])
-        sizes.append((d.Ho, d.Wo))
-    t = x16 if x16 is not None else _hip.nchw_to_f16k(x, in_op=in_op)
-    last = len(convs) - 1
-    for i, (cv, act) in enumerate(zip(convs, acts)):
-        if i == last:
-            if out16 is not None:
-                return cv.run_f16k(t, B, *sizes[i], act=act, out_coff=out_coff, gate=gate, gate_c=gate_c, out16=out16[0], out16_ctot=out16[1])[0]
-            return cv.run_f16k(t, B, *sizes[i], act=act, want_nchw=out is None, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)[0]
-        t = cv.run_f16k(t, B, *sizes[i], act=act)[0]
+        hw = cv.out_hw(*hw)
+    t = x if isinstance(x, _F16K) else _F16K.from_nchw(x, in_op=in_op)
+    for cv, act in zip(convs[:-1], acts):
+        t = cv.run_f16k(t, act=act)
+    return convs[-1].run_f16k(t, act=acts[-1], want_nchw=out is None, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
 
 
 def _pair_conv(conv, xa, xb, gdn_in=None, gdn_out=None):
@@ -197,8 +188,8 @@ def _gdn_f16k(gdn, x):
     return _hip.gdn_f16k(x, gdn.beta.detach(), gdn.gamma.detach(), inverse=gdn.inverse, beta_min=gdn.beta_min)
 
 
-def _analysis_f16k(owner, convs, gdns, x, layouts=None):
-    """conv+GDN x3 -> conv of an analysis transform on the float32 NCHW image `x` with bf16 operands: every GDN runs in
+def _analysis_f16k(owner, x, layouts=None):
+    """conv+GDN x3 -> conv of the analysis transform `owner` on the float32 NCHW image `x` with bf16 operands: every GDN runs in
     the epilogue of the convolution that feeds it and the 128-channel activations stay in F16K bf16 in between
     (conv_f16k.hip). None if a shape has no such configuration (the caller then takes the NCHW path).
     layouts (keyword arguments of Conv2d.run_f16k_multi): the last layer writes the latent once in every layout its consumers read
@@ -207,6 +198,8 @@ def _analysis_f16k(owner, convs, gdns, x, layouts=None):
     fp8 mode (masic_amd/fp8.py; `owner` calibrated): the two 128 -> 128 layers take fp8 operands -- the first layer and the
     second write F8K, the third writes F16K for the latent-producing last layer, which stays bf16."""
     from masic_amd import nn as _mnn
+    convs = (owner.g_a_conv1, owner.g_a_conv2, owner.g_a_conv3, owner.g_a_conv4)
+    gdns = (owner.g_a_gdn1, owner.g_a_gdn2, owner.g_a_gdn3)
     B, C, H, W = x.shape
     c1 = convs[0]
     if (C, c1.out_channels, tuple(c1.kernel_size), tuple(c1.stride), tuple(c1.padding)) != (3, 128, (5, 5), (2, 2), (2, 2)):
@@ -215,8 +208,7 @@ def _analysis_f16k(owner, convs, gdns, x, layouts=None):
     for cv in convs[1:]:
         if not cv.f16k_supported(B, *sizes[-1]):
             return None
-        d = cv._desc_f16k(B, *sizes[-1])
-        sizes.append((d.Ho, d.Wo))
+        sizes.append(cv.out_hw(*sizes[-1]))
     if convs[1].out_channels != 128 or convs[2].out_channels != 128:
         return None
     b1 = None if c1.bias is None else c1.bias.detach()
@@ -224,18 +216,18 @@ def _analysis_f16k(owner, convs, gdns, x, layouts=None):
     if layouts is not None and (sc is not None or _mnn._FP8 or _fp8.recording() or not convs[3].f16k_multi_supported(B, *sizes[2])):
         return None
     if sc is not None and convs[1].f8k_supported(B, *sizes[0]) and convs[2].f8k_supported(B, *sizes[1]):
-        t8, _, _ = _hip.conv_a_gdn_f8k(x, c1.packed_first_layer_weight(), b1, (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse), sc["a1"])
-        t8, _, _ = convs[1].run_f8k(t8, sc["a1"], B, *sizes[0], gdn=gdns[1], out="f8k", out_scale=sc["a2"])
-        t16, _, _ = convs[2].run_f8k(t8, sc["a2"], B, *sizes[1], gdn=gdns[2], out="f16k")
-        return convs[3].run_f16k(t16, B, *sizes[2], want_nchw=True)[0]
-    t16, _, _ = _hip.conv_a_gdn_f16k(x, c1.packed_first_layer_weight(), b1, (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse))
-    _fp8.record(owner, "a1", t16)
-    t16, _, _ = convs[1].run_f16k(t16, B, *sizes[0], gdn=gdns[1])
-    _fp8.record(owner, "a2", t16)
-    t16, _, _ = convs[2].run_f16k(t16, B, *sizes[1], gdn=gdns[2])
+        t8 = _hip.conv_a_gdn_f8k(x, c1.packed_first_layer_weight(), b1, (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse), sc["a1"])[0]
+        t = convs[1].run_f8k(_F8K(t8, B, 128, *sizes[0], sc["a1"]), gdn=gdns[1], out="f8k", out_scale=sc["a2"])
+        t = convs[2].run_f8k(t, gdn=gdns[2], out="f16k")
+        return convs[3].run_f16k(t, want_nchw=True)
+    t = _F16K(_hip.conv_a_gdn_f16k(x, c1.packed_first_layer_weight(), b1, (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse))[0], B, 128, *sizes[0], 128, 0)
+    _fp8.record(owner, "a1", t.buf)
+    t = convs[1].run_f16k(t, gdn=gdns[1])
+    _fp8.record(owner, "a2", t.buf)
+    t = convs[2].run_f16k(t, gdn=gdns[2])
     if layouts is not None:
-        return convs[3].run_f16k_multi(t16, B, *sizes[2], **layouts)
-    return convs[3].run_f16k(t16, B, *sizes[2], want_nchw=True)[0]
+        return convs[3].run_f16k_multi(t, **layouts)
+    return convs[3].run_f16k(t, want_nchw=True)
 
 
 # ------------------------------------------------------------------------------------------ sub-networks
@@ -250,10 +242,10 @@ class encode_hyper(nn.Module):
             conv(N, N, kernel_size=5))
 
     def forward(self, y, abs16=None):
-        """abs16: bf16(|y|) in F16K, where the layer that produced y wrote it (the bf16 eval forward)."""
+        """abs16: bf16(|y|) as an F16K, where the layer that produced y wrote it (the bf16 eval forward)."""
         s = self.encode_hyper
         if _bf16_inference(y, s[0].weight):
-            z = _f16k_chain((s[0], s[2], s[4]), (_RELU, _RELU, _NONE), y, in_op=_hip.INOP_ABS, x16=abs16)
+            z = _f16k_chain((s[0], s[2], s[4]), (_RELU, _RELU, _NONE), y if abs16 is None else abs16, in_op=_hip.INOP_ABS)
             if z is not None:
                 return z
         t = s[0].run(y, in_op=_hip.INOP_ABS, act=_RELU)
@@ -269,9 +261,9 @@ class _GmmHeads(nn.Module):
         t = seq[2].run(t, act=acts[1])
         return seq[4].run(t, act=acts[2])
 
-    def _branch_f16k(self, seq, xf, B, H, W, acts):
-        """The same three layers as bf16 GEMMs; activations between them stay in the F16K layout on the device."""
-        t = xf
+    def _branch_f16k(self, seq, x, acts):
+        """The same three layers as bf16 GEMMs on the whole F16K x; activations between them stay in the F16K layout on the device."""
+        t, (B, _, H, W) = x.buf, x.shape
         for i, (layer, act) in enumerate(zip((seq[0], seq[2], seq[4]), acts)):
             last = i == 2
             if layer.in_channels % 16 == 0 and layer.out_channels % 32 == 0:          # both operands staged by DMA
@@ -282,10 +274,11 @@ class _GmmHeads(nn.Module):
                                       H, W, act, want_nchw=last)
         return t
 
-    def _branch_f8k(self, seq, x8, sc, tag, B, H, W, acts):
-        """fp8 mode: the first two layers with fp8 operands (F8K in; the first writes F8K, the second F16K), the last -- the one
+    def _branch_f8k(self, seq, x, sc, tag, acts):
+        """fp8 mode: the first two layers with fp8 operands (x an F8K; the first writes F8K, the second F16K), the last -- the one
         that produces sigma / means / weight logits -- with bf16 operands."""
         l0, l1, l2 = seq[0], seq[2], seq[4]
+        x8, (B, _, H, W) = x.buf, x.shape
         wp, ws = l0.packed_gemm_f8k_weight(sc["c"])
         t = _hip.gemm_f8k(x8, wp, ws, l0.bias.detach(), B, l0.in_channels, l0.out_channels, H, W, acts[0], out="f8k", out_scale=sc[tag])
         wp, ws = l1.packed_gemm_f8k_weight(sc[tag])
@@ -299,10 +292,12 @@ class _GmmHeads(nn.Module):
         return all(getattr(self, n)[i].in_channels % 16 == 0 and getattr(self, n)[i].out_channels % 32 == 0
                    for n, _, _ in self._STACKS for i in (0, 2, 4))
 
-    def _heads_grouped(self, xf, sc, B, H, W):
-        """sigma, means, weight logits with layer i of the three stacks in one launch each (_hip.gemm_f16k_group); sc: the fp8
-        scales of this head (first two layers with fp8 operands, as _branch_f8k) or None (bf16 operands, as _branch_f16k)."""
-        t = [xf, xf, xf]
+    def _heads_grouped(self, x, sc):
+        """sigma, means, weight logits with layer i of the three stacks in one launch each (_hip.gemm_f16k_group); x: the whole F16K
+        input and sc None (bf16 operands, as _branch_f16k), or an F8K and the fp8 scales of this head (first two layers with fp8
+        operands, as _branch_f8k)."""
+        B, _, H, W = x.shape
+        t = [x.buf] * 3
         for i in range(3):
             layers = []
             for k, (name, tag, acts) in enumerate(self._STACKS):
@@ -323,24 +318,26 @@ class _GmmHeads(nn.Module):
         return all(seq[i].in_channels % 32 == 0 and seq[i].out_channels % 32 == 0 for seq in (self.gmm_sigma, self.gmm_means, self.gmm_weights) for i in (0, 2)) \
             and all(seq[4].in_channels % 16 == 0 and seq[4].out_channels % 32 == 0 for seq in (self.gmm_sigma, self.gmm_means, self.gmm_weights))
 
-    def heads(self, x, parallel=True, x16=None):
-        """parallel: the means / weights stacks on two side streams forked from the current one.  Callers that are themselves on
+    def heads(self, x, parallel=True):
+        """x: float32 NCHW, or the concat as a whole F16K (HSIC's bf16 eval forward builds it there).
+        parallel: the means / weights stacks on two side streams forked from the current one.  Callers that are themselves on
         a side stream pass False: a side stream that forks further streams (or a stream waiting for its own event) ends a
         HIP-graph capture on this ROCm with a fault in hipStreamEndCapture (measured; torch 2.10 / ROCm 7)."""
         from masic_amd import nn as _mnn
-        if x16 is not None:                # the input as an F16K buffer (x = its shape): HSIC's bf16 eval forward builds the concat there
-            B, _, H, W = x
-            return self._heads_grouped(x16, None, B, H, W)
+        if isinstance(x, _F16K):
+            if not x.whole:
+                raise RuntimeError(f"_GmmHeads.heads: the grouped GEMMs read a whole buffer, not {x!r}")
+            return self._heads_grouped(x, None)
         if _mnn.reduced_precision() and not (torch.is_grad_enabled() and (x.requires_grad or self.gmm_sigma[0].weight.requires_grad)):
             B, _, H, W = x.shape
             sc = _fp8.scales(self)
             use_f8 = sc is not None and self._f8k_heads_ok()
             if use_f8:
-                x8 = _hip.nchw_to_f8k(x, sc["c"])          # quantised once, read by the three stacks
-                branch = lambda seq, tag, acts: self._branch_f8k(seq, x8, sc, tag, B, H, W, acts)
-                xf = x8
+                xv = _F8K(_hip.nchw_to_f8k(x, sc["c"]), *x.shape, sc["c"])          # quantised once, read by the three stacks
+                branch = lambda seq, tag, acts: self._branch_f8k(seq, xv, sc, tag, acts)
             else:
-                xf = _hip.nchw_to_f16k(x)        # converted once, read by the three stacks
+                xv = _F16K.from_nchw(x)          # converted once, read by the three stacks
+                xf = xv.buf
 
                 def branch(seq, tag, acts):
                     if _fp8.recording():
@@ -349,10 +346,10 @@ class _GmmHeads(nn.Module):
                         _fp8.record(self, tag, _hip.gemm_f16k(xf, l0.packed_gemm_dma_weight(), l0.bias.detach(), B, l0.in_channels, l0.out_channels, H, W, acts[0])
                                     if l0.in_channels % 16 == 0 and l0.out_channels % 32 == 0 else
                                     _hip.gemm1x1_bf16(xf, l0.packed_gemm_weight(), l0.bias.detach(), B, l0.in_channels, l0.out_channels, H, W, acts[0]))
-                    return self._branch_f16k(seq, xf, B, H, W, acts)
+                    return self._branch_f16k(seq, xv, acts)
             # layer i of the three stacks as ONE launch (640 ... 864 workgroups instead of 3 x 192 ... 288): no streams needed
             if _HEADS_GROUPED and not _fp8.recording() and self._grouped_heads_ok():
-                return self._heads_grouped(xf, sc if use_f8 else None, B, H, W)
+                return self._heads_grouped(xv, sc if use_f8 else None)
             # the three stacks are independent and each of their GEMMs fills about one wave of workgroups: run them on
             # three HIP streams so that their tails overlap
             if not parallel:
@@ -371,7 +368,7 @@ class _GmmHeads(nn.Module):
             outs[0] = branch(self.gmm_sigma, "h_sigma", (_RELU, _RELU, _RELU))
             for st in side:
                 fj.join(st)
-            for t in outs[1:] + [xf]:
+            for t in outs[1:] + [xv.buf]:
                 _keep_until(t, cur)
             return tuple(outs)
         if torch.is_grad_enabled() and _ag.gmm_heads_supported(self, x):
@@ -446,40 +443,38 @@ class mask2weights(nn.Module):
         return s[6].run(t, act=_hip.ACT_SOFTMAX_C)
 
 
-def _synthesis_f16k(dec, y_hat, y16=None, shape=None):
+def _synthesis_f16k(dec, y_hat):
     """The synthesis transform deconv+IGDN x3 -> deconv(128 -> 3) with bf16 operands: F16K activations in between, the
     inverse GDNs fused into the transposed convolutions, the last layer as a 3x3 convolution with a depth-to-space store.
-    Returns the float32 NCHW output of g_s_conv4, or None if a shape is unsupported.
-    y16: y_hat in F16K already (written by the analysis transform, _analysis_f16k(layouts=...)); y_hat may then be None and
-    `shape` is its [B, M, h, w]."""
-    B, _, H, W = y_hat.shape if shape is None else shape
+    y_hat: float32 NCHW, or an F16K (written by the analysis transform, _analysis_f16k(layouts=...)).
+    Returns the float32 NCHW output of g_s_conv4, or None if a shape is unsupported."""
+    B, _, H, W = y_hat.shape
     convs = (dec.g_s_conv1, dec.g_s_conv2, dec.g_s_conv3)
     gdns = (dec.g_s_gdn1, dec.g_s_gdn2, dec.g_s_gdn3)
     sizes = [(H, W)]
     for cv in convs:
         if cv.out_channels != 128 or not cv.f16k_supported(B, *sizes[-1]):
             return None
-        d = cv._desc_f16k(B, *sizes[-1])
-        sizes.append((d.Ho, d.Wo))
+        sizes.append(cv.out_hw(*sizes[-1]))
     if not dec.g_s_conv4.d2s_supported(B, *sizes[3]):
         return None
-    t16 = y16 if y16 is not None else _hip.nchw_to_f16k(y_hat)
+    t = y_hat if isinstance(y_hat, _F16K) else _F16K.from_nchw(y_hat)
     sc = _fp8.scales(dec)
     if sc is not None and convs[1].f8k_supported(B, *sizes[1]) and convs[2].f8k_supported(B, *sizes[2]):
         # fp8 mode: g_s_conv1 keeps bf16 operands (its input are the integer symbols) and writes F8K for the two 128 -> 128 layers
-        t8, _, _ = convs[0].run_f16k_f8out(t16, B, *sizes[0], sc["d1"], gdn=gdns[0])
-        t8, _, _ = convs[1].run_f8k(t8, sc["d1"], B, *sizes[1], gdn=gdns[1], out="f8k", out_scale=sc["d2"])
-        t16, _, _ = convs[2].run_f8k(t8, sc["d2"], B, *sizes[2], gdn=gdns[2], out="f16k")
-        return dec.g_s_conv4.run_f16k_d2s(t16, B, *sizes[3])
+        t = convs[0].run_f16k_f8out(t, sc["d1"], gdn=gdns[0])
+        t = convs[1].run_f8k(t, gdn=gdns[1], out="f8k", out_scale=sc["d2"])
+        t = convs[2].run_f8k(t, gdn=gdns[2], out="f16k")
+        return dec.g_s_conv4.run_f16k_d2s(t)
     for i in range(3):
         # g_s_conv2 / g_s_conv3 (128 -> 128): deconv_igdn_f16k, the layer's own kernel; conv_f16k's packs, conv_f16k's bits
-        if _deconv.supported(convs[i], gdns[i], B, *sizes[i]):
-            t16, _, _ = _deconv.run(convs[i], gdns[i], t16, B, *sizes[i])
+        if t.whole and _deconv.supported(convs[i], gdns[i], B, t.H, t.W):
+            t = _deconv.run(convs[i], gdns[i], t)
         else:
-            t16, _, _ = convs[i].run_f16k(t16, B, *sizes[i], gdn=gdns[i])
+            t = convs[i].run_f16k(t, gdn=gdns[i])
         if i < 2:
-            _fp8.record(dec, "d%d" % (i + 1), t16)
-    return dec.g_s_conv4.run_f16k_d2s(t16, B, *sizes[3])
+            _fp8.record(dec, "d%d" % (i + 1), t.buf)
+    return dec.g_s_conv4.run_f16k_d2s(t)
 
 
 class Encoder1(nn.Module):
@@ -504,8 +499,7 @@ class Encoder1(nn.Module):
     def latent(self, x):
         """forward(x)[0]; with bf16 operands and no autograd the intermediate activations stay in F16K."""
         if _bf16_inference(x, self.g_a_conv1.weight):
-            y = _analysis_f16k(self, (self.g_a_conv1, self.g_a_conv2, self.g_a_conv3, self.g_a_conv4),
-                               (self.g_a_gdn1, self.g_a_gdn2, self.g_a_gdn3), x.contiguous())
+            y = _analysis_f16k(self, x.contiguous())
             if y is not None:
                 return y
         return self.forward(x)[0]
@@ -514,8 +508,7 @@ class Encoder1(nn.Module):
         """latent(x) written once in the layouts its consumers read (bf16 eval forward; _analysis_f16k(layouts=...)): a dict of the
         tensors, or None where that form does not apply -- the caller then uses latent() and the stand-alone conversions."""
         if _bf16_inference(x, self.g_a_conv1.weight):
-            return _analysis_f16k(self, (self.g_a_conv1, self.g_a_conv2, self.g_a_conv3, self.g_a_conv4),
-                                  (self.g_a_gdn1, self.g_a_gdn2, self.g_a_gdn3), x.contiguous(), layouts=layouts)
+            return _analysis_f16k(self, x.contiguous(), layouts=layouts)
         return None
 
     def latent_train(self, x):
@@ -545,10 +538,13 @@ class Decoder1(nn.Module):
         g3 = self.g_s_gdn3(self.g_s_conv3(g2))
         return self.g_s_conv4(g3), g1, g2, g3
 
-    def reconstruct(self, y_hat, y16=None):
-        """forward(y_hat)[0]; F16K chain with bf16 operands and no autograd (y16: y_hat in F16K already)."""
+    def reconstruct(self, y_hat):
+        """forward(y_hat)[0]; F16K chain with bf16 operands and no autograd.  y_hat: float32 NCHW, or an F16K holding it -- then the
+        result is None where the F16K chain does not apply (the caller passes the float32 tensor instead)."""
+        if isinstance(y_hat, _F16K):
+            return _synthesis_f16k(self, y_hat) if _bf16_inference(self.g_s_conv1.weight) else None
         if _bf16_inference(y_hat, self.g_s_conv1.weight):
-            x_hat = _synthesis_f16k(self, y_hat, y16=y16)
+            x_hat = _synthesis_f16k(self, y_hat)
             if x_hat is not None:
                 return x_hat
         return self.forward(y_hat)[0]
@@ -584,8 +580,7 @@ class Encoder2(nn.Module):
         layouts: as Encoder1.latent_layouts -- the dict of latent layouts where that form applies, else the float32 latent."""
         t = _pair_conv(self.pre_conv, x1_warp.contiguous(), x2.contiguous(), gdn_out=self.pre_gdn)
         if layouts is not None and _bf16_inference(t, self.g_a_conv1.weight):
-            lay = _analysis_f16k(self, (self.g_a_conv1, self.g_a_conv2, self.g_a_conv3, self.g_a_conv4),
-                                 (self.g_a_gdn1, self.g_a_gdn2, self.g_a_gdn3), t, layouts=layouts)
+            lay = _analysis_f16k(self, t, layouts=layouts)
             if lay is not None:
                 return lay
         return self._analysis(t)
@@ -595,8 +590,7 @@ class Encoder2(nn.Module):
 
     def _analysis(self, t):
         if _bf16_inference(t, self.g_a_conv1.weight):
-            y = _analysis_f16k(self, (self.g_a_conv1, self.g_a_conv2, self.g_a_conv3, self.g_a_conv4),
-                               (self.g_a_gdn1, self.g_a_gdn2, self.g_a_gdn3), t)
+            y = _analysis_f16k(self, t)
             if y is not None:
                 return y
         if torch.is_grad_enabled() and _ag.analysis_supported(self, t):
@@ -622,11 +616,11 @@ class Decoder2(nn.Module):
         self.after_gdn = GDN(3, inverse=True)
         self.after_conv = deconv(6, 3, stride=1)
 
-    def forward(self, y_hat, x1_hat_warp, y16=None, shape=None):
-        """y16 / shape (bf16 eval forward): round(y2) in F16K where the analysis transform wrote it, and its [B, M, h, w]; y_hat may then
-        be None -- the result is None as well where the F16K chain does not apply (the caller quantises to float32 and calls again)."""
-        if y_hat is None:
-            t = _synthesis_f16k(self, None, y16=y16, shape=shape) if _bf16_inference(x1_hat_warp, self.g_s_conv1.weight) else None
+    def forward(self, y_hat, x1_hat_warp):
+        """y_hat: float32 NCHW, or (bf16 eval forward) round(y2) as an F16K where the analysis transform wrote it -- the result is
+        then None where the F16K chain does not apply (the caller quantises to float32 and calls again)."""
+        if isinstance(y_hat, _F16K):
+            t = _synthesis_f16k(self, y_hat) if _bf16_inference(x1_hat_warp, self.g_s_conv1.weight) else None
             if t is None:
                 return None
         else:
@@ -695,47 +689,41 @@ class HSIC(CompressionModel):
         return self.gaussian1._standardized_cumulative(inputs)
 
     @staticmethod
-    def _into_f16k(y32, out16, out_coff):
-        """fallback of the F16K concat buffers: a float32 result converted into its slice (a layer without an F16K configuration)"""
-        _hip.nchw_to_f16k_view(y32, out16[0], out16[1], out_coff)
-        return out16[0]
+    def _slice(cat32, cat16, coff, C):
+        """Channels [coff, coff + C) of a head's concat as the `out` arguments of the layer that writes them: a view of the F16K buffer
+        where there is one, else the float32 buffer and the offset."""
+        return dict(out=cat32, out_coff=coff) if cat16 is None else dict(out=cat16.channels(coff, C))
 
-    def _hyper_up(self, seq, z_hat, out, out_coff, gate=None, gate_c=0, out16=None):
-        """out16 = (F16K buffer, channels): the result goes into that concat buffer instead of the float32 one (`out` is None then)."""
+    def _hyper_up(self, seq, z_hat, out=None, out_coff=0, gate=None, gate_c=0):
+        """out: the float32 concat buffer (written at out_coff) or an F16K view of the F16K one; None: a fresh float32 tensor."""
         if _bf16_inference(z_hat, seq[0].weight):
             # the two small transposed layers (8^2 -> 16^2 -> 32^2: a few dozen workgroups) are quicker on the register-streamed
             # NCHW kernel; the 3x3 288 -> 384 layer at 32^2 on the F16K one (measured: 21 + 58 + 46 us against 47 + 92 + 46)
             t = seq[0].run(z_hat, act=_LEAKY)
-            B = t.shape[0]
-            if seq[2].f16k_out_supported(t.shape):
+            if seq[2].f16k_out_supported(t.shape) and seq[4].f16k_supported(t.shape[0], *seq[2].out_hw(*t.shape[2:])):
                 # the second layer stores bf16 records for the 3x3 layer itself: no float32 tensor and no conversion pass in between
-                d2 = seq[2]._desc(tuple(t.shape))
-                if seq[4].f16k_supported(B, d2.Ho, d2.Wo):
-                    t16, Ho, Wo = seq[2].run_f16k_out(t, act=_LEAKY)
-                    return _f16k_chain((seq[4],), (_NONE,), None, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c, out16=out16,
-                                       x16=t16, shape=(B, seq[2].out_channels, Ho, Wo))
+                return _f16k_chain((seq[4],), (_NONE,), seq[2].run_f16k_out(t, act=_LEAKY), out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
             t = seq[2].run(t, act=_LEAKY)
-            r = _f16k_chain((seq[4],), (_NONE,), t, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c, out16=out16)
+            r = _f16k_chain((seq[4],), (_NONE,), t, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
             if r is not None:
                 return r
-            if out16 is not None:
-                return self._into_f16k(seq[4].run(t, gate=gate, gate_c=gate_c), out16, out_coff)
+            if isinstance(out, _F16K):           # a layer without an F16K configuration: its float32 result converted into the slice
+                return out.fill_from_nchw(seq[4].run(t, gate=gate, gate_c=gate_c))
             return seq[4].run(t, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
         t = seq[0].run(z_hat, act=_LEAKY)
         t = seq[2].run(t, act=_LEAKY)
         return seq[4].run(t, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
 
-    def _context(self, ctx, y, out, out_coff, gate=None, gate_c=0, out16=None, round16=None):
-        """Eval-mode context model: masked conv of round(y) into a slice of the concat buffer (optionally gated).
-        round16: bf16(round(y)) in F16K, where the layer that produced y wrote it."""
+    def _context(self, ctx, y, out, out_coff=0, gate=None, gate_c=0, round16=None):
+        """Eval-mode context model: masked conv of round(y) into a slice of the concat buffer (`out` as in _hyper_up; optionally gated).
+        round16: bf16(round(y)) as an F16K, where the layer that produced y wrote it."""
         if _bf16_inference(y, ctx.weight):
             ctx.zero_masked_taps()
-            r = _f16k_chain((ctx,), (_NONE,), y, in_op=_hip.INOP_ROUND, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c, out16=out16,
-                            x16=round16)
+            r = _f16k_chain((ctx,), (_NONE,), y if round16 is None else round16, in_op=_hip.INOP_ROUND, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
             if r is not None:
                 return r
-        if out16 is not None:
-            return self._into_f16k(ctx.run(y, in_op=_hip.INOP_ROUND, gate=gate, gate_c=gate_c), out16, out_coff)
+        if isinstance(out, _F16K):
+            return out.fill_from_nchw(ctx.run(y, in_op=_hip.INOP_ROUND, gate=gate, gate_c=gate_c))
         return ctx.run(y, in_op=_hip.INOP_ROUND, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
 
     def _needs_graph(self):
@@ -773,7 +761,7 @@ class HSIC(CompressionModel):
         with fj.on(sE):
             z1 = self._h_a1(y1)
             z1_hat, z1_lik = self.entropy_bottleneck1(z1)                                   # draw 1
-            params1 = self._hyper_up(self.h_s1_up, z1_hat, None, 0)
+            params1 = self._hyper_up(self.h_s1_up, z1_hat)
             ctx1 = self.context_prediction1.run(self.gaussian1._quantize(y1, "noise"))     # draw 2
             s1, m1, l1 = self._h_s1_same_resolution.heads(_ag.cat(params1, ctx1))
         # gaussian1(y1, s1, m1, l1) of the reference (:767) in its two halves: the draw here, the likelihood beside the synthesis transform
@@ -789,7 +777,7 @@ class HSIC(CompressionModel):
             y2 = self.encoder2(x1_warp, x2)
             z2 = self._h_a2(y2)
             z2_hat, z2_lik = self.entropy_bottleneck2(z2)                                   # draw 4
-            params2 = self._hyper_up(self.h_s2_up, z2_hat, None, 0)
+            params2 = self._hyper_up(self.h_s2_up, z2_hat)
             ctx2 = self.context_prediction2.run(self.gaussian2._quantize(y2, "noise"))     # draw 5
             if hgrad:
                 x1_mask_R = _ag.WarpOnesFn.apply(m_fwd, (B, H, W), (H, W))
@@ -835,11 +823,9 @@ class HSIC(CompressionModel):
         x1 = x1.contiguous()
         x2 = x2.contiguous()
         B, _, H, W = x1.shape
-        train = self.training
-        mode = "noise" if train else "dequantize"
 
         m_fwd, m_back = warp_matrices if warp_matrices is not None else _warp_matrices(h_matrix, (H, W), (H, W), want_inverse=True)
-        if not train:
+        if not self.training:
             if torch.is_grad_enabled():
                 # eval mode WITHOUT no_grad -- how the CQE driver calls the codec (newtrain_cqe_real.py:130, :160).  round() has zero
                 # gradient, so of the graph the reference records only the two synthesis transforms (and the warp between them) carry
@@ -860,11 +846,8 @@ class HSIC(CompressionModel):
         h, w = y1.shape[-2:]
         cat1 = torch.empty((B, 4 * M, h, w), dtype=x1.dtype, device=x1.device)      # params1 | ctx_params1
         self._hyper_up(self.h_s1_up, z1_hat, cat1, 0)
-        if train:
-            y1_ctx = self.gaussian1._quantize(y1, "noise")
-            self.context_prediction1.run(y1_ctx, out=cat1, out_coff=2 * M)
-        else:
-            self.context_prediction1.run(y1, in_op=_hip.INOP_ROUND, out=cat1, out_coff=2 * M)
+        y1_ctx = self.gaussian1._quantize(y1, "noise")
+        self.context_prediction1.run(y1_ctx, out=cat1, out_coff=2 * M)
         s1, m1, l1 = self._h_s1_same_resolution.heads(cat1)
         y1_hat, y1_lik = self.gaussian1(y1, s1, m1, l1, weights_are_logits=True)
         x1_hat = self.decoder1.reconstruct(y1_hat)
@@ -880,16 +863,13 @@ class HSIC(CompressionModel):
 
         cat2 = torch.empty((B, 5 * M, h, w), dtype=x1.dtype, device=x1.device)      # params2*g0 | ctx2*g1 | y1_warp_hat*g2
         self._hyper_up(self.h_s2_up, z2_hat, cat2, 0, gate=gates, gate_c=0)
-        if train:
-            y2_ctx = self.gaussian2._quantize(y2, "noise")
-            self.context_prediction2.run(y2_ctx, out=cat2, out_coff=2 * M, gate=gates, gate_c=1)
-        else:
-            self.context_prediction2.run(y2, in_op=_hip.INOP_ROUND, out=cat2, out_coff=2 * M, gate=gates, gate_c=1)
+        y2_ctx = self.gaussian2._quantize(y2, "noise")
+        self.context_prediction2.run(y2_ctx, out=cat2, out_coff=2 * M, gate=gates, gate_c=1)
 
         x1_hat_warp = _hip.warp_perspective(x1_hat, m_fwd, (H, W))                   # used twice (:821, :833)
         y1_warp = self.encoder1.latent(x1_hat_warp)
-        noise = self.gaussian1._get_noise_cached(y1_warp) if train else None
-        _hip.quantize(y1_warp, mode, noise=noise, out=cat2, out_coff=4 * M, gate=gates, gate_c=2)
+        noise = self.gaussian1._get_noise_cached(y1_warp)
+        _hip.quantize(y1_warp, "noise", noise=noise, out=cat2, out_coff=4 * M, gate=gates, gate_c=2)
 
         s2, m2, l2 = self._h_s2_same_resolution.heads(cat2)
         y2_hat, y2_lik = self.gaussian2(y2, s2, m2, l2, weights_are_logits=True)
@@ -930,12 +910,12 @@ class HSIC(CompressionModel):
         x1_mask_R = _hip.warp_perspective(None, m_fwd, (H, W), ones_like=(B, H, W))
         x1_mask_L = _hip.warp_perspective(x1_mask_R, m_back, (H, W))
         gates = self.mask2weights_unit(x1_mask_R)                                    # [B,3,h,w]
-        self._hyper_up(self.h_s2_up, z2_hat, cat2, 0, gate=gates, gate_c=0, out16=cat16)
-        self._context(self.context_prediction2, y2, cat2, 2 * M, gates, 1, out16=cat16, round16=y2_round16)
+        self._hyper_up(self.h_s2_up, z2_hat, gate=gates, gate_c=0, **self._slice(cat2, cat16, 0, 2 * M))
+        self._context(self.context_prediction2, y2, gate=gates, gate_c=1, round16=y2_round16, **self._slice(cat2, cat16, 2 * M, 2 * M))
         return {"y2": y2, "y2_round16": y2_round16, "y2_abs16": y2_abs16, "z2_hat": z2_hat, "z2_lik": z2_lik, "cat2": cat2, "cat16": cat16, "gates": gates, "x1_mask_R": x1_mask_R, "x1_mask_L": x1_mask_L}
 
     def _cat_f16k(self, head, y, C):
-        """(F16K buffer, C) for the concat in front of an entropy-parameter head when the bf16 eval forward can keep it in F16K: the
+        """A whole F16K of C channels for the concat in front of an entropy-parameter head when the bf16 eval forward can keep it in F16K: the
         producers (last hyper-synthesis layer, context model, the rounded warped latent) then write their gated slices as bf16 records
         and the head's grouped GEMMs read them directly -- no float32 concat, no conversion pass of the whole buffer on the entropy
         chain (same values bit for bit: the gate multiplies in float32 before the one rounding to bf16 either way).  None otherwise
@@ -945,7 +925,7 @@ class HSIC(CompressionModel):
                 and _fp8.scales(head) is None and head._grouped_heads_ok()):
             return None
         B, _, h, w = y.shape
-        return (_hip.f16k_empty(B, C, h, w, y.device), C)
+        return _F16K.empty(B, C, h, w, y.device)
 
     def _eval_left_entropy(self, y1, round16=None, abs16=None):
         """On the current (side) stream: everything of the left view that only feeds likelihoods.
@@ -954,14 +934,11 @@ class HSIC(CompressionModel):
         B = y1.shape[0]
         cat16 = self._cat_f16k(self._h_s1_same_resolution, y1, 4 * M)
         cat1 = None if cat16 is not None else torch.empty((B, 4 * M) + tuple(y1.shape[-2:]), dtype=y1.dtype, device=y1.device)   # params1 | ctx_params1
-        self._context(self.context_prediction1, y1, cat1, 2 * M, out16=cat16, round16=round16)
+        self._context(self.context_prediction1, y1, round16=round16, **self._slice(cat1, cat16, 2 * M, 2 * M))
         z1 = self._h_a1(y1, abs16=abs16)
         z1_hat, z1_lik = self.entropy_bottleneck1(z1)
-        self._hyper_up(self.h_s1_up, z1_hat, cat1, 0, out16=cat16)
-        if cat16 is not None:
-            s1, m1, l1 = self._h_s1_same_resolution.heads((B, 4 * M) + tuple(y1.shape[-2:]), x16=cat16[0])
-        else:
-            s1, m1, l1 = self._h_s1_same_resolution.heads(cat1, parallel=False)
+        self._hyper_up(self.h_s1_up, z1_hat, **self._slice(cat1, cat16, 0, 2 * M))
+        s1, m1, l1 = self._h_s1_same_resolution.heads(cat1 if cat16 is None else cat16, parallel=False)
         _, y1_lik = self.gaussian1(y1, s1, m1, l1, weights_are_logits=True, want_y_hat=False)
         return {"z1_hat": z1_hat, "z1_lik": z1_lik, "y1_lik": y1_lik}
 
@@ -972,13 +949,12 @@ class HSIC(CompressionModel):
         cat2, cat16, gates, y2 = right["cat2"], right["cat16"], right["gates"], right["y2"]
         if cat16 is not None:             # round(y1_warp) * gate straight into its F16K slice ...
             # ... from the epilogue of the analysis transform's last layer: no float32 y1_warp, no pass over it in front of the heads
-            if self.encoder1.latent_layouts(x1_hat_warp, want=("round16",), round16=cat16[0], round16_ctot=cat16[1], round16_coff=4 * M,
-                                            gate=gates, gate_c=2) is None:
-                _hip.nchw_to_f16k_view(self.encoder1.latent(x1_hat_warp), cat16[0], cat16[1], 4 * M, in_op=_hip.INOP_ROUND, gate=gates, gate_c=2)
-            s2, m2, l2 = self._h_s2_same_resolution.heads((y2.shape[0], 5 * M) + tuple(y2.shape[-2:]), x16=cat16[0])
+            dst = cat16.channels(4 * M, M)
+            if self.encoder1.latent_layouts(x1_hat_warp, want=("round16",), round16=dst, gate=gates, gate_c=2) is None:
+                dst.fill_from_nchw(self.encoder1.latent(x1_hat_warp), in_op=_hip.INOP_ROUND, gate=gates, gate_c=2)
         else:
             _hip.quantize(self.encoder1.latent(x1_hat_warp), "dequantize", out=cat2, out_coff=4 * M, gate=gates, gate_c=2)
-            s2, m2, l2 = self._h_s2_same_resolution.heads(cat2, parallel=False)
+        s2, m2, l2 = self._h_s2_same_resolution.heads(cat2 if cat16 is None else cat16, parallel=False)
         _, y2_lik = self.gaussian2(y2, s2, m2, l2, weights_are_logits=True, want_y_hat=False)
         return y2_lik
 
@@ -1013,11 +989,14 @@ class HSIC(CompressionModel):
         with fj.on(sE):
             left = self._eval_left_entropy(y1, round16=y1_round16, abs16=y1_abs16)
             ev_left = fj.record(sE)
-        _keep_until((y1, y1_round16, y1_abs16), sE)
+        for t in (y1, y1_round16, y1_abs16):
+            _keep_until(t, sE)
         if y1_hat is None:
             y1_hat = _hip.quantize(y1, "dequantize")
         with recorded():
-            x1_hat = self.decoder1(y1_hat)[0] if synthesis_grad else self.decoder1.reconstruct(y1_hat, y16=y1_round16)
+            x1_hat = None if synthesis_grad or y1_round16 is None else self.decoder1.reconstruct(y1_round16)    # the context model's F16K round(y1)
+            if x1_hat is None:
+                x1_hat = self.decoder1(y1_hat)[0] if synthesis_grad else self.decoder1.reconstruct(y1_hat)
             x1_hat_warp = (_ag.WarpFn.apply(x1_hat, m_fwd, (H, W)) if synthesis_grad
                            else _hip.warp_perspective(x1_hat, m_fwd, (H, W)))        # used twice (:821, :833)
         if not serial:
@@ -1031,7 +1010,7 @@ class HSIC(CompressionModel):
             fj.wait(cur, ev_y2)
         x2_hat = None
         if right["y2_round16"] is not None and not synthesis_grad:       # round(y2) is there in F16K: the float32 y2_hat is no output of the model
-            x2_hat = self.decoder2(None, x1_hat_warp, y16=right["y2_round16"], shape=right["y2"].shape)
+            x2_hat = self.decoder2(right["y2_round16"], x1_hat_warp)
         if x2_hat is None:
             y2_hat = _hip.quantize(right["y2"], "dequantize")
             with recorded():
@@ -1110,21 +1089,22 @@ class HSIC(CompressionModel):
             for layers in k["heads"]:
                 _hip.skinny_group(layers, pix, step, list_stride, npix, k["h"], k["w"], nimg=k["B"])
 
-    def _skinny_params(self, head, ctx, cat16, C, h, w, gate, B):
-        """Buffers and layer descriptions of _PixelParams over B pairs (cat16 and gate stacked [B, ...]), or None when the pixel-list form
-        does not apply (float32 / fp8 operands, widths the kernels are not built for)."""
+    def _skinny_params(self, head, ctx, cat16, gate):
+        """Buffers and layer descriptions of _PixelParams over B pairs (cat16: the pairs' F16K concat buffers stacked into one whole
+        F16K, gate stacked [B, ...]), or None when the pixel-list form does not apply (widths the kernels are not built for)."""
         from masic_amd import nn as _mnn
         M, K = self.M, self.K
-        if (cat16 is None or M % 16 or (2 * M) % 32 or not head._grouped_heads_ok()
+        if (M % 16 or (2 * M) % 32 or not head._grouped_heads_ok()
                 or ctx.kernel_size != (5, 5)):
             return None
-        dev = cat16[0].device
+        B, C, h, w = cat16.shape
+        dev = cat16.buf.device
         ctx.zero_masked_taps()
         wpc = _mnn._cached(ctx, "_packed_skinny_cache", _mnn.weight_key(ctx.weight), (), lambda: _hip.pack_skinny_ctx_weight(ctx.weight.detach()))
         M16 = (M + 15) // 16 * 16
         y16 = torch.zeros(B * M16 * h * w, dtype=torch.int16, device=dev)
         outs = [torch.empty((B, K * M, h, w), dtype=torch.float32, device=dev) for _ in range(3)]
-        heads, t = [], [cat16[0]] * 3
+        heads, t = [], [cat16.buf] * 3
         for i in range(3):
             layers, nxt = [], []
             for k_, (name, tag, acts) in enumerate(head._STACKS):
@@ -1139,7 +1119,7 @@ class HSIC(CompressionModel):
                 layers.append(L)
             heads.append(layers)
             t = nxt
-        ctxl = dict(x=y16, wp=wpc, bias=None if ctx.bias is None else ctx.bias.detach(), Cin=M16, Cout=2 * M, act=_NONE, y16=cat16[0], out_ctot=C, out_coff=2 * M)
+        ctxl = dict(x=y16, wp=wpc, bias=None if ctx.bias is None else ctx.bias.detach(), Cin=M16, Cout=2 * M, act=_NONE, y16=cat16.buf, out_ctot=C, out_coff=2 * M)
         return dict(y16=y16, M16=M16, sigma=outs[0], mu=outs[1], logits=outs[2], ctx=ctxl, heads=heads, h=h, w=w, gate=gate, B=B)
 
     def _left_params_fn(self, z1_hat, h, w):
@@ -1148,13 +1128,11 @@ class HSIC(CompressionModel):
         # grouped head GEMMs read the buffer directly: no conversion pass over the 768-channel buffer per coding step)
         cat16 = self._cat_f16k(self._h_s1_same_resolution, z1_hat.new_empty((1, M, h, w)), 4 * M)
         cat1 = None if cat16 is not None else torch.empty((1, 4 * M, h, w), dtype=torch.float32, device=z1_hat.device)      # params1 | ctx_params1
-        self._hyper_up(self.h_s1_up, z1_hat, cat1, 0, out16=cat16)
+        self._hyper_up(self.h_s1_up, z1_hat, **self._slice(cat1, cat16, 0, 2 * M))
 
         def params(y_hat):
-            self._context(self.context_prediction1, y_hat, cat1, 2 * M, out16=cat16)
-            if cat16 is not None:
-                return self._h_s1_same_resolution.heads((1, 4 * M, h, w), x16=cat16[0])
-            return self._h_s1_same_resolution.heads(cat1)
+            self._context(self.context_prediction1, y_hat, **self._slice(cat1, cat16, 2 * M, 2 * M))
+            return self._h_s1_same_resolution.heads(cat1 if cat16 is None else cat16)
         return HSIC._PairParams(params, cat16)
 
     def _right_params_fn(self, z2_hat, x1_hat, m_fwd, m_back, H, W, h, w):
@@ -1165,19 +1143,17 @@ class HSIC(CompressionModel):
         gates = self.mask2weights_unit(x1_mask_R)
         cat16 = self._cat_f16k(self._h_s2_same_resolution, z2_hat.new_empty((1, M, h, w)), 5 * M)
         cat2 = None if cat16 is not None else torch.empty((1, 5 * M, h, w), dtype=torch.float32, device=dev)   # params2*g0 | ctx2*g1 | y1_warp_hat*g2
-        self._hyper_up(self.h_s2_up, z2_hat, cat2, 0, gate=gates, gate_c=0, out16=cat16)
+        self._hyper_up(self.h_s2_up, z2_hat, gate=gates, gate_c=0, **self._slice(cat2, cat16, 0, 2 * M))
         x1_hat_warp = _hip.warp_perspective(x1_hat, m_fwd, (H, W))
         y1_warp = self.encoder1.latent(x1_hat_warp)
         if cat16 is not None:
-            _hip.nchw_to_f16k_view(y1_warp, cat16[0], cat16[1], 4 * M, in_op=_hip.INOP_ROUND, gate=gates, gate_c=2)
+            cat16.channels(4 * M, M).fill_from_nchw(y1_warp, in_op=_hip.INOP_ROUND, gate=gates, gate_c=2)
         else:
             _hip.quantize(y1_warp, "dequantize", out=cat2, out_coff=4 * M, gate=gates, gate_c=2)
 
         def params(y_hat):
-            self._context(self.context_prediction2, y_hat, cat2, 2 * M, gates, 1, out16=cat16)
-            if cat16 is not None:
-                return self._h_s2_same_resolution.heads((1, 5 * M, h, w), x16=cat16[0])
-            return self._h_s2_same_resolution.heads(cat2)
+            self._context(self.context_prediction2, y_hat, gate=gates, gate_c=1, **self._slice(cat2, cat16, 2 * M, 2 * M))
+            return self._h_s2_same_resolution.heads(cat2 if cat16 is None else cat16)
         return HSIC._PairParams(params, cat16, gates.contiguous()), x1_hat_warp
 
     @staticmethod
@@ -1293,9 +1269,9 @@ class HSIC(CompressionModel):
         buffers sized for B; None when the pixel-list form does not apply."""
         if any(p.cat16 is None for p in parts):
             return None
-        cat = torch.cat([p.cat16[0] for p in parts])
+        cat = _F16K.wrap(torch.cat([p.cat16.buf for p in parts]), len(parts), C, h, w)
         gate = torch.cat([p.gate for p in parts]) if parts[0].gate is not None else None
-        sk = self._skinny_params(head, ctx, (cat, C), C, h, w, gate, len(parts))
+        sk = self._skinny_params(head, ctx, cat, gate)
         return None if sk is None else HSIC._PixelParams(sk)
 
     def _code_views(self, parts, head, ctx, C, y_hat, chans, minmaxes, bound, names):
@@ -1463,9 +1439,9 @@ class Enhancement_Block(nn.Module):
     def f16k_supported(self, B, H, W):
         return all(rb.f16k_supported(B, H, W) for rb in (self.RB1, self.RB2, self.RB3))
 
-    def forward_f16k(self, x16, B, H, W, out16=None, out_ctot=None, out_coff=0):
-        t = self.RB2.forward_f16k(self.RB1.forward_f16k(x16, B, H, W), B, H, W)
-        return self.RB3.forward_f16k(t, B, H, W, extra16=x16, out16=out16, out_ctot=out_ctot, out_coff=out_coff)
+    def forward_f16k(self, x, out=None):
+        t = self.RB2.forward_f16k(self.RB1.forward_f16k(x))
+        return self.RB3.forward_f16k(t, extra=x, out=out)
 
 
 class mask2weights_EN(nn.Module):
@@ -1564,29 +1540,29 @@ class Independent_EN(nn.Module):
             _hip.quantize(x_other_warp, "copy", out=inp, out_coff=0, gate=w, gate_c=0)
             _hip.quantize(x_own, "copy", out=inp, out_coff=3, gate=w, gate_c=1)
             if self.conv1.resident_supported(B, H, W):       # 6 -> 32 on the resident-weight kernel: one zero-padded record per pixel in, F16K out
-                t16 = self.conv1.run_f16k_res(_hip.nchw_to_f16k(inp), B, H, W)
+                t = self.conv1.run_f16k_res(_F16K.from_nchw(inp))
             else:
-                t16 = _hip.nchw_to_f16k(self.conv1.run(inp))
-            feats.append(EB1.forward_f16k(t16, B, H, W))
+                t = _F16K.from_nchw(self.conv1.run(inp))
+            feats.append(EB1.forward_f16k(t))
         # stage 2: own * w1 | warp(other) * w0   (:1481-1482)
-        c1 = _hip.f16k_empty(B, 64, H, W, dev)
-        c2 = _hip.f16k_empty(B, 64, H, W, dev)
-        _hip.f16k_gate(feats[0], B, 32, H, W, c1, 64, 0, gate=w_L, gate_c=1)
-        _hip.f16k_gate(feats[1], B, 32, H, W, c1, 64, 32, gate=w_L, gate_c=0, minv=m_back)
-        _hip.f16k_gate(feats[1], B, 32, H, W, c2, 64, 0, gate=w_R, gate_c=1)
-        _hip.f16k_gate(feats[0], B, 32, H, W, c2, 64, 32, gate=w_R, gate_c=0, minv=m_fwd)
+        c1 = _F16K.empty(B, 64, H, W, dev)
+        c2 = _F16K.empty(B, 64, H, W, dev)
+        c1.channels(0, 32).fill_gated(feats[0], gate=w_L, gate_c=1)
+        c1.channels(32, 32).fill_gated(feats[1], gate=w_L, gate_c=0, minv=m_back)
+        c2.channels(0, 32).fill_gated(feats[1], gate=w_R, gate_c=1)
+        c2.channels(32, 32).fill_gated(feats[0], gate=w_R, gate_c=0, minv=m_fwd)
         for x_own, c, EB2, EB3 in ((x1_hat, c1, self.EBl2, self.EBl3), (x2_hat, c2, self.EBr2, self.EBr3)):
-            d = _hip.f16k_empty(B, 96, H, W, dev)                                             # stage-2 output | conv0(x_hat)   (:1486-1487)
-            EB2.forward_f16k(c, B, H, W, out16=d, out_ctot=96, out_coff=0)
+            d = _F16K.empty(B, 96, H, W, dev)                                                 # stage-2 output | conv0(x_hat)   (:1486-1487)
+            EB2.forward_f16k(c, out=d.channels(0, 64))
             if self.conv0.resident_supported(B, H, W):       # 3 -> 32 straight into channels [64, 96) of the concat buffer
-                self.conv0.run_f16k_res(_hip.nchw_to_f16k(x_own), B, H, W, out16=d, out_ctot=96, out_coff=64)
+                self.conv0.run_f16k_res(_F16K.from_nchw(x_own), out=d.channels(64, 32))
             else:
-                _hip.nchw_to_f16k_view(self.conv0.run(x_own), d, 96, 64)
-            o16 = EB3.forward_f16k(d, B, H, W)
+                d.channels(64, 32).fill_from_nchw(self.conv0.run(x_own))
+            o = EB3.forward_f16k(d)
             if self.conv2.few_supported(B, H, W):
-                outs.append(self.conv2.run_f16k_few(o16, B, H, W, res32=x_own))               # 96 -> 3 on the MFMA kernel + the picture (:1495-1496)
+                outs.append(self.conv2.run_f16k_few(o, res32=x_own))                          # 96 -> 3 on the MFMA kernel + the picture (:1495-1496)
             else:
-                outs.append(self.conv2.run(_hip.f16k_to_nchw_dev(o16, B, 96, H, W), res1=x_own))
+                outs.append(self.conv2.run(o.to_nchw(), res1=x_own))
         return {"x1_hat": outs[0], "x2_hat": outs[1]}
 
     def _f16k_ok(self, B, H, W):

@@ -11,6 +11,7 @@ import torch
 from torch.autograd import Function
 
 from . import ops
+from .f16k import F16K
 from ._lib import PREC_BF16, PREC_F32
 
 PEDESTAL = 2.0 ** -36
@@ -47,17 +48,16 @@ class ConvFn(Function):
             # bf16-operand mode, 1x1 layers of the entropy-parameter stacks: the DMA-staged GEMM of the inference path (gemm_f16k.hip:
             # gemm_f16k, 4x the rate of the NCHW implicit-GEMM kernel at these shapes); x is converted once to F16K
             B, _, H, W = x.shape
-            x16 = ops.nchw_to_f16k(x)
-            y = ops.gemm_f16k(x16, mod.packed_gemm_dma_weight(), None if bias is None else bias.detach(), B, mod.in_channels,
+            x16 = F16K.from_nchw(x)
+            y = ops.gemm_f16k(x16.buf, mod.packed_gemm_dma_weight(), None if bias is None else bias.detach(), B, mod.in_channels,
                               mod.out_channels, H, W, act, want_nchw=True)
             ctx.x16 = x16 if _WGRAD1_F16K else None          # kept for the weight gradient (masic_gemm_wgrad_bias_f16k)
         elif _fwd_f16k(mod, x, act):
             # bf16 mode, the hyper transforms and context models (3x3 / 5x5, 128 ... 384 channels at latent resolution): the DMA-staged
             # F16K kernel of inference (x converted once; the 3x3 weight gradient reads the same F16K copy) instead of the NCHW
             # implicit-GEMM kernel -- 38 against 54 ... 70 us per layer at 8 x 32 x 32
-            B, _, H, W = x.shape
-            x16 = ops.nchw_to_f16k(x)
-            y = mod.run_f16k(x16, B, H, W, act=act, want_nchw=True)[0]
+            x16 = F16K.from_nchw(x)
+            y = mod.run_f16k(x16, act=act, want_nchw=True)
             ctx.x16 = x16
         else:
             y = mod.run(x, act=act)
@@ -71,7 +71,7 @@ class ConvFn(Function):
     def backward(ctx, g):
         x, weight, y = ctx.saved_tensors
         gx, gw, gb = conv_backward(ctx.mod, x, weight, y, g, ctx.act, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                   ctx.has_bias and ctx.needs_input_grad[2], x16=ctx.x16)
+                                   ctx.has_bias and ctx.needs_input_grad[2], x_f16k=ctx.x16)
         ctx.x16 = None
         return gx, gw, gb, None, None
 
@@ -79,31 +79,33 @@ class ConvFn(Function):
 _WGRAD1_F16K = True     # 1x1 weight gradients from the two F16K operands; tests set False for the float32 NCHW kernel as their reference
 
 
-def conv_backward(mod, x, weight, y, g, act, need_gx=True, need_gw=True, need_gb=True, x16=None, g16=None, gb=None, gx_f16k=False,
-                  x_shape=None, g_shape=None):
-    """(dx, dW, db) of y = act(conv(x, W) + b) for the module's layer geometry; x, g float32 NCHW (x16: x in F16K if the caller has it).
-    g16 / gb: dy in F16K and its channel sums when the caller's producer already wrote them (ops.gdn_bwd_fused_ex): no conversion and
-    no reduction pass here.  gx_f16k: return dx as an F16K buffer (int16) when the F16K kernel computes it (the consumer is another
-    F16K-operand kernel), float32 NCHW otherwise.
-    x = None / g = None with x_shape / g_shape: the caller has that tensor in F16K only (x16 / g16 + gb) -- the picture-end layers, whose
-    weight gradient reads the 128-channel operand in F16K (ops.pic_wgrad_f16k) and never needs its float32 NCHW form.
+def conv_backward(mod, x, weight, y, g, act, need_gx=True, need_gw=True, need_gb=True, gb=None, gx_f16k=False, x_f16k=None, g_f16k=None):
+    """(dx, dW, db) of y = act(conv(x, W) + b) for the module's layer geometry.  x, g: float32 (or bf16) NCHW, or a whole F16K where the
+    caller has that tensor in F16K only -- the picture-end layers, whose weight gradient reads the 128-channel operand in F16K
+    (ops.pic_wgrad_f16k) and never needs its NCHW form; an F16K g comes with gb and no activation.
+    x_f16k / g_f16k: the F16K twin of an NCHW x / g where the caller holds both forms (the forward's converted input; dy as
+    ops.gdn_bwd_fused_ex wrote it twice) -- the two gradients read one form each: no conversion pass here.  gb: the channel sums of dy
+    when the producer already wrote them: no reduction pass here.  gx_f16k: return dx as an F16K when the F16K kernel computes it (the
+    consumer is another F16K-operand kernel), float32 NCHW otherwise.
     (Issuing dW / db on a side stream next to dx was measured twice: 24.9 -> 25.2 ms per HSIC training step in round 2, 13.14 -> 13.00 in
     round 3 and 12.33 -> 12.62 on top of the two-stream forward -- the eager step is bound by the host's launch rate, and a gradient
     produced beside the node's stream is unsafe for a layer used twice in one forward, whose two contributions autograd adds on the node's
     stream before `.grad` exists.  Not kept.)"""
-    if g is None:
-        if g16 is None or g_shape is None or act != ops.ACT_NONE or (need_gb and gb is None):
-            raise RuntimeError("masic_amd.conv_backward: g = None needs g16, g_shape, the bias gradient and no activation")
+    if isinstance(x, F16K):
+        x, x_f16k = None, x
+    if isinstance(g, F16K):
+        g, g_f16k = None, g
+        if act != ops.ACT_NONE or (need_gb and gb is None):
+            raise RuntimeError("masic_amd.conv_backward: an F16K g needs the bias gradient and no activation")
     else:
         g = _c(g)
-        g_shape = tuple(g.shape)
         if act != ops.ACT_NONE:
             g = ops.elementwise(ops.EW_ACT_BWD, g, y, s0=act)
-    if x is None:
-        if x16 is None or x_shape is None:
-            raise RuntimeError("masic_amd.conv_backward: x = None needs x16 and x_shape")
-    else:
-        x_shape = tuple(x.shape)
+    for t in (x_f16k, g_f16k):
+        if t is not None and not t.whole:
+            raise RuntimeError(f"masic_amd.conv_backward: whole F16K tensors only, not {t!r}")
+    x_shape, g_shape = tuple((x_f16k if x is None else x).shape), tuple((g_f16k if g is None else g).shape)
+    x16, g16 = (None if t is None else t.buf for t in (x_f16k, g_f16k))
     kh, kw, s, p = mod._geometry()
     B, Cin, Hi, Wi = x_shape
     Cout, Ho, Wo = g_shape[1], g_shape[2], g_shape[3]
@@ -161,7 +163,7 @@ def conv_backward(mod, x, weight, y, g, act, need_gx=True, need_gw=True, need_gb
                 return ops.conv2d_f16k_d2s(g16, ops.pack_conv_f16k_weight(wc, dd), bc, dd, Cin)
         if dx_conv_a:
             # dx of ConvTranspose2d(128 -> 3) = Conv2d(3 -> 128) with the same tensor: the first-layer kernel without its GDN, F16K out
-            return ops.conv_a_f16k(g, ops.pack_conv_a_weight(weight.detach().contiguous()))[0]
+            return F16K(ops.conv_a_f16k(g, ops.pack_conv_a_weight(weight.detach().contiguous()))[0], B, Cin, Hi, Wi, Cin, 0)
         if dx_gemm:
             # dx = W^T g: the same GEMM kernel on the transposed weight (packed per step: the weights change with every optimizer step)
             wt = ops.pack_gemm_f16k_weight(weight.detach().contiguous(), Cout, Cin, not mod.transposed_conv)
@@ -171,8 +173,10 @@ def conv_backward(mod, x, weight, y, g, act, need_gx=True, need_gw=True, need_gb
             wpad[:, :Cin] = weight.detach()
             return ops.conv2d_f16k_few(g16, ops.pack_conv_f16k_weight(wpad, d_few), ops.zeros(32, torch.float32, weight.device), d_few, Cin)
         if dx_f16k:
-            return ops.conv2d_f16k(g16, ops.pack_conv_f16k_weight(weight.detach(), d16, persistent=weight.is_leaf and weight.is_contiguous() and not mod.masked_conv), None, d16,
-                                   want_nchw=not (gx_f16k and Cin % 16 == 0))
+            to16 = gx_f16k and Cin % 16 == 0
+            gx = ops.conv2d_f16k(g16, ops.pack_conv_f16k_weight(weight.detach(), d16, persistent=weight.is_leaf and weight.is_contiguous() and not mod.masked_conv), None, d16,
+                                 want_nchw=not to16)
+            return F16K(gx, B, Cin, Hi, Wi, Cin, 0) if to16 else gx
         g32 = ops.f16k_to_nchw_dev(g16, B, Cout, Ho, Wo) if g is None else (g if g.dtype == torch.float32 else g.float())
         return ops.conv2d(g32, ops.pack_conv_weight(weight.detach(), d), None, d)
 
@@ -525,18 +529,18 @@ class EnhancementBlockFn(Function):
     def forward(ctx, x, eb, tail, res, *params):
         x = _c(x)
         B, C, H, W = x.shape
-        x0 = ops.nchw_to_f16k(x)
+        x0 = F16K.from_nchw(x)
         saved, cur = [x0], x0
         for i, rb in enumerate((eb.RB1, eb.RB2, eb.RB3)):
-            t = rb.conv1.run_f16k_res(cur, B, H, W, act=ops.ACT_LEAKY)
-            u = ops.f16k_empty(B, C, H, W, x.device)
-            cur = rb.conv2.run_f16k_res(t, B, H, W, act=ops.ACT_LEAKY, res1=cur, res2=x0 if i == 2 else None, res_ctot=C, y_pre=u)
+            t = rb.conv1.run_f16k_res(cur, act=ops.ACT_LEAKY)
+            u = F16K.empty(B, C, H, W, x.device)
+            cur = rb.conv2.run_f16k_res(t, act=ops.ACT_LEAKY, res1=cur, res2=x0 if i == 2 else None, y_pre=u)
             saved += [t, u] if i == 2 and tail is None else [t, u, cur]
         ctx.eb, ctx.tail, ctx.shape = eb, tail, (B, C, H, W)
-        ctx.save_for_backward(*params, *saved)
+        ctx.save_for_backward(*params, *[t.buf for t in saved])      # (autograd tracks tensors; backward reads the raw buffers: one shape)
         if tail is None:
-            return ops.f16k_to_nchw_dev(cur, B, C, H, W)
-        return tail.run_f16k_few(cur, B, H, W, res32=None if res is None else _c(res))      # the block's output never leaves F16K
+            return cur.to_nchw()
+        return tail.run_f16k_few(cur, res32=None if res is None else _c(res))      # the block's output never leaves F16K
 
     @staticmethod
     def backward(ctx, g):
@@ -715,11 +719,24 @@ def _wgrad_b16(mod, B, hw_in):
                                                              transposed=mod.transposed_conv, prec=PREC_BF16))
 
 
-def _gdn_backward_f16k(u16, g, shape, gdn, want_f16k=True, want_b16=False, want_nchw=True):
+def _gdn_backward_f16k(u, g, gdn, want_f16k=True, want_b16=False, want_nchw=True):
     """GDN backward inside the fused transforms: (dx NCHW -- float32, or bf16 with want_b16 --, dx F16K | None, channel sums of dx | None,
-    d beta, d gamma); u16: the GDN's saved input (F16K), g: float32 NCHW or F16K."""
-    return ops.gdn_bwd_fused_ex(u16, _c(g), shape, gdn.beta.detach(), gdn.gamma.detach(), gdn.inverse, gdn.beta_min, want_nchw=want_nchw,
-                                want_f16k=want_f16k, want_sum=True, want_b16=want_b16)
+    d beta, d gamma); u: the GDN's saved input (F16K), g: float32 NCHW or F16K."""
+    gx, gx16, *rest = ops.gdn_bwd_fused_ex(u.buf, g.buf if isinstance(g, F16K) else _c(g), u.shape, gdn.beta.detach(), gdn.gamma.detach(), gdn.inverse,
+                                           gdn.beta_min, want_nchw=want_nchw, want_f16k=want_f16k, want_sum=True, want_b16=want_b16)
+    return (gx, None if gx16 is None else F16K(gx16, *u.shape, u.C, 0), *rest)
+
+
+def _save_f16k(ctx, tensors, values, *params):
+    """save_for_backward for a node that keeps F16K values: autograd tracks their buffers, ctx keeps the shapes they are rebuilt from."""
+    ctx.f16k_shapes = [v.shape for v in values]
+    ctx.save_for_backward(*tensors, *[v.buf for v in values], *params)
+
+
+def _saved_f16k(ctx, n_tensors):
+    """-> (tensors, F16K values, params) as _save_f16k stored them."""
+    saved, n = ctx.saved_tensors, n_tensors + len(ctx.f16k_shapes)
+    return saved[:n_tensors], [F16K.wrap(b, *shp) for b, shp in zip(saved[n_tensors:n], ctx.f16k_shapes)], saved[n:]
 
 
 class GmmHeadsFn(Function):
@@ -850,37 +867,36 @@ class AnalysisFn(Function):
         c1 = convs[0]
         u1, a1, h1, w1 = ops.conv_a_gdn_dual(x, c1.packed_first_layer_weight(), None if c1.bias is None else c1.bias.detach(),
                                              (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse))
-        u2, a2, h2, w2 = convs[1].run_f16k_dual(a1, B, h1, w1, gdns[1])
-        u3, a3, h3, w3 = convs[2].run_f16k_dual(a2, B, h2, w2, gdns[2])
-        y = convs[3].run_f16k(a3, B, h3, w3, want_nchw=True)[0]
-        ctx.enc, ctx.sizes = enc, ((h1, w1), (h2, w2), (h3, w3))
-        ctx.save_for_backward(x, u1, a1, u2, a2, u3, a3, *params)
-        return y
+        u1, a1 = F16K(u1, B, 128, h1, w1, 128, 0), F16K(a1, B, 128, h1, w1, 128, 0)
+        u2, a2 = convs[1].run_f16k_dual(a1, gdns[1])
+        u3, a3 = convs[2].run_f16k_dual(a2, gdns[2])
+        ctx.enc = enc
+        _save_f16k(ctx, (x,), (u1, a1, u2, a2, u3, a3), *params)
+        return convs[3].run_f16k(a3, want_nchw=True)
 
     @staticmethod
     def backward(ctx, g):
-        x, u1, a1, u2, a2, u3, a3, *params = ctx.saved_tensors
+        (x,), (u1, a1, u2, a2, u3, a3), _ = _saved_f16k(ctx, 1)
         enc = ctx.enc
         convs = (enc.g_a_conv1, enc.g_a_conv2, enc.g_a_conv3, enc.g_a_conv4)
         gdns = (enc.g_a_gdn1, enc.g_a_gdn2, enc.g_a_gdn3)
         B = x.shape[0]
-        nchw = lambda t16, hw, bf16=False: ops.f16k_to_nchw_dev(t16, B, 128, hw[0], hw[1], bf16=bf16)
         grads = {}
         # The GDN backward reads its saved input (and the gradient, when an F16K kernel produced it) as F16K and writes dx twice --
         # float32 NCHW for the weight-gradient kernel, F16K for the input-gradient convolution -- plus dx's channel sums (the bias
         # gradient): no F16K -> NCHW pass on u, no NCHW -> F16K pass and no reduction pass on dx.
-        gx, grads["w4"], grads["b4"] = conv_backward(convs[3], nchw(a3, ctx.sizes[2]), convs[3].weight, None, g, ops.ACT_NONE, gx_f16k=True)
-        for i, (u, a_in, hw, hw_in) in ((2, (u3, a2, ctx.sizes[2], ctx.sizes[1])), (1, (u2, a1, ctx.sizes[1], ctx.sizes[0]))):
-            b16 = _wgrad_b16(convs[i], B, hw_in)       # the weight gradient's two operands as bf16 NCHW: half the bytes on every side of it
-            gu, gu16, gsum, grads["beta%d" % (i + 1)], grads["gamma%d" % (i + 1)] = _gdn_backward_f16k(u, gx, (B, 128) + tuple(hw), gdns[i], want_b16=b16)
-            gx, grads["w%d" % (i + 1)], grads["b%d" % (i + 1)] = conv_backward(convs[i], nchw(a_in, hw_in, b16), convs[i].weight, None, gu, ops.ACT_NONE,
-                                                                                g16=gu16, gb=gsum, gx_f16k=True)
+        gx, grads["w4"], grads["b4"] = conv_backward(convs[3], a3.to_nchw(), convs[3].weight, None, g, ops.ACT_NONE, gx_f16k=True)
+        for i, (u, a_in) in ((2, (u3, a2)), (1, (u2, a1))):
+            b16 = _wgrad_b16(convs[i], B, (a_in.H, a_in.W))       # the weight gradient's two operands as bf16 NCHW: half the bytes on every side of it
+            gu, gu16, gsum, grads["beta%d" % (i + 1)], grads["gamma%d" % (i + 1)] = _gdn_backward_f16k(u, gx, gdns[i], want_b16=b16)
+            gx, grads["w%d" % (i + 1)], grads["b%d" % (i + 1)] = conv_backward(convs[i], a_in.to_nchw(bf16=b16), convs[i].weight, None, gu, ops.ACT_NONE,
+                                                                                g_f16k=gu16, gb=gsum, gx_f16k=True)
         # the first layer takes dy in F16K for both gradients (ops.pic_wgrad_f16k, the depth-to-space input gradient): no float32 NCHW dx here
-        f16k_only = tuple(x.shape[2:]) == (2 * ctx.sizes[0][0], 2 * ctx.sizes[0][1])
-        gu, gu16, gsum, grads["beta1"], grads["gamma1"] = _gdn_backward_f16k(u1, gx, (B, 128) + tuple(ctx.sizes[0]), gdns[0],
-                                                                             want_f16k=ctx.needs_input_grad[0] or f16k_only, want_nchw=not f16k_only)
-        gimg, grads["w1"], grads["b1"] = conv_backward(convs[0], x, convs[0].weight, None, gu, ops.ACT_NONE, need_gx=ctx.needs_input_grad[0], g16=gu16, gb=gsum,
-                                                       g_shape=(B, 128) + tuple(ctx.sizes[0]))
+        f16k_only = tuple(x.shape[2:]) == (2 * u1.H, 2 * u1.W)
+        gu, gu16, gsum, grads["beta1"], grads["gamma1"] = _gdn_backward_f16k(u1, gx, gdns[0], want_f16k=ctx.needs_input_grad[0] or f16k_only,
+                                                                             want_nchw=not f16k_only)
+        gimg, grads["w1"], grads["b1"] = conv_backward(convs[0], x, convs[0].weight, None, gu16 if f16k_only else gu, ops.ACT_NONE,
+                                                       need_gx=ctx.needs_input_grad[0], g_f16k=gu16, gb=gsum)
         return (gimg, None, grads["w1"], grads["b1"], grads["beta1"], grads["gamma1"], grads["w2"], grads["b2"], grads["beta2"], grads["gamma2"],
                 grads["w3"], grads["b3"], grads["beta3"], grads["gamma3"], grads["w4"], grads["b4"])
 
@@ -906,8 +922,7 @@ def analysis_supported(enc, x):
     for m in c[1:]:
         if not m.f16k_supported(B, h, w):
             return False
-        d = m._desc_f16k(B, h, w)
-        h, w = d.Ho, d.Wo
+        h, w = m.out_hw(h, w)
     return True
 
 
@@ -920,40 +935,34 @@ class SynthesisFn(Function):
         convs = (dec.g_s_conv1, dec.g_s_conv2, dec.g_s_conv3, dec.g_s_conv4)
         gdns = (dec.g_s_gdn1, dec.g_s_gdn2, dec.g_s_gdn3)
         B, _, H, W = y_hat.shape
-        t16 = ops.nchw_to_f16k(y_hat)
-        saved, sizes, hw = [], [], (H, W)
+        t, saved = F16K.from_nchw(y_hat), []
         for i in range(3):
-            u, t16, ho, wo = convs[i].run_f16k_dual(t16, B, hw[0], hw[1], gdns[i])
-            hw = (ho, wo)
-            saved += [u, t16]
-            sizes.append(hw)
-        x_hat = convs[3].run_f16k_d2s(t16, B, hw[0], hw[1])
-        ctx.dec, ctx.sizes = dec, sizes
-        ctx.save_for_backward(y_hat, *saved, *params)
-        return x_hat
+            u, t = convs[i].run_f16k_dual(t, gdns[i])
+            saved += [u, t]
+        ctx.dec = dec
+        _save_f16k(ctx, (y_hat,), saved, *params)
+        return convs[3].run_f16k_d2s(t)
 
     @staticmethod
     def backward(ctx, g):
-        y_hat, u1, a1, u2, a2, u3, a3, *params = ctx.saved_tensors
+        (y_hat,), (u1, a1, u2, a2, u3, a3), _ = _saved_f16k(ctx, 1)
         dec = ctx.dec
         convs = (dec.g_s_conv1, dec.g_s_conv2, dec.g_s_conv3, dec.g_s_conv4)
         gdns = (dec.g_s_gdn1, dec.g_s_gdn2, dec.g_s_gdn3)
         B = y_hat.shape[0]
-        nchw = lambda t16, hw, bf16=False: ops.f16k_to_nchw_dev(t16, B, 128, hw[0], hw[1], bf16=bf16)
         grads = {}
         # the last layer's weight gradient reads its saved input where it is, in F16K (ops.pic_wgrad_f16k): no float32 NCHW copy of a3
-        hw3 = tuple(ctx.sizes[2])
-        f16k_only = tuple(convs[3].weight.shape[:2]) == (128, 3) and tuple(g.shape[2:]) == (2 * hw3[0], 2 * hw3[1])
-        gx, grads["w4"], grads["b4"] = conv_backward(convs[3], None if f16k_only else nchw(a3, hw3), convs[3].weight, None, g, ops.ACT_NONE,
-                                                     gx_f16k=True, x16=a3, x_shape=(B, 128) + hw3)
-        for i, (u, a_in, hw, hw_in) in ((2, (u3, a2, ctx.sizes[2], ctx.sizes[1])), (1, (u2, a1, ctx.sizes[1], ctx.sizes[0]))):
-            b16 = _wgrad_b16(convs[i], B, hw_in)       # the weight gradient's two operands as bf16 NCHW: half the bytes on every side of it
-            gu, gu16, gsum, grads["beta%d" % (i + 1)], grads["gamma%d" % (i + 1)] = _gdn_backward_f16k(u, gx, (B, 128) + tuple(hw), gdns[i], want_b16=b16)
-            gx, grads["w%d" % (i + 1)], grads["b%d" % (i + 1)] = conv_backward(convs[i], nchw(a_in, hw_in, b16), convs[i].weight, None, gu, ops.ACT_NONE,
-                                                                                g16=gu16, gb=gsum, gx_f16k=True)
-        gu, gu16, gsum, grads["beta1"], grads["gamma1"] = _gdn_backward_f16k(u1, gx, (B, 128) + tuple(ctx.sizes[0]), gdns[0])
+        f16k_only = tuple(convs[3].weight.shape[:2]) == (128, 3) and tuple(g.shape[2:]) == (2 * a3.H, 2 * a3.W)
+        gx, grads["w4"], grads["b4"] = conv_backward(convs[3], a3 if f16k_only else a3.to_nchw(), convs[3].weight, None, g, ops.ACT_NONE,
+                                                     gx_f16k=True, x_f16k=a3)
+        for i, (u, a_in) in ((2, (u3, a2)), (1, (u2, a1))):
+            b16 = _wgrad_b16(convs[i], B, (a_in.H, a_in.W))       # the weight gradient's two operands as bf16 NCHW: half the bytes on every side of it
+            gu, gu16, gsum, grads["beta%d" % (i + 1)], grads["gamma%d" % (i + 1)] = _gdn_backward_f16k(u, gx, gdns[i], want_b16=b16)
+            gx, grads["w%d" % (i + 1)], grads["b%d" % (i + 1)] = conv_backward(convs[i], a_in.to_nchw(bf16=b16), convs[i].weight, None, gu, ops.ACT_NONE,
+                                                                                g_f16k=gu16, gb=gsum, gx_f16k=True)
+        gu, gu16, gsum, grads["beta1"], grads["gamma1"] = _gdn_backward_f16k(u1, gx, gdns[0])
         gy, grads["w1"], grads["b1"] = conv_backward(convs[0], y_hat, convs[0].weight, None, gu, ops.ACT_NONE, need_gx=ctx.needs_input_grad[0],
-                                                     g16=gu16, gb=gsum)
+                                                     g_f16k=gu16, gb=gsum)
         return (gy, None, grads["w1"], grads["b1"], grads["beta1"], grads["gamma1"], grads["w2"], grads["b2"], grads["beta2"], grads["gamma2"],
                 grads["w3"], grads["b3"], grads["beta3"], grads["gamma3"], grads["w4"], grads["b4"])
 
@@ -974,6 +983,5 @@ def synthesis_supported(dec, y_hat):
     for m in c:
         if m.out_channels != 128 or m.bias is None or not m.f16k_supported(B, *hw):
             return False
-        d = m._desc_f16k(B, *hw)
-        hw = (d.Ho, d.Wo)
+        hw = m.out_hw(*hw)
     return dec.g_s_conv4.bias is not None and dec.g_s_conv4.d2s_supported(B, *hw)

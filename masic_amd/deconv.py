@@ -2,7 +2,7 @@
 kernel of its own (masic_amd/csrc/deconv_igdn.hip).
 
     if deconv.supported(cv, gdn, B, Hi, Wi):
-        y16, Ho, Wo = deconv.run(cv, gdn, x16, B, Hi, Wi)        # the bits of cv.run_f16k(x16, B, Hi, Wi, gdn=gdn)
+        y = deconv.run(cv, gdn, x)        # x, y F16K values; the bits of cv.run_f16k(x, gdn=gdn)
 
 Operands are conv_f16k's: the weight stream of `cv.packed_f16k_weight`, the GDN image of `nn.packed_gdn_f16k` -- no pack and no cache of
 its own.  The form is fixed (bf16 F16K in and out without a channel view, one-product inverse GDN); `supported` answers False for
@@ -18,6 +18,7 @@ import os
 import torch
 
 from . import _lib, ops
+from .f16k import F16K
 from .ops import _p, _stream
 
 HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_deconv.h")
@@ -89,8 +90,8 @@ def deconv_igdn_f16k(x16, packed, bias, gdn_packed, B, Hi, Wi, out16=None, tile=
 
 
 def supported(cv, gdn, B, Hi, Wi, out_ctot=None, out_coff=0, in_ctot=None, in_coff=0, y_pre=None, prec=_lib.PREC_BF16, products=None):
-    """True where run(cv, gdn, ...) stands for cv.run_f16k(..., gdn=gdn): a ConvTranspose2d(128, 128, 5, stride 2, padding 2,
-    output_padding 1) followed by a 128-channel inverse GDN in its one-product form, bf16 operands, whole F16K tensors in and out.
+    """True where run(cv, gdn, x) stands for cv.run_f16k(x, gdn=gdn) on a whole F16K x of [B, 128, Hi, Wi]: a ConvTranspose2d(128, 128,
+    5, stride 2, padding 2, output_padding 1) followed by a 128-channel inverse GDN in its one-product form, bf16 operands.
     The keyword arguments name what the caller would ask of conv_f16k besides: a channel view of the input or the output, a second
     pre-GDN output, fp8 operands, the three-product contraction -- each of them is refused."""
     if gdn is None or not getattr(cv, "transposed_conv", False) or cv.in_channels != CHANNELS or cv.out_channels != CHANNELS:
@@ -104,10 +105,12 @@ def supported(cv, gdn, B, Hi, Wi, out_ctot=None, out_coff=0, in_ctot=None, in_co
     return bool(_lib.lib.masic_deconv_igdn_f16k_supported(B, Hi, Wi)) and cv.f16k_supported(B, Hi, Wi)
 
 
-def run(cv, gdn, x16, B, Hi, Wi):
-    """(y16, Ho, Wo) of cv.run_f16k(x16, B, Hi, Wi, gdn=gdn) where supported(cv, gdn, B, Hi, Wi); the packs are the ones that call uses."""
+def run(cv, gdn, x):
+    """The F16K of cv.run_f16k(x, gdn=gdn) where supported(cv, gdn, x.B, x.H, x.W); the packs are the ones that call uses."""
     from .nn import packed_gdn_f16k
-    desc = cv._desc_f16k(B, Hi, Wi, out_ctot=CHANNELS)
+    if not x.whole or x.C != CHANNELS:
+        raise RuntimeError(f"masic_amd.deconv.run: the kernel takes whole 128-channel tensors, not {x!r}")
+    desc = cv._desc_f16k(x.B, x.H, x.W, out_ctot=CHANNELS)
     bias = None if cv.bias is None else cv.bias.detach()
-    y16 = deconv_igdn_f16k(x16, cv.packed_f16k_weight(desc), bias, packed_gdn_f16k(gdn), B, Hi, Wi)
-    return y16, desc.Ho, desc.Wo
+    y16 = deconv_igdn_f16k(x.buf, cv.packed_f16k_weight(desc), bias, packed_gdn_f16k(gdn), x.B, x.H, x.W)
+    return F16K(y16, x.B, CHANNELS, desc.Ho, desc.Wo, CHANNELS, 0)

@@ -450,6 +450,7 @@ def test_picture_end_input_gradients_f16k_forms():
     first-layer kernel without its GDN -- against torch's float32 operators on the bf16-rounded operands the kernels see."""
     from compressai.models.utils import conv, deconv
     from masic_amd import autograd as ag, nn as mnn, ops
+    from masic_amd.f16k import F16K
     q = lambda t: t.bfloat16().float()
     B, H, W = 2, 48, 80
     mnn.set_precision("bf16")
@@ -458,7 +459,7 @@ def test_picture_end_input_gradients_f16k_forms():
         x = _rand(B, 3, H, W, seed=1).to(DEV)
         dy = _rand(B, 128, H // 2, W // 2, seed=2)
         want = F.conv_transpose2d(q(dy), q(ca.weight.detach().cpu()), None, stride=2, padding=2, output_padding=1)
-        gx, gw, gb = ag.conv_backward(ca, x, ca.weight, None, dy.to(DEV), ops.ACT_NONE, need_gw=False, need_gb=False, g16=ops.nchw_to_f16k(dy.to(DEV)))
+        gx, gw, gb = ag.conv_backward(ca, x, ca.weight, None, dy.to(DEV), ops.ACT_NONE, need_gw=False, need_gb=False, g_f16k=F16K.from_nchw(dy.to(DEV)))
         assert gx.dtype == torch.float32 and gw is None and gb is None
         assert_close(gx, want, "dx of Conv2d(3->128) (depth-to-space form)", 2e-3)
         dt = deconv(128, 3).to(DEV)                                 # dx = Conv2d(3 -> 128)(dy)
@@ -466,8 +467,8 @@ def test_picture_end_input_gradients_f16k_forms():
         dy = _rand(B, 3, H, W, seed=4)
         want = F.conv2d(q(dy), q(dt.weight.detach().cpu()), None, stride=2, padding=2)
         gx, _, _ = ag.conv_backward(dt, xin, dt.weight, None, dy.to(DEV), ops.ACT_NONE, need_gw=False, need_gb=False, gx_f16k=True)
-        assert gx.dtype == torch.int16
-        assert_close(ops.f16k_to_nchw_dev(gx, B, 128, H // 2, W // 2), want, "dx of ConvTranspose2d(128->3) (first-layer kernel, no GDN)", 2 ** -8)
+        assert isinstance(gx, F16K) and gx.buf.dtype == torch.int16 and gx.shape == (B, 128, H // 2, W // 2) and gx.whole
+        assert_close(ops.f16k_to_nchw_dev(gx.buf, B, 128, H // 2, W // 2), want, "dx of ConvTranspose2d(128->3) (first-layer kernel, no GDN)", 2 ** -8)
     finally:
         mnn.set_precision("f32")
     # the one-launch weight relayout equals the torch-op form

@@ -244,16 +244,18 @@ def test_conv_f16k_residual_block_kernels(C):
     with torch.no_grad():
         conv.weight.mul_(3.0)
     assert conv.f16k_supported(B, H, W)
-    x16, r116, r216 = (ops.nchw_to_f16k(t.to(DEV)) for t in (x, r1, r2))
+    from masic_amd.f16k import F16K
+    x16, r116, r216 = (F16K.from_nchw(t.to(DEV)) for t in (x, r1, r2))
     ref = F.leaky_relu(F.conv2d(_bf(x), _bf(conv.weight.detach().cpu()), conv.bias.detach().cpu(), padding=1), 0.01) + _bf(r1) + _bf(r2)
-    y16 = conv.run_f16k_res(x16, B, H, W, act=ops.ACT_LEAKY, res1=r116, res2=r216, res_ctot=C)
-    got = ops.f16k_to_nchw(y16, B, C, H, W)
+    y16 = conv.run_f16k_res(x16, act=ops.ACT_LEAKY, res1=r116, res2=r216)
+    assert y16.shape == (B, C, H, W) and y16.whole
+    got = ops.f16k_to_nchw(y16.buf, B, C, H, W)
     assert_close(got, ref, f"conv_f16k_res C={C}", 2 ** -8 + 1e-4)
-    assert torch.equal(ops.f16k_to_nchw_dev(y16, B, C, H, W), got)                 # the HIP conversion == the torch-op checker
+    assert torch.equal(y16.to_nchw(), got)                 # the HIP conversion == the torch-op checker
     # one residual, written into channels [0, C) of a buffer of C + 32 channels whose other channels must stay untouched
-    wide = ops.nchw_to_f16k(torch.full((B, C + 32, H, W), 7.0).to(DEV))
-    conv.run_f16k_res(x16, B, H, W, act=ops.ACT_LEAKY, res1=r116, res_ctot=C, out16=wide, out_ctot=C + 32, out_coff=0)
-    w = ops.f16k_to_nchw(wide, B, C + 32, H, W)
+    wide = F16K.from_nchw(torch.full((B, C + 32, H, W), 7.0).to(DEV))
+    conv.run_f16k_res(x16, act=ops.ACT_LEAKY, res1=r116, out=wide.channels(0, C))
+    w = ops.f16k_to_nchw(wide.buf, B, C + 32, H, W)
     ref1 = F.leaky_relu(F.conv2d(_bf(x), _bf(conv.weight.detach().cpu()), conv.bias.detach().cpu(), padding=1), 0.01) + _bf(r1)
     assert_close(w[:, :C], ref1, f"conv_f16k_res view C={C}", 2 ** -8 + 1e-4)
     assert float((w[:, C:] - 7.0).abs().max()) == 0.0

@@ -171,7 +171,7 @@ def test_decoder_takes_either_path():
     mnn.set_precision("bf16")
     try:
         with torch.no_grad(), pytest.MonkeyPatch.context() as mp:
-            mp.setattr(deconv, "run", lambda *a, **k: calls.append(a[3:6]) or run(*a, **k))
+            mp.setattr(deconv, "run", lambda *a, **k: calls.append((a[2].B, a[2].H, a[2].W)) or run(*a, **k))
             new = dec.reconstruct(y_hat)
             assert calls == [(1, 8, 8), (1, 16, 16)]
             mp.setattr(deconv, "supported", lambda *a, **k: False)

@@ -57,14 +57,19 @@ def test_conv_f8k_exact_on_representable_operands(transposed, B, H, W):
     in_scale = 0.5                   # x / 0.5 in {0, +-1, ..., +-8}: exact; exercises the input-scale factor of the dequantisation
     x8 = ops.nchw_to_f8k(x.to(DEV), in_scale)
     assert torch.equal(ops.f8k_to_nchw(x8, B, C, H, W, in_scale).cpu(), x)
-    y32, Ho, Wo = mod.run_f8k(x8, in_scale, B, H, W, out="nchw")
-    assert (Ho, Wo) == tuple(ref.shape[-2:])
+    from masic_amd.f16k import F8K
+    x8k = F8K.wrap(x8, B, C, H, W, in_scale)
+    y32 = mod.run_f8k(x8k, out="nchw")
+    Ho, Wo = mod.out_hw(H, W)
+    assert (Ho, Wo) == tuple(ref.shape[-2:]) == tuple(y32.shape[-2:])
     e = assert_close(y32, ref, "conv_f8k -> float32", 2e-7)        # the only rounding: accumulator x (weight scale x input scale)
-    y16, _, _ = mod.run_f8k(x8, in_scale, B, H, W, out="f16k")
-    assert_close(ops.f16k_to_nchw(y16, B, C, Ho, Wo), ref.bfloat16().float(), "conv_f8k -> F16K", 2e-7 + 2 ** -8)
+    y16 = mod.run_f8k(x8k, out="f16k")
+    assert y16.shape == (B, C, Ho, Wo) and y16.whole
+    assert_close(ops.f16k_to_nchw(y16.buf, B, C, Ho, Wo), ref.bfloat16().float(), "conv_f8k -> F16K", 2e-7 + 2 ** -8)
     out_scale = float(ref.abs().max()) / 448.0
-    y8, _, _ = mod.run_f8k(x8, in_scale, B, H, W, out="f8k", out_scale=out_scale)
-    got, want = ops.f8k_to_nchw(y8, B, C, Ho, Wo, out_scale).cpu(), _fp8_round(ref, out_scale)
+    y8 = mod.run_f8k(x8k, out="f8k", out_scale=out_scale)
+    assert y8.shape == (B, C, Ho, Wo) and y8.scale == out_scale
+    got, want = ops.f8k_to_nchw(y8.buf, B, C, Ho, Wo, out_scale).cpu(), _fp8_round(ref, out_scale)
     off = (got != want)
     # a value that the 1e-7 dequantisation rounding moves across an fp8 rounding boundary may land on the neighbouring code
     assert float(off.float().mean()) < 1e-3 and float((got - want).abs().max()) <= float(ref.abs().max()) * 2 ** -3, float(off.float().mean())
@@ -76,6 +81,7 @@ def test_conv_f8k_fused_gdn_and_bf16_producer():
     float32 convolution on the same (exactly representable) operands."""
     from compressai.layers import GDN
     from masic_amd import nn as mnn, ops, synth
+    from masic_amd.f16k import F16K, F8K
     C, B, H, W = 128, 2, 32, 32
     x = _exact((B, C, H, W), [0.0, 0.5, -0.5, 1.0, -1.0, 2.0, -2.0], 5)
     w = _exact((C, C, 5, 5), [0.0, 0.0, 0.0, 0.125, -0.125, 0.25, -0.25], 6)
@@ -88,19 +94,20 @@ def test_conv_f8k_fused_gdn_and_bf16_producer():
         with torch.no_grad():
             mod.weight.copy_(w); mod.bias.zero_(); gdn.beta.copy_(beta); gdn.gamma.copy_(gamma)
         ref = O.gdn(F.conv2d(x, w, None, stride=2, padding=2), beta, gamma, inverse=inverse)
-        x8 = ops.nchw_to_f8k(x.to(DEV), 1.0)
-        y16, Ho, Wo = mod.run_f8k(x8, 1.0, B, H, W, out="f16k", gdn=gdn)
-        assert_close(ops.f16k_to_nchw(y16, B, C, Ho, Wo), ref, f"conv_f8k + GDN(inverse={inverse}) -> F16K", 2 ** -8 + 1e-3)
+        x8 = F8K.wrap(ops.nchw_to_f8k(x.to(DEV), 1.0), B, C, H, W, 1.0)
+        y16 = mod.run_f8k(x8, out="f16k", gdn=gdn)
+        Ho, Wo = y16.H, y16.W
+        assert_close(ops.f16k_to_nchw(y16.buf, B, C, Ho, Wo), ref, f"conv_f8k + GDN(inverse={inverse}) -> F16K", 2 ** -8 + 1e-3)
         sc = float(ref.abs().max()) / 448.0
-        y8, _, _ = mod.run_f8k(x8, 1.0, B, H, W, out="f8k", out_scale=sc, gdn=gdn)
-        got = ops.f8k_to_nchw(y8, B, C, Ho, Wo, sc).cpu()
+        y8 = mod.run_f8k(x8, out="f8k", out_scale=sc, gdn=gdn)
+        got = ops.f8k_to_nchw(y8.buf, B, C, Ho, Wo, sc).cpu()
         assert float((got - ref).abs().max()) <= float(ref.abs().max()) * (2 ** -4 + 2e-3)      # half an fp8 step at the top binade
         assert float(((got - ref).abs() > ref.abs() * 2 ** -4 + sc * 2 ** -9 * 1.01 + 2e-3 * ref.abs().max()).float().mean()) == 0.0
         # bf16-operand producer with an F8K output == the F16K result pushed through the fp8 cast
-        x16 = ops.nchw_to_f16k(x.to(DEV))
-        ref16, _, _ = mod.run_f16k(x16, B, H, W, gdn=gdn)
-        y8b, _, _ = mod.run_f16k_f8out(x16, B, H, W, sc, gdn=gdn)
-        a, b = ops.f8k_to_nchw(y8b, B, C, Ho, Wo, sc).cpu(), ops.f16k_to_nchw(ref16, B, C, Ho, Wo).cpu()
+        x16 = F16K.from_nchw(x.to(DEV))
+        ref16 = mod.run_f16k(x16, gdn=gdn)
+        y8b = mod.run_f16k_f8out(x16, sc, gdn=gdn)
+        a, b = ops.f8k_to_nchw(y8b.buf, B, C, Ho, Wo, sc).cpu(), ops.f16k_to_nchw(ref16.buf, B, C, Ho, Wo).cpu()
         assert float((a - b).abs().max()) <= float(b.abs().max()) * (2 ** -4 + 2 ** -8)
 
 

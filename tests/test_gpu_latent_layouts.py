@@ -187,6 +187,7 @@ def _bits(t):
 @pytest.mark.parametrize("B,H,W", [(2, 64, 128), (1, 128, 128)])
 def test_eval_forward_hands_its_consumers_what_the_separate_launches_made(net, monkeypatch, B, H, W):
     from masic_amd import nn as mnn, ops, synth
+    from masic_amd.f16k import F16K
     from masic_amd.graph import GraphedHSIC
     x1, x2, hm = (t.to(DEV) for t in synth.synth_inputs(B, H, W, seed=32))
     seen = {}
@@ -199,7 +200,7 @@ def test_eval_forward_hands_its_consumers_what_the_separate_launches_made(net, m
             return orig(*a, **kw)
         monkeypatch.setattr(obj, name, f)
 
-    spy(net.decoder1, "reconstruct", "dec1", lambda a, kw: kw.get("y16"))
+    spy(net.decoder1, "reconstruct", "dec1", lambda a, kw: a[0] if isinstance(a[0], F16K) else None)
     spy(net, "_context", "ctx", lambda a, kw: (a[0], kw.get("round16")))
     spy(net._h_a1, "forward", "h_a1", lambda a, kw: kw.get("abs16"))
     spy(net, "_eval_right_entropy", "right", lambda a, kw: a)
@@ -212,20 +213,20 @@ def test_eval_forward_hands_its_consumers_what_the_separate_launches_made(net, m
             y1 = net.encoder1.latent(x1)
             assert torch.equal(_bits(out["y1_hat"]), _bits(ops.quantize(y1, "dequantize")))
             r16 = ops.nchw_to_f16k(y1, in_op=ops.INOP_ROUND)
-            assert seen["dec1"][0] is not None and torch.equal(seen["dec1"][0], r16)
+            assert seen["dec1"][0] is not None and torch.equal(seen["dec1"][0].buf, r16) and seen["dec1"][0].shape == tuple(y1.shape)
             ctx1 = [r for c, r in seen["ctx"] if c is net.context_prediction1]
             assert len(ctx1) == 1 and ctx1[0] is seen["dec1"][0], "context model and decoder1 share one round buffer"
-            assert seen["h_a1"][0] is not None and torch.equal(seen["h_a1"][0], ops.nchw_to_f16k(y1, in_op=ops.INOP_ABS))
+            assert seen["h_a1"][0] is not None and torch.equal(seen["h_a1"][0].buf, ops.nchw_to_f16k(y1, in_op=ops.INOP_ABS))
             x1_hat_warp, right = seen["right"][0]
             h, w = y1.shape[-2:]
-            want = torch.zeros_like(right["cat16"][0])
+            want = torch.zeros_like(right["cat16"].buf)
             ops.nchw_to_f16k_view(net.encoder1.latent(x1_hat_warp), want, 5 * M, 4 * M, in_op=ops.INOP_ROUND, gate=right["gates"], gate_c=2)
-            got = right["cat16"][0].view(B, 5 * M // 16, h * w, 16)[:, 4 * M // 16:]
+            got = right["cat16"].buf.view(B, 5 * M // 16, h * w, 16)[:, 4 * M // 16:]
             assert torch.equal(got, want.view(B, 5 * M // 16, h * w, 16)[:, 4 * M // 16:]), "cat2 slice of the second encoder1 pass"
             # the right view: round(y2) / |y2| against the conversions of its float32 latent
             ctx2 = [r for c, r in seen["ctx"] if c is net.context_prediction2]
-            assert torch.equal(ctx2[0], ops.nchw_to_f16k(right["y2"], in_op=ops.INOP_ROUND))
-            assert torch.equal(right["y2_abs16"], ops.nchw_to_f16k(right["y2"], in_op=ops.INOP_ABS))
+            assert torch.equal(ctx2[0].buf, ops.nchw_to_f16k(right["y2"], in_op=ops.INOP_ROUND))
+            assert torch.equal(right["y2_abs16"].buf, ops.nchw_to_f16k(right["y2"], in_op=ops.INOP_ABS))
             # decoder2 on the F16K round(y2) against decoder2 on the float32 y2_hat
             assert torch.equal(_bits(out["x2_hat"]), _bits(net.decoder2(ops.quantize(right["y2"], "dequantize"), x1_hat_warp)))
             monkeypatch.undo()

@@ -44,3 +44,9 @@ class F(torch.autograd.Function):
     def backward(ctx, g): return g
 xr = x.clone().requires_grad_(True)
 t("autograd.Function.apply (identity)", lambda: F.apply(xr), 5000)
+from masic_amd import nn as mnn
+from masic_amd.f16k import F16K
+cv = mnn.Conv2d(16, 128, 5, stride=2, padding=2).cuda(); xv = F16K.wrap(x16, 1, 16, 16, 16)
+t("Conv2d.run_f16k (whole F16K, 1 x 16 -> 128, 5x5 s2, 16^2)", lambda: cv.run_f16k(xv), 5000)
+c3 = mnn.Conv2d(32, 32, 3, padding=1).cuda(); x3v = F16K.wrap(x3, 1, 32, 16, 32); view = F16K.empty(1, 96, 16, 32, "cuda").channels(64, 32)
+t("Conv2d.run_f16k_res (into a channel view of 96)", lambda: c3.run_f16k_res(x3v, act=ops.ACT_LEAKY, out=view), 5000)
