@@ -33,6 +33,7 @@ from masic_amd import autograd as _ag
 from masic_amd.streams import ForkJoin as _ForkJoin
 from masic_amd import fp8 as _fp8
 from masic_amd import deconv as _deconv
+from masic_amd import conv_s2 as _conv_s2
 from masic_amd.f16k import F16K as _F16K, F8K as _F8K
 
 _RELU, _LEAKY, _NONE = _hip.ACT_RELU, _hip.ACT_LEAKY, _hip.ACT_NONE
@@ -222,9 +223,14 @@ def _analysis_f16k(owner, x, layouts=None):
         return convs[3].run_f16k(t, want_nchw=True)
     t = _F16K(_hip.conv_a_gdn_f16k(x, c1.packed_first_layer_weight(), b1, (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse))[0], B, 128, *sizes[0], 128, 0)
     _fp8.record(owner, "a1", t.buf)
-    t = convs[1].run_f16k(t, gdn=gdns[1])
-    _fp8.record(owner, "a2", t.buf)
-    t = convs[2].run_f16k(t, gdn=gdns[2])
+    for i in (1, 2):
+        # g_a_conv2 / g_a_conv3 (128 -> 128): conv_s2_gdn_f16k, the layer's own kernel; conv_f16k's packs, conv_f16k's bits
+        if t.whole and _conv_s2.supported(convs[i], gdns[i], B, t.H, t.W):
+            t = _conv_s2.run(convs[i], gdns[i], t)
+        else:
+            t = convs[i].run_f16k(t, gdn=gdns[i])
+        if i == 1:
+            _fp8.record(owner, "a2", t.buf)
     if layouts is not None:
         return convs[3].run_f16k_multi(t, **layouts)
     return convs[3].run_f16k(t, want_nchw=True)
