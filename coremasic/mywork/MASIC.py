@@ -189,6 +189,14 @@ def _gdn_f16k(gdn, x):
     return _hip.gdn_f16k(x, gdn.beta.detach(), gdn.gamma.detach(), inverse=gdn.inverse, beta_min=gdn.beta_min)
 
 
+def _own_kernel_or_f16k(kernel, cv, gdn, t):
+    """cv + gdn on F16K t: on the layer's own kernel (masic_amd.deconv / masic_amd.conv_s2: conv_f16k's packs, conv_f16k's bits) where it
+    takes the layer and the form, else on conv_f16k"""
+    if t.whole and kernel.supported(cv, gdn, t.B, t.H, t.W):
+        return kernel.run(cv, gdn, t)
+    return cv.run_f16k(t, gdn=gdn)
+
+
 def _analysis_f16k(owner, x, layouts=None):
     """conv+GDN x3 -> conv of the analysis transform `owner` on the float32 NCHW image `x` with bf16 operands: every GDN runs in
     the epilogue of the convolution that feeds it and the 128-channel activations stay in F16K bf16 in between
@@ -224,11 +232,7 @@ def _analysis_f16k(owner, x, layouts=None):
     t = _F16K(_hip.conv_a_gdn_f16k(x, c1.packed_first_layer_weight(), b1, (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse))[0], B, 128, *sizes[0], 128, 0)
     _fp8.record(owner, "a1", t.buf)
     for i in (1, 2):
-        # g_a_conv2 / g_a_conv3 (128 -> 128): conv_s2_gdn_f16k, the layer's own kernel; conv_f16k's packs, conv_f16k's bits
-        if t.whole and _conv_s2.supported(convs[i], gdns[i], B, t.H, t.W):
-            t = _conv_s2.run(convs[i], gdns[i], t)
-        else:
-            t = convs[i].run_f16k(t, gdn=gdns[i])
+        t = _own_kernel_or_f16k(_conv_s2, convs[i], gdns[i], t)      # g_a_conv2 / g_a_conv3 (128 -> 128): conv_s2_gdn_f16k
         if i == 1:
             _fp8.record(owner, "a2", t.buf)
     if layouts is not None:
@@ -473,11 +477,7 @@ def _synthesis_f16k(dec, y_hat):
         t = convs[2].run_f8k(t, gdn=gdns[2], out="f16k")
         return dec.g_s_conv4.run_f16k_d2s(t)
     for i in range(3):
-        # g_s_conv2 / g_s_conv3 (128 -> 128): deconv_igdn_f16k, the layer's own kernel; conv_f16k's packs, conv_f16k's bits
-        if t.whole and _deconv.supported(convs[i], gdns[i], B, t.H, t.W):
-            t = _deconv.run(convs[i], gdns[i], t)
-        else:
-            t = convs[i].run_f16k(t, gdn=gdns[i])
+        t = _own_kernel_or_f16k(_deconv, convs[i], gdns[i], t)       # g_s_conv2 / g_s_conv3 (128 -> 128): deconv_igdn_f16k
         if i < 2:
             _fp8.record(dec, "d%d" % (i + 1), t.buf)
     return dec.g_s_conv4.run_f16k_d2s(t)

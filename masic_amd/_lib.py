@@ -50,7 +50,7 @@ def _ctype(decl, structs, what, named=True, void_ok=False, header="masic_hip.h")
 def parse_header(text, header="masic_hip.h"):
     """(signatures {name: (restype, [argtypes])}, constants {name: int}, structs {C name: Structure class}) of a C header
     written as include/masic_hip.h is; ValueError naming the declaration for anything else.  `header`: the name its messages start
-    with (a second header of the library, include/masic_align.h, is parsed by masic_amd/align.py)."""
+    with (the library's side headers are parsed by bind_header)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     constants, structs, signatures = {}, {}, {}
 
@@ -137,6 +137,27 @@ def _load():
 
 
 lib = _load()
+
+
+def bind_header(filename, prefix):
+    """Bind a side header of libmasic_hip.so: a file beside include/masic_hip.h (or an absolute path) that holds prototypes only, each
+    a `prefix`* entry point outside the pinned ABI of masic_hip.h (SIGNATURES, tests/golden/abi.json), which stays as it is.  Parses
+    it, sets restype and argtypes of every prototype on `lib` and returns {name: (restype, argtypes)}."""
+    path, header = os.path.join(os.path.dirname(HEADER_PATH), filename), os.path.basename(filename)
+    if not os.path.exists(path):
+        raise ImportError(f"masic_amd.{prefix[len('masic_'):].rstrip('_')}: {path} is missing: the binding is derived from it.  There is "
+                          "no CPU fallback for the HIP path.")
+    with open(path) as f:
+        signatures, constants, structs = parse_header(f.read(), header=header)
+    if constants or structs:
+        raise ValueError(f"{header}: declares constants or structs; it holds prototypes only")
+    for name, (res, args) in signatures.items():
+        if not name.startswith(prefix) or name in SIGNATURES:
+            raise ValueError(f"{header}: {name} is not a {prefix}* entry point of its own")
+        fn = getattr(lib, name)          # AttributeError if the symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+    return signatures
 
 
 def check(rc, what=""):

@@ -11,9 +11,8 @@ than a quarter of the pixels valid, a non-positive pivot, a corner outside [-P/2
 With status 1 or 2 `delta` is the start value (`delta0`, or zeros) exactly.  The result is bit-reproducible and an item's bits depend
 on neither B nor its batch mates.
 
-The entry points are declared in include/masic_align.h, a second header of libmasic_hip.so: include/masic_hip.h and what
-masic_amd._lib derives from it are a pinned ABI (tests/golden/abi.json) and stay as they are.  The header is parsed by
-_lib.parse_header and bound on _lib.lib here.  No CPU path: tensors must live on an MI355X (`cuda`) device.
+The entry points are declared in include/masic_align.h, a side header of libmasic_hip.so bound by _lib.bind_header.  No CPU path:
+tensors must live on an MI355X (`cuda`) device.
 """
 import os
 
@@ -28,24 +27,7 @@ PATCH_SIZES = (32, 64, 128)
 ITERS = (30, 15, 10)              # Gauss-Newton steps, coarse to fine; the last `levels` entries are used
 
 
-def _bind():
-    if not os.path.exists(HEADER_PATH):
-        raise ImportError(f"masic_amd.align: {HEADER_PATH} is missing: the binding is derived from it.  There is no CPU fallback for "
-                          "the HIP path.")
-    with open(HEADER_PATH) as f:
-        signatures, constants, structs = _lib.parse_header(f.read(), header="masic_align.h")
-    if constants or structs:
-        raise ValueError("masic_align.h: declares constants or structs; it holds prototypes only")
-    for name, (res, args) in signatures.items():
-        if not name.startswith("masic_align_") or name in _lib.SIGNATURES:
-            raise ValueError(f"masic_align.h: {name} is not a masic_align_* entry point of its own")
-        fn = getattr(_lib.lib, name)          # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    return signatures
-
-
-SIGNATURES = _bind()          # name -> (restype, argtypes) of every prototype of masic_align.h
+SIGNATURES = _lib.bind_header(HEADER_PATH, "masic_align_")          # name -> (restype, argtypes) of every prototype of masic_align.h
 
 
 def align_patches(a, b, delta0=None, *, search_radius=12, iters=ITERS, damping=1e-6):

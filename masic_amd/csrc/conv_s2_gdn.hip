@@ -21,6 +21,7 @@
 //     barrier of the K loop anyway, so the epilogue starts right behind that barrier: no DMA round trip and no barrier after the K loop.
 // LDS: 60 KiB weight ring | 2 patch buffers of 41 KiB | 512 B beta^ | 512 B bias = 143 KiB.
 #include "f16k_device.h"
+#include "f16k_layer.h"
 #include "masic_conv_s2.h"
 
 namespace {
@@ -45,7 +46,6 @@ constexpr int CS_PB = CS_NINSTR * 1024;                                      // 
 constexpr int CS_PSP = 6, CS_NPI = 2 * CS_PSP;                               // patch instructions per patch wave per slice / per chunk
 constexpr int CS_RING = 0, CS_PATCH0 = CS_RING + CS_NWS * CS_WST, CS_BETA = CS_PATCH0 + 2 * CS_PB, CS_BIAS = CS_BETA + 512;
 constexpr int CS_LDS = CS_BIAS + 512;
-constexpr int CS_OOB = 0x7ffffff0;                                           // a buffer offset past every resource: the DMA writes zeros
 static_assert(CS_LDS <= 160 * 1024, "LDS");
 static_assert(CS_NPI * 4 >= CS_NINSTR && (CS_NPI - 2) * 4 <= CS_NINSTR, "a surplus DMA slot repeats instruction 4 (NPI - 3) + wave of the chunk");
 static_assert(32 * 1024 + 4 * 1024 <= CS_PB && CS_NPI * 4 >= 32, "gamma^ and its surplus slots fit a patch buffer and the DMA slots of a chunk");
@@ -63,26 +63,15 @@ __global__ __launch_bounds__(512, 1) void conv_s2_gdn_f16k(const ConvS2Args a) {
     const bool wrole = wave < 4;
     const int wq = wave & 3;
 
-    // blockIdx.x, .z -> (tile, image): conv_f16k's maps -- with a multiple of 8 images, image 8 slot + k is walked tile by tile on XCD k
-    // (block ids go round-robin over the XCDs, gridDim.x is a multiple of 8), else tile = blockIdx.x, image = blockIdx.z
     int tile, b;
-    if (a.xcd_images) {
-        const int idx = (blockIdx.x >> 3) + (gridDim.x >> 3) * blockIdx.z;
-        const int slot = idx / (int)gridDim.x;
-        tile = idx - slot * (int)gridDim.x;
-        b = slot * 8 + (blockIdx.x & 7);
-    } else {
-        tile = blockIdx.x;
-        b = blockIdx.z;
-    }
+    layer_block_map(a.xcd_images, tile, b);
     if (tile >= a.ntiles) return;
     const int th_i = tile / a.tiles_w, tw_i = tile - th_i * a.tiles_w;
     const int r0 = th_i * CS_TH, c0 = tw_i * CS_TW;
     const int plane_bytes = a.Hi * a.Wi * 32;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + (size_t)b * 8 * (size_t)(a.Hi * a.Wi * 16)), 0, 8 * plane_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, CS_STEPS * CS_WST, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)a.gdn, 0, 65536 + 512, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = layer_rsrc(a.x + (size_t)b * 8 * (size_t)(a.Hi * a.Wi * 16), 8 * plane_bytes);
+    const __amdgpu_buffer_rsrc_t rw = layer_rsrc(a.w, CS_STEPS * CS_WST), rg = layer_rsrc(a.gdn, LAYER_GDN_BYTES);
 
     // ---- prologue: the first D slab groups (issued before anything is computed for the patch), the first patch chunk, beta^ and the bias
     int wsoff = 0;                                            // weight producer: byte offset of the next slab group in the stream
@@ -108,17 +97,14 @@ __global__ __launch_bounds__(512, 1) void conv_s2_gdn_f16k(const ConvS2Args a) {
         const int pr = rem / CS_PWH, pc = 2 * (rem - pr * CS_PWH) + par;
         const int ih = 2 * r0 - 2 + pr, iw = 2 * c0 - 2 + pc;
         const bool ok = pp < 2 * CS_HALF && pc < CS_PW && ih >= 0 && ih < a.Hi && iw >= 0 && iw < a.Wi;
-        goff[k] = ok ? (ih * a.Wi + iw) * 32 + hh * 16 : CS_OOB;
+        goff[k] = ok ? (ih * a.Wi + iw) * 32 + hh * 16 : LAYER_OOB;
     }
 
     if (!wrole) {
 #pragma unroll
         for (int k = 0; k < CS_NPI; ++k) dma_buf16(rx, lds + CS_PATCH0 + patch_instr(k) * 1024, goff[k], 0);
     }
-    if (tid < 128) {
-        reinterpret_cast<float*>(lds + CS_BETA)[tid] = reinterpret_cast<const float*>(a.gdn + 65536)[tid];
-        reinterpret_cast<float*>(lds + CS_BIAS)[tid] = a.bias != nullptr ? a.bias[tid] : 0.0f;
-    }
+    layer_beta_bias_to_lds(reinterpret_cast<float*>(lds + CS_BETA), reinterpret_cast<float*>(lds + CS_BIAS), a.gdn, a.bias, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -151,7 +137,7 @@ __global__ __launch_bounds__(512, 1) void conv_s2_gdn_f16k(const ConvS2Args a) {
     // wait; barrier.
     auto step = [&](auto slice, int t, bool last, int xs, bool gam) {
         constexpr int S = decltype(slice)::value;
-        const int wvo = wsoff < CS_STEPS * CS_WST ? wq * 1024 + lane * 16 : CS_OOB;      // slab groups past the end of the stream: zeros
+        const int wvo = wsoff < CS_STEPS * CS_WST ? wq * 1024 + lane * 16 : LAYER_OOB;      // slab groups past the end of the stream: zeros
         auto dma_pieces = [&](int first, int end) {
             if (wrole) {
 #pragma unroll
@@ -165,7 +151,7 @@ __global__ __launch_bounds__(512, 1) void conv_s2_gdn_f16k(const ConvS2Args a) {
                         if (gam) {
                             // piece p of gamma^'s hi plane = piece 2 p of the image; the slots past piece 31 write zeros behind it
                             const int p = (k0 + u) * 4 + wq;
-                            dma_buf16(rg, lds + pb + (p < 32 ? p : 32 + wq) * 1024, p < 32 ? lane * 16 : CS_OOB, p < 32 ? p * 2048 : 0);
+                            dma_buf16(rg, lds + pb + (p < 32 ? p : 32 + wq) * 1024, p < 32 ? lane * 16 : LAYER_OOB, p < 32 ? p * 2048 : 0);
                         } else {
                             dma_buf16(rx, lds + pb + patch_instr(k0 + u) * 1024, goff[k0 + u], xs);
                         }
@@ -201,9 +187,9 @@ __global__ __launch_bounds__(512, 1) void conv_s2_gdn_f16k(const ConvS2Args a) {
         });
         if (wrole) {
             wsoff += CS_WST;
-            pslot = pslot + CS_WST == CS_NWS * CS_WST ? 0 : pslot + CS_WST;
+            pslot = layer_ring_next<CS_NWS, CS_WST>(pslot);
         }
-        cslot = cslot + CS_WST == CS_NWS * CS_WST ? 0 : cslot + CS_WST;
+        cslot = layer_ring_next<CS_NWS, CS_WST>(cslot);
         // weight waves: the slab group of the next step has landed, the D - 1 groups after it stay in flight.
         // patch waves: at the end of a chunk the next chunk's patch (gamma^ at the end of the last one) has landed.
         if (wrole) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((CS_D - 1) * CS_T) : "memory");
@@ -241,10 +227,7 @@ struct ConvS2Plan {
     dim3 grid;
 };
 
-bool conv_s2_shape_ok(int B, int Hi, int Wi) {
-    // 32-bit offsets: an image's input is one buffer resource (the output is a quarter of it); grid limits
-    return B >= 1 && B <= 65535 && Hi >= 1 && Wi >= 1 && (long long)Hi * Wi * 256 < (1ll << 31);
-}
+bool conv_s2_shape_ok(int B, int Hi, int Wi) { return layer_shape_ok(B, Hi, Wi, 256); }      // the input (the output is a quarter of it)
 
 ConvS2Plan conv_s2_plan(int B, int Hi, int Wi) {
     ConvS2Plan p{};

@@ -23,6 +23,7 @@
 // LDS: 32 KiB gamma^ | 512 B beta^ | 512 B bias | 48 KiB weight ring | 2 patch buffers (39 KiB each for the 16 x 32 tile: the four
 // (channel block, k-half) planes of 18 x 34 records) = 159 KiB.
 #include "f16k_device.h"
+#include "f16k_layer.h"
 #include "masic_deconv.h"
 
 namespace {
@@ -39,7 +40,6 @@ struct DeconvArgs {
 
 constexpr int DI_D = 2, DI_NWS = DI_D + 1, DI_WST = 16384;      // weight look-ahead (steps), ring slots, bytes per step (2 taps x 2 blocks x 4 KiB)
 constexpr int DI_STEPS = 4 * (5 + 3 + 3 + 2);                   // slab groups of the whole stream
-constexpr int DI_OOB = 0x7ffffff0;                              // a buffer offset past every resource: the DMA writes zeros
 
 // NW waves (half of them stream weights, half the patch), NP 32-pixel sub-tiles per wave, tile = (32 / TW) NW NP rows of TW = 2^TWLOG pixels
 template <int NW, int NP, int TWLOG>
@@ -63,27 +63,15 @@ __global__ __launch_bounds__(NW * 64, 1) void deconv_igdn_f16k(const DeconvArgs 
     const bool wrole = wave < NWW;
     const int wq = wave & (NWW - 1);
 
-    // blockIdx.x, .z -> (tile, image): conv_f16k's maps -- with a multiple of 8 images, image 8 slot + k is walked tile by tile on XCD k
-    // (block ids go round-robin over the XCDs, gridDim.x is a multiple of 8), else tile = blockIdx.x, image = blockIdx.z.  The workgroups
-    // of a tile (blockIdx.y) are gridDim.x block ids apart: on one XCD and close in time, so their interleaved output pixels meet in one L2.
     int tile, b;
-    if (a.xcd_images) {
-        const int idx = (blockIdx.x >> 3) + (gridDim.x >> 3) * blockIdx.z;
-        const int slot = idx / (int)gridDim.x;
-        tile = idx - slot * (int)gridDim.x;
-        b = slot * 8 + (blockIdx.x & 7);
-    } else {
-        tile = blockIdx.x;
-        b = blockIdx.z;
-    }
+    layer_block_map(a.xcd_images, tile, b);
     if (tile >= a.ntiles) return;
     const int th_i = tile / a.tiles_w, tw_i = tile - th_i * a.tiles_w;
     const int r0 = th_i * TH, c0 = tw_i * TW;
     const int plane_bytes = a.Hi * a.Wi * 32;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + (size_t)b * 8 * (size_t)(a.Hi * a.Wi * 16)), 0, 8 * plane_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, DI_STEPS * DI_WST, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)a.gdn, 0, 65536 + 512, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = layer_rsrc(a.x + (size_t)b * 8 * (size_t)(a.Hi * a.Wi * 16), 8 * plane_bytes);
+    const __amdgpu_buffer_rsrc_t rw = layer_rsrc(a.w, DI_STEPS * DI_WST), rg = layer_rsrc(a.gdn, LAYER_GDN_BYTES);
 
     // Patch DMA instruction I of a chunk fills bytes [1024 I, 1024 I + 1024) of the patch buffer: records q = 64 I + lane of the image
     // [block ks][k-half hh][row][col], planes packed back to back.  The lane's source offset is recomputed where the instruction is issued
@@ -97,7 +85,7 @@ __global__ __launch_bounds__(NW * 64, 1) void deconv_igdn_f16k(const DeconvArgs 
         const int pr = pp / PW, pc = pp - pr * PW;
         const int ih = r0 - 1 + pr, iw = c0 - 1 + pc;
         const bool ok = !dead && plane < 4 && ih >= 0 && ih < a.Hi && iw >= 0 && iw < a.Wi;
-        dma_buf16(rx, lds + pbuf + Ie * 1024, ok ? (plane >> 1) * plane_bytes + (ih * a.Wi + iw) * 32 + (plane & 1) * 16 : DI_OOB, xs);
+        dma_buf16(rx, lds + pbuf + Ie * 1024, ok ? (plane >> 1) * plane_bytes + (ih * a.Wi + iw) * 32 + (plane & 1) * 16 : LAYER_OOB, xs);
     };
 
     // ---- prologue: gamma^ (hi plane: the even 1 KiB pieces), beta^, bias; the first D slab groups; the first patch chunk
@@ -127,27 +115,13 @@ __global__ __launch_bounds__(NW * 64, 1) void deconv_igdn_f16k(const DeconvArgs 
 #pragma unroll
         for (int k = 0; k < NPI; ++k) patch_dma(k, PATCH0, 0, false);
     }
-    if (tid < 128) {
-        reinterpret_cast<float*>(lds + BETA)[tid] = reinterpret_cast<const float*>(a.gdn + 65536)[tid];
-        reinterpret_cast<float*>(lds + BIAS)[tid] = a.bias != nullptr ? a.bias[tid] : 0.0f;
-    }
+    layer_beta_bias_to_lds(reinterpret_cast<float*>(lds + BETA), reinterpret_cast<float*>(lds + BIAS), a.gdn, a.bias, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
     // wave w owns all 128 output channels of its NP pixel sub-tiles (conv_f16k's layout: the GDN finds a pixel's channels in the wave's registers)
     f32x16 acc[NP][4];
-    auto acc_from_bias = [&]() {
-        const float* bp = reinterpret_cast<const float*>(lds + BIAS) + 4 * h;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 bv = *reinterpret_cast<const float4*>(bp + m * 32 + 8 * q);
-#pragma unroll
-                for (int n = 0; n < NP; ++n) { acc[n][m][4 * q + 0] = bv.x; acc[n][m][4 * q + 1] = bv.y; acc[n][m][4 * q + 2] = bv.z; acc[n][m][4 * q + 3] = bv.w; }
-            }
-    };
-    acc_from_bias();
+    layer_acc_from_bias<NP>(acc, reinterpret_cast<const float*>(lds + BIAS), h);
 
     const int jr = j >> TWLOG, jc = j & (TW - 1);
     int bl[NP];                                               // lane part of the B-fragment addresses
@@ -162,7 +136,7 @@ __global__ __launch_bounds__(NW * 64, 1) void deconv_igdn_f16k(const DeconvArgs 
     // slab group of step g + D, patch waves: slice S of the next chunk -- go out behind the MFMAs of each k-step; counted wait; barrier.
     auto step = [&](auto slice, int t, int ntw, int ntaps, bool last, int xs, bool dead) {
         constexpr int S = decltype(slice)::value;
-        const int wvo = wsoff < DI_STEPS * DI_WST ? lane * 16 : DI_OOB;      // slab groups past the end of the stream: zeros
+        const int wvo = wsoff < DI_STEPS * DI_WST ? lane * 16 : LAYER_OOB;      // slab groups past the end of the stream: zeros
         auto dma_pieces = [&](int first, int end) {
             if (wrole) {
 #pragma unroll
@@ -225,9 +199,9 @@ __global__ __launch_bounds__(NW * 64, 1) void deconv_igdn_f16k(const DeconvArgs 
                 wsoff = wpi < p_count ? phase_first(np) * DI_WST : DI_STEPS * DI_WST;
                 wleft = wpi < p_count ? phase_steps(np) : 1 << 30;
             }
-            pslot = pslot + DI_WST == DI_NWS * DI_WST ? 0 : pslot + DI_WST;
+            pslot = layer_ring_next<DI_NWS, DI_WST>(pslot);
         }
-        cslot = cslot + DI_WST == DI_NWS * DI_WST ? 0 : cslot + DI_WST;
+        cslot = layer_ring_next<DI_NWS, DI_WST>(cslot);
         // weight waves: the slab group of the next step has landed, the D - 1 groups after it stay in flight (stores of an epilogue in
         // between only make the wait stricter).  patch waves: at the end of a chunk the next chunk's patch has landed.
         if (wrole) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DI_D - 1) * WI) : "memory");
@@ -266,7 +240,7 @@ __global__ __launch_bounds__(NW * 64, 1) void deconv_igdn_f16k(const DeconvArgs 
                 for (int m = 0; m < 4; ++m) store_f16k_tile(acc[n][m], yb + (size_t)(2 * m) * op16, op16);
             }
         }
-        if (!lastp) acc_from_bias();
+        if (!lastp) layer_acc_from_bias<NP>(acc, reinterpret_cast<const float*>(lds + BIAS), h);
     }
 }
 
@@ -280,10 +254,7 @@ struct DeconvPlan {
 
 constexpr size_t di_lds(int TH, int TW) { return 32768 + 1024 + DI_NWS * DI_WST + 2 * (size_t)((4 * (TH + 2) * (TW + 2) + 63) / 64) * 1024; }
 
-bool deconv_shape_ok(int B, int Hi, int Wi) {
-    // 32-bit offsets: an image's input is one buffer resource; grid limits
-    return B >= 1 && B <= 65535 && Hi >= 1 && Wi >= 1 && (long long)Hi * Wi * 256 * 4 < (1ll << 31);
-}
+bool deconv_shape_ok(int B, int Hi, int Wi) { return layer_shape_ok(B, Hi, Wi, 4 * 256); }      // the output: four pixels per input pixel
 bool deconv_form_ok(int tile, int split) { return tile >= 0 && tile <= 2 && (split == 0 || split == 1 || split == 2 || split == 4); }
 
 DeconvPlan deconv_plan(int B, int Hi, int Wi, int tile, int split) {

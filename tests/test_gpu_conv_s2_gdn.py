@@ -23,11 +23,12 @@ import pytest
 import torch
 
 from tests import f16k_ref as R
+from tests import layer_kernel_cases as L
+from tests.layer_kernel_cases import DEV, one_product as _one_product
 from tests.test_gpu_f16k_rows import _gdn_params
 from tests.util import rel_err
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 SHAPES = [(1, 5, 7), (2, 33, 130), (8, 16, 64), (9, 16, 64), (8, 32, 128)]
 SEED = 5200
 NAME = "conv_s2_gdn_f16k"
@@ -38,38 +39,14 @@ def _case(B, H, W):
     return R.case_of((B, 128, H, W, 128, 5, 2, 0, 0), flags=R.F16K_GDN)
 
 
-class _one_product:
-    def __enter__(self):
-        from masic_amd import ops
-        self.was = ops._FUSED_GDN_PRODUCTS
-        ops.set_fused_gdn_products(1)
-
-    def __exit__(self, *exc):
-        from masic_amd import ops
-        ops.set_fused_gdn_products(self.was)
-        return False
-
-
 def _prefilled(shape):
-    B, H, W = shape
-    Ho, Wo = R.out_hw(_case(*shape))
-    return torch.full((B * 128 * Ho * Wo,), R.PREFILL_BITS, dtype=torch.int16, device=DEV)
+    return L.prefilled(_case(*shape))
 
 
 @functools.lru_cache(maxsize=None)
 def _operands(shape):
     """x16, packed weights, bias, packed GDN on the device and the output of the existing kernel (computed once per shape, never written)"""
-    from masic_amd import ops
-    c = _case(*shape)
-    x, w, bias = R.inputs(c, SEED + sum(shape))
-    beta, gamma = _gdn_params(SEED)
-    d = R.desc_of(c)
-    x16, wp, bd = R.to_f16k(x).to(DEV), ops.pack_conv_f16k_weight(w.to(DEV), d), bias.to(DEV)
-    gp = ops.pack_gdn_f16k(beta.to(DEV), gamma.to(DEV))
-    with _one_product():
-        want = ops.conv2d_f16k(x16, wp, bd, d, gdn=(gp, False), out16=_prefilled(shape))
-    torch.cuda.synchronize()
-    return x16, wp, bd, gp, want.cpu()
+    return L.operands(_case(*shape), SEED + sum(shape), SEED, False, out16=_prefilled(shape))
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=["x".join(map(str, s)) for s in SHAPES])

@@ -23,11 +23,12 @@ import pytest
 import torch
 
 from tests import f16k_ref as R
+from tests import layer_kernel_cases as L
+from tests.layer_kernel_cases import DEV, one_product as _one_product
 from tests.test_gpu_f16k_rows import _gdn_params
 from tests.util import rel_err
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 SHAPES = [(1, 8, 8), (2, 20, 36), (8, 16, 32), (9, 16, 32), (8, 32, 32)]
 SEED = 4100
 
@@ -36,32 +37,10 @@ def _case(B, H, W):
     return R.case_of((B, 128, H, W, 128, 5, 2, 1, 0), flags=R.F16K_GDN)
 
 
-class _one_product:
-    def __enter__(self):
-        from masic_amd import ops
-        self.was = ops._FUSED_GDN_PRODUCTS
-        ops.set_fused_gdn_products(1)
-
-    def __exit__(self, *exc):
-        from masic_amd import ops
-        ops.set_fused_gdn_products(self.was)
-        return False
-
-
 @functools.lru_cache(maxsize=None)
 def _operands(shape):
     """x16, packed weights, bias, packed GDN on the device and the output of the existing kernel (computed once per shape, never written)"""
-    from masic_amd import ops
-    c = _case(*shape)
-    x, w, bias = R.inputs(c, SEED + sum(shape))
-    beta, gamma = _gdn_params(SEED)
-    d = R.desc_of(c)
-    x16, wp, bd = R.to_f16k(x).to(DEV), ops.pack_conv_f16k_weight(w.to(DEV), d), bias.to(DEV)
-    gp = ops.pack_gdn_f16k(beta.to(DEV), gamma.to(DEV))
-    with _one_product():
-        want = ops.conv2d_f16k(x16, wp, bd, d, gdn=(gp, True))
-    torch.cuda.synchronize()
-    return x16, wp, bd, gp, want.cpu()
+    return L.operands(_case(*shape), SEED + sum(shape), SEED, True)
 
 
 NAMES = {1: "deconv_igdn_f16k<8, 2, 5>", 2: "deconv_igdn_f16k<8, 1, 5>"}
