@@ -34,6 +34,7 @@ from masic_amd.streams import ForkJoin as _ForkJoin
 from masic_amd import fp8 as _fp8
 from masic_amd import deconv as _deconv
 from masic_amd import conv_s2 as _conv_s2
+from masic_amd.bands import check_band_rows as _check_band_rows
 from masic_amd.f16k import F16K as _F16K, F8K as _F8K
 
 _RELU, _LEAKY, _NONE = _hip.ACT_RELU, _hip.ACT_LEAKY, _hip.ACT_NONE
@@ -720,9 +721,12 @@ class HSIC(CompressionModel):
         t = seq[2].run(t, act=_LEAKY)
         return seq[4].run(t, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
 
-    def _context(self, ctx, y, out, out_coff=0, gate=None, gate_c=0, round16=None):
+    def _context(self, ctx, y, out, out_coff=0, gate=None, gate_c=0, round16=None, band_rows=0):
         """Eval-mode context model: masked conv of round(y) into a slice of the concat buffer (`out` as in _hyper_up; optionally gated).
-        round16: bf16(round(y)) as an F16K, where the layer that produced y wrote it."""
+        round16: bf16(round(y)) as an F16K, where the layer that produced y wrote it.  band_rows: the row bands of the bitstream coder
+        (_context_bands)."""
+        if 0 < band_rows < y.shape[-2]:
+            return self._context_bands(ctx, y, out, out_coff, gate, gate_c, band_rows)
         if _bf16_inference(y, ctx.weight):
             ctx.zero_masked_taps()
             r = _f16k_chain((ctx,), (_NONE,), y if round16 is None else round16, in_op=_hip.INOP_ROUND, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
@@ -731,6 +735,27 @@ class HSIC(CompressionModel):
         if isinstance(out, _F16K):
             return out.fill_from_nchw(ctx.run(y, in_op=_hip.INOP_ROUND, gate=gate, gate_c=gate_c))
         return ctx.run(y, in_op=_hip.INOP_ROUND, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
+
+    def _context_bands(self, ctx, y, out, out_coff, gate, gate_c, S):
+        """The context model of the full-latent parameter form with the latent cut into bands of S rows that do not see across their top
+        edge (masic_amd.codec.wavefront_steps): the bands as images of one call of _context.  h is padded to a multiple of S with zero
+        rows at the bottom (the mask is causal: they reach no row above them), [B, M, T S, w] is viewed as [B T, M, S, w], the
+        convolution's own zero padding above each image is the band top, and the rows go back in place.  The gate multiplies in
+        float32 as in the layers' epilogues.  Encoder and decoder both come through here, so their tables agree."""
+        B, M, h, w = y.shape
+        T = -(-h // S)
+        yb = F.pad(y, (0, 0, 0, T * S - h)).view(B, M, T, S, w).permute(0, 2, 1, 3, 4).reshape(B * T, M, S, w).contiguous()
+        cb = self._context(ctx, yb, None)
+        C = cb.shape[1]
+        c = cb.view(B, T, C, S, w).permute(0, 2, 1, 3, 4).reshape(B, C, T * S, w)[:, :, :h]
+        if gate is not None:
+            c = c * gate[:, gate_c:gate_c + 1]
+        if isinstance(out, _F16K):
+            return out.fill_from_nchw(c.contiguous())
+        if out is None:
+            return c.contiguous()
+        out[:, out_coff:out_coff + C] = c
+        return out
 
     def _needs_graph(self):
         return self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.encoder1.parameters())
@@ -1076,7 +1101,7 @@ class HSIC(CompressionModel):
 
     class _PixelParams:
         """The same layers, with bf16 operands, evaluated on a LIST OF PIXELS of B pairs by the kernels of masic_amd/csrc/skinny.hip --
-        `run(pix, step, list_stride, npix)` reads the latent from `y16` (F16K; the device decoder writes it, the encoder fills it with
+        `run(pix, step, list_stride, npix, band_rows=0)` reads the latent from `y16` (F16K; the device decoder writes it, the encoder fills it with
         `set_latent`) and writes `sigma`, `mu`, `logits` ([B, K*M, h, w] float32) at those pixels.  Encoder (all pixels in one launch
         per layer) and decoder (one coding wavefront per launch) run the same kernels with the same k order, and a pixel's result does
         not depend on its tile mates: bit-identical parameters on both sides."""
@@ -1089,9 +1114,10 @@ class HSIC(CompressionModel):
         def set_latent(self, y_hat):
             _hip.nchw_to_f16k_view(y_hat.contiguous(), self.y16, self._sk["M16"], 0)
 
-        def run(self, pix, step, list_stride, npix):
+        def run(self, pix, step, list_stride, npix, band_rows=0):
             k = self._sk
-            _hip.skinny_group([k["ctx"]], pix, step, list_stride, npix, k["h"], k["w"], ctx=True, gate=k["gate"], gate_c=1, nimg=k["B"])
+            _hip.skinny_group([k["ctx"]], pix, step, list_stride, npix, k["h"], k["w"], ctx=True, gate=k["gate"], gate_c=1, nimg=k["B"],
+                              band_rows=band_rows)
             for layers in k["heads"]:
                 _hip.skinny_group(layers, pix, step, list_stride, npix, k["h"], k["w"], nimg=k["B"])
 
@@ -1128,7 +1154,7 @@ class HSIC(CompressionModel):
         ctxl = dict(x=y16, wp=wpc, bias=None if ctx.bias is None else ctx.bias.detach(), Cin=M16, Cout=2 * M, act=_NONE, y16=cat16.buf, out_ctot=C, out_coff=2 * M)
         return dict(y16=y16, M16=M16, sigma=outs[0], mu=outs[1], logits=outs[2], ctx=ctxl, heads=heads, h=h, w=w, gate=gate, B=B)
 
-    def _left_params_fn(self, z1_hat, h, w):
+    def _left_params_fn(self, z1_hat, h, w, band_rows=0):
         M = self.M
         # (bf16 operands: the concat buffer is F16K, as in the eval forward -- the context model writes its slice as bf16 records and the
         # grouped head GEMMs read the buffer directly: no conversion pass over the 768-channel buffer per coding step)
@@ -1137,12 +1163,13 @@ class HSIC(CompressionModel):
         self._hyper_up(self.h_s1_up, z1_hat, **self._slice(cat1, cat16, 0, 2 * M))
 
         def params(y_hat):
-            self._context(self.context_prediction1, y_hat, **self._slice(cat1, cat16, 2 * M, 2 * M))
+            self._context(self.context_prediction1, y_hat, band_rows=band_rows, **self._slice(cat1, cat16, 2 * M, 2 * M))
             return self._h_s1_same_resolution.heads(cat1 if cat16 is None else cat16)
         return HSIC._PairParams(params, cat16)
 
-    def _right_params_fn(self, z2_hat, x1_hat, m_fwd, m_back, H, W, h, w):
-        """-> (params_fn, x1_hat_warp): everything of the right view's tables that the decoder knows before y2."""
+    def _right_params_fn(self, z2_hat, x1_hat, m_fwd, m_back, H, W, h, w, band_rows=0):
+        """-> (params_fn, x1_hat_warp): everything of the right view's tables that the decoder knows before y2.  band_rows: the row
+        bands of the full-latent form's context model (the pixel-list form takes them per launch)."""
         M = self.M
         dev = z2_hat.device
         x1_mask_R = _hip.warp_perspective(None, m_fwd, (H, W), ones_like=(1, H, W))
@@ -1158,7 +1185,7 @@ class HSIC(CompressionModel):
             _hip.quantize(y1_warp, "dequantize", out=cat2, out_coff=4 * M, gate=gates, gate_c=2)
 
         def params(y_hat):
-            self._context(self.context_prediction2, y_hat, gate=gates, gate_c=1, **self._slice(cat2, cat16, 2 * M, 2 * M))
+            self._context(self.context_prediction2, y_hat, gate=gates, gate_c=1, band_rows=band_rows, **self._slice(cat2, cat16, 2 * M, 2 * M))
             return self._h_s2_same_resolution.heads(cat2 if cat16 is None else cat16)
         return HSIC._PairParams(params, cat16, gates.contiguous()), x1_hat_warp
 
@@ -1175,11 +1202,14 @@ class HSIC(CompressionModel):
     # several bf16 layers pick or order their kernels by batch shape, so their bits at B > 1 differ from those at B = 1 -- and the
     # coding-step loops, where the time goes, run over all B pairs at once (codec.encode_views / decode_views).  float32 / fp8 operands
     # (no pixel-list form) code the pairs one after the other.
-    def compress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu"):
+    def compress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu", band_rows=0):
         """Writes <output_name>.npz (picture size, z1 / z2 strings, channel flags, minmax: the reference's header layout,
         :916-948) and <output_name>.bin (the y1 / y2 streams, masic_amd/codec.py) under output_path.  `device` is accepted
-        for signature compatibility; tensors stay where x1 is."""
-        out = self._compress_pairs("HSIC.compress", x1, x2, h_matrix, [output_name], output_path, batch=False)
+        for signature compatibility; tensors stay where x1 is.  band_rows (0 .. 255; 0: off, today's file): code the y latents in
+        independent bands of that many latent rows -- w + 3 (band_rows - 1) decode steps instead of w + 3 (h - 1), a slightly larger
+        .bin that carries the value ("MSR3"; decompress reads it from there)."""
+        band_rows = _check_band_rows(band_rows, "HSIC.compress")
+        out = self._compress_pairs("HSIC.compress", x1, x2, h_matrix, [output_name], output_path, batch=False, band_rows=band_rows)
         out["bytes"], out["bpp"] = out["bytes"][0], out["bpp"][0]
         return out
 
@@ -1188,20 +1218,23 @@ class HSIC(CompressionModel):
         :1308-1310) and may be None; tensors are created on the model's device."""
         return self._decompress_pairs("HSIC.decompress", [output_name], h_matrix, output_path, batch=False)
 
-    def compress_batch(self, x1, x2, h_matrix, output_names, output_path=""):
+    def compress_batch(self, x1, x2, h_matrix, output_names, output_path="", band_rows=0):
         """compress for B pairs: x1, x2 [B, 3, H, W], h_matrix [B, 3, 3], B output names.  Writes <name_i>.npz / <name_i>.bin, byte for
         byte what compress(x1[i:i+1], x2[i:i+1], h_matrix[i:i+1], name_i) writes, and returns compress's dict with [B, ...] tensors
-        ("bytes" / "bpp": lists of B)."""
-        return self._compress_pairs("HSIC.compress_batch", x1, x2, h_matrix, output_names, output_path, batch=True)
+        ("bytes" / "bpp": lists of B).  band_rows: as in compress, one value for the batch."""
+        band_rows = _check_band_rows(band_rows, "HSIC.compress_batch")
+        return self._compress_pairs("HSIC.compress_batch", x1, x2, h_matrix, output_names, output_path, batch=True, band_rows=band_rows)
 
     def decompress_batch(self, output_names, h_matrix, output_path=""):
-        """decompress for B pairs written by compress or compress_batch (one picture size, the current operand mode, in the fp8 mode
-        one activation-scale table) -> decompress's dict with [B, ...] tensors; slice i equals decompress of pair i alone."""
+        """decompress for B pairs written by compress or compress_batch (one picture size, one band_rows, the current operand mode, in
+        the fp8 mode one activation-scale table) -> decompress's dict with [B, ...] tensors; slice i equals decompress of pair i alone."""
         return self._decompress_pairs("HSIC.decompress_batch", output_names, h_matrix, output_path, batch=True)
 
     @staticmethod
-    def _write_pair(output_path, output_name, H, W, views, fp8_table):
-        """The two files of one pair; views: per view (z string, channel flags, minmax, framed y streams).  -> bytes written."""
+    def _write_pair(output_path, output_name, H, W, views, fp8_table, band_rows=0):
+        """The two files of one pair; views: per view (z string, channel flags, minmax, framed y streams).  -> bytes written.
+        band_rows = 0: magic "MSR2", bytes 6-7 zero; > 0: magic "MSR3" with byte 6 = band_rows, so that a build without the row bands
+        refuses the file at the magic."""
         import os
         from masic_amd import codec, nn as _mnn
         for s_z, _, mm, _ in views:
@@ -1216,7 +1249,8 @@ class HSIC(CompressionModel):
                 f.write(s_z)
         out2 = os.path.join(output_path, str(output_name) + ".bin")
         with open(out2, "wb") as f:
-            f.write(codec.MAGIC + bytes([{"f32": 0, "bf16": 1, "fp8": 2}[_mnn.get_precision()], 1 if fp8_table is not None else 0, 0, 0]))
+            f.write((codec.MAGIC_BANDS if band_rows else codec.MAGIC)
+                    + bytes([{"f32": 0, "bf16": 1, "fp8": 2}[_mnn.get_precision()], 1 if fp8_table is not None else 0, band_rows, 0]))
             if fp8_table is not None:
                 # the coding tables of the fp8 mode depend on the activation scales of masic_amd.fp8.calibrate, which live outside
                 # state_dict(): the stream carries them, so any decoder holding the same weights rebuilds the same tables
@@ -1228,7 +1262,8 @@ class HSIC(CompressionModel):
 
     def _read_pair(self, output_path, output_name, who):
         """The two files of one pair -> H, W, per view (z string, minmax, coded channels as a list), per view the framed
-        y streams, the fp8 scale table or None.  ValueError for a foreign stream, one written in another operand mode, or a
+        y streams, the fp8 scale table or None, band_rows (0 for an "MSR2" file, whose bytes 6-7 are not read; byte 6 of an "MSR3"
+        file, where 0 is an error).  ValueError for a foreign stream, one written in another operand mode, or a
         container that is cut short, holds impossible length fields or carries bytes after its last field."""
         import os
         from masic_amd import codec, nn as _mnn
@@ -1251,10 +1286,13 @@ class HSIC(CompressionModel):
                 raise ValueError(f"{who}: bytes follow the second view in the .npz header file")
         with open(os.path.join(output_path, str(output_name) + ".bin"), "rb") as f:
             head = f.read(8)
-            if head[:4] != codec.MAGIC:
+            if head[:4] not in (codec.MAGIC, codec.MAGIC_BANDS):
                 raise ValueError(f"{who}: not a stream of this library (magic %r)" % head[:4])
             if len(head) != 8:
                 raise ValueError(f"{who}: truncated file: the .bin header needs 8 bytes, {len(head)} are there")
+            band_rows = head[6] if head[:4] == codec.MAGIC_BANDS else 0
+            if head[:4] == codec.MAGIC_BANDS and band_rows == 0:
+                raise ValueError(f"{who}: an MSR3 stream must carry its band_rows (1 .. 255) in byte 6 of the .bin header, found 0")
             if head[4] != {"f32": 0, "bf16": 1, "fp8": 2}[_mnn.get_precision()]:
                 raise ValueError(f"{who}: the stream was written in the %s operand mode; the coding tables depend on it "
                                  "(masic_amd.nn.set_precision)" % ("f32", "bf16", "fp8")[head[4] if head[4] < 3 else 0])
@@ -1268,7 +1306,7 @@ class HSIC(CompressionModel):
                 streams = codec.split_views(f.read(), 2)
             except ValueError as e:
                 raise ValueError(f"{who}: {e}") from e
-        return H, W, views, streams, fp8_table
+        return H, W, views, streams, fp8_table, band_rows
 
     def _batch_params(self, parts, head, ctx, C, h, w):
         """One _PixelParams over the B >= 1 pairs of `parts` (_PairParams): their concat buffers and gates stacked, the pixel-list
@@ -1280,33 +1318,34 @@ class HSIC(CompressionModel):
         sk = self._skinny_params(head, ctx, cat, gate)
         return None if sk is None else HSIC._PixelParams(sk)
 
-    def _code_views(self, parts, head, ctx, C, y_hat, chans, minmaxes, bound, names):
+    def _code_views(self, parts, head, ctx, C, y_hat, chans, minmaxes, bound, names, band_rows=0):
         """compress side of one view over the pairs -> per pair the framed y streams.  names: the pairs' names for error messages (a
         batch) or None."""
         from masic_amd import codec
         h, w = y_hat.shape[-2:]
         bp = self._batch_params(parts, head, ctx, C, h, w)
         if bp is not None:
-            return codec.encode_views(bp, y_hat, self.M, self.K, chans, minmaxes, bound, names=names)
+            return codec.encode_views(bp, y_hat, self.M, self.K, chans, minmaxes, bound, names=names, band_rows=band_rows)
         out = []
         for i, p in enumerate(parts):
             with _pair_errors(i, names):
-                out += codec.encode_views(p, y_hat[i:i + 1], self.M, self.K, chans[i:i + 1], minmaxes[i:i + 1], bound)
+                out += codec.encode_views(p, y_hat[i:i + 1], self.M, self.K, chans[i:i + 1], minmaxes[i:i + 1], bound, band_rows=band_rows)
         return out
 
-    def _decode_views(self, parts, head, ctx, C, blobs, hw, chans, minmaxes, bound, names, dev):
+    def _decode_views(self, parts, head, ctx, C, blobs, hw, chans, minmaxes, bound, names, dev, band_rows=0):
         """decompress side of one view over the pairs -> y_hat [B, M, h, w]."""
         from masic_amd import codec
         bp = self._batch_params(parts, head, ctx, C, *hw)
         if bp is not None:
-            return codec.decode_views(bp, blobs, hw, self.M, self.K, chans, minmaxes, bound, dev, names=names)
+            return codec.decode_views(bp, blobs, hw, self.M, self.K, chans, minmaxes, bound, dev, names=names, band_rows=band_rows)
         out = []
         for i, p in enumerate(parts):
             with _pair_errors(i, names):
-                out.append(codec.decode_views(p, blobs[i:i + 1], hw, self.M, self.K, chans[i:i + 1], minmaxes[i:i + 1], bound, dev))
+                out.append(codec.decode_views(p, blobs[i:i + 1], hw, self.M, self.K, chans[i:i + 1], minmaxes[i:i + 1], bound, dev,
+                                              band_rows=band_rows))
         return torch.cat(out)
 
-    def _compress_pairs(self, who, x1, x2, h_matrix, output_names, output_path, batch):
+    def _compress_pairs(self, who, x1, x2, h_matrix, output_names, output_path, batch, band_rows=0):
         from masic_amd import nn as _mnn
         x1, x2 = x1.contiguous(), x2.contiguous()
         B, _, H, W = x1.shape
@@ -1335,10 +1374,10 @@ class HSIC(CompressionModel):
                 pr.append(dict(x1=a, x2=b_, m_fwd=m_fwd, m_back=m_back, z1_strings=z1_strings, z1_hat=z1_hat, y1_hat=y1_hat, flag1=flag1,
                                minmax1=minmax1))
             h, w = pr[0]["y1_hat"].shape[-2:]
-            s_y1 = self._code_views([self._left_params_fn(p["z1_hat"], h, w) for p in pr], self._h_s1_same_resolution,
+            s_y1 = self._code_views([self._left_params_fn(p["z1_hat"], h, w, band_rows) for p in pr], self._h_s1_same_resolution,
                                     self.context_prediction1, 4 * M, torch.cat([p["y1_hat"] for p in pr]),
                                     [np.flatnonzero(p["flag1"]).tolist() for p in pr], [p["minmax1"] for p in pr],
-                                    self.gaussian1._scale_bound_value, tags)
+                                    self.gaussian1._scale_bound_value, tags, band_rows)
             parts2 = []
             for p in pr:                # right view, per pair
                 p["x1_hat"] = self.decoder1.reconstruct(p["y1_hat"])
@@ -1348,15 +1387,16 @@ class HSIC(CompressionModel):
                 p["z2_hat"] = self.entropy_bottleneck2.decompress(p["z2_strings"], z2.size()[-2:])
                 p["y2_hat"] = _hip.quantize(y2, "dequantize")
                 p["flag2"], p["minmax2"] = self._channel_flags(p["y2_hat"])
-                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w)
+                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w, band_rows)
                 parts2.append(params2)
             s_y2 = self._code_views(parts2, self._h_s2_same_resolution, self.context_prediction2, 5 * M, torch.cat([p["y2_hat"] for p in pr]),
                                     [np.flatnonzero(p["flag2"]).tolist() for p in pr], [p["minmax2"] for p in pr],
-                                    self.gaussian2._scale_bound_value, tags)
+                                    self.gaussian2._scale_bound_value, tags, band_rows)
             for p in pr:
                 p["x2_hat"] = self.decoder2(p["y2_hat"], p["x1_hat_warp"])
         nbytes = [self._write_pair(output_path, names[i], H, W, ((p["z1_strings"][0], p["flag1"], p["minmax1"], s_y1[i]),
-                                                                  (p["z2_strings"][0], p["flag2"], p["minmax2"], s_y2[i])), fp8_table)
+                                                                  (p["z2_strings"][0], p["flag2"], p["minmax2"], s_y2[i])), fp8_table,
+                                    band_rows)
                   for i, p in enumerate(pr)]
         out = {k: torch.cat([p[k] for p in pr]) for k in ("x1_hat", "x2_hat", "y1_hat", "y2_hat", "z1_hat", "z2_hat")}
         out.update(bytes=nbytes, bpp=[n * 8.0 / (H * W) for n in nbytes])
@@ -1380,6 +1420,9 @@ class HSIC(CompressionModel):
                 raise ValueError(f"{who}: pair {i} ({names[i]}) is {f[0]}x{f[1]}, pair 0 is {H}x{W}: one picture size per batch")
             if f[4] != files[0][4]:
                 raise ValueError(f"{who}: pair {i} ({names[i]}) carries other fp8 activation scales than pair 0: one calibration per batch")
+            if f[5] != files[0][5]:
+                raise ValueError(f"{who}: pair {i} ({names[i]}) was coded with band_rows {f[5]}, pair 0 with {files[0][5]}: one band_rows per batch")
+        band_rows = files[0][5]
         self._codec_check(who, H, W)
         h, w = H // 16, W // 16
         views = [f[2] for f in files]
@@ -1390,17 +1433,18 @@ class HSIC(CompressionModel):
                 pr.append(dict(m_fwd=m_fwd, m_back=m_back,
                                z1_hat=self.entropy_bottleneck1.decompress([views[i][0][0]], (h // 4, w // 4)),
                                z2_hat=self.entropy_bottleneck2.decompress([views[i][1][0]], (h // 4, w // 4))))
-            y1_hat = self._decode_views([self._left_params_fn(p["z1_hat"], h, w) for p in pr], self._h_s1_same_resolution,
+            y1_hat = self._decode_views([self._left_params_fn(p["z1_hat"], h, w, band_rows) for p in pr], self._h_s1_same_resolution,
                                         self.context_prediction1, 4 * M, [f[3][0] for f in files], (h, w), [v[0][2] for v in views],
-                                        [v[0][1] for v in views], self.gaussian1._scale_bound_value, tags, dev)
+                                        [v[0][1] for v in views], self.gaussian1._scale_bound_value, tags, dev, band_rows)
             parts2 = []
             for i, p in enumerate(pr):
                 p["y1_hat"] = y1_hat[i:i + 1]
                 p["x1_hat"] = self.decoder1.reconstruct(p["y1_hat"])
-                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w)
+                params2, p["x1_hat_warp"] = self._right_params_fn(p["z2_hat"], p["x1_hat"], p["m_fwd"], p["m_back"], H, W, h, w, band_rows)
                 parts2.append(params2)
             y2_hat = self._decode_views(parts2, self._h_s2_same_resolution, self.context_prediction2, 5 * M, [f[3][1] for f in files], (h, w),
-                                        [v[1][2] for v in views], [v[1][1] for v in views], self.gaussian2._scale_bound_value, tags, dev)
+                                        [v[1][2] for v in views], [v[1][1] for v in views], self.gaussian2._scale_bound_value, tags, dev,
+                                        band_rows)
             for i, p in enumerate(pr):
                 p["y2_hat"] = y2_hat[i:i + 1]
                 p["x2_hat"] = self.decoder2(p["y2_hat"], p["x1_hat_warp"])

@@ -21,7 +21,7 @@ one pass per wavefront.  The encoder's rANS chains run on the device too, one la
 (masic_rans_encode_channels_batch), and a second kernel frames the pairs: only the flags, the pairs' offsets and the finished bytes
 cross to the host.  The host coder (encode_channels) is kept as its byte-for-byte checker (encode_views(coder="host")).
 Container (.bin): b"MSR2", u8 precision id (0 f32 / 1 bf16 / 2 fp8 operands: the tables depend on it), u8 flags (bit 0: an
-activation-scale table follows), 2 pad bytes, [u32 length + the fp8 mode's calibration table as JSON, masic_amd/fp8.py], then per
+activation-scale table follows), 2 pad bytes (b"MSR3": u8 band_rows >= 1 -- the row bands of wavefront_steps -- and 1 pad byte), [u32 length + the fp8 mode's calibration table as JSON, masic_amd/fp8.py], then per
 view u32 number of channel streams n, n x u32 stream lengths in bytes, the streams back to back (round 2's "MSR1" had one stream per view).  The .npz header keeps the reference's layout (MASIC.py:916-948).
 The container carries no checksum; what is read back is checked instead: split_views parses the framing strictly, and after the last
 coding step every channel stream must have consumed exactly its words and left the coder at 2^31, the state every encoder starts from
@@ -34,22 +34,35 @@ import torch
 from ._lib import check, lib
 
 MAGIC = b"MSR2"
+MAGIC_BANDS = b"MSR3"            # the same layout with byte 6 = band_rows >= 1 (wavefront_steps)
 
 
 import functools
 
 
 @functools.lru_cache(maxsize=16)
-def wavefront_steps(h, w):
-    """Pixel indices (i * w + j), rows ascending, of each wavefront t = j + 3 i.  (A function of the latent's shape alone: cached -- the
-    125 numpy selections of a 32 x 32 latent were 0.5 ms of every encode_views / decode_views call.  Callers must not write to the arrays.)"""
+def _wavefront_steps(h, w, S):
     ii = np.arange(h)
     steps = []
-    for t in range(w + 3 * (h - 1)):
-        j = t - 3 * ii
+    for t in range(w + 3 * (S - 1)):
+        j = t - 3 * (ii % S)
         keep = (j >= 0) & (j < w)
         steps.append((ii[keep] * w + j[keep]).astype(np.int32))
     return steps
+
+
+def wavefront_steps(h, w, band_rows=0):
+    """Pixel indices (i * w + j), rows ascending, of each wavefront t = j + 3 i.  (A function of the latent's shape alone: cached -- the
+    125 numpy selections of a 32 x 32 latent were 0.5 ms of every encode_views / decode_views call.  Callers must not write to the arrays.)
+    band_rows = S in 1 .. h - 1: the latent's rows are cut into bands of S rows whose context model does not look across the band's top
+    edge (masic_amd/bands.py), the bands' wavefronts run side by side -- step t holds the pixels with j + 3 (i mod S) = t, still at most
+    one per row, and there are w + 3 (S - 1) steps.  0, or S >= h (one band): the lists above, the same cached object."""
+    return _wavefront_steps(h, w, band_rows if 0 < band_rows < h else h)
+
+
+def effective_band_rows(h, band_rows):
+    """band_rows as the kernels and step lists take it: 0 when one band covers the latent."""
+    return band_rows if 0 < band_rows < h else 0
 
 
 def _p(t):
@@ -304,28 +317,31 @@ def _first_streams(chans):
     return [0] + np.cumsum([len(ch) for ch in chans]).tolist()
 
 
-def encode_views(params_fn, y_hat, M, K, chans, minmaxes, scale_bound, names=None, coder="device"):
+def encode_views(params_fn, y_hat, M, K, chans, minmaxes, scale_bound, names=None, coder="device", band_rows=0):
     """One pass over B pairs: y_hat [B, M, h, w]; chans / minmaxes: pair b's coded channels (int sequence) and alphabet half-width;
     params_fn: see _pixel_list_form.  Parameters of every pixel -> (start, freq) of every coded symbol in wavefront order -> per pair
     u32 n, n x u32 lengths and one rANS stream per coded channel.  A pair's bytes do not depend on its batch mates (the same parameters
     bit for bit: a pixel's result depends on its own operands only; the same table arithmetic on them).
     coder: "device" codes and frames the streams where the table is (one lane per channel stream; the flags, the pairs' offsets and the
     finished bytes are all that cross to the host); "host" copies the table to the host and runs encode_channels per pair -- the same
-    bytes, kept as the checker of the device coder."""
+    bytes, kept as the checker of the device coder.
+    band_rows: the row bands of wavefront_steps -- the order of the pass and the band top of the context model (params_fn.run's
+    band_rows; a full-latent params_fn must evaluate the same band top itself); the decoder must be given the same value."""
     if coder not in ("device", "host"):
         raise ValueError(f"masic_amd.codec.encode_views: coder={coder!r} (\"device\" or \"host\")")
     B, _, h, w = y_hat.shape
     HW, dev = h * w, y_hat.device
     pixel_list = _pixel_list_form(params_fn, B, "encode_views")
+    band_rows = effective_band_rows(h, band_rows)
     desc, n, _, nrows = _stream_table(chans, minmaxes, HW, dev)
     err = torch.zeros(B, dtype=torch.int32, device=dev)
     sf = torch.empty((max(nrows, 1), 2), dtype=torch.int32, device=dev)
     if n:
-        order = np.concatenate(wavefront_steps(h, w))
+        order = np.concatenate(wavefront_steps(h, w, band_rows))
         pix = torch.from_numpy((np.arange(B, dtype=np.int64)[:, None] * HW + order[None, :]).reshape(-1).astype(np.int32)).to(dev)
         if pixel_list:                                        # the decoder's own kernels, on all pixels at once (bit-identical parameters)
             params_fn.set_latent(y_hat)
-            params_fn.run(pix, None, 0, B * HW)
+            params_fn.run(pix, None, 0, B * HW, **_band_kw(band_rows))
             sigma, mu, logits = params_fn.sigma, params_fn.mu, params_fn.logits
         else:
             sigma, mu, logits = _full_latent_params(params_fn, y_hat, K * M)
@@ -346,14 +362,19 @@ def encode_views(params_fn, y_hat, M, K, chans, minmaxes, scale_bound, names=Non
 _BATCH_LISTS = {}
 
 
-def _batch_step_lists(h, w, B, device):
+def _band_kw(band_rows):
+    """params_fn.run's keyword: only passed with bands on, so that a params_fn without bands keeps its four-argument run."""
+    return {"band_rows": band_rows} if band_rows else {}
+
+
+def _batch_step_lists(h, w, B, device, band_rows=0):
     """Per coding step, two int32 [steps][B * h] device lists of entries b * h * w + p (-1 padded), kept per shape: the tables' and the
     decoder's (pair b's pixels at [b * h, (b + 1) * h), the layout of one pair's list), and the pixel-list kernels' (the same pixels packed
     to the front: workgroups whose 32 entries are all padding leave at once)."""
-    key = (h, w, B, str(device))
+    key = (h, w, B, str(device), effective_band_rows(h, band_rows))
     t = _BATCH_LISTS.get(key)
     if t is None:
-        steps = wavefront_steps(h, w)
+        steps = wavefront_steps(h, w, band_rows)
         per = np.full((len(steps), B, h), -1, dtype=np.int64)
         packed = np.full((len(steps), B * h), -1, dtype=np.int64)
         for i, p in enumerate(steps):
@@ -366,12 +387,14 @@ def _batch_step_lists(h, w, B, device):
     return t
 
 
-def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, device, names=None, use_graph=True, verify=True):
+def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, device, names=None, use_graph=True, verify=True,
+                 band_rows=0):
     """The inverse of encode_views (datas: pair b's y stream as it framed it) -> y_hat [B, M, h, w]; a pair's slice does not depend on
     its batch mates.  Coding step by coding step, entirely on the device: parameters from what is decoded so far -> tables of the
     step's pixels -> one wavefront per channel stream finds the symbols and writes them into the latent.  The device side of a step
     (context convolution, nine head layers, table kernel, decode kernel, each over every pair: ~18 launches of a few microseconds) is
-    captured once into a HIP graph over static buffers and replayed w + 3 (h - 1) times back to back; the step index lives in device
+    captured once into a HIP graph over static buffers and replayed w + 3 (h - 1) times back to back (w + 3 (band_rows - 1) times with
+    the row bands of wavefront_steps: band_rows must be the encoder's); the step index lives in device
     memory (incremented by the decode kernel), so the host neither feeds nor waits for anything until the last replay.  After the
     last step one more launch (masic_rans_decode_finish_batch, outside the graph) checks that every channel stream consumed exactly its
     words and left the coder in the encoder's initial state; its flag comes back with the others in the one read of `err`
@@ -380,6 +403,7 @@ def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, de
     h, w = shape
     B, HW = len(datas), h * w
     pixel_list = _pixel_list_form(params_fn, B, "decode_views")
+    band_rows = effective_band_rows(h, band_rows)
     y_hat = torch.zeros((B, M, h, w), dtype=torch.float32, device=device)
     blobs, wo, wc, base = [], [], [], 0
     for b, data in enumerate(datas):
@@ -406,12 +430,12 @@ def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, de
     done_d = torch.zeros(1, dtype=torch.int32, device=device)
     err = torch.zeros(B, dtype=torch.int32, device=device)
     starts = torch.empty(nstarts, dtype=torch.int16, device=device)
-    pix_d, pix_packed = _batch_step_lists(h, w, B, device)
+    pix_d, pix_packed = _batch_step_lists(h, w, B, device, band_rows)
     y16 = params_fn.y16 if pixel_list else None
 
     def device_step():
         if pixel_list:                                        # the step's <= B * h pixels only (masic_amd/csrc/skinny.hip)
-            params_fn.run(pix_packed, step_d, B * h, B * h)
+            params_fn.run(pix_packed, step_d, B * h, B * h, **_band_kw(band_rows))
             sigma, mu, logits = params_fn.sigma, params_fn.mu, params_fn.logits
         else:
             sigma, mu, logits = _full_latent_params(params_fn, y_hat, K * M)
@@ -431,7 +455,7 @@ def decode_views(params_fn, datas, shape, M, K, chans, minmaxes, scale_bound, de
         done_d.zero_()
         err.zero_()
 
-    nsteps = len(wavefront_steps(h, w))
+    nsteps = len(wavefront_steps(h, w, band_rows))
     cur = torch.cuda.current_stream()
     if use_graph:
         side = torch.cuda.Stream()

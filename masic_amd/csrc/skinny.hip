@@ -21,7 +21,10 @@
 // b = q / HW, pixel p = q % HW of a batch of nimg images: every buffer is [nimg][image] with its own per-image stride, the masked taps
 // stay inside image b (out-of-range rows / columns read zeros as at the picture edge), so a pixel's result still depends on its own
 // operands alone -- batched and one-image launches, in any list order and split, give the same bits.  One image: entries are p.
+// The banded context model (skinny_f16k_bands, include/masic_bands.h) moves the top edge the masked taps stop at from the image's first
+// row to the first row of the pixel's band of band_rows rows; everything above holds for it as it stands.
 #include "f16k_device.h"      // bf16x8, v4u, static_for, pack2bf
+#include "masic_bands.h"
 
 namespace {
 
@@ -48,9 +51,12 @@ struct SkArgs {
 constexpr int SK_CH = 8;          // k-steps per load batch and wave
 constexpr unsigned SK_OOR = 0xC0000000u;
 
-// NW waves per workgroup (K split); CTX: the masked 5x5 context model (12 live taps) instead of a 1x1 layer
-template <int NW, bool CTX>
-__global__ __launch_bounds__(NW * 64) void skinny_f16k(const SkArgs a) {
+// The body of the kernels below.  NW waves per workgroup (K split); CTX: the masked 5x5 context model (12 live taps) instead of a 1x1
+// layer; BANDS (CTX only): the latent is cut into bands of band_rows rows and a tap above the top of its pixel's band reads zeros, as a
+// tap above the latent does -- one integer division per lane for the band top, nothing else in the K loop differs, so a pixel's result
+// is what the unbanded kernel computes for it on its band cut out as an image (and the same whatever the list, split or batch)
+template <int NW, bool CTX, bool BANDS>
+__device__ __forceinline__ void skinny_body(const SkArgs a, const int band_rows) {
     __shared__ float red[NW][16][64];
     SkGroup g = a.g[0];
     int t0 = 0;
@@ -76,13 +82,14 @@ __global__ __launch_bounds__(NW * 64) void skinny_f16k(const SkArgs a) {
                                : (unsigned)((ct >> 2) * nsteps) * 4096u + h * 2048u + ((ct & 3) * 32 + j) * 16u;
     const unsigned wstep = CTX ? 1024u : 4096u;
     const int pr = p >= 0 ? p / a.w : 0, pc = p >= 0 ? p - pr * a.w : 0;
+    const int rtop = BANDS ? (pr / band_rows) * band_rows : 0;         // first row of the pixel's band
     auto boff = [&](int s) -> unsigned {                              // the lane's activation operand of k-step s
         if (p < 0 || s >= nsteps) return SK_OOR;
         if (!CTX) return s < g.Cin16 ? xoff + (unsigned)(s * a.HW + p) * 32u + 16u * h : SK_OOR;
         const int tap = s / g.Cin16, k16 = s - tap * g.Cin16;         // live taps of the type-A 5x5 mask: rows -2, -1 (5 columns each), row 0 columns -2, -1
         const int dy = tap < 10 ? tap / 5 - 2 : 0, dx = tap < 10 ? tap % 5 - 2 : tap - 12;
         const int r = pr + dy, c = pc + dx;
-        return (r >= 0 && c >= 0 && c < a.w) ? xoff + (unsigned)(k16 * a.HW + r * a.w + c) * 32u + 16u * h : SK_OOR;
+        return (r >= rtop && c >= 0 && c < a.w) ? xoff + (unsigned)(k16 * a.HW + r * a.w + c) * 32u + 16u * h : SK_OOR;
     };
     v4u A[2][SK_CH], Bq[2][SK_CH];
     auto load = [&](auto PB, int base) {
@@ -154,6 +161,13 @@ __global__ __launch_bounds__(NW * 64) void skinny_f16k(const SkArgs a) {
     }
 }
 
+template <int NW, bool CTX>
+__global__ __launch_bounds__(NW * 64) void skinny_f16k(const SkArgs a) { skinny_body<NW, CTX, false>(a, 0); }
+
+// the context model with a band top (masic_bands_skinny_ctx_fwd_batch, include/masic_bands.h): band_rows >= 1
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void skinny_f16k_bands(const SkArgs a, const int band_rows) { skinny_body<NW, true, true>(a, band_rows); }
+
 // context-model weights [Cout][Cin][5][5] (masked taps already zero) -> bf16 fragments [co tile][step = tap * Cin16 + k16][lane (j, h)][8]:
 // element e of lane (j, h) = W[32 tile + j][16 k16 + 8 h + e][kh][kw], (kh, kw) = the live tap's position
 __global__ void pack_ctx_skinny_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, int Cin, int Cout, int Cin16) {
@@ -191,9 +205,9 @@ extern "C" int masic_skinny_ctx_pack_weight(const float* w, void* w_packed, int 
 // masic_skinny_ctx_pack_weight, latent h x w) on the pixels pix[(*step) * list_stride + i], i < npix, of a batch of nimg images (entry
 // q = image q / HW, pixel q % HW).  x / y_f16k / y_nchw are FULL-SIZE buffers (nimg x HW pixels, x with exactly Cin channels per image);
 // only the listed pixels are read (plus, for the masked convolution, their causal neighbours in the same image) and written.
-extern "C" int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step,
-                                            int list_stride, int npix, int nimg, int h, int w, const float* gate, int gate_ctot, int gate_c,
-                                            void* stream) {
+// band_rows: 0, or (ctx only) the rows of a band of the banded context model
+static int skinny_launch(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step, int list_stride,
+                         int npix, int nimg, int h, int w, const float* gate, int gate_ctot, int gate_c, int band_rows, void* stream) {
     MASIC_REQUIRE(groups && pix && ngroups >= 1 && ngroups <= SK_MAXG && (!ctx || ngroups == 1), MASIC_ERR_ARG, "skinny_group_fwd: bad argument");
     MASIC_REQUIRE(npix >= 1 && nimg >= 1 && h >= 1 && w >= 1, MASIC_ERR_SHAPE, "skinny_group_fwd: bad shape");
     MASIC_REQUIRE(gate == nullptr || (gate_c >= 0 && (nimg == 1 || gate_c < gate_ctot)), MASIC_ERR_ARG, "skinny_group_fwd: gate plane");
@@ -217,7 +231,22 @@ extern "C" int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, in
     a.pix = pix; a.step = step; a.list_stride = list_stride; a.npix = npix; a.HW = h * w; a.h = h; a.w = w; a.nimg = nimg;
     a.gate = gate; a.gate_c = gate_c; a.gate_ctot = gate_ctot;
     const dim3 grid(tiles, ceil_div(npix, 32));
-    if (ctx) hipLaunchKernelGGL((skinny_f16k<8, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
+    if (ctx && band_rows > 0) hipLaunchKernelGGL((skinny_f16k_bands<8>), grid, dim3(512), 0, (hipStream_t)stream, a, band_rows);
+    else if (ctx) hipLaunchKernelGGL((skinny_f16k<8, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((skinny_f16k<4, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
     return masic_launch_status("skinny_group_fwd");
+}
+
+extern "C" int masic_skinny_group_fwd_batch(const masic_gemm_group_t* groups, int ngroups, int ctx, const int32_t* pix, const int32_t* step,
+                                            int list_stride, int npix, int nimg, int h, int w, const float* gate, int gate_ctot, int gate_c,
+                                            void* stream) {
+    return skinny_launch(groups, ngroups, ctx, pix, step, list_stride, npix, nimg, h, w, gate, gate_ctot, gate_c, 0, stream);
+}
+
+// include/masic_bands.h: the ctx case of the call above with the latent's rows cut into bands of band_rows rows
+extern "C" int masic_bands_skinny_ctx_fwd_batch(const void* group, const int32_t* pix, const int32_t* step, int list_stride, int npix, int nimg,
+                                                int h, int w, const float* gate, int gate_ctot, int gate_c, int band_rows, void* stream) {
+    MASIC_REQUIRE(band_rows >= 1, MASIC_ERR_ARG, "bands_skinny_ctx_fwd: band_rows = %d (at least 1)", band_rows);
+    return skinny_launch((const masic_gemm_group_t*)group, 1, 1, pix, step, list_stride, npix, nimg, h, w, gate, gate_ctot, gate_c, band_rows,
+                         stream);
 }

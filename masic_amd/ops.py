@@ -1708,11 +1708,14 @@ def pack_skinny_ctx_weight(weight):
     return out
 
 
-def skinny_group(layers, pix, step, list_stride, npix, h, w, ctx=False, gate=None, gate_c=0, nimg=1):
+def skinny_group(layers, pix, step, list_stride, npix, h, w, ctx=False, gate=None, gate_c=0, nimg=1, band_rows=0):
     """masic_skinny_group_fwd_batch: up to three 1x1 layers (or one masked 5x5 convolution, ctx=True) on the pixels
     pix[step * list_stride + i], i < npix, of a batch of nimg images (list entries b * h * w + p).  layers: dicts with x (F16K), wp, bias,
     Cin, Cout, act, out_ctot, out_coff and the FULL-SIZE output buffer y16 (F16K) or y32 (float32 [nimg, out_ctot, h, w]); gate
-    [nimg, C, h, w]; pix / step: int32 device tensors (step may be None)."""
+    [nimg, C, h, w]; pix / step: int32 device tensors (step may be None).  band_rows > 0 (ctx only): the banded context model of
+    masic_amd/bands.py -- taps above the top of the pixel's band of band_rows rows read zeros; 0: the call above."""
+    if band_rows < 0 or (band_rows and (not ctx or len(layers) != 1)):
+        raise ValueError(f"masic_amd.skinny_group: band_rows={band_rows} (>= 0, and > 0 only with the one layer of ctx=True)")
     arr = (_lib.GemmGroup * len(layers))()
     for g, L in zip(arr, layers):
         g.x, g.w_packed, g.wscale, g.bias = _p(L["x"]), _p(L["wp"]), None, _p(L["bias"])
@@ -1721,6 +1724,10 @@ def skinny_group(layers, pix, step, list_stride, npix, h, w, ctx=False, gate=Non
         g.Cin, g.Cout, g.out_ctot, g.out_coff, g.act = L["Cin"], L["Cout"], L["out_ctot"], L.get("out_coff", 0), int(L["act"])
     if gate is not None and (gate.dim() != 4 or gate.shape[0] != nimg or not gate.is_contiguous()):
         raise RuntimeError("masic_amd.skinny_group: the gate must be a contiguous [nimg, C, h, w] tensor")
+    if band_rows:
+        from . import bands
+        return bands.skinny_ctx(arr[0], _p(pix), _p(step), list_stride, npix, nimg, h, w, _p(gate), 0 if gate is None else int(gate.shape[1]),
+                                gate_c, band_rows, _stream())
     check(lib.masic_skinny_group_fwd_batch(arr, len(layers), 1 if ctx else 0, _p(pix), _p(step), int(list_stride), int(npix), int(nimg), int(h),
                                            int(w), _p(gate), 0 if gate is None else int(gate.shape[1]), int(gate_c), _stream()),
           "skinny_group_fwd_batch")

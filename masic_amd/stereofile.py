@@ -129,10 +129,13 @@ class StereoCodec:
     weights.  hsic (MASIC.HSIC), udh (any eval-mode module mapping two patches to `delta`: model.Net at patch size 128, or
     masic_amd.align.PatchAligner, which needs no weights; needed by encode only) and cqe (MASIC.Independent_EN; needed for
     decode(enhance=True) only) are modules of this tree on one MI355X device, in eval mode.  The operand mode is
-    masic_amd.nn.set_precision's, as for HSIC.compress; the file records it."""
+    masic_amd.nn.set_precision's, as for HSIC.compress; the file records it.  band_rows (0 .. 255): HSIC.compress_batch's, for encode
+    only -- the inner .bin carries the value, so decode needs nothing and a codec built without it decodes the files."""
 
-    def __init__(self, hsic, udh=None, cqe=None):
+    def __init__(self, hsic, udh=None, cqe=None, band_rows=0):
+        from .bands import check_band_rows
         self.hsic, self.udh, self.cqe = hsic, udh, cqe
+        self.band_rows = check_band_rows(band_rows, "StereoCodec")
 
     def _check_modules(self, who, *mods):
         for name, m in mods:
@@ -182,7 +185,7 @@ class StereoCodec:
             h_matrix = h_matrix_from_offsets(delta_q, (H0, W0), dev)
             inner = _inner_names(names)
             with tempfile.TemporaryDirectory(prefix="masic_msf_") as tmp:
-                out = self.hsic.compress_batch(planes[:B], planes[B:], h_matrix, inner, tmp)
+                out = self.hsic.compress_batch(planes[:B], planes[B:], h_matrix, inner, tmp, band_rows=self.band_rows)
                 files = []
                 for i, n in enumerate(inner):
                     with open(os.path.join(tmp, n + ".npz"), "rb") as f:
