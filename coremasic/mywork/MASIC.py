@@ -34,6 +34,7 @@ from masic_amd.streams import ForkJoin as _ForkJoin
 from masic_amd import fp8 as _fp8
 from masic_amd import deconv as _deconv
 from masic_amd import conv_s2 as _conv_s2
+from masic_amd import latent as _latent
 from masic_amd.bands import check_band_rows as _check_band_rows
 from masic_amd.f16k import F16K as _F16K, F8K as _F8K
 
@@ -237,6 +238,9 @@ def _analysis_f16k(owner, x, layouts=None):
         if i == 1:
             _fp8.record(owner, "a2", t.buf)
     if layouts is not None:
+        # g_a_conv4 (128 -> 192): conv_s2_latent_f16k where the launch is large enough for it, else conv_f16k_multi; the same bits
+        if t.whole and _latent.supported(convs[3], t.B, t.H, t.W) and _latent.preferred(convs[3], t.B, t.H, t.W):
+            return _latent.run(convs[3], t, **layouts)
         return convs[3].run_f16k_multi(t, **layouts)
     return convs[3].run_f16k(t, want_nchw=True)
 
