@@ -1010,6 +1010,25 @@ int masic_conv2d_wgrad_plan_name(const masic_conv_desc_t* d, int flags, char* bu
 int masic_conv2d_wgrad_row_name(int row, int det, char* buf, size_t n);
 int masic_wgrad_f16k_plan_name(int kind, int s0, int s1, int s2, int s3, int s4, int flags, char* buf, size_t n);
 int masic_wgrad_f16k_row_name(int row, int det, char* buf, size_t n);
+/* What the five persistent-workgroup launchers launch, in the same text form (one line per launch, finishing and packing passes
+ * included), from the plan function the launcher itself executes.  Host code only: shapes and form arguments, no device pointers.  The
+ * line of the persistent kernel carries, behind a fifth bar, the integers its tile loop runs on:
+ *   masic_conv_a_plan_name            masic_conv_a_[gdn_[dual_]]fwd[_ex]: x_aligned16 = the input pointer is 16-byte aligned, gdn = a GDN
+ *                                     follows, products = 1 or 3 (gdn_inverse & 2), out = 0 F16K, 1 fp8, 2 F16K + the pre-GDN result;
+ *                                     integers: ntiles tiles_w tiles_per_image Ho Wo
+ *   masic_gdn_fwd_plan_name           masic_gdn_fwd_ex (out_f16k = 0) / masic_gdn_fwd_f16k (out_f16k = 1, prec ignored); integers: work
+ *                                     items (strips or tiles), items a workgroup takes per round of its loop, pixels per item, items per image
+ *   masic_gdn_bwd_fused_plan_name     masic_gdn_bwd_fused_ex2 with x / g given as F16K (x_f16k, g_f16k) and g_sum asked for (want_sum);
+ *                                     integers: ntiles (128 pixels each) pixels H*W
+ *   masic_conv3x3_resident_plan_name  masic_conv3x3_resident_ex_fwd; ex = a second output or channel sums are asked for; integers:
+ *                                     ntiles tiles_w tiles_per_image NBUF (the kernel's patch ring)
+ *   masic_pic_wgrad_f16k_plan_name    masic_pic_wgrad_f16k; integers: chunks (64 coarse pixels each) chunks per image
+ * A shape or form the launcher refuses: its error code and an empty buffer; a buffer too small: MASIC_ERR_ARG. */
+int masic_conv_a_plan_name(int B, int Hi, int Wi, int x_aligned16, int gdn, int products, int out, char* buf, size_t n);
+int masic_gdn_fwd_plan_name(int B, int C, int H, int W, int prec, int out_f16k, char* buf, size_t n);
+int masic_gdn_bwd_fused_plan_name(int B, int C, int H, int W, int x_f16k, int g_f16k, int want_sum, char* buf, size_t n);
+int masic_conv3x3_resident_plan_name(int B, int Cin, int Cout, int H, int W, int ex, int sum_of, char* buf, size_t n);
+int masic_pic_wgrad_f16k_plan_name(int B, int Hc, int Wc, char* buf, size_t n);
 /* as masic_warp_perspective_bwd_gather, but where the gather form raises *flag the fallback is a deterministic store-and-sum (entries
  * grouped by source pixel with integer counting atomics, each group summed in destination-pixel order) instead of the float-atomic
  * scatter; it covers every homography, a horizon inside the picture included.  The flag is still tested on the device.  workspace:

@@ -61,6 +61,14 @@ static inline bool masic_plan_line(char* buf, size_t n, const char* kernel, dim3
     const size_t used = strlen(buf);
     return (size_t)snprintf(buf + used, n - used, "%s | %u,%u,%u | %d | %zu\n", kernel, grid.x, grid.y, grid.z, block, lds) < n - used;
 }
+// ... with the integers the launcher hands to the kernel behind a fifth bar: "kernel | gx,gy,gz | block | lds-bytes | v0 v1 ..."
+static inline bool masic_plan_line_ints(char* buf, size_t n, const char* kernel, dim3 grid, int block, size_t lds, const int* v, int nv) {
+    char ints[160];
+    size_t w = 0;
+    for (int i = 0; i < nv && w < sizeof ints; ++i) w += (size_t)snprintf(ints + w, sizeof ints - w, i ? " %d" : "%d", v[i]);
+    const size_t used = strlen(buf);
+    return w < sizeof ints && (size_t)snprintf(buf + used, n - used, "%s | %u,%u,%u | %d | %zu | %s\n", kernel, grid.x, grid.y, grid.z, block, lds, ints) < n - used;
+}
 static inline bool masic_plan_fill_line(char* buf, size_t n, size_t bytes) {      // masic_zero_async's launch, if it makes one
     return masic_zero_blocks(bytes) == 0 || masic_plan_line(buf, n, "masic_zero_kernel", dim3(masic_zero_blocks(bytes)), 256, 0);
 }

@@ -294,11 +294,17 @@ __global__ __launch_bounds__(256) void pack_c3_weights_kernel(const float* __res
 
 }  // namespace
 
-template <int CI, int C>
-static void c3_launch(bool ex, int grid, int lds_bytes, hipStream_t st, const C3Args& a) {
-    if (ex) launch_lds<conv3x3_resident_f16k<CI, C, true>>(dim3(grid), 768, lds_bytes, st, a);
-    else launch_lds<conv3x3_resident_f16k<CI, C, false>>(dim3(grid), 768, lds_bytes, st, a);
+// One row per compiled (CI, C) pair, the plain kernel in column 0 and the EX form in column 1; plan_c3 picks the row, the grid and the LDS
+// bytes for the launcher and for masic_conv3x3_resident_plan_name.
+typedef void (*C3LaunchFn)(int grid, int lds_bytes, hipStream_t st, const C3Args& a);
+template <int CI, int C, bool EX>
+static void c3_launch(int grid, int lds_bytes, hipStream_t st, const C3Args& a) {
+    launch_lds<conv3x3_resident_f16k<CI, C, EX>>(dim3(grid), 768, lds_bytes, st, a);
 }
+struct C3Row { int ci, c; C3LaunchFn launch[2]; };
+#define C3_ROW(CI, C) {CI, C, {c3_launch<CI, C, false>, c3_launch<CI, C, true>}}
+static const C3Row C3_ROWS[] = {C3_ROW(16, 32), C3_ROW(32, 32), C3_ROW(16, 64), C3_ROW(32, 64), C3_ROW(64, 64)};
+constexpr int C3_MAX_WGS = 256;            // one persistent workgroup per CU
 static bool c3_pair_ok(int CI, int C) { return (C == 32 || C == 64) && (CI == 16 || CI == 32 || CI == 64) && (CI <= C || CI == C); }
 
 extern "C" size_t masic_conv3x3_resident_packed_bytes(int Cin, int Cout) {
@@ -319,6 +325,27 @@ extern "C" int masic_conv3x3_resident_pack_weight(const float* w, void* w_packed
     hipLaunchKernelGGL(pack_c3_weights_kernel, dim3(ceil_div(9 * (CI / 16) * 2 * Cout, 256)), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)w_packed, Cin, CI,
                        Cout, transposed);
     return masic_launch_status("conv3x3_resident_pack_weight");
+}
+
+static const char* const C3_UNSUPPORTED = "conv3x3_resident_fwd: needs Cin <= 64, Cout = 32 (H % 16 == 0) or 64 (H % 8 == 0), W % 32 == 0";
+struct C3Plan { const C3Row* row; int grid, lds_bytes, tiles_w, tiles_per_image, ntiles, nbuf; };
+// ex: the second output / the channel sums are asked for (the EX kernel); sum_of as in masic_conv3x3_resident_ex_fwd
+static int plan_c3(int B, int Cin, int Cout, int H, int W, bool ex, int sum_of, C3Plan* p) {
+    MASIC_REQUIRE(sum_of >= 0 && sum_of <= 2 && (ex || sum_of == 0), MASIC_ERR_ARG, "conv3x3_resident_fwd: sum_of / sum_out / sum_workspace");
+    MASIC_REQUIRE(masic_conv3x3_resident_supported(B, Cin, Cout, H, W), MASIC_ERR_UNSUPPORTED, "%s", C3_UNSUPPORTED);
+    const int CI = round_up(Cin, 16), C = Cout;
+    p->row = nullptr;
+    for (const C3Row& r : C3_ROWS)
+        if (r.ci == CI && r.c == C) p->row = &r;
+    MASIC_REQUIRE(p->row != nullptr, MASIC_ERR_UNSUPPORTED, "%s", C3_UNSUPPORTED);
+    const int TH = 512 / C;
+    p->tiles_w = W / 32, p->tiles_per_image = p->tiles_w * (H / TH), p->ntiles = B * p->tiles_per_image;
+    // LDS: weights + patch ring + sink (the kernel's constants)
+    const int wbytes = 9 * (CI / 16) * 2 * C * 16, pbytes = ((CI / 16) * 2 * (TH + 2) * 34 + 63) / 64 * 1024;
+    p->nbuf = wbytes + 3 * pbytes + 1024 <= 160 * 1024 ? 3 : 2;
+    p->lds_bytes = wbytes + p->nbuf * pbytes + 1024;
+    p->grid = p->ntiles < C3_MAX_WGS ? round_up(p->ntiles, 8) : C3_MAX_WGS;
+    return MASIC_OK;
 }
 
 // y = act(conv3x3(x) + bias) * act'(mask) + res1 + res2 on F16K buffers, y_pre = the value before the adds (see
@@ -343,34 +370,40 @@ extern "C" int masic_conv3x3_resident_ex_fwd(const void* x_f16k, const void* w_p
                   MASIC_ERR_ARG, "conv3x3_resident_fwd: sum_of / sum_out / sum_workspace");
     MASIC_REQUIRE(y2_f16k == nullptr || (res_ctot % 16 == 0 && res_ctot >= C), MASIC_ERR_SHAPE, "conv3x3_resident_fwd: y2 / mask2 need res_ctot >= Cout channels");
     MASIC_REQUIRE(x_f16k && w_packed && y_f16k, MASIC_ERR_ARG, "conv3x3_resident_fwd: null pointer");
-    MASIC_REQUIRE(masic_conv3x3_resident_supported(B, Cin, Cout, H, W), MASIC_ERR_UNSUPPORTED,
-                  "conv3x3_resident_fwd: needs Cin <= 64, Cout = 32 (H %% 16 == 0) or 64 (H %% 8 == 0), W %% 32 == 0");
+    MASIC_REQUIRE(masic_conv3x3_resident_supported(B, Cin, Cout, H, W), MASIC_ERR_UNSUPPORTED, "%s", C3_UNSUPPORTED);
     MASIC_REQUIRE(in_ctot % 16 == 0 && in_coff % 16 == 0 && in_coff >= 0 && in_coff + CI <= in_ctot && out_ctot % 16 == 0 && out_coff % 16 == 0 &&
                       out_coff >= 0 && out_coff + C <= out_ctot, MASIC_ERR_SHAPE, "conv3x3_resident_fwd: channel views");
     MASIC_REQUIRE(res1 != nullptr || res2 == nullptr, MASIC_ERR_ARG, "conv3x3_resident_fwd: res2 without res1");
     MASIC_REQUIRE((res1 == nullptr && mask == nullptr && y_pre_f16k == nullptr) || (res_ctot % 16 == 0 && res_ctot >= C), MASIC_ERR_SHAPE,
                   "conv3x3_resident_fwd: residual / mask / pre tensors need >= Cout channels, a multiple of 16");
     MASIC_REQUIRE(act == MASIC_ACT_NONE || act == MASIC_ACT_RELU || act == MASIC_ACT_LEAKY, MASIC_ERR_UNSUPPORTED, "conv3x3_resident_fwd: activation");
-    const int TH = 512 / C, tiles_w = W / 32, tiles_h = H / TH;
+    const bool ex = y2_f16k != nullptr || sum_of;
+    C3Plan p;
+    const int rc = plan_c3(B, Cin, Cout, H, W, ex, sum_of, &p);
+    if (rc != MASIC_OK) return rc;
     C3Args a{(const unsigned short*)x_f16k, (const unsigned short*)w_packed, bias, (const unsigned short*)res1, (const unsigned short*)res2,
              (const unsigned short*)mask, (unsigned short*)y_pre_f16k, (unsigned short*)y_f16k, B, H, W, in_ctot / 16, in_coff / 16, out_ctot, out_coff,
-             res_ctot, act, mask_slope, tiles_w, tiles_w * tiles_h, B * tiles_w * tiles_h,
+             res_ctot, act, mask_slope, p.tiles_w, p.tiles_per_image, p.ntiles,
              (const unsigned short*)mask2, (unsigned short*)y2_f16k, mask2_slope, (float*)sum_workspace, sum_of};
-    // LDS: weights + patch ring + sink (the kernel's constants)
-    const int wbytes = 9 * (CI / 16) * 2 * C * 16, pbytes = ((CI / 16) * 2 * (TH + 2) * 34 + 63) / 64 * 1024;
-    const int lds_bytes = wbytes + (wbytes + 3 * pbytes + 1024 <= 160 * 1024 ? 3 : 2) * pbytes + 1024;
-    int grid = 256;                                                  // one persistent workgroup per CU
-    if (a.ntiles < grid) grid = round_up(a.ntiles, 8);
     hipStream_t st = (hipStream_t)stream;
-    const bool ex = y2_f16k != nullptr || sum_of;
-    if (C == 32) {
-        if (CI == 16) c3_launch<16, 32>(ex, grid, lds_bytes, st, a);
-        else c3_launch<32, 32>(ex, grid, lds_bytes, st, a);
-    } else {
-        if (CI == 16) c3_launch<16, 64>(ex, grid, lds_bytes, st, a);
-        else if (CI == 32) c3_launch<32, 64>(ex, grid, lds_bytes, st, a);
-        else c3_launch<64, 64>(ex, grid, lds_bytes, st, a);
-    }
-    if (sum_of) hipLaunchKernelGGL(c3_sum_finish_kernel, dim3(C), dim3(64), 0, st, (const float*)sum_workspace, sum_out, C, grid);
+    p.row->launch[ex](p.grid, p.lds_bytes, st, a);
+    if (sum_of) hipLaunchKernelGGL(c3_sum_finish_kernel, dim3(C), dim3(64), 0, st, (const float*)sum_workspace, sum_out, C, p.grid);
     return masic_launch_status("conv3x3_resident_fwd");
+}
+
+// the launches of masic_conv3x3_resident_[ex_]fwd (include/masic_hip.h); the integers of the kernel's line: ntiles tiles_w tiles_per_image NBUF
+extern "C" int masic_conv3x3_resident_plan_name(int B, int Cin, int Cout, int H, int W, int ex, int sum_of, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "conv3x3_resident_plan_name: no buffer");
+    buf[0] = 0;
+    C3Plan p;
+    const int rc = plan_c3(B, Cin, Cout, H, W, ex != 0, sum_of, &p);
+    if (rc != MASIC_OK) return rc;
+    char name[64];
+    snprintf(name, sizeof name, "conv3x3_resident_f16k<%d, %d, %s>", p.row->ci, p.row->c, ex ? "true" : "false");
+    const int v[4] = {p.ntiles, p.tiles_w, p.tiles_per_image, p.nbuf};
+    const bool ok = masic_plan_line_ints(buf, n, name, dim3(p.grid), 768, (size_t)p.lds_bytes, v, 4) &&
+                    (!sum_of || masic_plan_line(buf, n, "c3_sum_finish_kernel", dim3(Cout), 64, 0));
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "conv3x3_resident_plan_name: buffer of %zu bytes too small", n);
+    return MASIC_OK;
 }

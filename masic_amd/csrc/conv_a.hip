@@ -317,6 +317,13 @@ __global__ __launch_bounds__(512, 1) void conv_a_gdn_f16k(const ConvAArgs a) {
 // are [8 stores of k-2][5 DMA of k+1][8 stores of k-1] = 21: vmcnt(21) is exact, and two tiles of stores stay in flight.
 constexpr int CW_PCS = 18, CW_ROWS = 15, CW_NP = CW_ROWS * CW_PCS, CW_NI = (CW_NP + 63) / 64, CW_BYTES = CW_NP * 16, CW_PITCH = CW_PCS * 4;
 static_assert(CW_NI == 5 && CW_BYTES == 4320, "vmcnt(21) below counts 5 DMA instructions per tile");
+// One zeroed patch row behind the last wave's second buffer: the zero-weight kernel row 5 of ci = 2 reads row 15 of a patch, i.e. the first
+// row of whatever follows it.  For waves 0..6 and for wave 7's first buffer that is another patch (finite floats); for wave 7 on every tile
+// it computes from its SECOND buffer (a workgroup's 2nd, 4th, ... tile) it was past the allocation, where LDS holds what the last kernel on
+// the CU left: a NaN or Inf pattern there times the zero weight made a NaN output pixel.
+constexpr int CW_TAIL_BYTES = CW_PITCH * 4;
+constexpr int CW_LDS = 65536 + CA_WIMG_BYTES + 1024 + 16 * CW_BYTES + CW_TAIL_BYTES;
+static_assert(CW_LDS <= 160 * 1024, "LDS");
 __global__ __launch_bounds__(512, 1) void conv_a_gdn_f16k_w(const ConvAArgs a) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     constexpr int WIMG = 65536, VEC = WIMG + CA_WIMG_BYTES, PATCH = VEC + 1024;      // LDS map: gamma image | weights | bias, beta^ | 8 x 2 patches
@@ -338,6 +345,7 @@ __global__ __launch_bounds__(512, 1) void conv_a_gdn_f16k_w(const ConvAArgs a) {
             vec[tid] = a.bias != nullptr ? a.bias[tid] : 0.0f;
             vec[128 + tid] = reinterpret_cast<const float*>(a.gdn_img + 4 * 8 * 2 * 64)[tid];
         }
+        if (tid < CW_PITCH) reinterpret_cast<float*>(lds + PATCH + 16 * CW_BYTES)[tid] = 0.0f;      // (visible after the barriers below)
     }
     // piece map of this lane (tile independent): piece p = lane + 64 i -> patch row r = p / 18 = 5 ci + kh, 16-byte column piece pc = p % 18
     const size_t plane = (size_t)a.Hi * a.Wi;
@@ -406,8 +414,8 @@ __global__ __launch_bounds__(512, 1) void conv_a_gdn_f16k_w(const ConvAArgs a) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 const int pair = 8 * (sx & 1) + c, ci = pair < 15 ? pair / 5 : 0, kw = pair < 15 ? pair % 5 : 0;
-                // (kernel row 5 -- k-steps 4, 5, lane half 1 -- has zero weights and reads row 0 of the next ci / the 280 bytes behind this
-                // buffer: the wave's other buffer, the next wave's, or past the allocation (reads as 0) -- all filled with finite floats
+                // (kernel row 5 -- k-steps 4, 5, lane half 1 -- has zero weights and reads row 0 of the next ci / the 288 bytes behind this
+                // buffer: the wave's other buffer, the next wave's, or the zeroed tail row (CW_TAIL_BYTES) -- all filled with finite floats
                 // before the first tile)
                 if (sx == 1 && c == 7) bfr[c] = (__bf16)1.0f;
                 else bfr[c] = (__bf16)pl[(ci * 5 + 2 * (sx >> 1)) * CW_PITCH + kw];
@@ -448,34 +456,63 @@ extern "C" int masic_conv_a_pack_weight(const float* w, void* w_packed, void* st
     return masic_launch_status("conv_a_pack_weight");
 }
 namespace {
+// One row per compiled kernel; plan_conv_a picks the row, the grid and the LDS bytes for the launcher and for masic_conv_a_plan_name.
+typedef void (*ConvALaunchFn)(dim3 grid, size_t lds, hipStream_t st, const ConvAArgs& a);
+template <auto K>
+void conv_a_run(dim3 grid, size_t lds, hipStream_t st, const ConvAArgs& a) { launch_lds<K>(grid, 512, lds, st, a); }
+struct ConvARow { const char* name; ConvALaunchFn launch; };
+#define CONV_A_ROW(X3, OUT) {"conv_a_gdn_f16k<" #X3 ", " #OUT ">", conv_a_run<conv_a_gdn_f16k<X3, OUT>>}
+const ConvARow CONV_A_ROWS[] = {{"conv_a_gdn_f16k_w", conv_a_run<conv_a_gdn_f16k_w>},
+                                CONV_A_ROW(false, 0), CONV_A_ROW(false, 1), CONV_A_ROW(false, 2), CONV_A_ROW(false, 3),
+                                CONV_A_ROW(true, 0), CONV_A_ROW(true, 1), CONV_A_ROW(true, 2)};
+constexpr int CONV_A_MAX_WGS = 256;         // persistent workgroups: one per CU
+struct ConvAPlan { const ConvARow* row; dim3 grid; size_t lds; int Ho, Wo, tiles_w, tiles_per_img, ntiles; };
+
+// x_aligned16: the first input plane starts on a 16-byte boundary; gdn: a GDN follows; x3: its three-product form; out: 0 F16K, 1 fp8, 2 F16K
+// plus the pre-GDN result
+int plan_conv_a(int B, int Hi, int Wi, bool x_aligned16, bool gdn, bool x3, int out, ConvAPlan* p) {
+    MASIC_REQUIRE(out >= 0 && out <= 2 && (gdn || (out == 0 && !x3)), MASIC_ERR_ARG, "conv_a_fwd: without a GDN the output is one F16K tensor");
+    MASIC_REQUIRE(B > 0 && Hi > 0 && Wi > 0, MASIC_ERR_SHAPE, "conv_a_gdn_fwd: bad shape");
+    p->Ho = (Hi + 4 - 5) / 2 + 1, p->Wo = (Wi + 4 - 5) / 2 + 1;
+    p->tiles_w = ceil_div(p->Wo, 32), p->tiles_per_img = p->tiles_w * ceil_div(p->Ho, 8), p->ntiles = p->tiles_per_img * B;
+    p->grid = dim3(p->ntiles < CONV_A_MAX_WGS ? p->ntiles : CONV_A_MAX_WGS);
+    // the wave-private kernel where it applies; the shared-patch kernel for the rest (no GDN, x3, fp8 or pre-GDN outputs, unaligned input)
+    const bool w = gdn && !x3 && out == 0 && Wi % 4 == 0 && x_aligned16 && ((size_t)Hi * Wi) % 4 == 0;
+    p->row = &CONV_A_ROWS[w ? 0 : (!gdn ? 4 : (x3 ? 5 : 1) + out)];
+    p->lds = w ? (size_t)CW_LDS : 65536 + CA_WIMG_BYTES + 1024 + (size_t)2 * CA_PATCH_BYTES;
+    return MASIC_OK;
+}
+
 int conv_a_launch(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse, void* y_f16k, void* y_f8k,
                   float out_inv_scale, void* y_pre, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream) {
     MASIC_REQUIRE(x && w_packed && ((y_f16k != nullptr) != (y_f8k != nullptr)), MASIC_ERR_ARG, "conv_a_gdn_fwd: null pointer / exactly one output");
     MASIC_REQUIRE(gdn_packed != nullptr || (y_f16k != nullptr && y_pre == nullptr), MASIC_ERR_ARG, "conv_a_fwd: without a GDN the output is one F16K tensor");
     MASIC_REQUIRE(y_f8k == nullptr || out_inv_scale > 0.0f, MASIC_ERR_ARG, "conv_a_gdn_fwd: an fp8 output needs out_inv_scale > 0");
     MASIC_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && in_coff >= 0 && in_coff + 3 <= in_ctot, MASIC_ERR_SHAPE, "conv_a_gdn_fwd: bad shape");
-    const int Ho = (Hi + 4 - 5) / 2 + 1, Wo = (Wi + 4 - 5) / 2 + 1;
-    const int tiles_w = ceil_div(Wo, 32), tiles_per_img = tiles_w * ceil_div(Ho, 8), ntiles = tiles_per_img * B;
+    const bool gdn = gdn_packed != nullptr;
+    ConvAPlan p;
+    const int rc = plan_conv_a(B, Hi, Wi, ((size_t)x & 15) == 0, gdn, gdn && (gdn_inverse & 2) != 0, y_f8k != nullptr ? 1 : (y_pre != nullptr ? 2 : 0), &p);
+    if (rc != MASIC_OK) return rc;
     ConvAArgs a{x, (const uint4*)w_packed, bias, (const uint4*)gdn_packed, (unsigned short*)y_f16k, gdn_inverse, Hi, Wi, in_ctot, in_coff,
-                Ho, Wo, tiles_w, tiles_per_img, ntiles, (unsigned char*)y_f8k, out_inv_scale, (unsigned short*)y_pre, g_f16k_stamps};
-    const size_t lds_bytes = 65536 + CA_WIMG_BYTES + 1024 + 2 * CA_PATCH_BYTES;
-    const dim3 grid(ntiles < 256 ? ntiles : 256);
-    hipStream_t st = (hipStream_t)stream;
-    const bool x3 = (gdn_inverse & 2) != 0;
-    const int out = y_f8k != nullptr ? 1 : (y_pre != nullptr ? 2 : 0);
-    // the wave-private kernel where it applies; the shared-patch kernel for the rest (no GDN, x3, fp8 or pre-GDN outputs, unaligned input)
-    if (gdn_packed != nullptr && !x3 && out == 0 && Wi % 4 == 0 && ((size_t)x & 15) == 0 && ((size_t)Hi * Wi) % 4 == 0)
-        launch_lds<conv_a_gdn_f16k_w>(grid, 512, 65536 + CA_WIMG_BYTES + 1024 + 16 * CW_BYTES, st, a);
-    else if (gdn_packed == nullptr) launch_lds<conv_a_gdn_f16k<false, 3>>(grid, 512, lds_bytes, st, a);
-    else if (x3 && out == 0) launch_lds<conv_a_gdn_f16k<true, 0>>(grid, 512, lds_bytes, st, a);
-    else if (x3 && out == 1) launch_lds<conv_a_gdn_f16k<true, 1>>(grid, 512, lds_bytes, st, a);
-    else if (x3) launch_lds<conv_a_gdn_f16k<true, 2>>(grid, 512, lds_bytes, st, a);
-    else if (out == 0) launch_lds<conv_a_gdn_f16k<false, 0>>(grid, 512, lds_bytes, st, a);
-    else if (out == 1) launch_lds<conv_a_gdn_f16k<false, 1>>(grid, 512, lds_bytes, st, a);
-    else launch_lds<conv_a_gdn_f16k<false, 2>>(grid, 512, lds_bytes, st, a);
+                p.Ho, p.Wo, p.tiles_w, p.tiles_per_img, p.ntiles, (unsigned char*)y_f8k, out_inv_scale, (unsigned short*)y_pre, g_f16k_stamps};
+    p.row->launch(p.grid, p.lds, (hipStream_t)stream, a);
     return masic_launch_status("conv_a_gdn_fwd");
 }
 }  // namespace
+// the launch of the first-layer call that the form arguments name (include/masic_hip.h); the integers: ntiles tiles_w tiles_per_img Ho Wo
+extern "C" int masic_conv_a_plan_name(int B, int Hi, int Wi, int x_aligned16, int gdn, int products, int out, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "conv_a_plan_name: no buffer");
+    buf[0] = 0;
+    MASIC_REQUIRE(products == 1 || products == 3, MASIC_ERR_ARG, "conv_a_plan_name: products %d (1 or 3)", products);
+    ConvAPlan p;
+    const int rc = plan_conv_a(B, Hi, Wi, x_aligned16 != 0, gdn != 0, products == 3, out, &p);
+    if (rc != MASIC_OK) return rc;
+    const int v[5] = {p.ntiles, p.tiles_w, p.tiles_per_img, p.Ho, p.Wo};
+    const bool ok = masic_plan_line_ints(buf, n, p.row->name, p.grid, 512, p.lds, v, 5);
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "conv_a_plan_name: buffer of %zu bytes too small", n);
+    return MASIC_OK;
+}
 // the same with the result optionally written as F8K fp8 (y_f8k, quantised with out_inv_scale) for an fp8-operand second layer
 extern "C" int masic_conv_a_gdn_fwd_ex(const float* x, const void* w_packed, const float* bias, const void* gdn_packed, int gdn_inverse,
                                        void* y_f16k, void* y_f8k, float out_inv_scale, int B, int Hi, int Wi, int in_ctot, int in_coff, void* stream) {

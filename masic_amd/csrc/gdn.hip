@@ -281,11 +281,34 @@ extern "C" int masic_gdn_fwd(const float* x, const float* beta, const float* gam
     return masic_gdn_fwd_ex(x, beta, gamma, y, B, C, H, W, inverse, beta_min, MASIC_PREC_F32, stream);
 }
 
+// What masic_gdn_fwd_ex / masic_gdn_fwd_f16k launch: the launchers and masic_gdn_fwd_plan_name read kernel and grid from here.
+// kernel 0 gdn_bf16x3_c128 (work items: 32-pixel strips, one per wave and round), 1 gdn_mfma_c128 (64-pixel tiles), 2 gdn_generic
+constexpr int GF_X3_WGS = 512, GF_MFMA_WGS = 1024;
+struct GdnFwdPlan { int kernel; dim3 grid; int block; size_t lds; int per_image, nitems; };
+static const char* const GF_NAMES[3] = {"gdn_bf16x3_c128", "gdn_mfma_c128", "gdn_generic"};
+static int plan_gdn_fwd(int B, int C, int H, int W, int prec, bool out_f16k, GdnFwdPlan* p) {
+    MASIC_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, MASIC_ERR_SHAPE, "gdn_fwd: non-positive dimension");
+    const int HW = H * W;
+    if (out_f16k) MASIC_REQUIRE(C == 128 && HW % 32 == 0, MASIC_ERR_UNSUPPORTED, "gdn_fwd_f16k: needs C = 128 and H*W %% 32 == 0");
+    else MASIC_REQUIRE(C <= 512, MASIC_ERR_UNSUPPORTED, "gdn_fwd: C=%d > 512", C);
+    if (out_f16k || (C == 128 && HW % 32 == 0 && prec == MASIC_PREC_BF16)) {
+        const int spi = HW / 32, nstrips = spi * B;
+        *p = {0, dim3(nstrips < 4 * GF_X3_WGS ? (nstrips + 3) / 4 : GF_X3_WGS), 256, 0, spi, nstrips};
+    } else if (C == 128 && HW % PT == 0) {
+        const int tpi = HW / PT, ntiles = tpi * B;
+        *p = {1, dim3(ntiles < GF_MFMA_WGS ? ntiles : GF_MFMA_WGS), 256, 0, tpi, ntiles};
+    } else {
+        *p = {2, dim3(ceil_div(HW, 64), B), 64, (size_t)C * 64 * sizeof(float), ceil_div(HW, 64), ceil_div(HW, 64) * B};
+    }
+    return MASIC_OK;
+}
+
 extern "C" int masic_gdn_fwd_ex(const float* x, const float* beta, const float* gamma, float* y,
                                 int B, int C, int H, int W, int inverse, double beta_min, int prec, void* stream) {
     MASIC_REQUIRE(x && beta && gamma && y, MASIC_ERR_ARG, "gdn_fwd: null pointer");
-    MASIC_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, MASIC_ERR_SHAPE, "gdn_fwd: non-positive dimension");
-    MASIC_REQUIRE(C <= 512, MASIC_ERR_UNSUPPORTED, "gdn_fwd: C=%d > 512", C);
+    GdnFwdPlan p;
+    const int rc = plan_gdn_fwd(B, C, H, W, prec, false, &p);
+    if (rc != MASIC_OK) return rc;
     // parametrizers.py:47-56: pedestal = (2^-18)^2, bound = sqrt(minimum + pedestal), held as float32 buffers
     const double ped = 0x1p-36;
     const float pedestal = (float)ped;
@@ -293,18 +316,14 @@ extern "C" int masic_gdn_fwd_ex(const float* x, const float* beta, const float* 
     const float gamma_bound = (float)__builtin_sqrt(ped);
     const int HW = H * W;
     hipStream_t st = (hipStream_t)stream;
-    if (C == 128 && HW % 32 == 0 && prec == MASIC_PREC_BF16) {
-        const int spi = HW / 32, nstrips = spi * B;
-        const int grid = nstrips < 4 * 512 ? (nstrips + 3) / 4 : 512;
-        hipLaunchKernelGGL(gdn_bf16x3_c128, dim3(grid), dim3(256), 0, st, x, beta, gamma, y, (unsigned short*)nullptr, HW, spi, nstrips,
+    if (p.kernel == 0) {
+        hipLaunchKernelGGL(gdn_bf16x3_c128, p.grid, dim3(p.block), p.lds, st, x, beta, gamma, y, (unsigned short*)nullptr, HW, p.per_image, p.nitems,
                            inverse, beta_bound, gamma_bound, pedestal);
-    } else if (C == 128 && HW % PT == 0) {
-        const int tpi = HW / PT, ntiles = tpi * B;
-        const int grid = ntiles < 1024 ? ntiles : 1024;
-        hipLaunchKernelGGL(gdn_mfma_c128, dim3(grid), dim3(256), 0, st, x, beta, gamma, y, HW, tpi, ntiles, inverse,
+    } else if (p.kernel == 1) {
+        hipLaunchKernelGGL(gdn_mfma_c128, p.grid, dim3(p.block), p.lds, st, x, beta, gamma, y, HW, p.per_image, p.nitems, inverse,
                            beta_bound, gamma_bound, pedestal);
     } else {
-        hipLaunchKernelGGL(gdn_generic, dim3(ceil_div(HW, 64), B), dim3(64), (size_t)C * 64 * sizeof(float), st,
+        hipLaunchKernelGGL(gdn_generic, p.grid, dim3(p.block), p.lds, st,
                            x, beta, gamma, y, C, HW, inverse, beta_bound, gamma_bound, pedestal, 0);
     }
     return masic_launch_status("gdn_fwd");
@@ -332,15 +351,29 @@ extern "C" int masic_gdn1_fwd(const float* x, const float* beta, const float* ga
 extern "C" int masic_gdn_fwd_f16k(const float* x, const float* beta, const float* gamma, void* y_f16k,
                                   int B, int C, int H, int W, int inverse, double beta_min, void* stream) {
     MASIC_REQUIRE(x && beta && gamma && y_f16k, MASIC_ERR_ARG, "gdn_fwd_f16k: null pointer");
-    MASIC_REQUIRE(B > 0 && H > 0 && W > 0, MASIC_ERR_SHAPE, "gdn_fwd_f16k: non-positive dimension");
-    MASIC_REQUIRE(C == 128 && (H * W) % 32 == 0, MASIC_ERR_UNSUPPORTED, "gdn_fwd_f16k: needs C = 128 and H*W %% 32 == 0");
+    GdnFwdPlan p;
+    const int rc = plan_gdn_fwd(B, C, H, W, MASIC_PREC_BF16, true, &p);
+    if (rc != MASIC_OK) return rc;
     const double ped = 0x1p-36;
-    const int HW = H * W, spi = HW / 32, nstrips = spi * B;
-    const int grid = nstrips < 4 * 512 ? (nstrips + 3) / 4 : 512;
-    hipLaunchKernelGGL(gdn_bf16x3_c128, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, beta, gamma, (float*)nullptr,
-                       (unsigned short*)y_f16k, HW, spi, nstrips, inverse, (float)__builtin_sqrt(beta_min + ped),
+    hipLaunchKernelGGL(gdn_bf16x3_c128, p.grid, dim3(p.block), p.lds, (hipStream_t)stream, x, beta, gamma, (float*)nullptr,
+                       (unsigned short*)y_f16k, H * W, p.per_image, p.nitems, inverse, (float)__builtin_sqrt(beta_min + ped),
                        (float)__builtin_sqrt(ped), (float)ped);
     return masic_launch_status("gdn_fwd_f16k");
+}
+
+// the launch of masic_gdn_fwd_ex (out_f16k = 0) or masic_gdn_fwd_f16k (out_f16k = 1) (include/masic_hip.h); the integers: work items
+// (strips / tiles), items a workgroup takes per round of its loop (one per wave of gdn_bf16x3_c128), pixels per item, items per image
+extern "C" int masic_gdn_fwd_plan_name(int B, int C, int H, int W, int prec, int out_f16k, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "gdn_fwd_plan_name: no buffer");
+    buf[0] = 0;
+    GdnFwdPlan p;
+    const int rc = plan_gdn_fwd(B, C, H, W, prec, out_f16k != 0, &p);
+    if (rc != MASIC_OK) return rc;
+    const int v[4] = {p.nitems, p.kernel == 0 ? p.block / 64 : 1, p.kernel == 0 ? 32 : 64, p.per_image};
+    const bool ok = masic_plan_line_ints(buf, n, GF_NAMES[p.kernel], p.grid, p.block, p.lds, v, 4);
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "gdn_fwd_plan_name: buffer of %zu bytes too small", n);
+    return MASIC_OK;
 }
 
 // Parameters of a 128-channel GDN re-laid out for the fused epilogue of masic_conv_f16k_gdn_fwd: 65536 + 512 bytes.

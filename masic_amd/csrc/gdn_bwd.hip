@@ -570,6 +570,30 @@ __global__ __launch_bounds__(256) void gdn_bwd_reduce_kernel(const float* __rest
     if (isg) g_gamma[idx] = r; else g_beta[idx - 128 * 128] = r;
 }
 
+// One row per compiled main kernel (x F16K, g F16K); plan_gdn_bwd picks the row and the grids for the launcher and for
+// masic_gdn_bwd_fused_plan_name.
+typedef void (*GdnBwdLaunchFn)(int nblk, hipStream_t st, const GdnBwdArgs& a);
+template <bool X16, bool G16>
+void gdn_bwd_run(int nblk, hipStream_t st, const GdnBwdArgs& a) { hipLaunchKernelGGL((gdn_bwd_c128<X16, G16>), dim3(nblk), dim3(256), GB_LDS, st, a); }
+void gdn_bwd_run_wn(int nblk, hipStream_t st, const GdnBwdArgs& a) { hipLaunchKernelGGL(gdn_bwd_c128_wn<2>, dim3(nblk), dim3(512), G8_LDS, st, a); }
+struct GdnBwdRow { const char* name; const void* fn; GdnBwdLaunchFn launch; int block, lds; bool attr_set; };
+GdnBwdRow GB_ROWS[4] = {      // index = x F16K + 2 * g F16K
+    {"gdn_bwd_c128<false, false>", (const void*)gdn_bwd_c128<false, false>, gdn_bwd_run<false, false>, 256, GB_LDS, false},
+    {"gdn_bwd_c128<true, false>", (const void*)gdn_bwd_c128<true, false>, gdn_bwd_run<true, false>, 256, GB_LDS, false},
+    {"gdn_bwd_c128<false, true>", (const void*)gdn_bwd_c128<false, true>, gdn_bwd_run<false, true>, 256, GB_LDS, false},
+    {"gdn_bwd_c128_wn<2>", (const void*)gdn_bwd_c128_wn<2>, gdn_bwd_run_wn, 512, G8_LDS, false}};
+constexpr int GB_PACK_GRID = 16;
+struct GdnBwdPlan { GdnBwdRow* row; int ntiles, nblk, reduce_grid; };
+int plan_gdn_bwd(int B, int C, int H, int W, bool x16, bool g16, bool want_sum, GdnBwdPlan* p) {
+    MASIC_REQUIRE(C == 128, MASIC_ERR_UNSUPPORTED, "gdn_bwd_fused: C=%d (128 only; other widths use the unfused pieces)", C);
+    MASIC_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)H * W * 128 < (1ll << 31), MASIC_ERR_SHAPE, "gdn_bwd_fused: shape");
+    p->row = &GB_ROWS[(x16 ? 1 : 0) + (g16 ? 2 : 0)];
+    p->ntiles = (int)(((long long)B * H * W + 127) / 128);
+    p->nblk = p->ntiles < GB_NBLK ? p->ntiles : GB_NBLK;
+    p->reduce_grid = (128 * 128 + 128 + (want_sum ? 128 : 0)) / 32;
+    return MASIC_OK;
+}
+
 }  // namespace
 
 extern "C" size_t masic_gdn_bwd_fused_workspace_bytes(void) {
@@ -591,44 +615,30 @@ extern "C" int masic_gdn_bwd_fused_ex2(const float* x, const void* x_f16k, const
     MASIC_REQUIRE(((x != nullptr) != (x_f16k != nullptr)) && ((g != nullptr) != (g_f16k != nullptr)) && (gx || gx_f16k || gx_bf16), MASIC_ERR_ARG,
                   "gdn_bwd_fused: exactly one of x / x_f16k and of g / g_f16k, at least one of gx / gx_f16k / gx_bf16");
     MASIC_REQUIRE(beta && gamma && g_beta && g_gamma && workspace, MASIC_ERR_ARG, "gdn_bwd_fused: null pointer");
-    MASIC_REQUIRE(C == 128, MASIC_ERR_UNSUPPORTED, "gdn_bwd_fused: C=%d (128 only; other widths use the unfused pieces)", C);
-    MASIC_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)H * W * 128 < (1ll << 31), MASIC_ERR_SHAPE, "gdn_bwd_fused: shape");
+    GdnBwdPlan p;
+    const int rc = plan_gdn_bwd(B, C, H, W, x_f16k != nullptr, g_f16k != nullptr, g_sum != nullptr, &p);
+    if (rc != MASIC_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const double ped = 1.4551915228366852e-11;      // (2^-18)^2, parametrizers.py:47-56
     const float pedestal = (float)ped, beta_bound = (float)__builtin_sqrt(beta_min + ped), gamma_bound = (float)__builtin_sqrt(ped);
     uint4* img = (uint4*)workspace;
     float* part = reinterpret_cast<float*>((unsigned char*)workspace + 2 * GB_IMG + 512);
-    hipLaunchKernelGGL(gdn_bwd_pack_kernel, dim3(16), dim3(256), 0, st, beta, gamma, img, beta_bound, gamma_bound, pedestal);
+    hipLaunchKernelGGL(gdn_bwd_pack_kernel, dim3(GB_PACK_GRID), dim3(256), 0, st, beta, gamma, img, beta_bound, gamma_bound, pedestal);
     GdnBwdArgs a{};
     a.x = x; a.g = g; a.gx = gx; a.img = img; a.part = part;
     a.x16 = (const unsigned short*)x_f16k; a.g16 = (const unsigned short*)g_f16k; a.gx16 = (unsigned short*)gx_f16k; a.gxb = (unsigned short*)gx_bf16;
     a.HW = H * W; a.npix = (long long)B * H * W; a.inverse = inverse; a.want_sum = g_sum != nullptr;
-    a.ntiles = (int)((a.npix + 127) / 128);
-    const int nblk = a.ntiles < GB_NBLK ? a.ntiles : GB_NBLK;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[3] = {(const void*)gdn_bwd_c128<false, false>, (const void*)gdn_bwd_c128<true, false>, (const void*)gdn_bwd_c128<false, true>};
-        for (const void* fn : fns)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS) != hipSuccess) {
-                masic_set_error("gdn_bwd_fused: cannot reserve %d bytes of LDS", GB_LDS);
-                return MASIC_ERR_LAUNCH;
-            }
-        attr_set = true;
-    }
-    if (x_f16k && g_f16k) {
-        static bool attr8 = false;
-        if (!attr8) {
-            if (hipFuncSetAttribute((const void*)gdn_bwd_c128_wn<2>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) != hipSuccess) {
-                masic_set_error("gdn_bwd_fused: cannot reserve %d bytes of LDS", G8_LDS);
-                return MASIC_ERR_LAUNCH;
-            }
-            attr8 = true;
+    a.ntiles = p.ntiles;
+    const int nblk = p.nblk;
+    if (!p.row->attr_set) {
+        if (hipFuncSetAttribute(p.row->fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.row->lds) != hipSuccess) {
+            masic_set_error("gdn_bwd_fused: cannot reserve %d bytes of LDS", p.row->lds);
+            return MASIC_ERR_LAUNCH;
         }
-        hipLaunchKernelGGL(gdn_bwd_c128_wn<2>, dim3(nblk), dim3(512), G8_LDS, st, a);
-    } else if (x_f16k) hipLaunchKernelGGL((gdn_bwd_c128<true, false>), dim3(nblk), dim3(256), GB_LDS, st, a);
-    else if (g_f16k) hipLaunchKernelGGL((gdn_bwd_c128<false, true>), dim3(nblk), dim3(256), GB_LDS, st, a);
-    else hipLaunchKernelGGL((gdn_bwd_c128<false, false>), dim3(nblk), dim3(256), GB_LDS, st, a);
-    hipLaunchKernelGGL(gdn_bwd_reduce_kernel, dim3((128 * 128 + 128 + (g_sum ? 128 : 0)) / 32), dim3(256), 0, st, (const float*)part, nblk,
+        p.row->attr_set = true;
+    }
+    p.row->launch(nblk, st, a);
+    hipLaunchKernelGGL(gdn_bwd_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, st, (const float*)part, nblk,
                        beta, gamma, g_beta, g_gamma, g_sum, beta_bound, gamma_bound);
     return masic_launch_status("gdn_bwd_fused");
 }
@@ -638,4 +648,22 @@ extern "C" int masic_gdn_bwd_fused(const float* x, const float* g, const float* 
                                    double beta_min, void* stream) {
     MASIC_REQUIRE(x && g && gx, MASIC_ERR_ARG, "gdn_bwd_fused: null pointer");
     return masic_gdn_bwd_fused_ex(x, nullptr, g, nullptr, beta, gamma, gx, nullptr, nullptr, g_beta, g_gamma, workspace, B, C, H, W, inverse, beta_min, stream);
+}
+
+// the launches of masic_gdn_bwd_fused_ex2 (include/masic_hip.h); the integers of the main kernel's line: ntiles (128-pixel tiles) npix HW
+extern "C" int masic_gdn_bwd_fused_plan_name(int B, int C, int H, int W, int x_f16k, int g_f16k, int want_sum, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "gdn_bwd_fused_plan_name: no buffer");
+    buf[0] = 0;
+    GdnBwdPlan p;
+    const int rc = plan_gdn_bwd(B, C, H, W, x_f16k != 0, g_f16k != 0, want_sum != 0, &p);
+    if (rc != MASIC_OK) return rc;
+    const long long npix = (long long)B * H * W;
+    MASIC_REQUIRE(npix < (1ll << 31), MASIC_ERR_ARG, "gdn_bwd_fused_plan_name: pixel count does not fit the line's integers");
+    const int v[3] = {p.ntiles, (int)npix, H * W};
+    const bool ok = masic_plan_line(buf, n, "gdn_bwd_pack_kernel", dim3(GB_PACK_GRID), 256, 0) &&
+                    masic_plan_line_ints(buf, n, p.row->name, dim3(p.nblk), p.row->block, p.row->lds, v, 3) &&
+                    masic_plan_line(buf, n, "gdn_bwd_reduce_kernel", dim3(p.reduce_grid), 256, 0);
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "gdn_bwd_fused_plan_name: buffer of %zu bytes too small", n);
+    return MASIC_OK;
 }

@@ -810,6 +810,17 @@ extern "C" int masic_conv5x5_wgrad_f16k_det(const void* x_f16k, const void* dy_f
 
 constexpr int WP_MAX_WGS = 512;
 extern "C" size_t masic_pic_wgrad_f16k_workspace_bytes() { return (size_t)WP_MAX_WGS * WP_NOUT * sizeof(float); }
+// what masic_pic_wgrad_f16k launches: the launcher and masic_pic_wgrad_f16k_plan_name both read it from here
+struct WgPicPlan { int tpi, ntk, grid, fin_grid; };
+static int plan_wg_pic(int B, int Hc, int Wc, WgPicPlan* p) {
+    MASIC_REQUIRE(B > 0 && Hc > 0 && Wc > 0, MASIC_ERR_SHAPE, "pic_wgrad_f16k: bad shape");
+    MASIC_REQUIRE((long)B * 128 * Hc * Wc * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "pic_wgrad_f16k: tensor too large for 32-bit offsets");
+    p->tpi = ceil_div(Hc * Wc, 64);
+    p->ntk = B * p->tpi;
+    p->grid = p->ntk < WP_MAX_WGS ? p->ntk : WP_MAX_WGS;
+    p->fin_grid = ceil_div(WP_NOUT, 64);
+    return MASIC_OK;
+}
 
 // dW (float32, 128 x 3 x 5 x 5) of the picture-end 5x5 stride-2 layers in the bf16 mode: p_f16k = the 128-channel tensor at the
 // coarse resolution (Hc x Wc) in F16K -- dy of Conv2d(3 -> 128) (dW = [Cout][Cin][5][5]) or x of ConvTranspose2d(128 -> 3) (dW =
@@ -818,15 +829,29 @@ extern "C" size_t masic_pic_wgrad_f16k_workspace_bytes() { return (size_t)WP_MAX
 extern "C" int masic_pic_wgrad_f16k(const void* p_f16k, const float* q, float* dw, void* workspace, int B, int Hc, int Wc,
                                     int q_ctot, int q_coff, void* stream) {
     MASIC_REQUIRE(p_f16k && q && dw && workspace, MASIC_ERR_ARG, "pic_wgrad_f16k: null pointer");
-    MASIC_REQUIRE(B > 0 && Hc > 0 && Wc > 0 && q_coff >= 0 && q_coff + 3 <= q_ctot, MASIC_ERR_SHAPE, "pic_wgrad_f16k: bad shape");
-    MASIC_REQUIRE((long)B * 128 * Hc * Wc * 2 < (1l << 31), MASIC_ERR_UNSUPPORTED, "pic_wgrad_f16k: tensor too large for 32-bit offsets");
+    MASIC_REQUIRE(q_coff >= 0 && q_coff + 3 <= q_ctot, MASIC_ERR_SHAPE, "pic_wgrad_f16k: bad shape");
+    WgPicPlan p;
+    const int rc = plan_wg_pic(B, Hc, Wc, &p);
+    if (rc != MASIC_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    WgPicArgs a{(const unsigned short*)p_f16k, q, (float*)workspace, B, Hc, Wc, q_ctot, q_coff, ceil_div(Hc * Wc, 64), 0};
-    a.ntk = a.B * a.tpi;
-    const int grid = a.ntk < WP_MAX_WGS ? a.ntk : WP_MAX_WGS;
-    launch_lds<wgrad_pic_f16k>(dim3(grid), 256, WP_LDS, st, a);
-    hipLaunchKernelGGL(wgrad_pic_finish, dim3(ceil_div(WP_NOUT, 64)), dim3(256), 0, st, (const float*)workspace, dw, grid);
+    WgPicArgs a{(const unsigned short*)p_f16k, q, (float*)workspace, B, Hc, Wc, q_ctot, q_coff, p.tpi, p.ntk};
+    launch_lds<wgrad_pic_f16k>(dim3(p.grid), 256, WP_LDS, st, a);
+    hipLaunchKernelGGL(wgrad_pic_finish, dim3(p.fin_grid), dim3(256), 0, st, (const float*)workspace, dw, p.grid);
     return masic_launch_status("pic_wgrad_f16k");
+}
+// the two launches of masic_pic_wgrad_f16k (include/masic_hip.h); the integers of the first line: ntk (64-pixel chunks) tpi (chunks per image)
+extern "C" int masic_pic_wgrad_f16k_plan_name(int B, int Hc, int Wc, char* buf, size_t n) {
+    MASIC_REQUIRE(buf && n > 0, MASIC_ERR_ARG, "pic_wgrad_f16k_plan_name: no buffer");
+    buf[0] = 0;
+    WgPicPlan p;
+    const int rc = plan_wg_pic(B, Hc, Wc, &p);
+    if (rc != MASIC_OK) return rc;
+    const int v[2] = {p.ntk, p.tpi};
+    const bool ok = masic_plan_line_ints(buf, n, "wgrad_pic_f16k", dim3(p.grid), 256, WP_LDS, v, 2) &&
+                    masic_plan_line(buf, n, "wgrad_pic_finish", dim3(p.fin_grid), 256, 0);
+    if (!ok) buf[0] = 0;
+    MASIC_REQUIRE(ok, MASIC_ERR_ARG, "pic_wgrad_f16k_plan_name: buffer of %zu bytes too small", n);
+    return MASIC_OK;
 }
 
 // dw [CA][CQ] (float32) = sum over batch and pixels of rows[b][a][p] * cols[b][q][p], both operands F16K ([B][C/16][HW][16] bf16),

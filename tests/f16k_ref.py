@@ -258,3 +258,41 @@ def fp8_out_ref(v32, out_scale):
     """store_f8k_tile: fp8(clamp(v * (1 / out_scale), +-448)), round to nearest even, decoded (times out_scale)"""
     inv = torch.tensor(1.0 / out_scale, dtype=torch.float32)
     return (v32 * inv).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float() * out_scale
+
+
+# ------------------------------------------------------------------------------------------------ the fused GDN backward
+def gdn_bwd_rule(d, p, bound):
+    """the parametrizer's backward of gdn_bwd_reduce_kernel: g = 2 max(p, bound) d, passed where p >= bound or the step would raise p"""
+    g = d * 2 * torch.maximum(p, bound)
+    return torch.where((p >= bound) | (g < 0), g, torch.zeros_like(g))
+
+
+def gdn_bwd_emulation(xf, gf, beta, gamma, inverse, beta_min=1e-6):
+    """masic_gdn_bwd_fused with the kernel's roundings, everything else float64: gamma^, x^2 and t are rounded to bf16 where they enter
+    a contraction.  xf, gf: [128, pixels] (any subset of the pixels: every pixel is independent but for the sums over them).  Returns
+    float64 (dx [128, pixels], d beta [128], d gamma [128, 128], channel sums of dx [128]); the parameter gradients have passed the
+    parametrizer's rule."""
+    rnd = lambda t: t.float().bfloat16().double()
+    ped = torch.tensor(2.0 ** -36, dtype=torch.float32)
+    b_bound = torch.tensor((beta_min + 2.0 ** -36) ** 0.5, dtype=torch.float32)
+    g_bound = torch.tensor((2.0 ** -36) ** 0.5, dtype=torch.float32)
+    bh = (torch.maximum(beta, b_bound) ** 2 - ped).double()
+    gh = rnd(torch.maximum(gamma, g_bound) ** 2 - ped)
+    xf, gf = xf.double(), gf.double()
+    x2 = rnd(xf * xf)
+    n = bh[:, None] + gh @ x2
+    if inverse:
+        sv, tv = gf * n.sqrt(), 0.5 * gf * xf / n.sqrt()
+    else:
+        sv, tv = gf / n.sqrt(), -0.5 * gf * xf / (n * n.sqrt())
+    tb = rnd(tv)
+    dx = sv + 2.0 * xf * (gh.t() @ tb)
+    return dx, gdn_bwd_rule(tb.sum(1), beta.double(), b_bound.double()), gdn_bwd_rule(tb @ x2.t(), gamma.double(), g_bound.double()), dx.sum(1)
+
+
+def gdn_bwd_autograd64(xf, gf, beta, gamma, inverse):
+    """(dx, d beta, d gamma) of the oracle's (inverse) GDN by float64 autograd; xf, gf: [128, pixels]"""
+    xr = xf.double().reshape(1, 128, 1, -1).clone().requires_grad_(True)
+    br, gr = beta.double().clone().requires_grad_(True), gamma.double().clone().requires_grad_(True)
+    O.gdn(xr, br, gr, inverse=inverse).backward(gf.double().reshape(1, 128, 1, -1))
+    return xr.grad.reshape(128, -1), br.grad, gr.grad
