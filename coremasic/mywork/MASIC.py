@@ -845,6 +845,79 @@ class HSIC(CompressionModel):
             "likelihoods": {"y1": y1_lik, "y2": y2_lik, "z1": z1_lik, "z2": z2_lik},
         }
 
+    def _forward_refine(self, y1, y2, z1, z2, x1, x2, m_fwd, m_back, noise, gates=None):
+        """The graph of the encoder-side latent refinement (masic_amd/refine.py): from the four latents as
+        leaves to the reconstructions and likelihoods, built from the nodes of _forward_graph.  "Mixed" quantisation -- everything the
+        decoder will see is the rounded value with an identity gradient (autograd.RoundSteFn): round(y) into the synthesis transforms,
+        both context models and, through x1_hat -> warp -> encoder1, round(y1_warp) into the right heads; round(z - median) + median
+        into the hyper synthesis.  Only the points where a likelihood is evaluated carry noise: the mixtures at y + u, the bottlenecks
+        at z + u, u = noise[0..3] for (y1, y2, z1, z2) in the tensors' own [B, C, h, w] layout.  m_fwd / m_back: the sampling matrices;
+        gates: mask2weights_unit of the right-view mask, computed once per call by the caller (None: computed here, without a
+        graph).  The weights are the caller's business: with requires_grad off everywhere (refine._Frozen) no weight-, bias- or
+        table-gradient launch runs.  x2 is not read: y2 is a leaf, and the picture enters through the objective only."""
+        B, _, H, W = x1.shape
+        n_y1, n_y2, n_z1, n_z2 = noise
+        if gates is None:
+            with torch.no_grad():
+                gates = self.mask2weights_unit(_hip.warp_perspective(None, m_fwd, (H, W), ones_like=(B, H, W)))
+
+        def bottleneck(eb, z, u):
+            """(round(z - median) + median with the identity gradient, the likelihood at z + u)"""
+            med = eb.quantiles.detach()[:, 0, 1].contiguous()
+            table = eb._table().detach()
+            lb = eb.likelihood_bound if eb.use_likelihood_bound else 0.0
+            # EntropyBottleneckFn reads its noise in the reference's (C, 1, h w B) draw layout
+            lik = _ag.EntropyBottleneckFn.apply(z, table, u.permute(1, 2, 3, 0).contiguous(), med, lb)[1]
+            return _ag.RoundSteFn.apply(z, med, table), lik
+
+        # ---- left view
+        y1_r = _ag.RoundSteFn.apply(y1, None, None)
+        z1_r, z1_lik = bottleneck(self.entropy_bottleneck1, z1, n_z1)
+        params1 = self._hyper_up(self.h_s1_up, z1_r)
+        ctx1 = self.context_prediction1.run(y1_r)
+        s1, m1, l1 = self._h_s1_same_resolution.heads(_ag.cat(params1, ctx1))
+        y1_lik = self.gaussian1.likelihood_of(_ag.AddNoiseFn.apply(y1, n_y1), s1, m1, l1, weights_are_logits=True)
+        x1_hat = self.decoder1.reconstruct_train(y1_r)
+        # ---- right view
+        y2_r = _ag.RoundSteFn.apply(y2, None, None)
+        z2_r, z2_lik = bottleneck(self.entropy_bottleneck2, z2, n_z2)
+        params2 = self._hyper_up(self.h_s2_up, z2_r)
+        ctx2 = self.context_prediction2.run(y2_r)
+        x1_hat_warp = _ag.WarpFn.apply(x1_hat, m_fwd, (H, W))
+        y1_warp_r = _ag.RoundSteFn.apply(self.encoder1.latent_train(x1_hat_warp), None, None)
+        cat2 = _ag.cat(_ag.GateFn.apply(params2, gates, 0), _ag.GateFn.apply(ctx2, gates, 1), _ag.GateFn.apply(y1_warp_r, gates, 2))
+        s2, m2, l2 = self._h_s2_same_resolution.heads(cat2)
+        y2_lik = self.gaussian2.likelihood_of(_ag.AddNoiseFn.apply(y2, n_y2), s2, m2, l2, weights_are_logits=True)
+        x2_hat = self.decoder2(y2_r, x1_hat_warp)
+        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "likelihoods": {"y1": y1_lik, "y2": y2_lik, "z1": z1_lik, "z2": z2_lik}}
+
+    def _eval_from_latents(self, y1, y2, z1, z2, m_fwd, gates):
+        """The eval-mode forward from GIVEN latents (called under no_grad): what a file coded from them costs and reconstructs -- the
+        pieces of _forward_eval on one stream, with z1 / z2 taken as given instead of computed from y1 / y2.  The true objective of the
+        latent refinement (masic_amd/refine.py)."""
+        M = self.M
+        B, _, h, w = y1.shape
+        H, W = 16 * h, 16 * w
+        # left view
+        z1_hat, z1_lik = self.entropy_bottleneck1(z1)
+        cat16 = self._cat_f16k(self._h_s1_same_resolution, y1, 4 * M)
+        cat1 = None if cat16 is not None else torch.empty((B, 4 * M, h, w), dtype=y1.dtype, device=y1.device)
+        self._context(self.context_prediction1, y1, **self._slice(cat1, cat16, 2 * M, 2 * M))
+        self._hyper_up(self.h_s1_up, z1_hat, **self._slice(cat1, cat16, 0, 2 * M))
+        s1, m1, l1 = self._h_s1_same_resolution.heads(cat1 if cat16 is None else cat16, parallel=False)
+        _, y1_lik = self.gaussian1(y1, s1, m1, l1, weights_are_logits=True, want_y_hat=False)
+        x1_hat = self.decoder1.reconstruct(_hip.quantize(y1, "dequantize"))
+        x1_hat_warp = _hip.warp_perspective(x1_hat, m_fwd, (H, W))
+        # right view
+        z2_hat, z2_lik = self.entropy_bottleneck2(z2)
+        cat16 = self._cat_f16k(self._h_s2_same_resolution, y2, 5 * M)
+        cat2 = None if cat16 is not None else torch.empty((B, 5 * M, h, w), dtype=y2.dtype, device=y2.device)
+        self._hyper_up(self.h_s2_up, z2_hat, gate=gates, gate_c=0, **self._slice(cat2, cat16, 0, 2 * M))
+        self._context(self.context_prediction2, y2, gate=gates, gate_c=1, **self._slice(cat2, cat16, 2 * M, 2 * M))
+        y2_lik = self._eval_right_entropy(x1_hat_warp, {"cat2": cat2, "cat16": cat16, "gates": gates, "y2": y2})
+        x2_hat = self.decoder2(_hip.quantize(y2, "dequantize"), x1_hat_warp)
+        return {"x1_hat": x1_hat, "x2_hat": x2_hat, "likelihoods": {"y1": y1_lik, "y2": y2_lik, "z1": z1_lik, "z2": z2_lik}}
+
     def forward(self, x1, x2, h_matrix, warp_matrices=None):
         """`warp_matrices` (optional): the (forward, inverse) normalised sampling matrices of masic_amd.homography for
         this h_matrix, precomputed by the caller -- lets the whole forward be captured into a HIP graph
@@ -1206,14 +1279,17 @@ class HSIC(CompressionModel):
     # several bf16 layers pick or order their kernels by batch shape, so their bits at B > 1 differ from those at B = 1 -- and the
     # coding-step loops, where the time goes, run over all B pairs at once (codec.encode_views / decode_views).  float32 / fp8 operands
     # (no pixel-list form) code the pairs one after the other.
-    def compress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu", band_rows=0):
+    def compress(self, x1, x2, h_matrix, output_name, output_path="", device="cpu", band_rows=0, latents=None):
         """Writes <output_name>.npz (picture size, z1 / z2 strings, channel flags, minmax: the reference's header layout,
         :916-948) and <output_name>.bin (the y1 / y2 streams, masic_amd/codec.py) under output_path.  `device` is accepted
         for signature compatibility; tensors stay where x1 is.  band_rows (0 .. 255; 0: off, today's file): code the y latents in
         independent bands of that many latent rows -- w + 3 (band_rows - 1) decode steps instead of w + 3 (h - 1), a slightly larger
-        .bin that carries the value ("MSR3"; decompress reads it from there)."""
+        .bin that carries the value ("MSR3"; decompress reads it from there).  latents (None: off, today's file): a
+        masic_amd.refine.Refined or a 4-tuple (y1, y2, z1, z2) of float latents that are coded INSTEAD of the analysis transforms'
+        outputs -- rounded and entropy-coded exactly as those are; the file decodes with decompress as any other."""
         band_rows = _check_band_rows(band_rows, "HSIC.compress")
-        out = self._compress_pairs("HSIC.compress", x1, x2, h_matrix, [output_name], output_path, batch=False, band_rows=band_rows)
+        out = self._compress_pairs("HSIC.compress", x1, x2, h_matrix, [output_name], output_path, batch=False, band_rows=band_rows,
+                                   latents=latents)
         out["bytes"], out["bpp"] = out["bytes"][0], out["bpp"][0]
         return out
 
@@ -1222,12 +1298,13 @@ class HSIC(CompressionModel):
         :1308-1310) and may be None; tensors are created on the model's device."""
         return self._decompress_pairs("HSIC.decompress", [output_name], h_matrix, output_path, batch=False)
 
-    def compress_batch(self, x1, x2, h_matrix, output_names, output_path="", band_rows=0):
+    def compress_batch(self, x1, x2, h_matrix, output_names, output_path="", band_rows=0, latents=None):
         """compress for B pairs: x1, x2 [B, 3, H, W], h_matrix [B, 3, 3], B output names.  Writes <name_i>.npz / <name_i>.bin, byte for
         byte what compress(x1[i:i+1], x2[i:i+1], h_matrix[i:i+1], name_i) writes, and returns compress's dict with [B, ...] tensors
-        ("bytes" / "bpp": lists of B).  band_rows: as in compress, one value for the batch."""
+        ("bytes" / "bpp": lists of B).  band_rows: as in compress, one value for the batch.  latents: as in compress, [B, ...] tensors."""
         band_rows = _check_band_rows(band_rows, "HSIC.compress_batch")
-        return self._compress_pairs("HSIC.compress_batch", x1, x2, h_matrix, output_names, output_path, batch=True, band_rows=band_rows)
+        return self._compress_pairs("HSIC.compress_batch", x1, x2, h_matrix, output_names, output_path, batch=True, band_rows=band_rows,
+                                    latents=latents)
 
     def decompress_batch(self, output_names, h_matrix, output_path=""):
         """decompress for B pairs written by compress or compress_batch (one picture size, one band_rows, the current operand mode, in
@@ -1349,7 +1426,18 @@ class HSIC(CompressionModel):
                                               band_rows=band_rows))
         return torch.cat(out)
 
-    def _compress_pairs(self, who, x1, x2, h_matrix, output_names, output_path, batch, band_rows=0):
+    def _given_latents(self, who, latents, B, H, W):
+        """latents= of compress / compress_batch -> four contiguous float32 tensors [B, M | N, ...] on the device, shapes checked."""
+        lat = tuple(latents[:4]) if isinstance(latents, tuple) else tuple(latents)
+        if len(lat) != 4:
+            raise ValueError(f"{who}: latents must be a masic_amd.refine.Refined or a 4-tuple (y1, y2, z1, z2)")
+        want = [(B, self.M, H // 16, W // 16)] * 2 + [(B, self.N, H // 64, W // 64)] * 2
+        for t, name, shape in zip(lat, ("y1", "y2", "z1", "z2"), want):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape:
+                raise ValueError(f"{who}: latents: {name} must be a float32 device tensor of shape {shape}")
+        return [t.detach().contiguous() for t in lat]
+
+    def _compress_pairs(self, who, x1, x2, h_matrix, output_names, output_path, batch, band_rows=0, latents=None):
         from masic_amd import nn as _mnn
         x1, x2 = x1.contiguous(), x2.contiguous()
         B, _, H, W = x1.shape
@@ -1364,18 +1452,19 @@ class HSIC(CompressionModel):
         M = self.M
         tags = names if batch else None
         fp8_table = _fp8.stream_table(self) if _mnn.get_precision() == "fp8" else None
+        given = None if latents is None else self._given_latents(who, latents, B, H, W)
         pr = []
         with torch.no_grad():
             for i in range(B):          # left view, per pair
                 a, b_ = x1[i:i + 1], x2[i:i + 1]
                 m_fwd, m_back = _warp_matrices(h_matrix[i:i + 1], (H, W), (H, W), want_inverse=True)
-                y1 = self.encoder1.latent(a)
-                z1 = self._h_a1(y1)
+                y1 = self.encoder1.latent(a) if given is None else given[0][i:i + 1]
+                z1 = self._h_a1(y1) if given is None else given[2][i:i + 1]
                 z1_strings = self.entropy_bottleneck1.compress(z1)
                 z1_hat = self.entropy_bottleneck1.decompress(z1_strings, z1.size()[-2:])
                 y1_hat = _hip.quantize(y1, "dequantize")
                 flag1, minmax1 = self._channel_flags(y1_hat)
-                pr.append(dict(x1=a, x2=b_, m_fwd=m_fwd, m_back=m_back, z1_strings=z1_strings, z1_hat=z1_hat, y1_hat=y1_hat, flag1=flag1,
+                pr.append(dict(i=i, x1=a, x2=b_, m_fwd=m_fwd, m_back=m_back, z1_strings=z1_strings, z1_hat=z1_hat, y1_hat=y1_hat, flag1=flag1,
                                minmax1=minmax1))
             h, w = pr[0]["y1_hat"].shape[-2:]
             s_y1 = self._code_views([self._left_params_fn(p["z1_hat"], h, w, band_rows) for p in pr], self._h_s1_same_resolution,
@@ -1385,8 +1474,8 @@ class HSIC(CompressionModel):
             parts2 = []
             for p in pr:                # right view, per pair
                 p["x1_hat"] = self.decoder1.reconstruct(p["y1_hat"])
-                y2 = self.encoder2.forward_views(_hip.warp_perspective(p["x1"], p["m_fwd"], (H, W)), p["x2"])
-                z2 = self._h_a2(y2)
+                y2 = self.encoder2.forward_views(_hip.warp_perspective(p["x1"], p["m_fwd"], (H, W)), p["x2"]) if given is None else given[1][p["i"]:p["i"] + 1]
+                z2 = self._h_a2(y2) if given is None else given[3][p["i"]:p["i"] + 1]
                 p["z2_strings"] = self.entropy_bottleneck2.compress(z2)
                 p["z2_hat"] = self.entropy_bottleneck2.decompress(p["z2_strings"], z2.size()[-2:])
                 p["y2_hat"] = _hip.quantize(y2, "dequantize")

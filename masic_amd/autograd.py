@@ -151,7 +151,7 @@ def conv_backward(mod, x, weight, y, g, act, need_gx=True, need_gw=True, need_gb
             dw_pic = 1
         elif mod.transposed_conv and (Cin, Cout) == (128, 3) and x16 is not None and g is not None and (Ho, Wo) == (2 * Hi, 2 * Wi):
             dw_pic = 2
-    if (x is None or g is None) and not dw_pic:
+    if need_gw and (x is None or g is None) and not dw_pic:
         raise RuntimeError("masic_amd.conv_backward: x / g given in F16K only, but this layer's weight gradient needs the NCHW tensor")
 
     def input_gradient():
@@ -226,11 +226,13 @@ class GdnFn(Function):
     @staticmethod
     def backward(ctx, g):
         x, beta, gamma = ctx.saved_tensors
-        return gdn_backward(x, g, beta, gamma, ctx.inverse, ctx.beta_min, ctx.needs_input_grad[0]) + (None, None)
+        return gdn_backward(x, g, beta, gamma, ctx.inverse, ctx.beta_min, ctx.needs_input_grad[0],
+                            need_gp=ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) + (None, None)
 
 
-def gdn_backward(x, g, beta, gamma, inverse, beta_min, need_gx=True):
-    """(dx, d beta, d gamma) of the (inverse) GDN; x, g float32 NCHW."""
+def gdn_backward(x, g, beta, gamma, inverse, beta_min, need_gx=True, need_gp=True):
+    """(dx, d beta, d gamma) of the (inverse) GDN; x, g float32 NCHW.  need_gp False (frozen parameters): the launches that only serve
+    d beta / d gamma are not made where they are launches of their own (the one-kernel forms write all three anyway)."""
     g = _c(g)
     B, C, H, W = x.shape
     from . import nn as _mnn
@@ -251,6 +253,8 @@ def gdn_backward(x, g, beta, gamma, inverse, beta_min, need_gx=True):
     d_t = ops.make_conv_desc(B, C, H, W, C, 1, 1, 1, 0, transposed=True)
     u = ops.conv2d(t, ops.pack_conv_weight(w4, d_t), None, d_t)
     gx = ops.gdn_bwd_post(x, s, u) if need_gx else None
+    if not need_gp:
+        return gx, None, None
     d_w = ops.make_conv_desc(B, C, H, W, C, 1, 1, 1, 0, prec=_mnn._PRECISION)
     g_gam = ops.conv2d_wgrad(x2, t, d_w, (C, C, 1, 1)).view(C, C)
     g_bet = ops.channel_sum(t)
@@ -700,6 +704,46 @@ class RateDistortionFn(Function):
         return (None, None, None, g1, g2, *gl)
 
 
+class RoundSteFn(Function):
+    """round(x) -- or, with the per-channel `medians` [C], round(x - median) + median, what eval-mode EntropyBottleneck returns -- with
+    the identity as its gradient: the value the decoder will see, differentiable for the latent refinement (masic_amd/refine.py)."""
+
+    @staticmethod
+    def forward(ctx, x, medians=None, table=None):
+        x = _c(x)
+        if medians is None:
+            return ops.quantize(x, "dequantize")
+        return ops.entropy_bottleneck(x, table, medians, training=False)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None, None
+
+
+class PairRateDistortionFn(Function):
+    """J_b = bits_b / (H W) + lmbda 255^2 (MSE1_b + MSE2_b) per pair b, float64 [B] on the device: forward = the rows of
+    metrics.pair_rd combined by metrics.pair_objective; backward = one launch (masic_refine_rd_seeds) that scales every seed by the
+    pair's own incoming gradient.  Unlike RateDistortionFn nothing is divided by B: the gradient a pair's tensors receive from sum_b J_b
+    does not depend on how many pairs share the call."""
+
+    @staticmethod
+    def forward(ctx, lmbda, x1, x2, x1_hat, x2_hat, *liks):
+        from . import metrics
+        x1, x2, x1_hat, x2_hat = _c(x1), _c(x2), _c(x1_hat), _c(x2_hat)
+        liks = [_c(l) for l in liks]
+        H, W = x1.shape[-2:]
+        ctx.lmbda, ctx.hw = float(lmbda), float(H * W)
+        ctx.save_for_backward(x1, x2, x1_hat, x2_hat, *liks)
+        return metrics.pair_objective(metrics.pair_rd(x1_hat, x1, x2_hat, x2, liks), lmbda, H * W, x1[0].numel())
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import refine
+        x1, x2, x1_hat, x2_hat, *liks = ctx.saved_tensors
+        g1, g2, gl = refine.rd_seeds(x1_hat, x1, x2_hat, x2, liks, ctx.lmbda, ctx.hw, _c(g))
+        return (None, None, None, g1, g2, *gl)
+
+
 _RD_FUSED = True             # the criterion as two launches; tests set False for six reductions + torch scalar arithmetic as their reference
 
 
@@ -788,6 +832,7 @@ class GmmHeadsFn(Function):
         mods = [[getattr(head, name)[2 * i] for i in range(3)] for name, _, _ in stacks]
         slope = lambda act: 0.01 if act == ops.ACT_LEAKY else 0.0
         grads = [None] * 18
+        need_w = any(ctx.needs_input_grad[2:])      # frozen weights (latent refinement): input gradients only
 
         def wgrad(mod, a16, g16, with_bias=False):  # dW in the module's weight layout (+ the bias gradient: channel sums of dy, same launch)
             Cin, Cout = mod.in_channels, mod.out_channels
@@ -813,14 +858,16 @@ class GmmHeadsFn(Function):
                 g = ops.elementwise(ops.EW_ACT_BWD, g, ys[k], s0=acts[2])
             g16.append(ops.nchw_to_f16k(g))
             # (the bias gradient: sums of dy as the weight gradient sees it, bf16-rounded)
-            grads[6 * k + 4], grads[6 * k + 5] = wgrad(mods[k][2], t1[k], g16[k], with_bias=True)
+            if need_w:
+                grads[6 * k + 4], grads[6 * k + 5] = wgrad(mods[k][2], t1[k], g16[k], with_bias=True)
         for level, saved in ((1, t1), (0, t0)):
             gin = dgrad(level + 1, g16, "f16k")
             g16 = []
             for k, (_, _, acts) in enumerate(stacks):
                 gm = gin[k] if acts[level] == ops.ACT_NONE else ops.f16k_act_bwd(gin[k], saved[k], slope(acts[level]))
                 g16.append(gm)
-                grads[6 * k + 2 * level], grads[6 * k + 2 * level + 1] = wgrad(mods[k][level], x16 if level == 0 else t0[k], gm, with_bias=True)
+                if need_w:
+                    grads[6 * k + 2 * level], grads[6 * k + 2 * level + 1] = wgrad(mods[k][level], x16 if level == 0 else t0[k], gm, with_bias=True)
         gx = None
         if ctx.needs_input_grad[0]:
             parts = dgrad(0, g16, "nchw")
@@ -854,6 +901,19 @@ def gmm_heads(head, x):
 _GMM_HEADS_FN = True     # the three head stacks as one node; tests set False for one ConvFn per head layer as their reference
 
 
+def _frozen_chain_backward(convs, gdns, us, xs, g, need_gx):
+    """The input gradient of conv+(I)GDN x3 -> conv (AnalysisFn / SynthesisFn) when no parameter of the transform requires a gradient
+    (the latent refinement, masic_amd/refine.py): the same input-gradient kernels on the same operands as the full backward, and none of
+    its weight-, bias- or activation-conversion launches -- the gradient stays in F16K between the layers.  us: the GDNs' saved inputs,
+    xs: the four layers' inputs (float32 NCHW for the first, F16K after it), g: float32 NCHW."""
+    gx = conv_backward(convs[3], xs[3], convs[3].weight, None, g, ops.ACT_NONE, need_gw=False, need_gb=False, gx_f16k=True)[0]
+    for i in (2, 1, 0):
+        gu16 = _gdn_backward_f16k(us[i], gx, gdns[i], want_f16k=True, want_nchw=False)[1]
+        gx = conv_backward(convs[i], xs[i], convs[i].weight, None, gu16, ops.ACT_NONE, need_gx=need_gx or i > 0, need_gw=False, need_gb=False,
+                           gx_f16k=i > 0)[0]
+    return gx
+
+
 class AnalysisFn(Function):
     """conv(3->128)+GDN, conv+GDN, conv+GDN, conv(128->M) of Encoder1 / Encoder2 (reference MASIC.py:510-531): x float32 NCHW -> y float32 NCHW."""
 
@@ -881,6 +941,8 @@ class AnalysisFn(Function):
         convs = (enc.g_a_conv1, enc.g_a_conv2, enc.g_a_conv3, enc.g_a_conv4)
         gdns = (enc.g_a_gdn1, enc.g_a_gdn2, enc.g_a_gdn3)
         B = x.shape[0]
+        if not any(ctx.needs_input_grad[2:]):
+            return (_frozen_chain_backward(convs, gdns, (u1, u2, u3), (x, a1, a2, a3), g, ctx.needs_input_grad[0]),) + (None,) * 15
         grads = {}
         # The GDN backward reads its saved input (and the gradient, when an F16K kernel produced it) as F16K and writes dx twice --
         # float32 NCHW for the weight-gradient kernel, F16K for the input-gradient convolution -- plus dx's channel sums (the bias
@@ -950,6 +1012,8 @@ class SynthesisFn(Function):
         convs = (dec.g_s_conv1, dec.g_s_conv2, dec.g_s_conv3, dec.g_s_conv4)
         gdns = (dec.g_s_gdn1, dec.g_s_gdn2, dec.g_s_gdn3)
         B = y_hat.shape[0]
+        if not any(ctx.needs_input_grad[2:]):
+            return (_frozen_chain_backward(convs, gdns, (u1, u2, u3), (y_hat, a1, a2, a3), g, ctx.needs_input_grad[0]),) + (None,) * 15
         grads = {}
         # the last layer's weight gradient reads its saved input where it is, in F16K (ops.pic_wgrad_f16k): no float32 NCHW copy of a3
         f16k_only = tuple(convs[3].weight.shape[:2]) == (128, 3) and tuple(g.shape[2:]) == (2 * a3.H, 2 * a3.W)

@@ -11,6 +11,7 @@ by construction.  Both calls are two launches on torch's current stream, without
 The entry points are declared in include/masic_metrics.h, a side header of libmasic_hip.so bound by _lib.bind_header.  No CPU path.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -61,6 +62,14 @@ def pair_rd(x1_hat, x1, x2_hat, x2, liks=()):
     _lib.check(_lib.lib.masic_metrics_pair_rd(ops._p(x1_hat), ops._p(x1), ops._p(x2_hat), ops._p(x2), x1.numel() // B, arr, cnt, len(liks),
                                               B, ops._p(out), ops._p(ws), ops._stream()), "metrics_pair_rd")
     return out
+
+
+def pair_objective(rows, lmbda, hw, n_pic):
+    """float64 [B]: J_b = bits_b / hw + lmbda 255^2 (MSE1_b + MSE2_b) from pair_rd's rows -- bits_b = -sum of the four log columns
+    / ln 2, MSE_b = squared error / n_pic (n_pic = 3 hw for RGB pictures).  The rate-distortion objective of ONE pair: nothing is
+    averaged over the batch.  A few float64 torch operations on [B]-sized tensors, on the device."""
+    bits = rows[:, 2:].sum(dim=1) * (-1.0 / math.log(2.0))
+    return bits / float(hw) + (float(lmbda) * 255.0 ** 2 / float(n_pic)) * (rows[:, 0] + rows[:, 1])
 
 
 def u8_sse(a, b):

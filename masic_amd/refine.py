@@ -1,0 +1,296 @@
+"""Encoder-side latent refinement: smaller files from the same decoder (INTEGRATION.md "Latent refinement").
+
+`HSIC.compress` rounds whatever the analysis transforms output, but the decoder never sees those transforms -- only round(y1),
+round(y2) and the two z streams.  `refine_latents` therefore optimises the four latents of each pair against the pair's own
+rate-distortion objective before they are coded; weights, decoder and file format stay as they are, and a file written from the result
+(`HSIC.compress(..., latents=refined)`) decodes with today's `decompress`.
+
+    refine_latents(hsic, x1, x2, h_matrix, lmbda, RefineConfig(steps=100))   -> Refined(y1, y2, z1, z2, cost_start, cost_best)
+
+The loop: Adam on the latents (one launch per step for all four), gradient of the "mixed" surrogate `HSIC._forward_refine` -- rounded
+values with an identity gradient wherever the decoder sees a rounded value, uniform noise where a likelihood is evaluated -- summed
+over the pairs' objectives J_b = bits_b / (H W) + lmbda 255^2 (MSE1_b + MSE2_b) (autograd.PairRateDistortionFn: nothing is divided
+by B).  Every `check_every` steps and at the last one the TRUE objective -- J_b on the eval-mode path from the latents, what the file
+will cost and how the decoder will reconstruct -- is evaluated and the best iterate per pair is kept on the device; the host never
+reads a cost inside the loop.  cost_best <= cost_start by construction, and steps = 0 returns the encoder's latents bit for bit.
+
+The noise is the library's own (Philox4x32-10, keyed by seed and pair key, masic_refine_noise): torch's generators are not touched,
+and a pair's noise does not depend on its batch mates.  The weights are frozen for the call (requires_grad off, restored after it):
+no weight-, bias- or table-gradient launch runs and no parameter's .grad changes.
+
+Limits.  The result of a pair is NOT promised to be bit-equal across batch compositions: several bf16 layers pick their kernels by
+batch shape.  The surrogate models the unbanded context model; files coded with band_rows > 0 from refined latents decode exactly (the
+coder uses the final latents) but the rate the loop minimised is that of the unbanded file.  fp8 operands are not supported.
+
+The four elementwise kernels are declared in include/masic_refine.h, a side header of libmasic_hip.so bound by _lib.bind_header.
+No CPU path.
+"""
+import collections
+import ctypes
+import os
+
+import torch
+
+from . import _lib
+
+HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_refine.h")
+MAX_PAIRS = 65535                # the pair is a grid dimension of the kernels
+
+SIGNATURES = _lib.bind_header(HEADER_PATH, "masic_refine_")          # name -> (restype, argtypes) of every prototype of masic_refine.h
+
+# The default step size rests on tools/bench_refine.py's table (profiles/refine_bench.txt: a briefly trained full-width model, 8 pairs of
+# 512 x 512, bf16): of 0.1 / 0.05 / 0.02, 0.05 reached the lowest true objective after 10 and after 50 steps and was within 0.2 % of
+# the best (0.02) after 200.  On the tiny untrained fixture (tests/test_cpu_refine.py) 0.1 moves 8x further than 0.02 in 100 steps.
+DEFAULT_LR = 0.05
+
+Refined = collections.namedtuple("Refined", "y1 y2 z1 z2 cost_start cost_best")
+Refined.__doc__ = """The best iterate of refine_latents as float32 latents [B, ...] and the true objective of every pair at the start and at
+that iterate (float64 [B] on the device).  HSIC.compress / compress_batch take it as `latents=`."""
+
+
+class RefineConfig:
+    """steps: Adam steps (0: off -- the encoder's latents come back bit for bit); lr: Adam's step size (betas 0.9 / 0.999, eps 1e-8, no
+    decay); check_every: the true objective is evaluated every that many steps (and at the last); seed: 0 .. 2^32 - 1, the first key
+    word of the noise; pair_keys: one 0 .. 2^32 - 1 key per pair (None: the pair's index in the call) -- a pair refined under the same
+    seed and key sees the same noise whatever its position; lmbda: the rate-distortion weight for callers that carry no lmbda of their
+    own (StereoCodec, tools/eval_folder.py); refine_latents' own argument wins."""
+
+    def __init__(self, steps=0, lr=DEFAULT_LR, check_every=5, seed=0, pair_keys=None, lmbda=None):
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+            raise ValueError(f"RefineConfig: steps must be an integer >= 0, got {steps!r}")
+        if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
+            raise ValueError(f"RefineConfig: check_every must be an integer >= 1, got {check_every!r}")
+        if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not (0.0 < float(lr) < float("inf")):
+            raise ValueError(f"RefineConfig: lr must be a positive finite number, got {lr!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+            raise ValueError(f"RefineConfig: seed must be an integer in 0 .. 2^32 - 1, got {seed!r}")
+        if pair_keys is not None:
+            pair_keys = [k for k in pair_keys]
+            for k in pair_keys:
+                if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < 2 ** 32:
+                    raise ValueError(f"RefineConfig: pair_keys must be integers in 0 .. 2^32 - 1, got {k!r}")
+        if lmbda is not None and (isinstance(lmbda, bool) or not isinstance(lmbda, (int, float)) or not (0.0 < float(lmbda) < float("inf"))):
+            raise ValueError(f"RefineConfig: lmbda must be a positive finite number or None, got {lmbda!r}")
+        self.steps, self.lr, self.check_every, self.seed = steps, float(lr), check_every, seed
+        self.pair_keys, self.lmbda = pair_keys, None if lmbda is None else float(lmbda)
+
+    def keys_for(self, B):
+        """The B pair keys of a call as a list."""
+        if self.pair_keys is None:
+            return list(range(B))
+        if len(self.pair_keys) != B:
+            raise ValueError(f"RefineConfig: {len(self.pair_keys)} pair keys for {B} pairs")
+        return list(self.pair_keys)
+
+    def __repr__(self):
+        return (f"RefineConfig(steps={self.steps}, lr={self.lr}, check_every={self.check_every}, seed={self.seed}, "
+                f"pair_keys={self.pair_keys}, lmbda={self.lmbda})")
+
+
+# ------------------------------------------------------------------------------------------------------------------ the kernels
+def _four(ts, name, like=None):
+    """Four contiguous float32 device tensors [B, ...] -> (host pointer array, host array of elements per pair, B)."""
+    ts = list(ts)
+    if len(ts) != 4:
+        raise RuntimeError(f"masic_amd.refine: {name} must be four tensors, got {len(ts)}")
+    for k, t in enumerate(ts):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"masic_amd.refine: {name}[{k}] must be a CUDA (HIP) tensor -- the MI355X path has no CPU fallback")
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.numel() == 0:
+            raise RuntimeError(f"masic_amd.refine: {name}[{k}] must be a non-empty contiguous float32 tensor [B, ...]")
+    B = int(ts[0].shape[0])
+    if not 1 <= B <= MAX_PAIRS or any(t.shape[0] != B for t in ts):
+        raise RuntimeError(f"masic_amd.refine: {name}: one B in 1 .. {MAX_PAIRS} for the four tensors")
+    if like is not None and [tuple(t.shape) for t in ts] != [tuple(t.shape) for t in like]:
+        raise RuntimeError(f"masic_amd.refine: {name} must have the shapes of the first four tensors")
+    ptr = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in ts])
+    cnt = (ctypes.c_size_t * 4)(*[t.numel() // B for t in ts])
+    return ptr, cnt, B
+
+
+def _scalar(t, name, dtype, n=1):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise RuntimeError(f"masic_amd.refine: {name} must be a contiguous {dtype} device tensor of {n} element(s)")
+    return t
+
+
+def pair_keys_tensor(keys, device):
+    """B integers 0 .. 2^32 - 1 -> the int32 device tensor that carries their 32 bits."""
+    return torch.tensor([k - 2 ** 32 if k >= 2 ** 31 else k for k in keys], dtype=torch.int32, device=device)
+
+
+def noise(outs, seed, pair_keys, step):
+    """Fills the four tensors `outs` ([B, ...] each) with the noise of one step (masic_refine_noise): U[-1/2, 1/2) on a 2^-24 grid from
+    Philox4x32-10, key (seed, pair_keys[b]), counter (element index within pair b's slice, tensor 0..3, step, 0).  pair_keys: int32 [B]
+    device tensor (pair_keys_tensor); step: int32 device scalar.  One launch."""
+    from . import ops
+    ptr, cnt, B = _four(outs, "outs")
+    _scalar(pair_keys, "pair_keys", torch.int32, B); _scalar(step, "step", torch.int32)
+    _lib.check(_lib.lib.masic_refine_noise(ptr, cnt, B, int(seed) & 0xffffffff, ops._p(pair_keys), ops._p(step), ops._stream()), "refine_noise")
+    return outs
+
+
+def adam(params, grads, ms, vs, lr, step):
+    """One bias-corrected Adam step on the four tensors in place (masic_refine_adam): betas 0.9 / 0.999, eps 1e-8, no decay, float32
+    states ms / vs; step: int32 device scalar holding t >= 1.  One launch."""
+    from . import ops
+    p, cnt, B = _four(params, "params")
+    g, _, _ = _four(grads, "grads", params)
+    m, _, _ = _four(ms, "ms", params)
+    v, _, _ = _four(vs, "vs", params)
+    _scalar(step, "step", torch.int32)
+    _lib.check(_lib.lib.masic_refine_adam(p, g, m, v, cnt, B, float(lr), ops._p(step), ops._stream()), "refine_adam")
+
+
+def keep_best(cur, best, j_now, j_best):
+    """For every pair b with j_now[b] < j_best[b]: pair b's slices of the four `cur` tensors are copied into `best` and j_best[b] =
+    j_now[b] (masic_refine_keep_best).  j_now, j_best: float64 [B] on the device; the decision is the device's."""
+    from . import ops
+    c, cnt, B = _four(cur, "cur")
+    b, _, _ = _four(best, "best", cur)
+    _scalar(j_now, "j_now", torch.float64, B); _scalar(j_best, "j_best", torch.float64, B)
+    _lib.check(_lib.lib.masic_refine_keep_best(c, b, cnt, B, ops._p(j_now), ops._p(j_best), ops._stream()), "refine_keep_best")
+
+
+def rd_seeds(x1_hat, x1, x2_hat, x2, liks, lmbda, hw, g=None):
+    """Backward of autograd.PairRateDistortionFn in one launch (masic_refine_rd_seeds) -> (g1, g2, [gl_k]):
+    g1 = g[b] 2 lmbda 255^2 (x1_hat - x1) / n_pic, g2 likewise, gl_k = -g[b] / (ln 2 hw lik_k); g: float64 [B] or None for ones."""
+    from . import ops
+    liks = list(liks)
+    if len(liks) > 4:
+        raise RuntimeError(f"masic_amd.refine.rd_seeds: at most 4 likelihood tensors, got {len(liks)}")
+    for t in (x1_hat, x1, x2_hat, x2, *liks):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0:
+            raise RuntimeError("masic_amd.refine.rd_seeds: non-empty contiguous float32 device tensors only")
+    if not (x1_hat.shape == x1.shape == x2_hat.shape == x2.shape) or x1.dim() < 1:
+        raise RuntimeError("masic_amd.refine.rd_seeds: the four pictures must have one shape [B, ...]")
+    B = int(x1.shape[0])
+    if not 1 <= B <= MAX_PAIRS or any(l.dim() < 1 or l.shape[0] != B for l in liks):
+        raise RuntimeError(f"masic_amd.refine.rd_seeds: one B in 1 .. {MAX_PAIRS} for every tensor")
+    if g is not None:
+        _scalar(g, "g", torch.float64, B)
+    g1, g2, gl = torch.empty_like(x1_hat), torch.empty_like(x2_hat), [torch.empty_like(l) for l in liks]
+    n = max(len(liks), 1)
+    arr = (ctypes.c_void_p * n)(*[l.data_ptr() for l in liks])
+    out = (ctypes.c_void_p * n)(*[l.data_ptr() for l in gl])
+    cnt = (ctypes.c_size_t * n)(*[l.numel() // B for l in liks])
+    _lib.check(_lib.lib.masic_refine_rd_seeds(ops._p(x1_hat), ops._p(x1), ops._p(x2_hat), ops._p(x2), x1.numel() // B, arr, cnt, len(liks), B,
+                                              float(lmbda), float(hw), ops._p(g), ops._p(g1), ops._p(g2), out, ops._stream()), "refine_rd_seeds")
+    return g1, g2, gl
+
+
+# ------------------------------------------------------------------------------------------------------------------ the loop
+class _Frozen:
+    """requires_grad off on every parameter of the model for the duration (restored on exit, also after an error)."""
+
+    def __init__(self, module):
+        self._params = [p for _, p in module.named_parameters()]
+
+    def __enter__(self):
+        self._flags = [p.requires_grad for p in self._params]
+        for p in self._params:
+            p.requires_grad_(False)
+
+    def __exit__(self, *exc):
+        for p, f in zip(self._params, self._flags):
+            p.requires_grad_(f)
+        return False
+
+
+def surrogate_grads(hsic, latents, x1, x2, m_fwd, m_back, noise, lmbda, gates=None):
+    """One gradient of the loop: (d sum_b J_b / d (y1, y2, z1, z2), J [B] float64) of the surrogate HSIC._forward_refine at `latents`
+    under the noise tensors `noise`, the weights frozen for the call.  m_fwd / m_back: homography.warp_matrices of the pairs."""
+    from .autograd import PairRateDistortionFn
+    with _Frozen(hsic), torch.enable_grad():
+        leaves = [t.detach().requires_grad_(True) for t in latents]
+        out = hsic._forward_refine(*leaves, x1, x2, m_fwd, m_back, noise, gates=gates)
+        L = out["likelihoods"]
+        J = PairRateDistortionFn.apply(lmbda, x1, x2, out["x1_hat"], out["x2_hat"], L["y1"], L["y2"], L["z1"], L["z2"])
+        grads = torch.autograd.grad(J.sum(), leaves)
+    return [g.contiguous() for g in grads], J.detach()
+
+
+def _check_call(hsic, x1, x2, h_matrix, lmbda, config, who):
+    from . import nn as _mnn
+    if not isinstance(config, RefineConfig):
+        raise TypeError(f"{who}: config must be a RefineConfig, got {type(config).__name__}")
+    if _mnn.get_precision() == "fp8":
+        raise NotImplementedError(f"{who}: the latent refinement runs with bf16 or f32 operands; the fp8 mode has no backward")
+    if hsic.training:
+        raise RuntimeError(f"{who}: call .eval() first (the files are coded in eval mode)")
+    if lmbda is None:
+        lmbda = config.lmbda
+    if lmbda is None or not (0.0 < float(lmbda) < float("inf")):
+        raise ValueError(f"{who}: needs a positive lmbda (the argument, or RefineConfig(lmbda=...))")
+    for t, name in ((x1, "x1"), (x2, "x2"), (h_matrix, "h_matrix")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must be a CUDA (HIP) tensor -- the MI355X path has no CPU fallback")
+    if x1.dim() != 4 or x1.shape != x2.shape or x1.shape[1] != 3 or h_matrix.shape[0] != x1.shape[0]:
+        raise ValueError(f"{who}: x1, x2 [B,3,H,W] of one shape and h_matrix [B,3,3]")
+    hsic._codec_check(who, x1.shape[2], x1.shape[3])
+    return float(lmbda)
+
+
+def refine_latents(hsic, x1, x2, h_matrix, lmbda=None, config=None, trace=None):
+    """-> Refined.  hsic: an eval-mode MASIC.HSIC on the device; x1, x2: float32 [B,3,H,W] with H, W multiples of 64 (what compress
+    codes); h_matrix [B,3,3]; lmbda: the rate-distortion weight the checkpoint was trained with (or config.lmbda); config: a
+    RefineConfig.  Starts from exactly the latents compress computes (each pair on its own, as there).  After the call no parameter's
+    .grad or requires_grad, no entry of the state dict, hsic.training and neither of torch's default generators has changed.
+    trace (a list, for measurements): receives (step, float64 [B] device tensor) of every evaluation of the true objective -- device
+    tensors, so the loop still reads nothing on the host."""
+    who = "masic_amd.refine.refine_latents"
+    config = RefineConfig() if config is None else config
+    lmbda = _check_call(hsic, x1, x2, h_matrix, lmbda, config, who)
+    from . import ops
+    from .homography import warp_matrices
+    x1, x2 = x1.contiguous(), x2.contiguous()
+    B, _, H, W = x1.shape
+    dev = x1.device
+    keys = pair_keys_tensor(config.keys_for(B), dev)
+    with torch.no_grad():
+        mats = [warp_matrices(h_matrix[i:i + 1], (H, W), (H, W), want_inverse=True) for i in range(B)]
+        m_fwd, m_back = torch.cat([m[0] for m in mats]).contiguous(), torch.cat([m[1] for m in mats]).contiguous()
+        start = [[], [], [], []]
+        for i in range(B):          # the latents of HSIC._compress_pairs, pair by pair as there
+            a, b_ = x1[i:i + 1], x2[i:i + 1]
+            y1 = hsic.encoder1.latent(a)
+            y2 = hsic.encoder2.forward_views(ops.warp_perspective(a, mats[i][0], (H, W)), b_)
+            for k, t in enumerate((y1, y2, hsic._h_a1(y1), hsic._h_a2(y2))):
+                start[k].append(t)
+        cur = [torch.cat(ts).contiguous() for ts in start]
+        gates = hsic.mask2weights_unit(ops.warp_perspective(None, m_fwd, (H, W), ones_like=(B, H, W))).contiguous()
+
+        def true_cost():
+            out = hsic._eval_from_latents(*cur, m_fwd, gates)
+            L = out["likelihoods"]
+            return metrics_cost(out["x1_hat"], out["x2_hat"], (L["y1"], L["y2"], L["z1"], L["z2"]))
+
+        def metrics_cost(x1_hat, x2_hat, liks):
+            from . import metrics
+            return metrics.pair_objective(metrics.pair_rd(x1_hat.contiguous(), x1, x2_hat.contiguous(), x2, [l.contiguous() for l in liks]),
+                                          lmbda, H * W, 3 * H * W)
+
+        cost_start = true_cost()
+        if trace is not None:
+            trace.append((0, cost_start.clone()))
+        if config.steps == 0:
+            return Refined(*cur, cost_start, cost_start.clone())
+        best = [t.clone() for t in cur]
+        cost_best = cost_start.clone()
+        ms, vs = [torch.zeros_like(t) for t in cur], [torch.zeros_like(t) for t in cur]
+        us = [torch.empty_like(t) for t in cur]
+        step = torch.zeros(1, dtype=torch.int32, device=dev)
+    with _Frozen(hsic):
+        for s in range(1, config.steps + 1):
+            with torch.no_grad():
+                step.add_(1)
+                noise(us, config.seed, keys, step)
+            grads, _ = surrogate_grads(hsic, cur, x1, x2, m_fwd, m_back, us, lmbda, gates=gates)
+            with torch.no_grad():
+                adam(cur, grads, ms, vs, config.lr, step)
+                if s % config.check_every == 0 or s == config.steps:
+                    now = true_cost()
+                    if trace is not None:
+                        trace.append((s, now))
+                    keep_best(cur, best, now, cost_best)
+    return Refined(*best, cost_start, cost_best)

@@ -130,12 +130,24 @@ class StereoCodec:
     masic_amd.align.PatchAligner, which needs no weights; needed by encode only) and cqe (MASIC.Independent_EN; needed for
     decode(enhance=True) only) are modules of this tree on one MI355X device, in eval mode.  The operand mode is
     masic_amd.nn.set_precision's, as for HSIC.compress; the file records it.  band_rows (0 .. 255): HSIC.compress_batch's, for encode
-    only -- the inner .bin carries the value, so decode needs nothing and a codec built without it decodes the files."""
+    only -- the inner .bin carries the value, so decode needs nothing and a codec built without it decodes the files.  refine (None:
+    off, today's files byte for byte): a masic_amd.refine.RefineConfig with steps > 0 and its lmbda set (the rate-distortion weight the
+    checkpoint was trained with -- the codec has no other source for it); encode then refines every batch's latents
+    (refine.refine_latents) before coding them.  For encode only: the bytes layout, decode and evaluate_files are untouched."""
 
-    def __init__(self, hsic, udh=None, cqe=None, band_rows=0):
+    def __init__(self, hsic, udh=None, cqe=None, band_rows=0, refine=None):
         from .bands import check_band_rows
         self.hsic, self.udh, self.cqe = hsic, udh, cqe
         self.band_rows = check_band_rows(band_rows, "StereoCodec")
+        if refine is not None:
+            from .refine import RefineConfig
+            if not isinstance(refine, RefineConfig):
+                raise TypeError(f"StereoCodec: refine must be a masic_amd.refine.RefineConfig or None, got {type(refine).__name__}")
+            if refine.steps > 0 and refine.lmbda is None:
+                raise ValueError("StereoCodec: refine needs RefineConfig(lmbda=...), the rate-distortion weight of the checkpoint")
+            if refine.steps == 0:
+                refine = None
+        self.refine = refine
 
     def _check_modules(self, who, *mods):
         for name, m in mods:
@@ -185,7 +197,12 @@ class StereoCodec:
             h_matrix = h_matrix_from_offsets(delta_q, (H0, W0), dev)
             inner = _inner_names(names)
             with tempfile.TemporaryDirectory(prefix="masic_msf_") as tmp:
-                out = self.hsic.compress_batch(planes[:B], planes[B:], h_matrix, inner, tmp, band_rows=self.band_rows)
+                if self.refine is None:
+                    out = self.hsic.compress_batch(planes[:B], planes[B:], h_matrix, inner, tmp, band_rows=self.band_rows)
+                else:
+                    from .refine import refine_latents
+                    latents = refine_latents(self.hsic, planes[:B], planes[B:], h_matrix, None, self.refine)
+                    out = self.hsic.compress_batch(planes[:B], planes[B:], h_matrix, inner, tmp, band_rows=self.band_rows, latents=latents)
                 files = []
                 for i, n in enumerate(inner):
                     with open(os.path.join(tmp, n + ".npz"), "rb") as f:
