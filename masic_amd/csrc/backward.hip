@@ -59,13 +59,13 @@ __global__ __launch_bounds__(256) void ew_kernel(const float* __restrict__ a, co
 constexpr int CS_SPLIT = 64;
 
 __global__ __launch_bounds__(256) void channel_sum_stage1(const float* __restrict__ x, double* __restrict__ partial,
-                                                          int B, int C, int HW, int ctot, int coff, float* __restrict__ out_direct) {
+                                                          int B, int C, int HW, int ctot, int coff, int vec, float* __restrict__ out_direct) {
     __shared__ double red[256];
     const int c = blockIdx.x, sp = blockIdx.y;
     // chunks of 4096 pixels (16-byte loads: 4 per thread), dealt round-robin over (b, chunk) pairs to the CS_SPLIT blocks of this
     // channel; a thread sums at most a few hundred values in float32, the cross-thread tree is float64 (deterministic order)
+    // (vec: the launcher's decision -- HW % 4 == 0 and a 16-byte aligned base, so that every plane starts on a 16-byte line)
     const int chunks = (HW + 4095) / 4096;
-    const bool vec = (HW & 3) == 0;
     float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
     for (int w = sp; w < B * chunks; w += (int)gridDim.y) {
         const int b = w / chunks, ck = w - b * chunks;
@@ -906,11 +906,12 @@ extern "C" int masic_channel_sum(const float* x, float* out, void* workspace, in
     MASIC_REQUIRE(coff >= 0 && coff + C <= ctot, MASIC_ERR_SHAPE, "channel_sum: view out of range");
     // latent-resolution tensors of many channels (the 1x1 layers of the entropy-parameter stacks: 8 x 32 x 32 pixels, <= 1152 channels):
     // one block per channel already fills the chip and a second launch would cost more than the sum itself
+    const int vec = HW % 4 == 0 && ((size_t)x & 15) == 0;       // float4 loads: as masic_plane_copy decides
     if ((long)B * HW <= 16384 && C >= 128) {
-        hipLaunchKernelGGL(channel_sum_stage1, dim3(C, 1), dim3(256), 0, (hipStream_t)stream, x, (double*)workspace, B, C, HW, ctot, coff, out);
+        hipLaunchKernelGGL(channel_sum_stage1, dim3(C, 1), dim3(256), 0, (hipStream_t)stream, x, (double*)workspace, B, C, HW, ctot, coff, vec, out);
         return masic_launch_status("channel_sum");
     }
-    hipLaunchKernelGGL(channel_sum_stage1, dim3(C, CS_SPLIT), dim3(256), 0, (hipStream_t)stream, x, (double*)workspace, B, C, HW, ctot, coff, (float*)nullptr);
+    hipLaunchKernelGGL(channel_sum_stage1, dim3(C, CS_SPLIT), dim3(256), 0, (hipStream_t)stream, x, (double*)workspace, B, C, HW, ctot, coff, vec, (float*)nullptr);
     hipLaunchKernelGGL(channel_sum_stage2, dim3(ceil_div(C, 64)), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, out, C);
     return masic_launch_status("channel_sum");
 }
