@@ -744,6 +744,31 @@ class PairRateDistortionFn(Function):
         return (None, None, None, g1, g2, *gl)
 
 
+class PairBudgetFn(Function):
+    """J_b(mu) = mu_b bits_b / (H W) + lmbda 255^2 (MSE1_b + MSE2_b) per pair b, float64 [B] on the device: the surrogate objective
+    of the latent refinement under a bit budget (masic_amd/refine.py), mu float64 [B] on the device and no gradient to it.  Forward =
+    the rows of metrics.pair_rd combined with mu by a few float64 [B] operations; backward = one launch (masic_budget_rd_seeds).
+    With mu of ones the gradients are PairRateDistortionFn's bit for bit."""
+
+    @staticmethod
+    def forward(ctx, lmbda, mu, x1, x2, x1_hat, x2_hat, *liks):
+        from . import metrics, refine
+        x1, x2, x1_hat, x2_hat = _c(x1), _c(x2), _c(x1_hat), _c(x2_hat)
+        liks = [_c(l) for l in liks]
+        H, W = x1.shape[-2:]
+        ctx.lmbda, ctx.hw = float(lmbda), float(H * W)
+        ctx.save_for_backward(mu, x1, x2, x1_hat, x2_hat, *liks)
+        bits, mse = refine.bits_and_mse(metrics.pair_rd(x1_hat, x1, x2_hat, x2, liks), x1[0].numel())
+        return mu * bits / float(H * W) + (float(lmbda) * 255.0 ** 2) * mse
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import refine
+        mu, x1, x2, x1_hat, x2_hat, *liks = ctx.saved_tensors
+        g1, g2, gl = refine.budget_seeds(x1_hat, x1, x2_hat, x2, liks, ctx.lmbda, ctx.hw, _c(g), mu)
+        return (None, None, None, None, g1, g2, *gl)
+
+
 _RD_FUSED = True             # the criterion as two launches; tests set False for six reductions + torch scalar arithmetic as their reference
 
 

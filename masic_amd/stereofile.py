@@ -133,7 +133,9 @@ class StereoCodec:
     only -- the inner .bin carries the value, so decode needs nothing and a codec built without it decodes the files.  refine (None:
     off, today's files byte for byte): a masic_amd.refine.RefineConfig with steps > 0 and its lmbda set (the rate-distortion weight the
     checkpoint was trained with -- the codec has no other source for it); encode then refines every batch's latents
-    (refine.refine_latents) before coding them.  For encode only: the bytes layout, decode and evaluate_files are untouched."""
+    (refine.refine_latents) before coding them; a config with a bit budget (budget_bpp -- per pixel of the padded size H x W, a
+    sequence of them one per pair of every encode call -- or budget_rel) refines under it, the budget being on the estimated bits of
+    the inner streams, not on the .msf file's bytes.  For encode only: the bytes layout, decode and evaluate_files are untouched."""
 
     def __init__(self, hsic, udh=None, cqe=None, band_rows=0, refine=None):
         from .bands import check_band_rows
@@ -185,6 +187,8 @@ class StereoCodec:
         B, H0, W0 = left_u8.shape[:3]
         if len(names) != B:
             raise ValueError(f"{who}: {B} pairs and {len(names)} names")
+        if self.refine is not None:
+            self.refine.budget_bpp_for(B, who)          # a budget per pair must be one per pair of this call
         H, W = padded_hw(H0, W0)
         if max(H, W) > 65535:
             raise ValueError(f"{who}: picture size {H0}x{W0} padded to {H}x{W} exceeds 65535 (the header stores sizes as uint16)")

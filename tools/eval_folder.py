@@ -4,14 +4,16 @@ on this library -- masic_amd.evaluate.evaluate_folder (rate from the likelihoods
 
     python tools/eval_folder.py -d /data/instereo2k --checkpoint checkpoint.pth.tar [--homopath homo_best.pth.tar | --aligner]
         [--cqe second_checkpoint.pth.tar] [--split test] [--patch-size 256 256] [--batch-size 8] [--files] [--band-rows S]
-        [--refine-steps K --refine-lmbda L [--refine-lr R]] [--precision bf16] [--lpips-weights alex.pth] [--json report.json] [--timing]
+        [--refine-steps K --refine-lmbda L [--refine-lr R] [--refine-budget-bpp X | --refine-budget-rel X]] [--precision bf16] [--lpips-weights alex.pth] [--json report.json] [--timing]
 
 --checkpoint: what tools/train_folder.py --save writes ({'state_dict': ...} of MASIC.HSIC; --nmk for another width than 128 192 5).
 --aligner: masic_amd.align.PatchAligner in place of a trained homography net.  The line printed is Report.line(): fields 'Label: value'
 separated by '|' after 'Test epoch 0:'.  --json: the per-pair table.  --timing: the device time of evaluate.pair_metrics on one batch
 beside that of the B per-slice loss.rate_distortion calls it replaces.  --refine-steps (with --files): the encoder refines every pair's
 latents for that many Adam steps before coding (masic_amd.refine; --refine-lmbda: the rate-distortion weight the checkpoint was
-trained with, --refine-lr: Adam's step size, default the library's)."""
+trained with, --refine-lr: Adam's step size, default the library's).  --refine-budget-bpp X: every pair may cost at most X estimated
+bits per pixel of its padded size; --refine-budget-rel X: at most X times the estimated bits of its unrefined latents (1.0: refine, but
+never to more bits) -- RefineConfig's budget_bpp / budget_rel."""
 import argparse
 import os
 import sys
@@ -81,6 +83,9 @@ def main(argv=None):
     ap.add_argument("--refine-steps", type=int, default=0, help="--files: Adam steps of encoder-side latent refinement per batch (0: off)")
     ap.add_argument("--refine-lr", type=float, default=None, help="Adam's step size (default: masic_amd.refine.DEFAULT_LR)")
     ap.add_argument("--refine-lmbda", type=float, default=None, help="the rate-distortion weight of the checkpoint; needed with --refine-steps")
+    ap.add_argument("--refine-budget-bpp", type=float, default=None, help="with --refine-steps: a pair's estimated bits per pixel at most")
+    ap.add_argument("--refine-budget-rel", type=float, default=None, help="with --refine-steps: a pair's estimated bits at most this "
+                                                                          "multiple of its unrefined latents'")
     ap.add_argument("--precision", default="bf16", choices=("f32", "bf16"))
     ap.add_argument("--metrics", nargs="*", default=None, help="psnr ms_ssim lpips (default: psnr ms_ssim, and lpips with --lpips-weights)")
     ap.add_argument("--lpips-weights", default=None, help="the lin-layer weights (alex.pth) of lpips.LPIPS; the trunk's come from "
@@ -96,6 +101,10 @@ def main(argv=None):
         raise SystemExit("eval_folder: --refine-steps refines what is coded: it needs --files")
     if args.refine_steps and args.refine_lmbda is None:
         raise SystemExit("eval_folder: --refine-steps needs --refine-lmbda, the rate-distortion weight the checkpoint was trained with")
+    if (args.refine_budget_bpp is not None or args.refine_budget_rel is not None) and not args.refine_steps:
+        raise SystemExit("eval_folder: --refine-budget-bpp / --refine-budget-rel constrain the refinement: they need --refine-steps")
+    if args.refine_budget_bpp is not None and args.refine_budget_rel is not None:
+        raise SystemExit("eval_folder: --refine-budget-bpp and --refine-budget-rel exclude each other")
     if not torch.cuda.is_available():
         raise SystemExit("eval_folder: needs an MI355X -- the library has no CPU path")
     import MASIC
@@ -130,7 +139,8 @@ def main(argv=None):
             refine = None
             if args.refine_steps:
                 from masic_amd.refine import DEFAULT_LR, RefineConfig
-                refine = RefineConfig(steps=args.refine_steps, lr=DEFAULT_LR if args.refine_lr is None else args.refine_lr, lmbda=args.refine_lmbda)
+                refine = RefineConfig(steps=args.refine_steps, lr=DEFAULT_LR if args.refine_lr is None else args.refine_lr, lmbda=args.refine_lmbda,
+                                      budget_bpp=args.refine_budget_bpp, budget_rel=args.refine_budget_rel)
             codec = StereoCodec(hsic, homo, cqe, band_rows=args.band_rows, refine=refine)
             report = evaluate.evaluate_files(codec, args.dataset, args.split, args.batch_size, enhance=cqe is not None, metrics=metrics,
                                              lpips_fn=lpips_fn, out_dir=args.out_dir)
