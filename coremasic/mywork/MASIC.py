@@ -688,8 +688,34 @@ class HSIC(CompressionModel):
         self._h_s1_same_resolution = gmm_hyper_y1_same_resolution(N=N, M=M, K=K)
         self._h_s2_same_resolution = gmm_hyper_y2_same_resolution(N=N, M=M, K=K)
         self.mask2weights_unit = mask2weights(N=N, M=M, Kw=3)
+        self._band_rows = 0
         # NB: as in the reference, _initialize_weights() ran inside super().__init__() before any of
         # these children existed, so the convs keep torch's default initialisation.
+
+    @property
+    def band_rows(self):
+        """The row bands of the file this model ESTIMATES (DESIGN.md section 8.1 "Row bands in the model"): with S > 0 every context model
+        evaluated outside the coder -- forward in all its modes, the training graph, _forward_refine, _eval_from_latents -- is the banded
+        one of `compress(..., band_rows=S)`, whose bands of S latent rows do not see across their top edge.  0 (default): the unbanded
+        model, today's launches.  A plain attribute: no constructor argument, not in the state dict; how a file is CODED stays the
+        band_rows argument of compress / compress_batch.  masic_amd.bands.model_band_rows sets and restores it."""
+        return self.__dict__.get("_band_rows", 0)
+
+    @band_rows.setter
+    def band_rows(self, value):
+        self._band_rows = _check_band_rows(value, "HSIC.band_rows")
+
+    def _model_bands(self, h):
+        """self.band_rows as it cuts a latent of h rows: 0 where that is one band.  fp8 operands are refused: their scales were calibrated
+        on whole latents and the folded path has not been validated against them."""
+        S = self.band_rows
+        if not 0 < S < h:
+            return 0
+        from masic_amd import nn as _mnn
+        if _mnn._FP8 or _fp8.recording():
+            raise NotImplementedError(f"HSIC.band_rows = {S}: the band-aware entropy model runs with float32 or bf16 operands only; with fp8 operands "
+                                      "it is refused instead of returning the unbanded estimate (set band_rows = 0 or leave the fp8 mode)")
+        return S
 
     # `_quantize` / `_standardized_cumulative` duplicates of the reference (:710-742) for callers that
     # reach into the model
@@ -743,23 +769,11 @@ class HSIC(CompressionModel):
     def _context_bands(self, ctx, y, out, out_coff, gate, gate_c, S):
         """The context model of the full-latent parameter form with the latent cut into bands of S rows that do not see across their top
         edge (masic_amd.codec.wavefront_steps): the bands as images of one call of _context.  h is padded to a multiple of S with zero
-        rows at the bottom (the mask is causal: they reach no row above them), [B, M, T S, w] is viewed as [B T, M, S, w], the
-        convolution's own zero padding above each image is the band top, and the rows go back in place.  The gate multiplies in
-        float32 as in the layers' epilogues.  Encoder and decoder both come through here, so their tables agree."""
-        B, M, h, w = y.shape
-        T = -(-h // S)
-        yb = F.pad(y, (0, 0, 0, T * S - h)).view(B, M, T, S, w).permute(0, 2, 1, 3, 4).reshape(B * T, M, S, w).contiguous()
-        cb = self._context(ctx, yb, None)
-        C = cb.shape[1]
-        c = cb.view(B, T, C, S, w).permute(0, 2, 1, 3, 4).reshape(B, C, T * S, w)[:, :, :h]
-        if gate is not None:
-            c = c * gate[:, gate_c:gate_c + 1]
-        if isinstance(out, _F16K):
-            return out.fill_from_nchw(c.contiguous())
-        if out is None:
-            return c.contiguous()
-        out[:, out_coff:out_coff + C] = c
-        return out
+        rows at the bottom (the mask is causal: they reach no row above them), [B, M, T S, w] is folded to [B T, M, S, w], the
+        convolution's own zero padding above each image is the band top, and the rows go back in place -- one launch each way
+        (masic_amd/bandfold.py).  The gate multiplies in float32 as in the layers' epilogues.  Encoder and decoder both come through
+        here, so their tables agree; so does the model's own estimate (HSIC.band_rows)."""
+        return _ag.banded_context(ctx, y, S, call=lambda t: self._context(ctx, t, None), out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
 
     def _needs_graph(self):
         return self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.encoder1.parameters())
@@ -784,6 +798,7 @@ class HSIC(CompressionModel):
         else:
             m_fwd, m_back = _warp_matrices(h_matrix, (H, W), (H, W), want_inverse=True, device=_mnn.reduced_precision())
         y1 = self.encoder1.latent_train(x1)
+        S = self._model_bands(y1.shape[-2])             # 0: the calls below are the unbanded ones
         # Two branches of the step need nothing of the main chain (encoder1 -> y1 + noise -> decoder1 -> warp -> encoder1 -> heads2 ->
         # decoder2) until late: the left view's entropy chain (only its likelihoods leave it) and the right view up to its entropy
         # parameters.  With MASIC_TRAIN_STREAMS each is ISSUED where the reference has it -- the noise draws are numbered by the host --
@@ -797,7 +812,8 @@ class HSIC(CompressionModel):
             z1 = self._h_a1(y1)
             z1_hat, z1_lik = self.entropy_bottleneck1(z1)                                   # draw 1
             params1 = self._hyper_up(self.h_s1_up, z1_hat)
-            ctx1 = self.context_prediction1.run(self.gaussian1._quantize(y1, "noise"))     # draw 2
+            ctx1 = _ag.banded_context(self.context_prediction1, self.gaussian1._quantize(y1, "noise"), S,      # draw 2
+                                      call=self.context_prediction1.run)
             s1, m1, l1 = self._h_s1_same_resolution.heads(_ag.cat(params1, ctx1))
         # gaussian1(y1, s1, m1, l1) of the reference (:767) in its two halves: the draw here, the likelihood beside the synthesis transform
         y1_hat = self.gaussian1._quantize(y1, "noise")                                      # draw 3
@@ -813,7 +829,8 @@ class HSIC(CompressionModel):
             z2 = self._h_a2(y2)
             z2_hat, z2_lik = self.entropy_bottleneck2(z2)                                   # draw 4
             params2 = self._hyper_up(self.h_s2_up, z2_hat)
-            ctx2 = self.context_prediction2.run(self.gaussian2._quantize(y2, "noise"))     # draw 5
+            ctx2 = _ag.banded_context(self.context_prediction2, self.gaussian2._quantize(y2, "noise"), S,      # draw 5
+                                      call=self.context_prediction2.run)
             if hgrad:
                 x1_mask_R = _ag.WarpOnesFn.apply(m_fwd, (B, H, W), (H, W))
                 x1_mask_L = _ag.WarpFn.apply(x1_mask_R, m_back, (H, W))
@@ -874,7 +891,8 @@ class HSIC(CompressionModel):
         y1_r = _ag.RoundSteFn.apply(y1, None, None)
         z1_r, z1_lik = bottleneck(self.entropy_bottleneck1, z1, n_z1)
         params1 = self._hyper_up(self.h_s1_up, z1_r)
-        ctx1 = self.context_prediction1.run(y1_r)
+        S = self._model_bands(y1.shape[-2])
+        ctx1 = _ag.banded_context(self.context_prediction1, y1_r, S, call=self.context_prediction1.run)
         s1, m1, l1 = self._h_s1_same_resolution.heads(_ag.cat(params1, ctx1))
         y1_lik = self.gaussian1.likelihood_of(_ag.AddNoiseFn.apply(y1, n_y1), s1, m1, l1, weights_are_logits=True)
         x1_hat = self.decoder1.reconstruct_train(y1_r)
@@ -882,7 +900,7 @@ class HSIC(CompressionModel):
         y2_r = _ag.RoundSteFn.apply(y2, None, None)
         z2_r, z2_lik = bottleneck(self.entropy_bottleneck2, z2, n_z2)
         params2 = self._hyper_up(self.h_s2_up, z2_r)
-        ctx2 = self.context_prediction2.run(y2_r)
+        ctx2 = _ag.banded_context(self.context_prediction2, y2_r, S, call=self.context_prediction2.run)
         x1_hat_warp = _ag.WarpFn.apply(x1_hat, m_fwd, (H, W))
         y1_warp_r = _ag.RoundSteFn.apply(self.encoder1.latent_train(x1_hat_warp), None, None)
         cat2 = _ag.cat(_ag.GateFn.apply(params2, gates, 0), _ag.GateFn.apply(ctx2, gates, 1), _ag.GateFn.apply(y1_warp_r, gates, 2))
@@ -902,7 +920,8 @@ class HSIC(CompressionModel):
         z1_hat, z1_lik = self.entropy_bottleneck1(z1)
         cat16 = self._cat_f16k(self._h_s1_same_resolution, y1, 4 * M)
         cat1 = None if cat16 is not None else torch.empty((B, 4 * M, h, w), dtype=y1.dtype, device=y1.device)
-        self._context(self.context_prediction1, y1, **self._slice(cat1, cat16, 2 * M, 2 * M))
+        S = self._model_bands(h)
+        self._context(self.context_prediction1, y1, band_rows=S, **self._slice(cat1, cat16, 2 * M, 2 * M))
         self._hyper_up(self.h_s1_up, z1_hat, **self._slice(cat1, cat16, 0, 2 * M))
         s1, m1, l1 = self._h_s1_same_resolution.heads(cat1 if cat16 is None else cat16, parallel=False)
         _, y1_lik = self.gaussian1(y1, s1, m1, l1, weights_are_logits=True, want_y_hat=False)
@@ -913,7 +932,7 @@ class HSIC(CompressionModel):
         cat16 = self._cat_f16k(self._h_s2_same_resolution, y2, 5 * M)
         cat2 = None if cat16 is not None else torch.empty((B, 5 * M, h, w), dtype=y2.dtype, device=y2.device)
         self._hyper_up(self.h_s2_up, z2_hat, gate=gates, gate_c=0, **self._slice(cat2, cat16, 0, 2 * M))
-        self._context(self.context_prediction2, y2, gate=gates, gate_c=1, **self._slice(cat2, cat16, 2 * M, 2 * M))
+        self._context(self.context_prediction2, y2, gate=gates, gate_c=1, band_rows=S, **self._slice(cat2, cat16, 2 * M, 2 * M))
         y2_lik = self._eval_right_entropy(x1_hat_warp, {"cat2": cat2, "cat16": cat16, "gates": gates, "y2": y2})
         x2_hat = self.decoder2(_hip.quantize(y2, "dequantize"), x1_hat_warp)
         return {"x1_hat": x1_hat, "x2_hat": x2_hat, "likelihoods": {"y1": y1_lik, "y2": y2_lik, "z1": z1_lik, "z2": z2_lik}}
@@ -955,7 +974,8 @@ class HSIC(CompressionModel):
         cat1 = torch.empty((B, 4 * M, h, w), dtype=x1.dtype, device=x1.device)      # params1 | ctx_params1
         self._hyper_up(self.h_s1_up, z1_hat, cat1, 0)
         y1_ctx = self.gaussian1._quantize(y1, "noise")
-        self.context_prediction1.run(y1_ctx, out=cat1, out_coff=2 * M)
+        S = self._model_bands(h)
+        _ag.banded_context(self.context_prediction1, y1_ctx, S, call=self.context_prediction1.run, out=cat1, out_coff=2 * M)
         s1, m1, l1 = self._h_s1_same_resolution.heads(cat1)
         y1_hat, y1_lik = self.gaussian1(y1, s1, m1, l1, weights_are_logits=True)
         x1_hat = self.decoder1.reconstruct(y1_hat)
@@ -972,7 +992,7 @@ class HSIC(CompressionModel):
         cat2 = torch.empty((B, 5 * M, h, w), dtype=x1.dtype, device=x1.device)      # params2*g0 | ctx2*g1 | y1_warp_hat*g2
         self._hyper_up(self.h_s2_up, z2_hat, cat2, 0, gate=gates, gate_c=0)
         y2_ctx = self.gaussian2._quantize(y2, "noise")
-        self.context_prediction2.run(y2_ctx, out=cat2, out_coff=2 * M, gate=gates, gate_c=1)
+        _ag.banded_context(self.context_prediction2, y2_ctx, S, call=self.context_prediction2.run, out=cat2, out_coff=2 * M, gate=gates, gate_c=1)
 
         x1_hat_warp = _hip.warp_perspective(x1_hat, m_fwd, (H, W))                   # used twice (:821, :833)
         y1_warp = self.encoder1.latent(x1_hat_warp)
@@ -1019,7 +1039,8 @@ class HSIC(CompressionModel):
         x1_mask_L = _hip.warp_perspective(x1_mask_R, m_back, (H, W))
         gates = self.mask2weights_unit(x1_mask_R)                                    # [B,3,h,w]
         self._hyper_up(self.h_s2_up, z2_hat, gate=gates, gate_c=0, **self._slice(cat2, cat16, 0, 2 * M))
-        self._context(self.context_prediction2, y2, gate=gates, gate_c=1, round16=y2_round16, **self._slice(cat2, cat16, 2 * M, 2 * M))
+        self._context(self.context_prediction2, y2, gate=gates, gate_c=1, round16=y2_round16, band_rows=self._model_bands(h),
+                      **self._slice(cat2, cat16, 2 * M, 2 * M))
         return {"y2": y2, "y2_round16": y2_round16, "y2_abs16": y2_abs16, "z2_hat": z2_hat, "z2_lik": z2_lik, "cat2": cat2, "cat16": cat16, "gates": gates, "x1_mask_R": x1_mask_R, "x1_mask_L": x1_mask_L}
 
     def _cat_f16k(self, head, y, C):
@@ -1042,7 +1063,8 @@ class HSIC(CompressionModel):
         B = y1.shape[0]
         cat16 = self._cat_f16k(self._h_s1_same_resolution, y1, 4 * M)
         cat1 = None if cat16 is not None else torch.empty((B, 4 * M) + tuple(y1.shape[-2:]), dtype=y1.dtype, device=y1.device)   # params1 | ctx_params1
-        self._context(self.context_prediction1, y1, round16=round16, **self._slice(cat1, cat16, 2 * M, 2 * M))
+        self._context(self.context_prediction1, y1, round16=round16, band_rows=self._model_bands(y1.shape[-2]),
+                      **self._slice(cat1, cat16, 2 * M, 2 * M))
         z1 = self._h_a1(y1, abs16=abs16)
         z1_hat, z1_lik = self.entropy_bottleneck1(z1)
         self._hyper_up(self.h_s1_up, z1_hat, **self._slice(cat1, cat16, 0, 2 * M))

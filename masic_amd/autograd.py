@@ -646,6 +646,66 @@ def cat(*ts):
     return out
 
 
+class BandFoldFn(Function):
+    """[B, C, h, w] -> [B T, C, S, w]: the latent's bands of S rows as images of a batch (bandfold.fold).  Backward: the ungated float32
+    unfold, its adjoint -- the padding rows' gradient is dropped."""
+
+    @staticmethod
+    def forward(ctx, x, S):
+        from . import bandfold
+        x = _c(x)
+        ctx.B, ctx.h, ctx.S = x.shape[0], x.shape[2], S
+        return bandfold.fold(x, S)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import bandfold
+        return bandfold.unfold(_c(g), ctx.B, ctx.h, ctx.S), None
+
+
+class BandUnfoldFn(Function):
+    """[B T, C, S, w] -> [B, C, h, w], padding rows dropped (bandfold.unfold, ungated).  Backward: the fold, its adjoint -- the padding
+    rows get a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, xb, B, h, S):
+        from . import bandfold
+        ctx.S = S
+        return bandfold.unfold(_c(xb), B, h, S)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import bandfold
+        return bandfold.fold(_c(g), ctx.S), None, None, None
+
+
+def banded_context(ctx_mod, y, S, call=None, out=None, out_coff=0, gate=None, gate_c=0):
+    """The masked convolution `ctx_mod` of a latent y [B, M, h, w] whose bands of S rows do not see across their top edge (DESIGN.md
+    section 8.1): fold -> the convolution on [B T, M, S, w] -> unfold.  The convolution's own zero padding above each image is the band
+    top, as a tap above the latent's top reads zeros; the zero rows under a short last band reach no row above them (the mask is causal).
+
+    call(t, **dest): the caller's convolution, run as the caller runs it today (default: conv(ctx_mod, t) of this module).  S = 0 or
+    S >= h: no bands -- call(y, **dest) with the destination arguments that were given, today's call bit for bit.  Otherwise call(folded)
+    without a destination, and the unfold writes it: a fresh float32 tensor, channels [out_coff, ..) of the float32 NCHW `out`, or the
+    F16K view `out`, times gate[:, gate_c] in float32 where a gate is given.  Differentiable through both kernels when neither `out` nor
+    `gate` is given (BandFoldFn / BandUnfoldFn); a destination or a gate is an inference-only fusion, as in nn.run."""
+    from . import bandfold
+    if call is None:
+        def call(t):
+            return conv(ctx_mod, t)
+    B, _, h, _ = y.shape
+    if not 0 < S < h:
+        dest = {} if out is None else dict(out=out) if isinstance(out, F16K) else dict(out=out, out_coff=out_coff)
+        if gate is not None:
+            dest.update(gate=gate, gate_c=gate_c)
+        return call(y, **dest)
+    if out is None and gate is None:
+        return BandUnfoldFn.apply(call(BandFoldFn.apply(y, S)), B, h, S)
+    if torch.is_grad_enabled() and (y.requires_grad or ctx_mod.weight.requires_grad):
+        raise RuntimeError("masic_amd: writing the banded context into a concat buffer or gating it is an inference-only fusion")
+    return bandfold.unfold(_c(call(bandfold.fold(_c(y), S))), B, h, S, out=out, out_coff=out_coff, gate=gate, gate_c=gate_c)
+
+
 class SoftmaxKFn(Function):
     """softmax over K on the (B,K,M,H,W) view (MASIC.py:389-393; K=3, M=1 for the mask2weights gates)."""
 

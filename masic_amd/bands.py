@@ -9,6 +9,7 @@ do not depend on each other and run side by side (codec.wavefront_steps(h, w, ba
 
 The entry point is declared in include/masic_bands.h, a side header of libmasic_hip.so bound by _lib.bind_header.  No CPU path.
 """
+import contextlib
 import ctypes
 import operator
 import os
@@ -31,6 +32,19 @@ def check_band_rows(band_rows, who):
     if v is None or not 0 <= v <= MAX_BAND_ROWS:
         raise ValueError(f"{who}: band_rows must be an integer in 0 .. {MAX_BAND_ROWS} (0: one band, the whole latent), got {band_rows!r}")
     return v
+
+
+@contextlib.contextmanager
+def model_band_rows(hsic, band_rows):
+    """`with model_band_rows(hsic, S):` -- hsic.band_rows = S inside (the context model every forward, the training graph, the latent
+    refinement and evaluate_folder's estimate then model is that of a file coded with band_rows = S), the earlier value after it."""
+    S = check_band_rows(band_rows, "model_band_rows")
+    before = hsic.band_rows
+    hsic.band_rows = S
+    try:
+        yield hsic
+    finally:
+        hsic.band_rows = before
 
 
 def skinny_ctx(group, pix, step, list_stride, npix, nimg, h, w, gate, gate_ctot, gate_c, band_rows, stream):

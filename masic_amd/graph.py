@@ -77,16 +77,17 @@ class GraphedHSIC:
         self._packs = _mnn.cached_packs(net)
         self._sources = _mnn.pack_sources(net)
         self._signature = _mnn.pack_signature(self._sources)
-        self._precision = (_mnn.get_precision(), ops.get_warp_align_corners())     # settings baked into the captured launches
+        # settings baked into the captured launches
+        self._precision = (_mnn.get_precision(), ops.get_warp_align_corners(), getattr(net, "band_rows", 0))
 
     def _check_fresh(self):
         from . import nn as _mnn
-        if (_mnn.pack_signature(self._sources) == self._signature and (_mnn.get_precision(), ops.get_warp_align_corners()) == self._precision
-                and not self.net.training):
+        if (_mnn.pack_signature(self._sources) == self._signature and not self.net.training
+                and (_mnn.get_precision(), ops.get_warp_align_corners(), getattr(self.net, "band_rows", 0)) == self._precision):
             return
         if self.on_stale == "raise":
-            raise RuntimeError("GraphedHSIC: the model's parameters / buffers, its mode, the operand precision or the warp convention changed since the "
-                               "capture; build a new GraphedHSIC (or pass on_stale='recapture')")
+            raise RuntimeError("GraphedHSIC: the model's parameters / buffers, its mode, its band_rows, the operand precision or the warp convention "
+                               "changed since the capture; build a new GraphedHSIC (or pass on_stale='recapture')")
         self._capture()
 
     def _stage(self, h_matrix, after=None):
@@ -224,6 +225,7 @@ class GraphedTrainStep:
         self._params = [p for _, p in model.named_parameters()]
         self._precision = _mnn.get_precision()
         self._deterministic = is_deterministic()
+        self._band_rows = getattr(model, "band_rows", 0)
         # warm-up on a side stream (allocator pools, weight packs, one-time kernel attributes), then put parameters, buffers and
         # optimizer state back: the warm-up steps are not part of the training run
         saved = {k: v.clone() for k, v in model.state_dict().items()}
@@ -273,6 +275,9 @@ class GraphedTrainStep:
         if is_deterministic() != self._deterministic:
             raise RuntimeError(f"GraphedTrainStep: captured with the deterministic mode {'on' if self._deterministic else 'off'}, "
                                f"replayed with it {'on' if is_deterministic() else 'off'}: the graph replays the kernels of its capture")
+        if getattr(self.model, "band_rows", 0) != self._band_rows:
+            raise RuntimeError(f"GraphedTrainStep: captured with band_rows = {self._band_rows}, replayed with the model's band_rows = "
+                               f"{getattr(self.model, 'band_rows', 0)}: the graph replays the context models of its capture")
         self._refuse_h_grad(h_matrix)
         if d1 is not self.d1:
             self.d1.copy_(d1)

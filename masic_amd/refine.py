@@ -19,8 +19,10 @@ and a pair's noise does not depend on its batch mates.  The weights are frozen f
 no weight-, bias- or table-gradient launch runs and no parameter's .grad changes.
 
 Limits.  The result of a pair is NOT promised to be bit-equal across batch compositions: several bf16 layers pick their kernels by
-batch shape.  The surrogate models the unbanded context model; files coded with band_rows > 0 from refined latents decode exactly (the
-coder uses the final latents) but the rate the loop minimised is that of the unbanded file.  fp8 operands are not supported.
+batch shape.  The surrogate and the check model the context model of HSIC.band_rows (0: the unbanded one): set it to the band_rows the
+file will be coded with (bands.model_band_rows) and the loop descends and checks that file's rate; files coded with another band_rows
+from refined latents decode exactly (the coder uses the final latents) but the rate the loop minimised is not theirs.  The bands are
+those of the full-latent parameter form, not the pixel-list kernels' bf16 arithmetic.  fp8 operands are not supported.
 
 Under a bit budget (RefineConfig(budget_bpp=...) or (budget_rel=...); both None: everything above, unchanged).  The objective
 above follows lmbda wherever it leads -- on a model that sits at the wrong operating point to files three times the size
@@ -39,9 +41,9 @@ one pair_rd call it makes:
 By construction: if any checked iterate, the start included, was feasible, the result is feasible; if the start was feasible,
 D_best <= D_start; if nothing was feasible, R_best <= R_start.  The call returns a RefinedToBudget.
 
-Limits of the budget.  It is on the ESTIMATED bits of the unbanded context model, as the loop's rate is: file bytes exceed the
-estimate by the container and coder overhead (measured: profiles/refine_budget_bench.txt), and band_rows > 0 files are budgeted
-against the unbanded estimate.  fp8 is refused as without a budget.
+Limits of the budget.  It is on the ESTIMATED bits of the context model of HSIC.band_rows, as the loop's rate is: file bytes exceed
+the estimate by the container and coder overhead (measured: profiles/refine_budget_bench.txt), and a file coded with another
+band_rows than the attribute is budgeted against the attribute's estimate.  fp8 is refused as without a budget.
 
 The elementwise kernels are declared in include/masic_refine.h and include/masic_budget.h, side headers of libmasic_hip.so bound by
 _lib.bind_header.  No CPU path.

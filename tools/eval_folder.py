@@ -3,7 +3,7 @@
 on this library -- masic_amd.evaluate.evaluate_folder (rate from the likelihoods) or, with --files, evaluate_files (real .msf files).
 
     python tools/eval_folder.py -d /data/instereo2k --checkpoint checkpoint.pth.tar [--homopath homo_best.pth.tar | --aligner]
-        [--cqe second_checkpoint.pth.tar] [--split test] [--patch-size 256 256] [--batch-size 8] [--files] [--band-rows S]
+        [--cqe second_checkpoint.pth.tar] [--split test] [--patch-size 256 256] [--batch-size 8] [--files] [--band-rows S] [--model-band-rows S]
         [--refine-steps K --refine-lmbda L [--refine-lr R] [--refine-budget-bpp X | --refine-budget-rel X]] [--precision bf16] [--lpips-weights alex.pth] [--json report.json] [--timing]
 
 --checkpoint: what tools/train_folder.py --save writes ({'state_dict': ...} of MASIC.HSIC; --nmk for another width than 128 192 5).
@@ -13,7 +13,9 @@ beside that of the B per-slice loss.rate_distortion calls it replaces.  --refine
 latents for that many Adam steps before coding (masic_amd.refine; --refine-lmbda: the rate-distortion weight the checkpoint was
 trained with, --refine-lr: Adam's step size, default the library's).  --refine-budget-bpp X: every pair may cost at most X estimated
 bits per pixel of its padded size; --refine-budget-rel X: at most X times the estimated bits of its unrefined latents (1.0: refine, but
-never to more bits) -- RefineConfig's budget_bpp / budget_rel."""
+never to more bits) -- RefineConfig's budget_bpp / budget_rel.  --band-rows S: how --files codes (StereoCodec's band_rows).
+--model-band-rows S, in either mode: HSIC.band_rows = S, the file the model ESTIMATES -- the rate evaluate_folder reports, and the rate
+the refinement and its budget descend and constrain, are those of files coded with band_rows = S."""
 import argparse
 import os
 import sys
@@ -79,7 +81,8 @@ def main(argv=None):
     ap.add_argument("--patch-size", type=int, nargs=2, default=(256, 256))
     ap.add_argument("--batch-size", type=int, default=8)
     ap.add_argument("--files", action="store_true")
-    ap.add_argument("--band-rows", type=int, default=0)
+    ap.add_argument("--band-rows", type=int, default=0, help="--files: the row bands the files are coded with")
+    ap.add_argument("--model-band-rows", type=int, default=0, help="HSIC.band_rows: the row bands of the file the model estimates (and refines for)")
     ap.add_argument("--refine-steps", type=int, default=0, help="--files: Adam steps of encoder-side latent refinement per batch (0: off)")
     ap.add_argument("--refine-lr", type=float, default=None, help="Adam's step size (default: masic_amd.refine.DEFAULT_LR)")
     ap.add_argument("--refine-lmbda", type=float, default=None, help="the rate-distortion weight of the checkpoint; needed with --refine-steps")
@@ -115,6 +118,7 @@ def main(argv=None):
     hsic.load_state_dict(_state(args.checkpoint))
     hsic = hsic.to(device).eval()
     hsic.update()
+    hsic.band_rows = args.model_band_rows
     if args.aligner:
         from masic_amd.align import PatchAligner
         homo = PatchAligner().to(device).eval()

@@ -4,11 +4,13 @@
 cut from them by two launches, h_matrix from the frozen homography net, one masic_amd.train.train_step per batch.
 
     python tools/train_folder.py -d /data/instereo2k [--split train --patch-size 512 512 --batch-size 8 --steps 300 --lambda 0.01
-        --homopath homo_best.pth.tar --dataset-add DIR --precision bf16 --seed 0 --save checkpoint.pth.tar]
+        --homopath homo_best.pth.tar --dataset-add DIR --precision bf16 --seed 0 --band-rows S --save checkpoint.pth.tar]
 
 <dataset>/<split>/left/* and <dataset>/<split>/right/* pair up by name, as the reference's ImageFolder lists them.  The log line is the
 reference's, every 10th iteration.  --homopath: a checkpoint of the reference's HomographyModel ({'state_dict': ...}, keys 'model.*');
-without one the net keeps its initialisation, as the reference's driver goes on "homo from none"."""
+without one the net keeps its initialisation, as the reference's driver goes on "homo from none".  --band-rows S: train for files coded
+with compress(..., band_rows=S) -- HSIC.band_rows = S, the context models of the training graph do not see across the top edge of a
+band of S latent rows (0, the default: the unbanded model)."""
 import argparse
 import os
 import sys
@@ -51,6 +53,7 @@ def main(argv=None):
     ap.add_argument("--precision", default="bf16", choices=("f32", "bf16"))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-bytes", type=int, default=64 << 30)
+    ap.add_argument("--band-rows", type=int, default=0, help="HSIC.band_rows while training: the row bands of the files the model is trained for")
     ap.add_argument("--save", default=None, help="write {'state_dict': ...} of the trained codec here")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -68,6 +71,7 @@ def main(argv=None):
     nethomo = load_homography_net(args.homopath, ds.homopatch, device)
     torch.manual_seed(args.seed)
     net = MASIC.HSIC(N=128, M=192, K=5).to(device).train()
+    net.band_rows = args.band_rows
     optimizer, aux_optimizer = make_optimizers(net, lr=args.learning_rate, aux_lr=args.aux_learning_rate)
     print("lambda:", args.lmbda)
     per_epoch = len(ds) // args.batch_size
@@ -95,7 +99,7 @@ def main(argv=None):
     dt = time.perf_counter() - t
     print(f"{step} steps in {dt:.1f} s ({1e3 * dt / step:.1f} ms a step, {step * args.batch_size / dt:.0f} pairs/s)")
     if args.save:
-        torch.save({"state_dict": net.state_dict(), "steps": step, "lambda": args.lmbda}, args.save)
+        torch.save({"state_dict": net.state_dict(), "steps": step, "lambda": args.lmbda, "band_rows": net.band_rows}, args.save)
 
 
 if __name__ == "__main__":
