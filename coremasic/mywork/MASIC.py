@@ -35,6 +35,7 @@ from masic_amd import fp8 as _fp8
 from masic_amd import deconv as _deconv
 from masic_amd import conv_s2 as _conv_s2
 from masic_amd import latent as _latent
+from masic_amd import d2s_layer as _d2s_layer
 from masic_amd.bands import check_band_rows as _check_band_rows
 from masic_amd.f16k import F16K as _F16K, F8K as _F8K
 
@@ -485,6 +486,9 @@ def _synthesis_f16k(dec, y_hat):
         t = _own_kernel_or_f16k(_deconv, convs[i], gdns[i], t)       # g_s_conv2 / g_s_conv3 (128 -> 128): deconv_igdn_f16k
         if i < 2:
             _fp8.record(dec, "d%d" % (i + 1), t.buf)
+    # g_s_conv4 (128 -> 3): d2s_layer_f16k where it takes the shape (masic_amd.d2s_layer: conv_f16k's pack, conv_f16k's bits)
+    if t.whole and _d2s_layer.supported(dec.g_s_conv4, t.B, t.H, t.W) and _d2s_layer.preferred(dec.g_s_conv4, t.B, t.H, t.W):
+        return _d2s_layer.run(dec.g_s_conv4, t)
     return dec.g_s_conv4.run_f16k_d2s(t)
 
 

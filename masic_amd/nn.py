@@ -241,14 +241,10 @@ class _PackedWeightMixin:
             self.__dict__["_packed_conv_a_cache"] = cache
         return cache[1]
 
-    def run_f16k_d2s(self, x, out=None, out_coff=0):
-        """Inference-only, ConvTranspose2d(Cin -> C <= 8, k5, s2) on a whole F16K input: run as the equivalent stride-1 3x3 convolution
-        to 4C channels with a depth-to-space store (masic_conv_f16k_d2s_fwd). Returns float32 NCHW [B, C, 2Hi, 2Wi]."""
-        if not self.transposed_conv or self._geometry() != (5, 5, 2, 2):
-            raise RuntimeError("masic_amd: run_f16k_d2s is for ConvTranspose2d(k=5, s=2, p=2)")
-        if not x.whole or x.C != self.in_channels:
-            raise RuntimeError(f"masic_amd: run_f16k_d2s takes a whole tensor of {self.in_channels} channels, not {x!r}")
-        B, Hi, Wi = x.B, x.H, x.W
+    def packed_d2s(self, B, Hi, Wi):
+        """(descriptor, slab stream, 32-entry bias) of the equivalent stride-1 3x3 convolution to 4C (padded to 32) channels of a
+        ConvTranspose2d(Cin -> C <= 8, k5, s2) on a [B, Cin, Hi, Wi] input: what run_f16k_d2s launches with, packed once per weight
+        version and shape."""
         desc = ops.make_conv_desc(B, self.in_channels, Hi, Wi, 32, 3, 3, 1, 1, prec=PREC_BF16)
         w = self.weight
 
@@ -257,6 +253,16 @@ class _PackedWeightMixin:
             return ops.pack_conv_f16k_weight(wc, desc), bc
         wp, bc = _cached(self, "_packed_d2s_cache", weight_key(w) + (None if self.bias is None else weight_key(self.bias),),
                          (B, Hi, Wi), build)
+        return desc, wp, bc
+
+    def run_f16k_d2s(self, x, out=None, out_coff=0):
+        """Inference-only, ConvTranspose2d(Cin -> C <= 8, k5, s2) on a whole F16K input: run as the equivalent stride-1 3x3 convolution
+        to 4C channels with a depth-to-space store (masic_conv_f16k_d2s_fwd). Returns float32 NCHW [B, C, 2Hi, 2Wi]."""
+        if not self.transposed_conv or self._geometry() != (5, 5, 2, 2):
+            raise RuntimeError("masic_amd: run_f16k_d2s is for ConvTranspose2d(k=5, s=2, p=2)")
+        if not x.whole or x.C != self.in_channels:
+            raise RuntimeError(f"masic_amd: run_f16k_d2s takes a whole tensor of {self.in_channels} channels, not {x!r}")
+        desc, wp, bc = self.packed_d2s(x.B, x.H, x.W)
         return ops.conv2d_f16k_d2s(x.buf, wp, bc, desc, self.out_channels, out=out, out_coff=out_coff)
 
     def d2s_supported(self, B, Hi, Wi):
