@@ -192,12 +192,10 @@ def _gdn_f16k(gdn, x):
     return _hip.gdn_f16k(x, gdn.beta.detach(), gdn.gamma.detach(), inverse=gdn.inverse, beta_min=gdn.beta_min)
 
 
-def _own_kernel_or_f16k(kernel, cv, gdn, t):
-    """cv + gdn on F16K t: on the layer's own kernel (masic_amd.deconv / masic_amd.conv_s2: conv_f16k's packs, conv_f16k's bits) where it
-    takes the layer and the form, else on conv_f16k"""
-    if t.whole and kernel.supported(cv, gdn, t.B, t.H, t.W):
-        return kernel.run(cv, gdn, t)
-    return cv.run_f16k(t, gdn=gdn)
+def _own_kernel_takes(kernel, cv, t, *gdn):
+    """does the own-layer module `kernel` (masic_amd.conv_s2 / deconv with the layer's GDN, latent / d2s_layer without: conv_f16k's packs,
+    conv_f16k's bits) take the layer cv on the F16K t?  Where not, the caller keeps the conv_f16k method that kernel.run stands for."""
+    return t.whole and kernel.supported(cv, *gdn, t.B, t.H, t.W) and kernel.preferred(cv, t.B, t.H, t.W)
 
 
 def _analysis_f16k(owner, x, layouts=None):
@@ -235,12 +233,13 @@ def _analysis_f16k(owner, x, layouts=None):
     t = _F16K(_hip.conv_a_gdn_f16k(x, c1.packed_first_layer_weight(), b1, (_mnn.packed_gdn_f16k(gdns[0]), gdns[0].inverse))[0], B, 128, *sizes[0], 128, 0)
     _fp8.record(owner, "a1", t.buf)
     for i in (1, 2):
-        t = _own_kernel_or_f16k(_conv_s2, convs[i], gdns[i], t)      # g_a_conv2 / g_a_conv3 (128 -> 128): conv_s2_gdn_f16k
+        # g_a_conv2 / g_a_conv3 (128 -> 128): conv_s2_gdn_f16k
+        t = _conv_s2.run(convs[i], gdns[i], t) if _own_kernel_takes(_conv_s2, convs[i], t, gdns[i]) else convs[i].run_f16k(t, gdn=gdns[i])
         if i == 1:
             _fp8.record(owner, "a2", t.buf)
     if layouts is not None:
         # g_a_conv4 (128 -> 192): conv_s2_latent_f16k where the launch is large enough for it, else conv_f16k_multi; the same bits
-        if t.whole and _latent.supported(convs[3], t.B, t.H, t.W) and _latent.preferred(convs[3], t.B, t.H, t.W):
+        if _own_kernel_takes(_latent, convs[3], t):
             return _latent.run(convs[3], t, **layouts)
         return convs[3].run_f16k_multi(t, **layouts)
     return convs[3].run_f16k(t, want_nchw=True)
@@ -483,11 +482,12 @@ def _synthesis_f16k(dec, y_hat):
         t = convs[2].run_f8k(t, gdn=gdns[2], out="f16k")
         return dec.g_s_conv4.run_f16k_d2s(t)
     for i in range(3):
-        t = _own_kernel_or_f16k(_deconv, convs[i], gdns[i], t)       # g_s_conv2 / g_s_conv3 (128 -> 128): deconv_igdn_f16k
+        # g_s_conv2 / g_s_conv3 (128 -> 128): deconv_igdn_f16k
+        t = _deconv.run(convs[i], gdns[i], t) if _own_kernel_takes(_deconv, convs[i], t, gdns[i]) else convs[i].run_f16k(t, gdn=gdns[i])
         if i < 2:
             _fp8.record(dec, "d%d" % (i + 1), t.buf)
     # g_s_conv4 (128 -> 3): d2s_layer_f16k where it takes the shape (masic_amd.d2s_layer: conv_f16k's pack, conv_f16k's bits)
-    if t.whole and _d2s_layer.supported(dec.g_s_conv4, t.B, t.H, t.W) and _d2s_layer.preferred(dec.g_s_conv4, t.B, t.H, t.W):
+    if _own_kernel_takes(_d2s_layer, dec.g_s_conv4, t):
         return _d2s_layer.run(dec.g_s_conv4, t)
     return dec.g_s_conv4.run_f16k_d2s(t)
 

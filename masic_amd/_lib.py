@@ -139,11 +139,16 @@ def _load():
 lib = _load()
 
 
+def header_path(filename):
+    """The path of a side header: a file beside include/masic_hip.h (or an absolute path)."""
+    return os.path.join(os.path.dirname(HEADER_PATH), filename)
+
+
 def bind_header(filename, prefix):
-    """Bind a side header of libmasic_hip.so: a file beside include/masic_hip.h (or an absolute path) that holds prototypes only, each
-    a `prefix`* entry point outside the pinned ABI of masic_hip.h (SIGNATURES, tests/golden/abi.json), which stays as it is.  Parses
-    it, sets restype and argtypes of every prototype on `lib` and returns {name: (restype, argtypes)}."""
-    path, header = os.path.join(os.path.dirname(HEADER_PATH), filename), os.path.basename(filename)
+    """Bind a side header of libmasic_hip.so: a file of header_path that holds prototypes only, each a `prefix`* entry point outside
+    the pinned ABI of masic_hip.h (SIGNATURES, tests/golden/abi.json), which stays as it is.  Parses it, sets restype and argtypes of
+    every prototype on `lib` and returns {name: (restype, argtypes)}."""
+    path, header = header_path(filename), os.path.basename(filename)
     if not os.path.exists(path):
         raise ImportError(f"masic_amd.{prefix[len('masic_'):].rstrip('_')}: {path} is missing: the binding is derived from it.  There is "
                           "no CPU fallback for the HIP path.")

@@ -14,15 +14,13 @@ on neither B nor its batch mates.
 The entry points are declared in include/masic_align.h, a side header of libmasic_hip.so bound by _lib.bind_header.  No CPU path:
 tensors must live on an MI355X (`cuda`) device.
 """
-import os
-
 import torch
 import torch.nn as nn
 
 from . import _lib
 from .ops import _dev, _p, _stream
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_align.h")
+HEADER_PATH = _lib.header_path("masic_align.h")
 PATCH_SIZES = (32, 64, 128)
 ITERS = (30, 15, 10)              # Gauss-Newton steps, coarse to fine; the last `levels` entries are used
 

@@ -9,14 +9,12 @@ One launch each, no allocation below this file, capturable.  Fold and the ungate
 (autograd.BandFoldFn / BandUnfoldFn).  The entry points are declared in include/masic_bandfold.h, a side header of libmasic_hip.so bound
 by _lib.bind_header.  No CPU path.
 """
-import os
-
 import torch
 
 from . import _lib
 from .ops import _p, _stream
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_bandfold.h")
+HEADER_PATH = _lib.header_path("masic_bandfold.h")
 
 SIGNATURES = _lib.bind_header(HEADER_PATH, "masic_bandfold_")       # name -> (restype, argtypes) of every prototype of masic_bandfold.h
 

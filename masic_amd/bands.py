@@ -12,11 +12,10 @@ The entry point is declared in include/masic_bands.h, a side header of libmasic_
 import contextlib
 import ctypes
 import operator
-import os
 
 from . import _lib
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_bands.h")
+HEADER_PATH = _lib.header_path("masic_bands.h")
 MAX_BAND_ROWS = 255               # the .bin header stores band_rows in one byte (coremasic/mywork/MASIC.py: _write_pair)
 
 SIGNATURES = _lib.bind_header(HEADER_PATH, "masic_bands_")          # name -> (restype, argtypes) of every prototype of masic_bands.h

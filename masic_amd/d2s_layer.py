@@ -10,30 +10,35 @@ depth-to-space store); `supported` answers False for everything else -- and for 
 order (its 32-channel-chunk row) -- and the caller keeps run_f16k_d2s for it.  `preferred` is the library's rule for the eval forward
 (profiles/d2s_layer_ab.txt); the bits do not depend on it.
 
-The entry points are declared in include/masic_d2s.h, a side header of libmasic_hip.so bound by _lib.bind_header.  No CPU path.
+The entry points are declared in include/masic_d2s.h, a side header of libmasic_hip.so bound by _lib.bind_header; the launcher's first
+checks, the KernelTimer hook, the common part of `supported`, and `preferred` are layer_kernel.LayerKernel's.  No CPU path.
 """
 import ctypes
 import functools
-import os
 
 import torch
 
 from . import _lib, ops
 from .f16k import F16K
-from .ops import _p, _stream
+from .layer_kernel import IN_CHANNELS, LayerKernel
+from .ops import _p
 
-IN_CHANNELS, MAX_OUT_CHANNELS = 128, 8
+MAX_OUT_CHANNELS = 8
 PACKED_BYTES = 8 * 5 * 2 * 4096                   # the layer's slab stream: 8 chunks of 16 channels x 5 steps of 2 taps x 4 KiB
 ROW = "conv_f16k<1, 2, 3, 5, 2, false, 1, 4, false>"     # the conv_f16k row whose stream and sum order the kernel shares
-
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_d2s.h")
-SIGNATURES = _lib.bind_header(HEADER_PATH, "masic_d2s_")             # name -> (restype, argtypes) of every prototype of masic_d2s.h
-_WHO = "masic_amd.d2s_layer"
 
 
 def conv_desc(B, Hi, Wi):
     """The descriptor of the equivalent stride-1 3x3 convolution to 32 rows: run_f16k_d2s's."""
     return ops.make_conv_desc(B, IN_CHANNELS, Hi, Wi, 32, 3, 3, 1, 1, prec=_lib.PREC_BF16)
+
+
+_KERNEL = LayerKernel("masic_d2s.h", "masic_d2s_", "d2s_layer_f16k", who="d2s_layer", transposed=True, out_channels=range(1, MAX_OUT_CHANNELS + 1),
+                      layer="the 128 -> 32 3x3 layer", packed_bytes=PACKED_BYTES, bias_len=32, desc=conv_desc, cv_supported="d2s_supported")
+HEADER_PATH, SIGNATURES = _KERNEL.header_path, _KERNEL.signatures          # name -> (restype, argtypes) of every prototype of masic_d2s.h
+kernel_name = _KERNEL.kernel_name                 # (B, Hi, Wi)
+preferred = _KERNEL.preferred                     # (cv, B, Hi, Wi): masic_d2s_layer_f16k_preferred
+_WHO = _KERNEL.who
 
 
 @functools.lru_cache(maxsize=256)
@@ -44,30 +49,14 @@ def takes_row(B, Hi, Wi):
     return rc == 0 and buf.value.decode() == ROW
 
 
-def kernel_name(B, Hi, Wi):
-    """The symbol of the kernel the launcher starts for the shape, as rocprofv3 prints it."""
-    buf = ctypes.create_string_buffer(96)
-    _lib.check(_lib.lib.masic_d2s_layer_f16k_kernel_name(B, Hi, Wi, buf, 96), "d2s_layer_f16k_kernel_name")
-    return buf.value.decode()
-
-
 def launch(x16, packed, bias, B, Hi, Wi, C, out=None, out_coff=0, max_wgs=0):
     """The layer with the arguments, the tensor and -- where conv_f16k runs the shape on ROW -- the bits of ops.conv2d_f16k_d2s: x16 an
     F16K buffer [B][8][Hi*Wi][16], `packed` the slab stream of ops.pack_conv_f16k_weight for a descriptor that takes ROW, bias the 32
     values of ops.deconv_s2_as_conv_weight or None.  Returns float32 NCHW [B, C, 2Hi, 2Wi], or `out` written at channels out_coff ..;
     max_wgs > 0 caps the grid (tests)."""
-    if x16.dtype != torch.int16 or not x16.is_cuda or x16.numel() != B * IN_CHANNELS * Hi * Wi:
-        raise RuntimeError(f"{_WHO}: input must be an F16K int16 CUDA buffer of [{B},{IN_CHANNELS},{Hi},{Wi}]")
-    if packed.dtype != torch.int16 or packed.numel() * 2 != PACKED_BYTES or packed.device != x16.device:
-        raise RuntimeError(f"{_WHO}: `packed` is not the slab stream of the 128 -> 32 3x3 layer")
-    if bias is not None:
-        ops._dev(bias, "bias")
-        if bias.numel() != 32 or bias.device != x16.device:
-            raise RuntimeError(f"{_WHO}: bias must hold 32 values on the input's device")
+    _KERNEL.check(x16, packed, bias, B, Hi, Wi)
     if not 0 < C <= MAX_OUT_CHANNELS:
         raise RuntimeError(f"{_WHO}: 1 to {MAX_OUT_CHANNELS} output channels, not {C}")
-    if not _lib.lib.masic_d2s_layer_f16k_supported(B, Hi, Wi):
-        raise RuntimeError(f"{_WHO}: shape [{B},{IN_CHANNELS},{Hi},{Wi}] is not supported")
     if out is None:
         out_coff = 0
         out = torch.empty((B, C, 2 * Hi, 2 * Wi), dtype=torch.float32, device=x16.device)
@@ -76,35 +65,15 @@ def launch(x16, packed, bias, B, Hi, Wi, C, out=None, out_coff=0, max_wgs=0):
         if (out.dim() != 4 or (out.shape[0], out.shape[2], out.shape[3]) != (B, 2 * Hi, 2 * Wi) or out.device != x16.device
                 or not 0 <= out_coff <= out.shape[1] - C):
             raise RuntimeError(f"{_WHO}: `out` is not a float32 [{B}, >= {out_coff + C}, {2 * Hi}, {2 * Wi}] tensor on the input's device")
-    timed = None
-    if ops._timer is not None:
-        timed = ops._timer_open(conv_desc(B, Hi, Wi), lambda d, buf, n: _lib.lib.masic_d2s_layer_f16k_kernel_name(B, Hi, Wi, buf, n))
-    _lib.check(_lib.lib.masic_d2s_layer_f16k_fwd(_p(x16), _p(packed), _p(bias), _p(out), C, out.shape[1], out_coff, B, Hi, Wi, max_wgs,
-                                                 _stream()), "d2s_layer_f16k_fwd")
-    if timed is not None:
-        ops._timer_close(timed)
+    _KERNEL.fwd(B, Hi, Wi, (), _p(x16), _p(packed), _p(bias), _p(out), C, out.shape[1], out_coff, B, Hi, Wi, max_wgs)
     return out
 
 
 def supported(cv, B, Hi, Wi, in_ctot=None, in_coff=0, prec=_lib.PREC_BF16):
     """True where run(cv, x, ...) stands for cv.run_f16k_d2s(x, ...) on a whole F16K x of [B, 128, Hi, Wi]: ConvTranspose2d(128, C <= 8,
-    5, stride 2, padding 2), bf16 operands, and a shape at which conv_f16k runs the layer on ROW, so that the cached stream is in this
-    kernel's order.  The keyword arguments name what the caller would ask of conv_f16k besides: a channel view of the input, other
-    operands -- each of them is refused."""
-    if not getattr(cv, "transposed_conv", False) or getattr(cv, "masked_conv", True):
-        return False
-    if cv.in_channels != IN_CHANNELS or not 0 < cv.out_channels <= MAX_OUT_CHANNELS or cv._geometry() != (5, 5, 2, 2):
-        return False
-    if prec != _lib.PREC_BF16 or in_coff != 0 or in_ctot not in (None, IN_CHANNELS):
-        return False
-    if not _lib.lib.masic_d2s_layer_f16k_supported(B, Hi, Wi) or not cv.d2s_supported(B, Hi, Wi):
-        return False
-    return takes_row(B, Hi, Wi)
-
-
-def preferred(cv, B, Hi, Wi):
-    """True where the eval forward takes this kernel for the shape instead of conv_f16k (masic_d2s_layer_f16k_preferred)."""
-    return bool(_lib.lib.masic_d2s_layer_f16k_preferred(B, Hi, Wi))
+    5, stride 2, padding 2), bf16 operands (LayerKernel.supported), and a shape at which conv_f16k runs the layer on ROW, so that the
+    cached stream is in this kernel's order."""
+    return _KERNEL.supported(cv, B, Hi, Wi, in_ctot, in_coff, prec) and takes_row(B, Hi, Wi)
 
 
 def run(cv, x, out=None, out_coff=0):

@@ -9,53 +9,41 @@ Operands are conv_f16k's: the weight stream of `cv.packed_f16k_weight` -- no pac
 else and the caller keeps conv_f16k_multi for it.  `preferred` is the library's rule for the eval forward: a threshold on the launch's
 workgroup count (profiles/conv_s2_latent_ab.txt); the bits do not depend on it.
 
-The entry points are declared in include/masic_latent.h, a side header of libmasic_hip.so bound by _lib.bind_header.  No CPU path.
+The entry points are declared in include/masic_latent.h, a side header of libmasic_hip.so bound by _lib.bind_header; the launcher's
+first checks, the KernelTimer hook, `supported` and `preferred` are layer_kernel.LayerKernel's.  No CPU path.
 """
-import ctypes
-import os
-
 import torch
 
-from . import _lib, ops
+from . import ops
 from .f16k import F16K
-from .ops import _p, _stream
+from .layer_kernel import IN_CHANNELS, LayerKernel
+from .ops import _p
 
-IN_CHANNELS, OUT_CHANNELS = 128, 192
+OUT_CHANNELS = 192
 PACKED_BYTES = 2 * 8 * 5 * 20480                  # the layer's slab stream: 2 co-blocks x 8 chunks x 5 steps of 5 taps x 4 KiB
 WANT = ("y32", "round32", "round16", "abs16")
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_latent.h")
-SIGNATURES = _lib.bind_header(HEADER_PATH, "masic_latent_")          # name -> (restype, argtypes) of every prototype of masic_latent.h
-_WHO = "masic_amd.latent"
+_KERNEL = LayerKernel("masic_latent.h", "masic_latent_", "latent_s2_f16k", who="latent", transposed=False, out_channels=(OUT_CHANNELS,),
+                      layer="a 128 -> 192 5x5 stride-2 layer", packed_bytes=PACKED_BYTES, bias_len=OUT_CHANNELS,
+                      cv_supported="f16k_multi_supported")
+HEADER_PATH, SIGNATURES = _KERNEL.header_path, _KERNEL.signatures          # name -> (restype, argtypes) of every prototype of masic_latent.h
+kernel_name = _KERNEL.kernel_name                 # (B, Hi, Wi)
+supported = _KERNEL.supported                     # (cv, B, Hi, Wi, in_ctot=None, in_coff=0, prec=PREC_BF16): where run stands for cv.run_f16k_multi
+preferred = _KERNEL.preferred                     # (cv, B, Hi, Wi): masic_latent_s2_f16k_preferred
+_WHO = _KERNEL.who
 
 
 def out_hw(Hi, Wi):
     return (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
 
 
-def kernel_name(B, Hi, Wi):
-    """The symbol of the kernel the launcher starts for the shape, as rocprofv3 prints it."""
-    buf = ctypes.create_string_buffer(96)
-    _lib.check(_lib.lib.masic_latent_s2_f16k_kernel_name(B, Hi, Wi, buf, 96), "latent_s2_f16k_kernel_name")
-    return buf.value.decode()
-
-
 def launch(x16, packed, bias, B, Hi, Wi, want=WANT, round16=None, round16_ctot=0, round16_coff=0, gate=None, gate_c=0):
     """v = conv(x) + bias of the fixed layer written once in the layouts named by `want`, with the arguments, the dict of raw tensors and
     the bits of ops.conv2d_f16k_multi: x16 an F16K buffer [B][8][Hi*Wi][16], `packed` the slab stream of ops.pack_conv_f16k_weight for
     the layer."""
-    if x16.dtype != torch.int16 or not x16.is_cuda or x16.numel() != B * IN_CHANNELS * Hi * Wi:
-        raise RuntimeError(f"{_WHO}: input must be an F16K int16 CUDA buffer of [{B},{IN_CHANNELS},{Hi},{Wi}]")
-    if packed.dtype != torch.int16 or packed.numel() * 2 != PACKED_BYTES or packed.device != x16.device:
-        raise RuntimeError(f"{_WHO}: `packed` is not the slab stream of a 128 -> 192 5x5 stride-2 layer")
-    if bias is not None:
-        ops._dev(bias, "bias")
-        if bias.numel() != OUT_CHANNELS or bias.device != x16.device:
-            raise RuntimeError(f"{_WHO}: bias must hold 192 values on the input's device")
+    _KERNEL.check(x16, packed, bias, B, Hi, Wi)
     if not want or set(want) - set(WANT):
         raise ValueError(f"{_WHO}: want names some of {WANT}, got {want!r}")
-    if not _lib.lib.masic_latent_s2_f16k_supported(B, Hi, Wi):
-        raise RuntimeError(f"{_WHO}: shape [{B},{IN_CHANNELS},{Hi},{Wi}] is not supported")
     C, (Ho, Wo), dev = OUT_CHANNELS, out_hw(Hi, Wi), x16.device
     out = {}
     if "y32" in want:
@@ -78,34 +66,9 @@ def launch(x16, packed, bias, B, Hi, Wi, want=WANT, round16=None, round16_ctot=0
         if gate.shape[0] != B or tuple(gate.shape[2:]) != (Ho, Wo) or gate.device != dev:
             raise RuntimeError(f"{_WHO}: gate does not match the output")
         gate_ctot = gate.shape[1]
-    timed = None
-    if ops._timer is not None:
-        desc = ops.make_conv_desc(B, IN_CHANNELS, Hi, Wi, OUT_CHANNELS, 5, 5, 2, 2, in_ctot=IN_CHANNELS, prec=_lib.PREC_BF16)
-        timed = ops._timer_open(desc, lambda d, buf, n: _lib.lib.masic_latent_s2_f16k_kernel_name(B, Hi, Wi, buf, n))
-    _lib.check(_lib.lib.masic_latent_s2_f16k_fwd(_p(x16), _p(packed), _p(bias), _p(out.get("y32")), _p(out.get("round32")), _p(out.get("round16")),
-                                                 _p(out.get("abs16")), _p(gate), B, Hi, Wi, round16_ctot, round16_coff, gate_ctot, gate_c,
-                                                 _stream()), "latent_s2_f16k_fwd")
-    if timed is not None:
-        ops._timer_close(timed)
+    _KERNEL.fwd(B, Hi, Wi, (), _p(x16), _p(packed), _p(bias), _p(out.get("y32")), _p(out.get("round32")), _p(out.get("round16")),
+                _p(out.get("abs16")), _p(gate), B, Hi, Wi, round16_ctot, round16_coff, gate_ctot, gate_c)
     return out
-
-
-def supported(cv, B, Hi, Wi, in_ctot=None, in_coff=0, prec=_lib.PREC_BF16):
-    """True where run(cv, x, want, ...) stands for cv.run_f16k_multi(x, want, ...) on a whole F16K x of [B, 128, Hi, Wi]: a 128 -> 192
-    5x5 stride-2 convolution, padding 2, unmasked, not transposed, bf16 operands.  The keyword arguments name what the caller would ask
-    of conv_f16k besides: a channel view of the input, other operands -- each of them is refused."""
-    if getattr(cv, "transposed_conv", True) or getattr(cv, "masked_conv", True):
-        return False
-    if cv.in_channels != IN_CHANNELS or cv.out_channels != OUT_CHANNELS or cv._geometry() != (5, 5, 2, 2):
-        return False
-    if prec != _lib.PREC_BF16 or in_coff != 0 or in_ctot not in (None, IN_CHANNELS):
-        return False
-    return bool(_lib.lib.masic_latent_s2_f16k_supported(B, Hi, Wi)) and cv.f16k_multi_supported(B, Hi, Wi)
-
-
-def preferred(cv, B, Hi, Wi):
-    """True where the eval forward takes this kernel for the shape instead of conv_f16k_multi (masic_latent_s2_f16k_preferred)."""
-    return bool(_lib.lib.masic_latent_s2_f16k_preferred(B, Hi, Wi))
 
 
 def run(cv, x, want, round16=None, gate=None, gate_c=0):

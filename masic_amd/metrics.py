@@ -12,13 +12,12 @@ The entry points are declared in include/masic_metrics.h, a side header of libma
 """
 import ctypes
 import math
-import os
 
 import torch
 
 from . import _lib
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_metrics.h")
+HEADER_PATH = _lib.header_path("masic_metrics.h")
 MAX_LIKS = 4
 MAX_IMAGES = 65535                # the image is a grid dimension of the kernels
 

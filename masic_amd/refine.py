@@ -51,17 +51,16 @@ _lib.bind_header.  No CPU path.
 import collections
 import ctypes
 import math
-import os
 
 import torch
 
 from . import _lib
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_refine.h")
+HEADER_PATH = _lib.header_path("masic_refine.h")
 MAX_PAIRS = 65535                # the pair is a grid dimension of the kernels
 
 SIGNATURES = _lib.bind_header(HEADER_PATH, "masic_refine_")          # name -> (restype, argtypes) of every prototype of masic_refine.h
-BUDGET_HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "masic_budget.h")
+BUDGET_HEADER_PATH = _lib.header_path("masic_budget.h")
 BUDGET_SIGNATURES = _lib.bind_header(BUDGET_HEADER_PATH, "masic_budget_")          # likewise of masic_budget.h
 MU_MIN, MU_MAX = 2.0 ** -10, 2.0 ** 10          # the clamp of the rate multiplier of the budgeted loop
 

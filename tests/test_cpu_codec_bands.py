@@ -1,20 +1,13 @@
-"""The banded y bitstream without a device: the coding schedule codec.wavefront_steps(h, w, band_rows), the side header
-include/masic_bands.h (as tests/test_cpu_side_headers.py holds its three headers), the "MSR3" container header through
+"""The banded y bitstream without a device: the coding schedule codec.wavefront_steps(h, w, band_rows), the argument check of the entry
+point of include/masic_bands.h (the header itself is a row of tests/test_cpu_side_headers.py), the "MSR3" container header through
 HSIC._read_pair on files written by hand, and the refusal of a band_rows that is no integer in 0 .. 255 before any device work."""
-import ctypes
 import os
-import re
 import types
 
 import numpy as np
 import pytest
 
 from tests import bands_ref as BR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-I, P = ctypes.c_int, ctypes.c_void_p
-HEADER, PREFIX = "masic_bands.h", "masic_bands_"
-WANT = {"masic_bands_skinny_ctx_fwd_batch": (I, [P] * 3 + [I] * 5 + [P] + [I] * 3 + [P])}
 
 
 # ------------------------------------------------------------------------------------------ schedule
@@ -56,40 +49,7 @@ def test_one_band_is_the_unbanded_schedule(h, w):
         assert np.array_equal(p, (ii[keep] * w + j[keep]).astype(np.int32))
 
 
-# ------------------------------------------------------------------------------------------ header
-def _parsed():
-    from masic_amd import _lib
-    with open(os.path.join(ROOT, "include", HEADER)) as f:
-        return _lib.parse_header(f.read(), header=HEADER)
-
-
-def test_header_parses_to_prototypes_only_with_names_of_its_own():
-    from masic_amd import _lib
-    signatures, constants, structs = _parsed()
-    assert not constants and not structs
-    assert set(signatures) == set(WANT)
-    for name in signatures:
-        assert name.startswith(PREFIX) and name not in _lib.SIGNATURES, name
-
-
-def test_header_signatures():
-    sig = _parsed()[0]
-    for name, (res, args) in WANT.items():
-        assert sig[name] == (res, args), name
-
-
-def test_header_is_bound_on_the_library_and_the_source_is_built():
-    from masic_amd import _lib, bands
-    assert bands.HEADER_PATH == os.path.join(ROOT, "include", HEADER)
-    assert set(bands.SIGNATURES) == set(_parsed()[0])
-    for name, (res, args) in bands.SIGNATURES.items():
-        fn = getattr(_lib.lib, name)                        # exported by the built library
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    with open(os.path.join(ROOT, "masic_amd", "csrc", "Makefile")) as f:
-        srcs = re.search(r"^SRCS\s*:=\s*(.*)$", f.read(), flags=re.M).group(1).split()
-    assert "skinny.hip" in srcs and os.path.exists(os.path.join(ROOT, "masic_amd", "csrc", "skinny.hip"))
-
-
+# ------------------------------------------------------------------------------------------ entry point
 def test_band_rows_below_one_is_an_argument_error_of_the_entry_point():
     """before any pointer is looked at: no device needed"""
     from masic_amd import _lib

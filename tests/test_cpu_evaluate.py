@@ -1,31 +1,17 @@
-"""What the test-split evaluation answers without a GPU: include/masic_metrics.h and its binding (masic_amd/metrics.py), the arithmetic and
+"""What the test-split evaluation answers without a GPU: the host-side answers of masic_amd/metrics.py's entry points (include/masic_metrics.h
+and its binding are a row of tests/test_cpu_side_headers.py), the arithmetic and
 the summary line of masic_amd.evaluate.Report, and every refusal of evaluate_folder / evaluate_files / pair_metrics that happens before
 a launch.  The kernels and the two loops run in tests/test_gpu_metrics.py and tests/test_gpu_evaluate.py."""
 import ctypes
 import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-I, P, S = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
-HEADER, PREFIX, SOURCE = "masic_metrics.h", "masic_metrics_", "metrics.hip"
-WANT = {
-    "masic_metrics_pair_rd_workspace_bytes": (S, [I]),
-    "masic_metrics_pair_rd": (I, [P] * 4 + [S, P, P, I, I, P, P, P]),
-    "masic_metrics_u8_sse_workspace_bytes": (S, [I]),
-    "masic_metrics_u8_sse": (I, [P, P, S, I, P, P, P]),
-}
-
-
-def _parsed():
-    from masic_amd import _lib
-    with open(os.path.join(ROOT, "include", HEADER)) as f:
-        return _lib.parse_header(f.read(), header=HEADER)
 
 
 def parse_line(line):
@@ -39,28 +25,7 @@ def parse_line(line):
     return out
 
 
-# ------------------------------------------------------------------------------------------ the header
-def test_header_holds_prototypes_of_its_own():
-    from masic_amd import _lib
-    signatures, constants, structs = _parsed()
-    assert not constants and not structs
-    assert signatures == WANT
-    for name in signatures:
-        assert name.startswith(PREFIX) and name not in _lib.SIGNATURES, name
-
-
-def test_bound_on_the_library_and_built():
-    from masic_amd import _lib, metrics
-    assert metrics.HEADER_PATH == os.path.join(ROOT, "include", HEADER)
-    assert metrics.SIGNATURES == WANT
-    for name, (res, args) in WANT.items():
-        fn = getattr(_lib.lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    with open(os.path.join(ROOT, "masic_amd", "csrc", "Makefile")) as f:
-        srcs = re.search(r"^SRCS\s*:=\s*(.*)$", f.read(), flags=re.M).group(1).split()
-    assert SOURCE in srcs and os.path.exists(os.path.join(ROOT, "masic_amd", "csrc", SOURCE))
-
-
+# ------------------------------------------------------------------------------------------ the entry points
 def test_workspace_sizes_need_no_gpu():
     """pair_rd keeps masic_rd_loss's six rows of partials per image (so the partition of a slice is masic_sse's); 0 for a B the entry
     points refuse"""

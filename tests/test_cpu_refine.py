@@ -1,25 +1,14 @@
-"""Encoder-side latent refinement (masic_amd/refine.py), the parts that need no GPU: RefineConfig's validation, include/masic_refine.h
-as a side header of libmasic_hip.so (the checks of tests/test_cpu_latent_header.py), the CPU restatement of the loop on the tiny fixture
-(tests/refine_ref.py on oracle/hsic_oracle.py) and the admissibility of the fixture the GPU gradient test compares on."""
+"""Encoder-side latent refinement (masic_amd/refine.py), the parts that need no GPU: RefineConfig's validation, the host-side argument
+checks of the entry points of include/masic_refine.h (the header itself is a row of tests/test_cpu_side_headers.py), the CPU restatement
+of the loop on the tiny fixture (tests/refine_ref.py on oracle/hsic_oracle.py) and the admissibility of the fixture the GPU gradient test
+compares on."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from tests import refine_ref as R
-from tests.test_cpu_side_headers import ROOT, I, P, S, _parsed
-
-HEADER, PREFIX, SOURCE = "masic_refine.h", "masic_refine_", "refine.hip"
-U32, D = ctypes.c_uint32, ctypes.c_double
-WANT = {
-    "masic_refine_noise": (I, [P, P, I, U32, P, P, P]),
-    "masic_refine_adam": (I, [P, P, P, P, P, I, D, P, P]),
-    "masic_refine_keep_best": (I, [P, P, P, I, P, P, P]),
-    "masic_refine_rd_seeds": (I, [P] * 4 + [S, P, P, I, I, D, D] + [P] * 5),
-}
 
 
 # ---------------------------------------------------------------------------------------------------------------- RefineConfig
@@ -46,40 +35,7 @@ def test_config_pair_keys_must_match_the_batch():
         RefineConfig(pair_keys=[1, 2]).keys_for(3)
 
 
-# ---------------------------------------------------------------------------------------------------------------- the side header
-def test_header_parses_to_prototypes_only():
-    signatures, constants, structs = _parsed(HEADER)
-    assert not constants and not structs
-    assert set(signatures) == set(WANT)
-
-
-def test_names_are_its_own():
-    from masic_amd import _lib
-    for name in _parsed(HEADER)[0]:
-        assert name.startswith(PREFIX) and name not in _lib.SIGNATURES, name
-
-
-def test_signatures():
-    sig = _parsed(HEADER)[0]
-    for name, (res, args) in WANT.items():
-        assert sig[name] == (res, args), name
-
-
-def test_bound_on_the_library():
-    from masic_amd import _lib, refine
-    assert refine.HEADER_PATH == os.path.join(ROOT, "include", HEADER)
-    assert set(refine.SIGNATURES) == set(_parsed(HEADER)[0])
-    for name, (res, args) in refine.SIGNATURES.items():
-        fn = getattr(_lib.lib, name)                        # exported by the built library
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-
-
-def test_kernel_source_is_built():
-    with open(os.path.join(ROOT, "masic_amd", "csrc", "Makefile")) as f:
-        srcs = re.search(r"^SRCS\s*:=\s*(.*)$", f.read(), flags=re.M).group(1).split()
-    assert SOURCE in srcs and os.path.exists(os.path.join(ROOT, "masic_amd", "csrc", SOURCE))
-
-
+# ---------------------------------------------------------------------------------------------------------------- the entry points
 def test_bad_arguments_launch_nothing():
     """the argument checks are host code: a null pointer array, B out of range"""
     from masic_amd import _lib

@@ -1,11 +1,9 @@
-"""Latent refinement under a bit budget (masic_amd/refine.py), the parts that need no GPU: RefineConfig's budget fields,
-include/masic_budget.h as a side header of libmasic_hip.so, the host-side argument checks of its three entry points, the CPU
-restatement of the constrained keep-best and of the multiplier update (tests/budget_ref.py) with the guarantees they give, and the
+"""Latent refinement under a bit budget (masic_amd/refine.py), the parts that need no GPU: RefineConfig's budget fields, the host-side
+argument checks of the three entry points of include/masic_budget.h (the header itself is a row of tests/test_cpu_side_headers.py), the
+CPU restatement of the constrained keep-best and of the multiplier update (tests/budget_ref.py) with the guarantees they give, and the
 admissibility of the budget the GPU loop test runs under."""
 import ctypes
 import itertools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -15,15 +13,7 @@ from masic_amd.refine import MU_MAX, MU_MIN, RefinedToBudget          # the inte
 from tests import budget_ref as BR
 from tests import refine_ref as R
 from tests.test_cpu_refine import _encoder_latents
-from tests.test_cpu_side_headers import ROOT, I, P, S, _parsed
 
-HEADER, PREFIX, SOURCE = "masic_budget.h", "masic_budget_", "refine_budget.hip"
-D = ctypes.c_double
-WANT = {
-    "masic_budget_rd_seeds": (I, [P] * 4 + [S, P, P, I, I, D, D] + [P] * 6),
-    "masic_budget_select": (I, [P, P, P, I] + [P] * 6),
-    "masic_budget_mu": (I, [P, P, P, I, D, D, D, P]),
-}
 NAN, INF = float("nan"), float("inf")
 
 
@@ -75,40 +65,7 @@ def test_refined_to_budget_extends_refined():
     assert issubclass(RefinedToBudget, tuple) and tuple(RefinedToBudget(*range(12))[:4]) == (0, 1, 2, 3)
 
 
-# ---------------------------------------------------------------------------------------------------------------- the side header
-def test_header_parses_to_prototypes_only():
-    signatures, constants, structs = _parsed(HEADER)
-    assert not constants and not structs
-    assert set(signatures) == set(WANT)
-
-
-def test_names_are_its_own():
-    from masic_amd import _lib, refine
-    for name in _parsed(HEADER)[0]:
-        assert name.startswith(PREFIX) and name not in _lib.SIGNATURES and name not in refine.SIGNATURES, name
-
-
-def test_signatures():
-    sig = _parsed(HEADER)[0]
-    for name, (res, args) in WANT.items():
-        assert sig[name] == (res, args), name
-
-
-def test_bound_on_the_library():
-    from masic_amd import _lib, refine
-    assert refine.BUDGET_HEADER_PATH == os.path.join(ROOT, "include", HEADER)
-    assert set(refine.BUDGET_SIGNATURES) == set(WANT)
-    for name, (res, args) in refine.BUDGET_SIGNATURES.items():
-        fn = getattr(_lib.lib, name)                        # exported by the built library
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-
-
-def test_kernel_source_is_built():
-    with open(os.path.join(ROOT, "masic_amd", "csrc", "Makefile")) as f:
-        srcs = re.search(r"^SRCS\s*:=\s*(.*)$", f.read(), flags=re.M).group(1).split()
-    assert SOURCE in srcs and os.path.exists(os.path.join(ROOT, "masic_amd", "csrc", SOURCE))
-
-
+# ---------------------------------------------------------------------------------------------------------------- the entry points
 def test_bad_arguments_launch_nothing():
     """the argument checks are host code: null pointers, B out of range, a zero count, scalars outside their range"""
     from masic_amd import _lib

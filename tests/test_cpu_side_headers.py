@@ -1,15 +1,16 @@
-"""The side headers of libmasic_hip.so -- include/masic_align.h, masic_deconv.h, masic_conv_s2.h beside the pinned include/masic_hip.h
-(tests/test_cpu_abi.py, which this leaves as it is): each holds prototypes only, every name an entry point of its own under the header's
-prefix, each bound on the library by _lib.bind_header with the types the header states, and the own-layer kernels' sources are in the
-build.  Then bind_header's refusals, on headers written for the test."""
+"""The side headers of libmasic_hip.so -- the ten files of HEADERS beside the pinned include/masic_hip.h (tests/test_cpu_abi.py, which this
+leaves as it is): each holds prototypes only, every name an entry point of its own under the header's prefix, each bound on the library
+by _lib.bind_header with the types the header states, and the kernels' sources are in the build.  Then bind_header's refusals, on
+headers written for the test."""
 import ctypes
+import importlib
 import os
 import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-I, P, F, S, C = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_size_t, ctypes.c_char_p
+I, P, F, S, C, D, U32 = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_double, ctypes.c_uint32
 # module of masic_amd -> (header, prefix, {name: (restype, argtypes)}, kernel source or None)
 HEADERS = {
     "align": ("masic_align.h", "masic_align_", {
@@ -23,7 +24,39 @@ HEADERS = {
         "masic_conv_s2_gdn_f16k_supported": (I, [I] * 3),
         "masic_conv_s2_gdn_f16k_fwd": (I, [P] * 5 + [I] * 3 + [P]),
         "masic_conv_s2_gdn_f16k_kernel_name": (I, [I] * 3 + [C, S])}, "conv_s2_gdn.hip"),
+    "latent": ("masic_latent.h", "masic_latent_", {
+        "masic_latent_s2_f16k_supported": (I, [I] * 3),
+        "masic_latent_s2_f16k_preferred": (I, [I] * 3),
+        "masic_latent_s2_f16k_fwd": (I, [P] * 8 + [I] * 7 + [P]),
+        "masic_latent_s2_f16k_kernel_name": (I, [I] * 3 + [C, S])}, "conv_s2_latent.hip"),
+    "d2s_layer": ("masic_d2s.h", "masic_d2s_", {
+        "masic_d2s_layer_f16k_supported": (I, [I] * 3),
+        "masic_d2s_layer_f16k_preferred": (I, [I] * 3),
+        "masic_d2s_layer_f16k_fwd": (I, [P] * 4 + [I] * 7 + [P]),
+        "masic_d2s_layer_f16k_kernel_name": (I, [I] * 3 + [C, S])}, "d2s_layer.hip"),
+    "metrics": ("masic_metrics.h", "masic_metrics_", {
+        "masic_metrics_pair_rd_workspace_bytes": (S, [I]),
+        "masic_metrics_pair_rd": (I, [P] * 4 + [S, P, P, I, I, P, P, P]),
+        "masic_metrics_u8_sse_workspace_bytes": (S, [I]),
+        "masic_metrics_u8_sse": (I, [P, P, S, I, P, P, P])}, "metrics.hip"),
+    "bands": ("masic_bands.h", "masic_bands_", {
+        "masic_bands_skinny_ctx_fwd_batch": (I, [P] * 3 + [I] * 5 + [P] + [I] * 3 + [P])}, "skinny.hip"),
+    "bandfold": ("masic_bandfold.h", "masic_bandfold_", {
+        "masic_bandfold_fold": (I, [P, P] + [I] * 5 + [P]),
+        "masic_bandfold_unfold": (I, [P, P] + [I] * 7 + [P, I, I, P]),
+        "masic_bandfold_unfold_f16k": (I, [P, P] + [I] * 7 + [P, I, I, P]),
+        "masic_bandfold_max_blocks": (I, [])}, "band_fold.hip"),
+    "refine": ("masic_refine.h", "masic_refine_", {
+        "masic_refine_noise": (I, [P, P, I, U32, P, P, P]),
+        "masic_refine_adam": (I, [P, P, P, P, P, I, D, P, P]),
+        "masic_refine_keep_best": (I, [P, P, P, I, P, P, P]),
+        "masic_refine_rd_seeds": (I, [P] * 4 + [S, P, P, I, I, D, D] + [P] * 5)}, "refine.hip"),
+    "refine_budget": ("masic_budget.h", "masic_budget_", {
+        "masic_budget_rd_seeds": (I, [P] * 4 + [S, P, P, I, I, D, D] + [P] * 6),
+        "masic_budget_select": (I, [P, P, P, I] + [P] * 6),
+        "masic_budget_mu": (I, [P, P, P, I, D, D, D, P])}, "refine_budget.hip"),
 }
+BOUND_AS = {"refine_budget": ("refine", "BUDGET_")}     # row -> (module, prefix of its HEADER_PATH / SIGNATURES) where not (row, "")
 MODULES = sorted(HEADERS)
 
 
@@ -43,10 +76,12 @@ def test_header_parses_to_prototypes_only(module):
 
 @pytest.mark.parametrize("module", MODULES)
 def test_names_are_its_own(module):
+    """under the header's prefix, and in no other header: neither the pinned one nor another row's"""
     from masic_amd import _lib
     header, prefix, _, _ = HEADERS[module]
+    elsewhere = set(_lib.SIGNATURES).union(*(HEADERS[m][2] for m in MODULES if m != module))
     for name in _parsed(header)[0]:
-        assert name.startswith(prefix) and name not in _lib.SIGNATURES, name
+        assert name.startswith(prefix) and name not in elsewhere, name
 
 
 @pytest.mark.parametrize("module", MODULES)
@@ -59,13 +94,14 @@ def test_signatures(module):
 
 @pytest.mark.parametrize("module", MODULES)
 def test_bound_on_the_library(module):
-    import importlib
     from masic_amd import _lib
-    header = HEADERS[module][0]
-    mod = importlib.import_module("masic_amd." + module)
-    assert mod.HEADER_PATH == os.path.join(ROOT, "include", header)
-    assert set(mod.SIGNATURES) == set(_parsed(header)[0])
-    for name, (res, args) in mod.SIGNATURES.items():
+    header, _, want, _ = HEADERS[module]
+    name, attr = BOUND_AS.get(module, (module, ""))
+    mod = importlib.import_module("masic_amd." + name)
+    assert getattr(mod, attr + "HEADER_PATH") == os.path.join(ROOT, "include", header)
+    signatures = getattr(mod, attr + "SIGNATURES")
+    assert signatures == _parsed(header)[0] == want
+    for name, (res, args) in signatures.items():
         fn = getattr(_lib.lib, name)                        # exported by the built library
         assert fn.restype is res and list(fn.argtypes) == list(args)
 

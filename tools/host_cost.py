@@ -50,3 +50,24 @@ cv = mnn.Conv2d(16, 128, 5, stride=2, padding=2).cuda(); xv = F16K.wrap(x16, 1, 
 t("Conv2d.run_f16k (whole F16K, 1 x 16 -> 128, 5x5 s2, 16^2)", lambda: cv.run_f16k(xv), 5000)
 c3 = mnn.Conv2d(32, 32, 3, padding=1).cuda(); x3v = F16K.wrap(x3, 1, 32, 16, 32); view = F16K.empty(1, 96, 16, 32, "cuda").channels(64, 32)
 t("Conv2d.run_f16k_res (into a channel view of 96)", lambda: c3.run_f16k_res(x3v, act=ops.ACT_LEAKY, out=view), 5000)
+# the own-layer kernels on the layers of a synthetic-weight model, each at the smallest shape it takes: what the
+# eval forward asks per layer (supported, preferred) and the launch through the module
+sys.path.insert(0, os.path.join(ROOT, "coremasic", "mywork"))
+import MASIC
+from masic_amd import conv_s2, d2s_layer, deconv, latent, synth
+net = MASIC.HSIC(128, 192, 5); net.load_state_dict(synth.synth_state_dict(net.state_dict(), seed=31)); net = net.cuda().eval()
+enc, dec = net.encoder1, net.decoder1
+xa = F16K.wrap(torch.zeros(128 * 8 * 8, dtype=torch.int16, device="cuda"), 1, 128, 8, 8)
+xl = F16K.wrap(torch.zeros(128 * 5 * 7, dtype=torch.int16, device="cuda"), 1, 128, 5, 7)
+with torch.no_grad():
+    t("conv_s2.supported (g_a_conv2, 1 x 8 x 8)", lambda: conv_s2.supported(enc.g_a_conv2, enc.g_a_gdn2, 1, 8, 8))
+    t("deconv.supported (g_s_conv2, 1 x 8 x 8)", lambda: deconv.supported(dec.g_s_conv2, dec.g_s_gdn2, 1, 8, 8))
+    t("latent.supported and preferred (g_a_conv4, 8 x 64 x 64)", lambda: latent.supported(enc.g_a_conv4, 8, 64, 64) and latent.preferred(enc.g_a_conv4, 8, 64, 64))
+    t("d2s_layer.supported and preferred (g_s_conv4, 8 x 256 x 256)", lambda: d2s_layer.supported(dec.g_s_conv4, 8, 256, 256) and d2s_layer.preferred(dec.g_s_conv4, 8, 256, 256))
+    t("conv_s2.run (g_a_conv2, 1 x 8 x 8)", lambda: conv_s2.run(enc.g_a_conv2, enc.g_a_gdn2, xa), 5000)
+    t("deconv.run (g_s_conv2, 1 x 8 x 8)", lambda: deconv.run(dec.g_s_conv2, dec.g_s_gdn2, xa), 5000)
+    wl, bl = enc.g_a_conv4.packed_f16k_weight(enc.g_a_conv4._desc_of(xl, nchw=True)), enc.g_a_conv4._bias()
+    t("latent.launch (g_a_conv4, 1 x 5 x 7, four outputs)", lambda: latent.launch(xl.buf, wl, bl, 1, 5, 7), 5000)
+    assert d2s_layer.takes_row(512, 32, 32)           # the pack of a shape conv_f16k runs on d2s_layer.ROW is the kernel's stream at every shape
+    _, wd, bd = dec.g_s_conv4.packed_d2s(512, 32, 32)
+    t("d2s_layer.launch (g_s_conv4, 1 x 5 x 7)", lambda: d2s_layer.launch(xl.buf, wd, bd, 1, 5, 7, 3), 5000)
